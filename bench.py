@@ -26,6 +26,8 @@ T in [25, 10000], length-bucketed) and ``train_step`` (BASELINE configs[4]: one 
 ``engine.select_model`` measured when it admitted the arithmetic for these weights.
 
 ``python bench.py --gpus N`` with N > 1 starts its own N ranks (xvector_amd/launch.py) when it is not already one.
+``--dump-outputs DIR`` writes what the last timed step computed (``xvectors.npy``: [N x utts, 512] float32 in utterance order; in
+``--mode train`` the timed steps' losses and the weights after them) for output-by-output comparison of two builds.
 """
 import argparse
 import json
@@ -76,14 +78,45 @@ def parse():
                     help="GEMM arithmetic: f16bf8 (default) = one fp16 MFMA + one block-scaled bf8 MFMA of the cross terms per "
                          "product in the hidden layers, ~1.3e-5 rel-L2; bf16x3 = split-precision bf16 MFMA, ~5e-6; fp32 = exact "
                          "fp32-input MFMA.  All accumulate in fp32; the parity bar is 1e-4")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB in all; a fixed, seeded sample of rows beyond that).  The inputs are seeded: the same "
+                         "arguments give the same inputs, so two builds can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
-def _train_run(args, rank, world, dev, topo, feat, precision, steps, warmup):
+DUMP_CAP_BYTES = 64 << 20
+
+
+def _dump_outputs(path, arrays):
+    """Write ``arrays`` ({name: ndarray}) as ``path/<name>.npy``, float32 / float64 kept as they are (other dtypes become
+    float64).  Over DUMP_CAP_BYTES in all, every array with more than one row is cut to the same fixed, seeded sample of row
+    indices (sorted), so that the files of two runs with the same arguments line up row for row."""
+    import re
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: (v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)) for k, v in
+              ((k, np.ascontiguousarray(v)) for k, v in arrays.items())}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_CAP_BYTES:
+        keep = DUMP_CAP_BYTES / total
+        for k, v in arrays.items():
+            if v.ndim >= 1 and v.shape[0] > 1:
+                n = max(1, int(v.shape[0] * keep))
+                rows = np.sort(np.random.default_rng(0).choice(v.shape[0], size=n, replace=False))
+                arrays[k] = np.ascontiguousarray(v[rows])
+    for k, v in arrays.items():
+        np.save(os.path.join(path, re.sub(r"[^A-Za-z0-9_.-]", "_", k) + ".npy"), v)
+
+
+def _train_run(args, rank, world, dev, topo, feat, precision, steps, warmup, collect=False):
     """BASELINE configs[4]: minibatches of 64 chunks, one length T~U{200..400} per minibatch (create_egs.py:508-513), 64
     synthetic speakers, softmax-CE head as in models.py:96-113 (or the build-defined AM-softmax head), Adam; data parallel over
     ranks with bucketed gradient all-reduces.  A step = forward + backward + (all-reduce) + Adam on one resident minibatch per
-    rank.  Returns the measurements as a dictionary."""
+    rank.  Returns the measurements as a dictionary; with ``collect``, ``outputs`` holds what the timed steps computed (the loss of
+    each timed step, the weights after the last one)."""
     import torch
     import torch.distributed as dist
     from xvector_amd import synthetic, topology as tp, trainer
@@ -158,21 +191,27 @@ def _train_run(args, rank, world, dev, topo, feat, precision, steps, warmup):
     # MFMA-pipe time of a step at nominal rates: forward, input-gradient and weight-gradient GEMMs in the chosen arithmetic
     # (bf16x3: 3 bf16 MFMAs per product at 2.5 PF -- xv_wgrad_bf16x3 since round 4; fp32: the 157.3 TF fp32 MFMA)
     pipe = 3.0 * fwd * (3.0 / MFMA_BF16_PEAK if precision == "bf16x3" else 1.0 / MFMA_F32_PEAK)
-    return {"chunks_per_s": B * world * steps / dt, "ms_per_step": dt / steps * 1e3, "steps": steps, "warmup": warmup,
-            "steps_per_s": steps / dt, "frames_per_s": frames * world / dt, "approx_tflops_fwd_bwd": 3.0 * fwd * world / dt / 1e12,
-            "mfma_time_over_time": pipe / dt,
-            "peak_note": "3 x forward FLOPs (forward, input gradient, weight gradient); MFMA-pipe time = all three at %s"
-                         % ("2.5 PF / 3 (bf16x3: three bf16 MFMAs per product)" if precision == "bf16x3" else "the 157.3 TF fp32 MFMA peak"),
-            "fused_bn_sums": bool(tr.fused_sums),
-            "precision": precision, "head": head, "class": args.train_class or "ModelWithoutDropout",
-            "first_loss": losses[0], "last_loss": losses[-1]}
+    r = {"chunks_per_s": B * world * steps / dt, "ms_per_step": dt / steps * 1e3, "steps": steps, "warmup": warmup,
+         "steps_per_s": steps / dt, "frames_per_s": frames * world / dt, "approx_tflops_fwd_bwd": 3.0 * fwd * world / dt / 1e12,
+         "mfma_time_over_time": pipe / dt,
+         "peak_note": "3 x forward FLOPs (forward, input gradient, weight gradient); MFMA-pipe time = all three at %s"
+                      % ("2.5 PF / 3 (bf16x3: three bf16 MFMAs per product)" if precision == "bf16x3" else "the 157.3 TF fp32 MFMA peak"),
+         "fused_bn_sums": bool(tr.fused_sums),
+         "precision": precision, "head": head, "class": args.train_class or "ModelWithoutDropout",
+         "first_loss": losses[0], "last_loss": losses[-1]}
+    if collect:
+        r["outputs"] = {"losses": np.asarray(losses, np.float64)}
+        r["outputs"].update(("weights/" + k, v) for k, v in sorted(tr.export()[0].items()))
+    return r
 
 
 def bench_train(args, rank, world, dev, topo, feat):
     """``--mode train``: the training step as the headline of its own line."""
     import torch.distributed as dist
-    r = _train_run(args, rank, world, dev, topo, feat, args.train_precision, args.steps, args.warmup)
+    r = _train_run(args, rank, world, dev, topo, feat, args.train_precision, args.steps, args.warmup, collect=bool(args.dump_outputs))
     if rank == 0:
+        if args.dump_outputs:
+            _dump_outputs(args.dump_outputs, r["outputs"])
         print(json.dumps({
             "metric": "training chunks/sec (64-chunk minibatches, 200-400 frames, 64-way %s, Adam)" % ("AM-softmax" if r["head"] == "am_softmax" else "softmax-CE"),
             "value": r["chunks_per_s"], "unit": "chunks/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -411,19 +450,21 @@ def _cli_job_leg(args, ark_path, scp_path, model_dir, n):
 
 
 def _job_rehearsal_leg(args, model_dir, feat, cli):
-    """BASELINE configs[3] rehearsed at its real COUNTS on the one GPU of this box: 8 ranks x 125 k utterances = a 1 M-line scp through
-    the scp-sharded CLI (`extract_embedding.py` under the package's launcher, extract_xvectors.sh:63-95's twin), ONE gather of 8 x
-    125 k [emitted? | x-vector] rows (2 GB) into rank 0, which writes the 1 M-record ark + scp.  What cannot be real here: the ranks share
+    """BASELINE configs[3] (8 ranks x 125 k utterances) rehearsed at its real job COUNTS on the one GPU of this box: a 1 M-line scp
+    through the scp-sharded CLI (`extract_embedding.py` under the package's launcher, extract_xvectors.sh:63-95's twin), ONE gather of
+    1 M [emitted? | x-vector] rows (2 GB) into rank 0, which writes the 1 M-record ark + scp.  What cannot be real here: the ranks share
     one GPU (gloo transport -- RCCL refuses two ranks on a device -- and every utterance is 25 frames so that the shared device is not
-    what the job waits for), so `extraction` of the breakdown is replaced by the measured single-rank time of a 125 k-utterance shard at
-    T ~ U{200..400} (cli_job's extraction seconds per utterance) in `predicted_per_rank_job_s`.  Everything a rank's Python does per LINE
-    of the table, per KEY and per RECORD is at its real size."""
+    what the job waits for), and they are 4 of 250 k utterances each rather than 8 of 125 k: beside this process (and a test runner
+    above it) no more than six processes may hold one device.  So `extraction` of the breakdown is replaced by the measured single-rank
+    time of a 125 k-utterance shard at T ~ U{200..400} (cli_job's extraction seconds per utterance) in `predicted_per_rank_job_s`.  The
+    table's LINES, the KEYS and the RECORDS rank 0 gathers and writes are at their real size."""
     import re
     import shutil
     import subprocess
     import tempfile
-    ranks, per_rank, T = int(os.environ.get("XV_BENCH_REHEARSAL_RANKS", "8")), int(os.environ.get("XV_BENCH_REHEARSAL_UTTS", "125000")), 25
+    ranks, per_rank, T = int(os.environ.get("XV_BENCH_REHEARSAL_RANKS", "4")), int(os.environ.get("XV_BENCH_REHEARSAL_UTTS", "250000")), 25
     n = ranks * per_rank
+    node_ranks = 8                                                    # the job rehearsed: configs[3], n utterances over 8 GPUs
     shm_ok = os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK)
     work = tempfile.mkdtemp(prefix="xv_bench_1m_", dir="/dev/shm" if shm_ok else None)
     try:
@@ -466,7 +507,7 @@ def _job_rehearsal_leg(args, model_dir, feat, cli):
             import signal
             os.killpg(job.pid, signal.SIGKILL)
             job.communicate()
-            return {"error": "the 8-rank rehearsal did not finish within 240 s (stopped)"}
+            return {"error": "the %d-rank rehearsal did not finish within 240 s (stopped)" % ranks}
         wall = time.perf_counter() - t0
         log = raw.decode(errors="replace")
         if job.returncode != 0:
@@ -478,10 +519,11 @@ def _job_rehearsal_leg(args, model_dir, feat, cli):
         ark_gb = os.path.getsize(o_ark) / 1e9
     finally:
         shutil.rmtree(work, ignore_errors=True)
-    out = {"ranks": ranks, "utterances": n, "frames_per_utterance": T, "transport": "gloo (8 ranks on ONE device; RCCL over xGMI on the node)",
+    out = {"ranks": ranks, "utterances": n, "frames_per_utterance": T,
+           "transport": "gloo (%d ranks on ONE device; RCCL over xGMI on the node)" % ranks,
            "wall_s": wall, "vectors_written": written, "xvector_ark_gb": ark_gb, "breakdown_s_rank0": parts, "input_made_s": t_make,
-           "note": "8 ranks share this box's GPU and its host cores: model load, probe and extraction run 8-fold contended; lines / keys / "
-                   "records / gathered bytes / written bytes per rank are those of configs[3]"}
+           "note": "%d ranks share this box's GPU and its host cores: model load, probe and extraction run %d-fold contended; the "
+                   "table's lines, the gathered rows and bytes and the records written are those of the whole job" % (ranks, ranks)}
     # What a rank of the real job waits for, piece by piece: the pieces that follow the job's COUNTS (the 1 M-line table, the gathered
     # bytes, the records written) from rank 0 here; the pieces that belong to a rank's own device (runtime, weights + probe, first
     # window, the extraction of 125 k utterances at T ~ U{200..400}) from cli_job's single-rank job on this box, where nothing shares it
@@ -490,7 +532,7 @@ def _job_rehearsal_leg(args, model_dir, feat, cli):
     if parts and ext and cli.get("utterances") and ranks > 1:
         own = {k: cj.get(k, 0.0) for k in ("interpreter + imports", "weights read", "import torch", "hip runtime up",
                                            "weights packed on the device + accuracy probe", "first window launched", "wait for the process group")}
-        own["extraction (125 k utterances at cli_job's rate)"] = ext[0] * per_rank / cli["utterances"]
+        own["extraction (125 k utterances at cli_job's rate)"] = ext[0] * (n / node_ranks) / cli["utterances"]
         counts = {k: parts.get(k, 0.0) for k in ("tables opened", "gather", "write", "rename")}
         out["predicted_breakdown_s"] = {"from_this_rehearsal": counts, "from_cli_job_single_rank": own}
         out["predicted_per_rank_job_s"] = sum(counts.values()) + sum(own.values())
@@ -810,6 +852,16 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
         dist.barrier()                       # the ranks part here: everything below is rank 0's own post-processing
+    if args.dump_outputs and rank == 0:
+        # the x-vectors of the last timed step in utterance order (rank r's block: its seeded set of --utts utterances; the
+        # step ran them in length-sorted order)
+        blocks = []
+        for r, blk in enumerate(last):
+            order_r = np.argsort(synthetic.utterance_lengths(args.utts, args.tmin, args.tmax, 1234 + r), kind="stable")
+            v = np.empty((len(order_r), blk.shape[1]), np.float32)
+            v[order_r] = blk.cpu().numpy()
+            blocks.append(v)
+        _dump_outputs(args.dump_outputs, {"xvectors": np.concatenate(blocks)})
 
     # ---- per-kernel time from the HIP events recorded inside the timed region ------------------
     t_gemm = t_pool = 0.0

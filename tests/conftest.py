@@ -45,7 +45,7 @@ def default_weights():
 # rendezvous must not leave every parity row of SURVEY section 8 "untested".  Within a class the order of collection is kept.
 _FIRST = ("test_gpu_kernels.py", "test_gpu_toom.py", "test_gpu_f16bf8.py", "test_gpu_forward.py", "test_gpu_fuzz.py", "test_gpu_hostile.py",
           "test_gpu_frontend.py", "test_gpu_training.py", "test_gpu_config3.py", "test_gpu_trained_checkpoint.py")
-_LAST = ("test_gpu_two_ranks.py", "test_gpu_eight_ranks.py", "test_gpu_bench_contract.py")
+_LAST = ("test_gpu_two_ranks.py", "test_gpu_four_ranks.py", "test_gpu_bench_contract.py")
 
 
 def pytest_collection_modifyitems(session, config, items):

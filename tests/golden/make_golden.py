@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """Generate the committed golden fixtures in tests/golden/.
 
-Runs ONLY in the build container (it imports the reference's Python from /root/reference, which
-never travels to the GPU box).  Nothing here is copied from the reference: the fixtures are DATA --
+Needs a checkout of the reference project, named by XV_REFERENCE_DIR (it imports the reference's Python from there; the
+reference is not part of this repository).  Nothing here is copied from the reference: the fixtures are DATA --
 bytes the reference's own ``kaldi_io`` writes / arrays it decodes, and the output stream the
 reference's own ``Model.make_embedding`` (local/tf/models.py:356-432) produces, and -- since round 6 -- the values the
 reference's own GRAPH CODE computes: every ``build_model`` of local/tf/models.py (+ tf_block.py) is executed under
@@ -25,7 +25,7 @@ Fixtures
   train_refgraph.npz    the reference's train_one_iteration (3 Adam steps, lr 1e-4; class Model with dropout 0.2 and the
                         masks drawn) and eval on every class: per-step loss / accuracy, step-0 gradients, weights, moving
                         statistics and Adam slots after the steps (small tensors whole, large ones strided)
-Usage:  python tests/golden/make_golden.py
+Usage:  XV_REFERENCE_DIR=<reference checkout> python tests/golden/make_golden.py
 """
 import io
 import os
@@ -37,7 +37,8 @@ import numpy as np
 sys.dont_write_bytecode = True
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = "/root/reference/local/tf"
+REF = os.path.join(os.environ.get("XV_REFERENCE_DIR") or sys.exit("make_golden.py: set XV_REFERENCE_DIR to a checkout of the "
+                                                                     "reference project"), "local", "tf")
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(ROOT, "x-vector-kaldi-tf_amd"))
@@ -452,7 +453,7 @@ def golden_egs_ranges(out):
 
 
 def main():
-    # XV_GOLDEN_OUT: write somewhere else (tests/test_golden_reproducible.py regenerates into a scratch directory and compares)
+    # XV_GOLDEN_OUT: write somewhere else (tools/reference_checks/golden_reproducible.py regenerates into a scratch directory and compares)
     out_dir = os.environ.get("XV_GOLDEN_OUT", HERE)
     ref_io, ref_models, Session = import_reference()
     if sys.argv[1:] == ["schedules"]:            # leaves the other (byte-stable) fixtures untouched

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -19,7 +20,7 @@ def _run(*flags, **env):
 
 def test_extraction_bench_line():
     d = _run("--utts", "600", "--steps", "2", "--warmup", "1", "--cpu-budget", "6", "--parity-utts", "2", "--e2e-utts", "700",
-             XV_BENCH_REHEARSAL_UTTS="1500")                        # (the 8-rank job rehearsal at 8 x 1500 instead of 8 x 125 k utterances)
+             XV_BENCH_REHEARSAL_UTTS="3000")                        # (the job rehearsal at 4 x 3000 instead of 4 x 250 k utterances)
     for k, t in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
                  ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str), ("config", dict)):
         assert isinstance(d[k], t), k
@@ -71,10 +72,10 @@ def test_extraction_bench_line():
     assert j["rccl_gather"]["first_job"]["vectors_written"] == 700 and "RCCL pre-load (ok) joined after" in j["breakdown_s"]
     assert j["rccl_without_prewarm"]["transport"] == "nccl" and not any("pre-load" in k for k in j["rccl_without_prewarm"]["breakdown_s"])
     assert j["gloo_gather"]["transport"] == "gloo" and j["gloo_gather"]["vectors_written"] == 700
-    # BASELINE configs[3] rehearsed at 8 ranks on this one GPU (scp line ranges, ONE gather, rank 0 writes every record), with the node's
+    # BASELINE configs[3] rehearsed at 4 ranks on this one GPU (scp line ranges, ONE gather, rank 0 writes every record), with the node's
     # per-rank job predicted piece by piece from it and from the single-rank job above
     h = j["rehearsal_8x125k"]
-    assert h["ranks"] == 8 and h["utterances"] == 12000 == h["vectors_written"] and h["breakdown_s_rank0"]["gather"] >= 0
+    assert h["ranks"] == 4 and h["utterances"] == 12000 == h["vectors_written"] and h["breakdown_s_rank0"]["gather"] >= 0
     assert set(h["predicted_breakdown_s"]["from_this_rehearsal"]) == {"tables opened", "gather", "write", "rename"}
     assert 0 < h["predicted_per_rank_job_s"] < 60 and h["predicted_8gpu_utt_per_s"] == pytest.approx(12000 / h["predicted_per_rank_job_s"])
     assert r["same_arithmetic"]["cli_job"]["rehearsal_8x125k"]["predicted_per_rank_job_s"] == pytest.approx(h["predicted_per_rank_job_s"], abs=1e-3)
@@ -85,6 +86,19 @@ def test_extraction_bench_line():
     assert sa["train_step_ms"]["bf16x3"] == pytest.approx(t["ms_per_step"], rel=1e-3) and sa["cli_job"]["transport"] == "nccl"
     assert 0 < d["fp32_toomcook"]["frac"] < 1 and d["fp32_toomcook"]["frac"] == d["fp32_toomcook"]["executed_frac"]
     assert "no exchange at N = 1" in d["config"]["parallelism"]
+
+
+def test_dump_outputs_holds_the_last_step_and_repeats(tmp_path):
+    """--dump-outputs: the x-vectors of the timed path's last step, one row per utterance in utterance order, and the same
+    arguments give the same inputs -- two runs (with different step counts) write the same vectors."""
+    flags = ["--utts", "600", "--warmup", "1", "--cpu-budget", "0", "--e2e-utts", "0", "--no-fp32-leg", "--no-extra-legs"]
+    a = _run(*(flags + ["--steps", "3", "--dump-outputs", str(tmp_path / "a")]))
+    b = _run(*(flags + ["--steps", "1", "--dump-outputs", str(tmp_path / "b")]))
+    assert a["steps"] == 3 and b["steps"] == 1 and a["ms_per_step"] > 0 and b["ms_per_step"] > 0
+    assert os.listdir(str(tmp_path / "a")) == ["xvectors.npy"]
+    va, vb = np.load(str(tmp_path / "a" / "xvectors.npy")), np.load(str(tmp_path / "b" / "xvectors.npy"))
+    assert va.dtype == np.float32 and va.shape == (600, 512) and np.isfinite(va).all() and (np.linalg.norm(va, axis=1) > 0).all()
+    assert np.linalg.norm(va - vb) <= 1e-6 * np.linalg.norm(va)
 
 
 def test_two_ranks_through_the_self_launcher_on_one_gpu():

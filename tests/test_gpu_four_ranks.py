@@ -1,9 +1,9 @@
-"""EIGHT ranks of the real extractor / bench / trainer on the ONE GPU a test box has ("Next round" 5a): a rehearsal of
+"""FOUR ranks of the real extractor / bench / trainer on the ONE GPU a test box has ("Next round" 5a): a rehearsal of
 the 8-GPU node's jobs (BASELINE configs[3], [4]; the reference's mechanism is nj jobs + `cat xvector.*.scp`, extract_xvectors.sh:63-95)
 in the share-GPU mode of tests/test_gpu_two_ranks.py -- gloo transport (RCCL refuses two ranks on one device), everything else as
-on the node: the launcher at 8 processes, the side-thread group bring-up, scp line-range and ark byte-range sharding into 8 parts,
-ONE gather of 8 blocks, rank 0's writes, the bench's max-over-ranks timing.  So that the driver's first real 8-GPU run is not the
-first time eight ranks of this code meet."""
+on the node: the launcher at several processes, the side-thread group bring-up, scp line-range and ark byte-range sharding into
+RANKS parts, ONE gather of RANKS blocks, rank 0's writes, the bench's max-over-ranks timing.  RANKS is 4 and not the node's 8: the
+ranks share the device with this test process, and no more than six processes may hold one GPU at a time."""
 import io
 import json
 import os
@@ -17,6 +17,7 @@ from conftest import PKG, TWIN
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RANKS = 4
 
 
 def _clean_env(**extra):
@@ -26,35 +27,35 @@ def _clean_env(**extra):
     return env
 
 
-def test_bench_at_eight_ranks_prints_one_line():
-    """`python bench.py --gpus 8`, the driver's command form for SCALE_rNN.json."""
+def test_bench_at_four_ranks_prints_one_line():
+    """`python bench.py --gpus N`, the driver's command form for SCALE_rNN.json."""
     env = _clean_env(XV_BENCH_SHARE_GPU="1", XVECTOR_DIST_BACKEND="gloo")
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--utts", "400", "--steps", "2", "--warmup", "1",
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(RANKS), "--utts", "400", "--steps", "2", "--warmup", "1",
                           "--cpu-budget", "4", "--parity-utts", "4", "--e2e-utts", "0"], cwd=ROOT, env=env, stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, timeout=900)
     assert run.returncode == 0, run.stderr.decode()[-3000:]
     out = run.stdout.decode().strip().splitlines()
     assert len(out) == 1, out
     d = json.loads(out[0])
-    assert d["n_gpus"] == 8 and d["rccl_ranks"] == 8 and d["gather_ms"] > 0 and d["scaling"] == "weak"
-    assert abs(d["value"] - 8 * 400 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]           # whole-job aggregate over all ranks
+    assert d["n_gpus"] == RANKS and d["rccl_ranks"] == RANKS and d["gather_ms"] > 0 and d["scaling"] == "weak"
+    assert abs(d["value"] - RANKS * 400 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]           # whole-job aggregate over all ranks
     assert d["parity_rel_l2_max_vs_fp64_oracle"] < 1e-4
-    assert d["with_ark_write"]["ark_mb"] > 8 * 400 * 2000 / 1e6                                # every rank's vectors reached rank 0
+    assert d["with_ark_write"]["ark_mb"] > RANKS * 400 * 2000 / 1e6                                # every rank's vectors reached rank 0
     assert "cpu_baseline" not in d
 
 
-def test_training_bench_at_eight_ranks():
+def test_training_bench_at_four_ranks():
     env = _clean_env(XV_BENCH_SHARE_GPU="1", XVECTOR_DIST_BACKEND="gloo")
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "train", "--gpus", "8", "--steps", "2", "--warmup", "1"],
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "train", "--gpus", str(RANKS), "--steps", "2", "--warmup", "1"],
                          cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert run.returncode == 0, run.stderr.decode()[-3000:]
     out = run.stdout.decode().strip().splitlines()
     assert len(out) == 1, out
     d = json.loads(out[0])
-    assert d["n_gpus"] == 8 and d["unit"] == "chunks/s" and "x8" in d["config"]["parallelism"] and d["last_loss"] == d["last_loss"]
+    assert d["n_gpus"] == RANKS and d["unit"] == "chunks/s" and ("x%d" % RANKS) in d["config"]["parallelism"] and d["last_loss"] == d["last_loss"]
 
 
-def test_eight_rank_cli_jobs_write_the_single_process_bytes(tmp_path, oracle_mod):
+def test_four_rank_cli_jobs_write_the_single_process_bytes(tmp_path, oracle_mod):
     import kaldi_io
     import models
     from xvector_amd import hiplib, synthetic, topology
@@ -64,7 +65,7 @@ def test_eight_rank_cli_jobs_write_the_single_process_bytes(tmp_path, oracle_mod
     mdir = str(tmp_path / "nnet")
     models.Model.save_model(dict(weights=w, topology=topo, model_class="ModelWithoutDropout", num_classes=64, feat_dim=23), mdir, None)
     rng = np.random.default_rng(6)
-    n = 2005                                                          # not a multiple of 8
+    n = 2005                                                          # not a multiple of RANKS
     lens = rng.integers(40, 400, size=n)
     lens[::89] = 11                                                   # rejected: shorter than min_chunk_size
     pool = [(rng.standard_normal((400, 23)) * 3.0).astype(np.float32) for _ in range(53)]
@@ -88,18 +89,18 @@ def test_eight_rank_cli_jobs_write_the_single_process_bytes(tmp_path, oracle_mod
     one_ark, one_scp, _ = job("one", 1, "scp:" + scp)
     one_bytes, one_lines = open(one_ark, "rb").read(), open(one_scp).read().replace(one_ark, "ARK")
     assert len(one_lines.splitlines()) == int((lens >= 25).sum())
-    for tag, rspec in (("scp8", "scp:" + scp), ("ark8", "ark:" + ark)):            # line-range / byte-range sharding into 8 parts
-        a, s, log = job(tag, 8, rspec)
+    for tag, rspec in (("scpN", "scp:" + scp), ("arkN", "ark:" + ark)):            # line-range / byte-range sharding into RANKS parts
+        a, s, log = job(tag, RANKS, rspec)
         assert open(a, "rb").read() == one_bytes and open(s).read().replace(a, "ARK") == one_lines, tag
         assert "Job wall clock:" in log
-        if tag == "ark8":
-            assert all(("rank %d of 8: records " % r) in log for r in range(8)), log[-2000:]
-    # the reference's own output protocol at 8 ranks: one ark per rank + a concatenated scp, no process group
-    fa, fs, _ = job("files8", 8, "scp:" + scp, dict(base, XVECTOR_SHARD_OUTPUT="files"))
+        if tag == "arkN":
+            assert all(("rank %d of %d: records " % (r, RANKS)) in log for r in range(RANKS)), log[-2000:]
+    # the reference's own output protocol at RANKS ranks: one ark per rank + a concatenated scp, no process group
+    fa, fs, _ = job("filesN", RANKS, "scp:" + scp, dict(base, XVECTOR_SHARD_OUTPUT="files"))
     want = list(kaldi_io.read_vec_flt_ark(io.BytesIO(one_bytes)))
     got = list(kaldi_io.read_vec_flt_scp(fs))
     assert [k for k, _ in got] == [k for k, _ in want] and all(np.array_equal(x, y) for (_, x), (_, y) in zip(got, want))
-    assert all(os.path.exists("%s.%d" % (fa, r)) for r in range(8)) and not [f for f in os.listdir(str(tmp_path)) if f.endswith(".part")]
+    assert all(os.path.exists("%s.%d" % (fa, r)) for r in range(RANKS)) and not [f for f in os.listdir(str(tmp_path)) if f.endswith(".part")]
     vec = dict(want)
     for i in (0, n // 3, n - 1):
         if lens[i] >= 25:

@@ -1,6 +1,10 @@
 """The committed fixtures in tests/golden/ are what tests/golden/make_golden.py produces from the reference's own Python
-TODAY: when /root/reference is mounted (the build container; never the GPU box) the generator is re-run into a scratch
-directory and every array of every fixture must come out bit for bit.  This is what "pinned against the reference" means
+TODAY: the generator is re-run into a scratch directory and every array of every fixture must come out bit for bit.  It needs a
+checkout of the reference project, named by XV_REFERENCE_DIR, so it is not part of the suite under tests/:
+
+    XV_REFERENCE_DIR=<reference checkout> python -m pytest tools/reference_checks/golden_reproducible.py
+
+  This is what "pinned against the reference" means
 for the rows DESIGN.md section 5 lists as reference-pinned (control flow of make_embedding, ark framing, schedules, the egs
 loader) -- and, since round 6, for the arithmetic: forward_refgraph.npz / train_refgraph.npz are what the reference's own graphs and
 training loop compute when executed under tests/golden/numpy_tf1.py.  Byte fixtures must come out bit for bit; the float64 arrays of the
@@ -12,12 +16,12 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import ROOT
-
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/local/tf"), reason="the reference tree is only mounted in the build container")
+@pytest.mark.skipif(not os.environ.get("XV_REFERENCE_DIR") or not os.path.isdir(os.path.join(os.environ["XV_REFERENCE_DIR"], "local", "tf")),
+                    reason="XV_REFERENCE_DIR does not name a checkout of the reference project")
 def test_committed_fixtures_reproduce_bit_for_bit(tmp_path):
     env = dict(os.environ, XV_GOLDEN_OUT=str(tmp_path), PYTHONDONTWRITEBYTECODE="1")
     run = subprocess.run([sys.executable, os.path.join(GOLDEN, "make_golden.py")], env=env, stdout=subprocess.PIPE,

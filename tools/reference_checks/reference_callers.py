@@ -1,8 +1,12 @@
-"""The reference's OWN caller scripts driving this build's twins (CPU only, runs only where /root/reference is mounted).
+"""The reference's OWN caller scripts driving this build's twins (CPU only; needs a checkout of the reference project, named by
+XV_REFERENCE_DIR -- not part of the suite under tests/, since the reference's sources are not in this repository):
+
+    XV_REFERENCE_DIR=<reference checkout> python -m pytest tools/reference_checks/reference_callers.py
+
 
 The drop-in claim of SURVEY §8b is that ``local/tf/models.py`` + ``kaldi_io.py`` can be swapped under the reference's
 unchanged callers.  Here the reference's ``train_dnn_one_iteration.py`` (with its ``examples_io.TarFileDataLoader``) and
-``extract_embedding.py`` are imported from /root/reference and run against this build's ``models`` / ``kaldi_io`` modules;
+``extract_embedding.py`` are imported from the reference checkout and run against this build's ``models`` / ``kaldi_io`` modules;
 the GPU work is replaced by recording fakes (training) or the CPU oracle (extraction), so what is pinned is the
 interface: constructor, method names, argument order, ``args`` fields, the data-loader protocol, stream types, the
 model-directory contract and the log lines the reference's own parser (ze_utils.get_successful_models) reads.
@@ -19,12 +23,19 @@ import types
 import numpy as np
 import pytest
 
-REF = "/root/reference/local/tf"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted (GPU box)")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+PKG = os.path.join(ROOT, "x-vector-kaldi-tf_amd")
+TWIN = os.path.join(PKG, "local", "tf")
+for _p in (ROOT, PKG, TWIN):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+REF = os.path.join(os.environ.get("XV_REFERENCE_DIR", ""), "local", "tf")
+pytestmark = pytest.mark.skipif(not os.environ.get("XV_REFERENCE_DIR") or not os.path.isdir(REF),
+                                reason="XV_REFERENCE_DIR does not name a checkout of the reference project")
 
 
 def _load_ref(name, shims):
-    """Import /root/reference/local/tf/<name>.py as module ``name`` with ``shims`` pre-installed in sys.modules."""
+    """Import <reference>/local/tf/<name>.py as module ``name`` with ``shims`` pre-installed in sys.modules."""
     for k, v in shims.items():
         sys.modules[k] = v
     spec = importlib.util.spec_from_file_location(name, os.path.join(REF, name + ".py"))
@@ -38,7 +49,7 @@ def _load_ref(name, shims):
 def ref_env(monkeypatch):
     """sys.modules arranged as in a reference checkout whose models.py / kaldi_io.py were replaced by this build's."""
     import _thread
-    import kaldi_io      # this build's (tests/conftest.py put local/tf on sys.path)
+    import kaldi_io      # this build's (local/tf is on sys.path, above)
     import models        # this build's
     saved = {k: sys.modules.get(k) for k in ("ze_utils", "examples_io", "train_dnn_one_iteration", "extract_embedding", "thread",
                                              "h5py", "mkl", "numexpr")}
@@ -166,7 +177,7 @@ def test_eval_logs_parse_with_the_reference_accuracy_report(ref_env, tmp_path, m
         (tmp_path / "log" / ("train.%d.%d.log" % (it, job))).write_text(
             "2026-01-01 00:00:00,000 [x.py:1 - f - INFO ] Overall average objective function is -0.5 over 9 segments.\n"
             "# Accounting: time=%d threads=1\n" % sec)
-    from conftest import TWIN                   # sys.modules["ze_utils"] is the reference's here: load the twin by path
+    # (sys.modules["ze_utils"] is the reference's here: load the twin by path)
     spec = importlib.util.spec_from_file_location("ze_utils_twin", os.path.join(TWIN, "ze_utils.py"))
     twin = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(twin)
@@ -180,8 +191,7 @@ def test_eval_logs_parse_with_the_reference_accuracy_report(ref_env, tmp_path, m
 def test_egs_archives_interchange_with_the_reference_loader(ref_env, tmp_path):
     """An archive written by this build's examples_io.write_egs_tar is read by the reference's TarFileDataLoader
     (examples_io.py:223-255) exactly as by this build's loader."""
-    here = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "x-vector-kaldi-tf_amd", "local", "tf")
-    spec = importlib.util.spec_from_file_location("twin_examples_io", os.path.join(here, "examples_io.py"))
+    spec = importlib.util.spec_from_file_location("twin_examples_io", os.path.join(TWIN, "examples_io.py"))
     twin = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(twin)
     rng = np.random.default_rng(3)
