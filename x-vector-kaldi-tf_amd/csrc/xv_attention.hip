@@ -13,33 +13,9 @@
 //
 // Numerics: products and sums of the weighted moments are carried in fp64 (the vector fp64 rate equals the fp32 rate on
 // CDNA4 and the kernel is HBM-bound), so q = S2 - m^2 has no cancellation problem; q is clamped at 0.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-
-#include "xvector_hip.h"
-
-extern "C" void xv_internal_set_error(const char *msg);
+#include "xv_device.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-int att_fail(int code, const char *msg)
-{
-    xv_internal_set_error(msg);
-    return code;
-}
-
-int att_check(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    char buf[256];
-    snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-    xv_internal_set_error(buf);
-    return (int)e;
-}
 
 __device__ __forceinline__ double wave_sum(double x)
 {
@@ -338,21 +314,21 @@ int xv_attention_scores_f32(const float *u, int64_t ldu, int64_t R, int c, const
 {
     if (R <= 0) return 0;
     if (!u || !v || !scores || c <= 0 || (c & 3) || (ldu & 3) || ldu < c || (((uintptr_t)u) & 15) || (((uintptr_t)v) & 15))
-        return att_fail(XV_ERR_BAD_ARG, "attention_scores: C, ldu must be multiples of 4 and u/v 16-byte aligned");
+        return fail(XV_ERR_BAD_ARG, "attention_scores: C, ldu must be multiples of 4 and u/v 16-byte aligned");
     if (nonlin && ((ldn & 3) || ldn < c || (((uintptr_t)nonlin) & 15)))
-        return att_fail(XV_ERR_BAD_ARG, "attention_scores: bad nonlin buffer");
+        return fail(XV_ERR_BAD_ARG, "attention_scores: bad nonlin buffer");
     hipLaunchKernelGGL(attention_scores_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream, u, (long)ldu,
                        (long)R, c, v, scores, nonlin, (long)ldn);
-    return att_check("attention_scores_kernel");
+    return launch_status("attention_scores_kernel");
 }
 
 int xv_attention_softmax_f32(const float *scores, const int32_t *row_start, const int32_t *row_len, int nchunks, float *att,
                              void *stream)
 {
     if (nchunks <= 0) return 0;
-    if (!scores || !row_start || !row_len || !att) return att_fail(XV_ERR_BAD_ARG, "attention_softmax: NULL pointer");
+    if (!scores || !row_start || !row_len || !att) return fail(XV_ERR_BAD_ARG, "attention_softmax: NULL pointer");
     hipLaunchKernelGGL(attention_softmax_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, scores, row_start, row_len, att);
-    return att_check("attention_softmax_kernel");
+    return launch_status("attention_softmax_kernel");
 }
 
 size_t xv_attention_pool_workspace_bytes(int c, int nchunks, int max_len, int split_rows)
@@ -366,26 +342,26 @@ int xv_attention_pool_f32(const float *h, int64_t ldh, int c, const float *att, 
                           int nchunks, int max_len, int split_rows, float eps, float *out, void *workspace, void *stream)
 {
     if (nchunks <= 0) return 0;
-    if (!h || !att || !row_start || !row_len || !out) return att_fail(XV_ERR_BAD_ARG, "attention_pool: NULL pointer");
+    if (!h || !att || !row_start || !row_len || !out) return fail(XV_ERR_BAD_ARG, "attention_pool: NULL pointer");
     if (c <= 0 || (c & 3) || (ldh & 3) || ldh < c || (((uintptr_t)h) & 15) || (((uintptr_t)out) & 15))
-        return att_fail(XV_ERR_BAD_ARG, "attention_pool: C, ldh must be multiples of 4 and h/out 16-byte aligned");
-    if (split_rows <= 0 || max_len <= 0) return att_fail(XV_ERR_BAD_ARG, "attention_pool: split_rows/max_len must be > 0");
+        return fail(XV_ERR_BAD_ARG, "attention_pool: C, ldh must be multiples of 4 and h/out 16-byte aligned");
+    if (split_rows <= 0 || max_len <= 0) return fail(XV_ERR_BAD_ARG, "attention_pool: split_rows/max_len must be > 0");
     const int max_splits = (max_len + split_rows - 1) / split_rows;
     if (max_splits > 1 && (!workspace || (((uintptr_t)workspace) & 7)))
-        return att_fail(XV_ERR_BAD_ARG, "attention_pool: 8-byte aligned workspace required for split chunks");
-    if (max_splits > 65535) return att_fail(XV_ERR_UNSUPPORTED, "attention_pool: too many splits");
+        return fail(XV_ERR_BAD_ARG, "attention_pool: 8-byte aligned workspace required for split chunks");
+    if (max_splits > 65535) return fail(XV_ERR_UNSUPPORTED, "attention_pool: too many splits");
     hipStream_t st = (hipStream_t)stream;
     for (int b0 = 0; b0 < nchunks; b0 += 65535) {              // grid.z <= 65535
         const int nb = nchunks - b0 < 65535 ? nchunks - b0 : 65535;
         double *ws = (double *)workspace + (size_t)b0 * max_splits * 2 * c;
         hipLaunchKernelGGL(attention_pool_kernel, dim3((c + 255) / 256, max_splits, nb), dim3(256), 0, st, h, (long)ldh, c, att,
                            row_start + b0, row_len + b0, split_rows, max_splits, eps, out + (size_t)b0 * 2 * c, ws);
-        int rc = att_check("attention_pool_kernel");
+        int rc = launch_status("attention_pool_kernel");
         if (rc) return rc;
         if (max_splits > 1) {
             hipLaunchKernelGGL(attention_pool_merge_kernel, dim3((c + 255) / 256, nb), dim3(256), 0, st, ws, c, row_len + b0,
                                split_rows, max_splits, eps, out + (size_t)b0 * 2 * c);
-            rc = att_check("attention_pool_merge_kernel");
+            rc = launch_status("attention_pool_merge_kernel");
             if (rc) return rc;
         }
     }
@@ -398,11 +374,11 @@ int xv_attention_pool_backward_f32(const float *h, int64_t ldh, int c, const flo
 {
     if (nchunks <= 0 || max_len <= 0) return 0;
     if (!h || !att || !row_start || !row_len || !pooled || !dpooled || !dh || !datt)
-        return att_fail(XV_ERR_BAD_ARG, "attention_pool_backward: NULL pointer");
+        return fail(XV_ERR_BAD_ARG, "attention_pool_backward: NULL pointer");
     if (c <= 0 || (c & 3) || (ldh & 3) || (lddh & 3) || ldh < c || lddh < c || (((uintptr_t)h) & 15) || (((uintptr_t)dh) & 15) ||
         (((uintptr_t)pooled) & 15) || (((uintptr_t)dpooled) & 15))
-        return att_fail(XV_ERR_BAD_ARG, "attention_pool_backward: C, ld must be multiples of 4 and buffers 16-byte aligned");
-    if (c > 8192) return att_fail(XV_ERR_UNSUPPORTED, "attention_pool_backward: more than 8192 channels");      // 64 KB of LDS
+        return fail(XV_ERR_BAD_ARG, "attention_pool_backward: C, ld must be multiples of 4 and buffers 16-byte aligned");
+    if (c > 8192) return fail(XV_ERR_UNSUPPORTED, "attention_pool_backward: more than 8192 channels");      // 64 KB of LDS
     hipStream_t st = (hipStream_t)stream;
     for (int b0 = 0; b0 < nchunks; b0 += 65535) {
         const int nb = nchunks - b0 < 65535 ? nchunks - b0 : 65535;
@@ -410,7 +386,7 @@ int xv_attention_pool_backward_f32(const float *h, int64_t ldh, int c, const flo
                            2 * (size_t)c * sizeof(float), st, h, (long)ldh, c, att,
                            row_start + b0, row_len + b0, pooled + (size_t)b0 * 2 * c, dpooled + (size_t)b0 * 2 * c, dh, (long)lddh,
                            datt);
-        int rc = att_check("attention_pool_backward_kernel");
+        int rc = launch_status("attention_pool_backward_kernel");
         if (rc) return rc;
     }
     return 0;
@@ -420,10 +396,10 @@ int xv_attention_softmax_backward_f32(const float *att, const float *datt, const
                                       int nchunks, float *dscores, void *stream)
 {
     if (nchunks <= 0) return 0;
-    if (!att || !datt || !row_start || !row_len || !dscores) return att_fail(XV_ERR_BAD_ARG, "attention_softmax_backward: NULL pointer");
+    if (!att || !datt || !row_start || !row_len || !dscores) return fail(XV_ERR_BAD_ARG, "attention_softmax_backward: NULL pointer");
     hipLaunchKernelGGL(attention_softmax_backward_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, att, datt, row_start,
                        row_len, dscores);
-    return att_check("attention_softmax_backward_kernel");
+    return launch_status("attention_softmax_backward_kernel");
 }
 
 int xv_attention_scores_backward_f32(float *nonlin, int64_t ldn, const float *dscores, const float *v, int64_t R, int c, float *du,
@@ -432,10 +408,10 @@ int xv_attention_scores_backward_f32(float *nonlin, int64_t ldn, const float *ds
     if (R <= 0) return 0;
     if (!nonlin || !dscores || !v || !du || c <= 0 || (c & 3) || (ldn & 3) || (lddu & 3) || ldn < c || lddu < c ||
         (((uintptr_t)nonlin) & 15) || (((uintptr_t)du) & 15) || (((uintptr_t)v) & 15))
-        return att_fail(XV_ERR_BAD_ARG, "attention_scores_backward: C, ld must be multiples of 4 and buffers 16-byte aligned");
+        return fail(XV_ERR_BAD_ARG, "attention_scores_backward: C, ld must be multiples of 4 and buffers 16-byte aligned");
     hipLaunchKernelGGL(attention_scores_backward_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream, nonlin,
                        (long)ldn, dscores, v, (long)R, c, du, (long)lddu);
-    return att_check("attention_scores_backward_kernel");
+    return launch_status("attention_scores_backward_kernel");
 }
 
 }  // extern "C"

@@ -22,31 +22,12 @@
 //     whole chip's stores to the same few memory channels: the workgroups start at different passes and the waves of a workgroup
 //     at different tile pairs (measured: 0.184 -> 0.156 ms).
 // Arithmetic: bf16x3 as everywhere (hi*hi + hi*lo + lo*hi, fp32 accumulate).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-
-#include <atomic>
-#include <type_traits>
-
-#include "xvector_hip.h"
+#include "xv_device.h"
 #include "xv_split8.h"
-
-extern "C" void xv_internal_set_error(const char *msg);
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
 std::atomic<int> g_first_tiles{0};        // xv_internal_first_tiles(): tiles per wave, 0 = spread over the CUs
-
-int fail(int code, const char *msg)
-{
-    xv_internal_set_error(msg);
-    return code;
-}
 
 constexpr int FR_WAVES = 8;                // one workgroup per CU, two waves per SIMD: 256 VGPRs each
 constexpr int FR_TILES = 3;                // 16-frame tiles a wave works on at a time: a tile pair's weights and parameters are read once for the three
@@ -76,12 +57,9 @@ struct FirstParams {
     int *status;               // Y8: bit 0 set when a value had to be clamped (may be NULL)
 };
 
-#define XV_GLDS16_OFF(gptr, lptr, imm)                                                                          \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr),                    \
-                                     (__attribute__((address_space(3))) void *)(lptr), 16, imm, 0)
-
+// act_fn of the pair kernels (xv_device.h) but for its ReLU, which is one integer max here
 template <int MODE>
-__device__ __forceinline__ float act_fn(float z, float a)
+__device__ __forceinline__ float first_act(float z, float a)
 {
     // relu as ONE instruction: fmaxf() first canonicalises an MFMA result (v_max z, z); the signed-integer maximum of the bit pattern
     // with 0 is the same function (negative floats are negative integers; -0 and negative NaNs become +0).  (Not inline assembly:
@@ -104,8 +82,6 @@ __device__ __forceinline__ float sub_f16_half(float c, int hpair)
 }
 
 constexpr int FR_STORE_AUX = 2;                        // nt
-
-constexpr int FR_RSRC_FLAGS = 0x00020000;            // raw buffer, 32-bit data format (gfx9 family dword 3)
 
 // One tile pair (32 output channels) of NT 16-frame tiles: 24 MFMAs per tile, then activation / BN / gap-row mask / split encoding
 // and two 16-byte stores per lane, without a branch (rows past the end are dropped by the buffer descriptor's range check).
@@ -139,8 +115,8 @@ __device__ __forceinline__ void first_block(const bf16x8 (&xh)[FR_TILES][FR_NKS]
         float v[8];
 #pragma unroll
         for (int e = 0; e < 4; e += 2) {                          // activation, then BN as packed FMAs
-            const f32x2 r0 = {act_fn<MODE>(z0[e], a0[e]), act_fn<MODE>(z0[e + 1], a0[e + 1])};
-            const f32x2 r1 = {act_fn<MODE>(z1[e], a1[e]), act_fn<MODE>(z1[e + 1], a1[e + 1])};
+            const f32x2 r0 = {first_act<MODE>(z0[e], a0[e]), first_act<MODE>(z0[e + 1], a0[e + 1])};
+            const f32x2 r1 = {first_act<MODE>(z1[e], a1[e]), first_act<MODE>(z1[e + 1], a1[e + 1])};
             const f32x2 y0 = __builtin_elementwise_fma(r0, (f32x2){s0[e], s0[e + 1]}, (f32x2){o0[e], o0[e + 1]});
             const f32x2 y1 = __builtin_elementwise_fma(r1, (f32x2){s1[e], s1[e + 1]}, (f32x2){o1[e], o1[e + 1]});
             v[e] = y0[0]; v[e + 1] = y0[1]; v[4 + e] = y1[0]; v[5 + e] = y1[1];
@@ -223,7 +199,7 @@ __global__ __launch_bounds__(FR_WAVES * 64) void tdnn_first_kernel(const FirstPa
     const int n_groups = (p.tpw + FR_TILES - 1) / FR_TILES;
     const int steps = n_groups * n_pass;                         // a step = one pass of one group of tiles; the same for every wave
     const unsigned yrow = (unsigned)p.ychunks * SROW;
-    const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(p.y + (size_t)p.row_base * yrow, 0, (int)(unsigned)(p.rows_here * yrow), FR_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(p.y + (size_t)p.row_base * yrow, 0, (int)(unsigned)(p.rows_here * yrow), XV_RSRC_FLAGS);
 
     // weights of pass `ps` -> buffer `buf`: n_pairs * 2 tiles * 4 k-steps * 2 KB of lane-linear fragments, 1 KB DMA pieces
     auto fetch_weights = [&](int ps, int buf) {
@@ -417,9 +393,7 @@ int xv_pack_first_bf16x3(const float *w, int K, int cin, int cout, void *wt, voi
     const size_t total = xv_packed_first_bf16x3_bytes(K, cin, cout) / 4;
     hipLaunchKernelGGL(pack_first_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, K, cin,
                        (cin + 7) / 8 * 8, cout, (uint8_t *)wt, total);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
-    return 0;
+    return launch_status();
 }
 
 static int first_launch(const float *x, int64_t R, int cin, int ldx, const void *wt, const float *bias, const float *bn_scale,
@@ -443,22 +417,16 @@ static int first_launch(const float *x, int64_t R, int cin, int ldx, const void 
     typedef void (*kern_t)(const FirstParams);
     const kern_t kerns[6] = {tdnn_first_kernel<0, false>, tdnn_first_kernel<1, false>, tdnn_first_kernel<2, false>,
                              tdnn_first_kernel<0, true>,  tdnn_first_kernel<1, true>,  tdnn_first_kernel<2, true>};
-    static std::atomic<unsigned long long> attr_done{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!((attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-        for (kern_t k : kerns) {
-            hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FR_LDS_BYTES);
-            if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
-        }
-        attr_done.fetch_or(1ull << (dev & 63), std::memory_order_release);
-    }
+    static std::atomic<unsigned long long> lds_done{0};
+    if (const int rc = opt_in_dynamic_lds(lds_done, kerns, FR_LDS_BYTES)) return rc;
     const int mode = act_kind == XV_ACT_LRELU ? 1 : act_kind == XV_ACT_RELU ? 2 : 0;
     // one workgroup per CU, each wave a contiguous run of 16-frame tiles (at least one): the weights cycle through LDS once per
     // FR_TILES tiles of every wave, and nobody ends a round early
     static std::atomic<int> n_cu{0};
     int cus = n_cu.load(std::memory_order_relaxed);
     if (cus <= 0) {
+        int dev = 0;
+        (void)hipGetDevice(&dev);
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
         n_cu.store(cus, std::memory_order_relaxed);
     }
@@ -474,9 +442,7 @@ static int first_launch(const float *x, int64_t R, int cin, int ldx, const void 
         hipLaunchKernelGGL(kerns[mode + (y8 ? 3 : 0)], dim3((unsigned)((p.n_tiles + per_wg - 1) / per_wg)), dim3(FR_WAVES * 64), FR_LDS_BYTES,
                            (hipStream_t)stream, p);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
-    return 0;
+    return launch_status();
 }
 
 int xv_tdnn_first_bf16x3(const float *x, int64_t R, int cin, int ldx, const void *wt, const float *bias, const float *bn_scale,

@@ -15,13 +15,7 @@
 // HBM-bound, tiny next to the network (92 B/frame in, 96 B/frame out): one 32-lane group per (utterance, 64-frame
 // segment) slides a double-precision window sum over its segment (window/64 + 2 reads per frame, all L2 hits), lanes =
 // feature dimensions so a row is one coalesced 96-B access.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-
-#include "xvector_hip.h"
-
-extern "C" void xv_internal_set_error(const char *msg);
+#include "xv_device.h"
 
 namespace {
 
@@ -75,22 +69,14 @@ extern "C" int xv_cmn_sliding_scatter_f32(const float *x, int ldx, int feat_dim,
 {
     if (n_utts <= 0 || max_len <= 0) return 0;
     if (!x || !utt_start || !utt_len || !dst_row || !y || feat_dim <= 0 || ldx < feat_dim || ldy < feat_dim || cmn_window <= 0 ||
-        min_window <= 0) {
-        xv_internal_set_error("cmn_sliding_scatter: bad argument");
-        return XV_ERR_BAD_ARG;
-    }
+        min_window <= 0)
+        return fail(XV_ERR_BAD_ARG, "cmn_sliding_scatter: bad argument");
     const int gx = (max_len + SEG * GROUPS - 1) / (SEG * GROUPS);
     for (int u0 = 0; u0 < n_utts; u0 += 65535) {
         const int nu = n_utts - u0 < 65535 ? n_utts - u0 : 65535;
         hipLaunchKernelGGL(cmn_sliding_scatter_kernel, dim3(gx, nu), dim3(256), 0, (hipStream_t)stream, x, ldx, feat_dim,
                            utt_start + u0, utt_len + u0, cmn_window, center, min_window, dst_row, y, ldy);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            char buf[256];
-            snprintf(buf, sizeof(buf), "cmn_sliding_scatter_kernel: %s", hipGetErrorString(e));
-            xv_internal_set_error(buf);
-            return (int)e;
-        }
+        if (const int rc = launch_status("cmn_sliding_scatter_kernel")) return rc;
     }
     return 0;
 }

@@ -13,38 +13,12 @@
 //     phase 2:  4 scaled 8-bit MFMAs (32x32x64) on set G | DMA of stage s+2 | 8 ds_read_b128: set F = fp16 fragments of stage s+1
 // 8-bit fragment of lane (row = lane & 31, half = lane >> 5): slots 4+2*half and 5+2*half of the row-slab = channels
 // 16*half .. 16*half+15 as [8 x l8 | 8 x h8] twice -- and the weight tile holds [8 x h8 | 8 x l8] at the same positions.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-
-#include <atomic>
 #include <cstdlib>
-#include <type_traits>
 
-#include "xvector_hip.h"
+#include "xv_device.h"
 #include "xv_split8.h"
 
-extern "C" void xv_internal_set_error(const char *msg);
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
-
-int fail(int code, const char *msg)
-{
-    xv_internal_set_error(msg);
-    return code;
-}
-
-int hip_fail(hipError_t e, const char *where)
-{
-    char buf[256];
-    snprintf(buf, sizeof(buf), "%s: %s", where, hipGetErrorString(e));
-    xv_internal_set_error(buf);
-    return (int)e;
-}
 
 constexpr int BN = 128;                 // output channels per workgroup tile
 constexpr int BK = 32;                  // input channels per stage
@@ -96,13 +70,6 @@ struct Gemm8Params {
     int colmap;           // wide16, two column tiles: 1 = XCDs 0-3 work on column tile 0, XCDs 4-7 on tile 1 (XV_TUNE_XCD_COLUMNS)
 };
 
-#define XV_GLDS16_OFF(gptr, lptr, imm)                                                                          \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr),                    \
-                                     (__attribute__((address_space(3))) void *)(lptr), 16, imm, 0)
-#define XV_GLDS16(gptr, lptr) XV_GLDS16_OFF(gptr, lptr, 0)
-// MUBUF form: 16 bytes per lane from buffer rsrc at voff (per lane) + soff (wave-uniform) + imm to LDS lptr + imm + 16 * lane
-#define XV_BLDS16(rsrc, lptr, voff, soff, imm)                                                                  \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(lptr), 16, voff, soff, imm, 0)
 #define XV_BLDS16_X4(rsrc, lptr, voff, soff, imm)                                                               \
     do {                                                                                                        \
         XV_BLDS16(rsrc, lptr, voff, soff, (imm));                                                               \
@@ -110,7 +77,6 @@ struct Gemm8Params {
         XV_BLDS16(rsrc, lptr, voff, soff, (imm) + 2048);                                                        \
         XV_BLDS16(rsrc, lptr, voff, soff, (imm) + 3072);                                                        \
     } while (0)
-constexpr int XV_RSRC_FLAGS = 0x00020000;              // raw buffer, 32-bit data format (gfx9 family dword 3)
 #define XV_GLDS16_X4(gptr, lptr, imm)                                                                           \
     do {                                                                                                        \
         XV_GLDS16_OFF(gptr, lptr, (imm));                                                                       \
@@ -1403,20 +1369,12 @@ int launch_gemm8(const Gemm8Params &p0, hipStream_t st)
     for (const Gemm8Kernel &e : GEMM8_KERNELS)
         if (e.kt == p.K && e.pool == (p.blk != nullptr) && e.wm == wm) k = &e;
     if (!k) return fail(XV_ERR_UNSUPPORTED, "tdnn_f16bf8: no kernel for this configuration");
-    static std::atomic<unsigned long long> attr_done{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!((attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-        for (const Gemm8Kernel &e : GEMM8_KERNELS) {
-            hipError_t err = hipFuncSetAttribute((const void *)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g8_kernel_lds(e));
-            if (err != hipSuccess) return hip_fail(err, "hipFuncSetAttribute");
-        }
-        attr_done.fetch_or(1ull << (dev & 63), std::memory_order_release);
-    }
+    static std::atomic<unsigned long long> lds_done{0};
+    if (const int rc = opt_in_dynamic_lds(lds_done, GEMM8_KERNELS, [](const Gemm8Kernel &e) { return std::make_pair(e.fn, g8_kernel_lds(e)); }))
+        return rc;
     p.colmap = (wm == 16 && p.n_nt == 2 && p.n_mt >= 8 && g_xcd_columns.load(std::memory_order_relaxed)) ? 1 : 0;
     hipLaunchKernelGGL(k->fn, dim3((unsigned)(p.n_mt * p.n_nt)), dim3(wm >= 8 ? 512 : wm * 128), g8_kernel_lds(*k), st, p);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "tdnn_gemm_f16bf8_kernel launch");
+    return launch_status("tdnn_gemm_f16bf8_kernel launch");
 }
 
 // w[K, cin, cout] fp32 -> tiled f16bf8 weights: tile (nt, chunk, tap) = 16 KB [fp16 plane 128 x 64 B][8-bit plane 128 x 64 B]
@@ -1487,12 +1445,6 @@ __global__ void split8_decode_kernel(const uint8_t *__restrict__ xs, long R, int
     x[(size_t)r * ldx + cc] = (float)h + xv_bf8_to_float(l) * (1.f / XV_SPLIT8_LO_SCALE);
 }
 
-int check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, what);
-}
-
 }  // namespace
 
 extern "C" {
@@ -1514,7 +1466,7 @@ int xv_pack_weights_f16bf8(const float *w, int K, int cin, int cout, void *wt, v
     const size_t total = xv_packed_weights_f16bf8_bytes(K, cin, cout) / 32;     // one thread per 8-channel group (16 + 16 bytes)
     hipLaunchKernelGGL(pack_weights_f16bf8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, K,
                        cin, cout, n_chunks, (uint8_t *)wt, total);
-    return check_launch("pack_weights_f16bf8_kernel");
+    return launch_status("pack_weights_f16bf8_kernel");
 }
 
 int xv_split8_encode_f32(const float *x, int64_t R, int c, int ldx, void *xs, int32_t *status, void *stream)
@@ -1526,7 +1478,7 @@ int xv_split8_encode_f32(const float *x, int64_t R, int c, int ldx, void *xs, in
     const size_t n = (size_t)R * chunks * 4;
     hipLaunchKernelGGL(split8_encode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, (long)R, c, ldx,
                        (uint8_t *)xs, chunks, (int *)status);
-    return check_launch("split8_encode_kernel");
+    return launch_status("split8_encode_kernel");
 }
 
 int xv_split8_decode_f32(const void *xs, int64_t R, int c, float *x, int ldx, void *stream)
@@ -1536,7 +1488,7 @@ int xv_split8_decode_f32(const void *xs, int64_t R, int c, float *x, int ldx, vo
     const size_t n = (size_t)R * c;
     hipLaunchKernelGGL(split8_decode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const uint8_t *)xs, (long)R, c, (c + 31) / 32, x, ldx);
-    return check_launch("split8_decode_kernel");
+    return launch_status("split8_decode_kernel");
 }
 
 int xv_tdnn_layer_f16bf8(const void *x, int64_t R, int cin, const void *wt, const float *bias, const float *bn_scale,

@@ -10,35 +10,14 @@
 //                      16 B/lane loads, blocked two-pass + Chan merges, wave shuffle combine
 //   chunk_average, pack_weights, fold_bn   small helpers
 // See include/xvector_hip.h for the ABI contract and DESIGN.md for the layout / roofline notes.
-#include <hip/hip_runtime.h>
 #include <cstdlib>
-#include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 
-#include <atomic>
-#include <type_traits>
-
-#include "xvector_hip.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "xv_device.h"
 
 namespace {
 
 thread_local char g_err[256] = "";
-
-int fail(int code, const char *msg)
-{
-    snprintf(g_err, sizeof(g_err), "%s", msg);
-    return code;
-}
-
-int hip_fail(hipError_t e, const char *where)
-{
-    snprintf(g_err, sizeof(g_err), "%s: %s", where, hipGetErrorString(e));
-    return (int)e;
-}
 
 // ------------------------------------------------------------------------------------------------
 // TDNN / FC GEMM
@@ -87,17 +66,9 @@ __device__ __forceinline__ float apply_act(float z, int act, float a)
     }
 }
 
-// The same with the kind as a compile-time constant: identical expressions, hence identical bits -- but no switch per ELEMENT
-// (the row-wise epilogue below used to evaluate one: ~6 scalar compares / branches around every 4 VALU instructions, nothing
-// packed; beside an fp32 MFMA a co-resident workgroup pays for every one of them, cf. csrc/xv_toom.hip)
-template <int ACT>
-__device__ __forceinline__ float act_t(float z, float a)
-{
-    if constexpr (ACT == XV_ACT_RELU) return fmaxf(z, 0.0f);
-    else if constexpr (ACT == XV_ACT_LRELU) return z > 0.0f ? z : a * z;
-    else if constexpr (ACT == XV_ACT_PRELU) return fmaxf(z, 0.0f) + a * fminf(z, 0.0f);
-    else return z;
-}
+// act_t<ACT> (xv_device.h) is the same with the kind as a compile-time constant: identical expressions, hence identical bits -- but
+// no switch per ELEMENT (the row-wise epilogue below used to evaluate one: ~6 scalar compares / branches around every 4 VALU
+// instructions, nothing packed; beside an fp32 MFMA a co-resident workgroup pays for every one of them, cf. csrc/xv_toom.hip)
 
 // Fused epilogue shared by the fp32 and the bf16x3 GEMM kernels.
 // D layout of a 32x32 MFMA tile: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
@@ -481,9 +452,6 @@ __global__ void splitk_reduce_kernel(const float *__restrict__ part, long part_s
 // Epilogue: accumulators -> LDS (fp32 tile) -> bias/act/BN/gap-mask -> 16-byte NON-TEMPORAL stores (fp32 rows or
 // split): the outputs are 0.27-0.8 GB streams, and plain stores (L2 write-allocate) measured 7-16 % slower.
 // ------------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int SROW = 128;                         // bytes per (row, 32-channel slab): LDS A row and HBM split row-slab
 constexpr int B3_PLANE = BN * 64;                 // 8192
 constexpr int B3_BYTES = 2 * B3_PLANE;            // 16384: [hi tile][lo tile]
@@ -532,13 +500,6 @@ struct Gemm3Params {
     int cs_ldr;
     double *cs_part;
 };
-
-#define XV_GLDS16_OFF(gptr, lptr, imm)                                                                          \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr),                    \
-                                     (__attribute__((address_space(3))) void *)(lptr), 16, imm, 0)
-#define XV_GLDS16(gptr, lptr)                                                                                   \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr),                    \
-                                     (__attribute__((address_space(3))) void *)(lptr), 16, 0, 0)
 
 // KT: kernel size K of the split-input path as a compile-time constant (1, 3, 5, 7; 0 = the fp32-input path, runtime K).
 // The stage loop of that path is unrolled over the K taps of a slab, so everything that depends on the tap -- fragment
@@ -1365,20 +1326,11 @@ int launch_gemm3(const Gemm3Params &p0, hipStream_t st)
     p.n_mt = (int)((p.R + wm * 64 - 1) / (wm * 64));
     const Gemm3Kernel *k = find_gemm3(kt, p.blk != nullptr, wm, s16);
     if (!k) return fail(XV_ERR_UNSUPPORTED, "tdnn_bf16x3: no kernel for this configuration");
-    // the dynamic-LDS opt-in is per device and idempotent: one bit per device id, set after the first successful pass
-    static std::atomic<unsigned long long> attr_done{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!((attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-        for (const Gemm3Kernel &e : GEMM3_KERNELS) {
-            hipError_t err = hipFuncSetAttribute((const void *)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm3_lds_bytes(e.wm));
-            if (err != hipSuccess) return hip_fail(err, "hipFuncSetAttribute");
-        }
-        attr_done.fetch_or(1ull << (dev & 63), std::memory_order_release);
-    }
+    static std::atomic<unsigned long long> lds_done{0};
+    if (const int rc = opt_in_dynamic_lds(lds_done, GEMM3_KERNELS, [](const Gemm3Kernel &e) { return std::make_pair(e.fn, gemm3_lds_bytes(e.wm)); }))
+        return rc;
     hipLaunchKernelGGL(k->fn, dim3((unsigned)(p.n_mt * p.n_nt)), dim3(wm * 128), gemm3_lds_bytes(wm), st, p);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "tdnn_gemm_bf16x3_kernel launch");
+    return launch_status("tdnn_gemm_bf16x3_kernel launch");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1395,23 +1347,11 @@ int launch_gemm3(const Gemm3Params &p0, hipStream_t st)
 //    remaining 16 MFMAs (two fragment sets, k-group granularity) -- no wave starts a stage with an empty pipe.
 // Needs Cin % 32 == 0, 16-byte aligned rows, matrices below 2^31 bytes, the row-wise epilogue (else tdnn_gemm_kernel).
 // ------------------------------------------------------------------------------------------------
-#define XV_BLDS16(rsrc, lptr, voff, soff, imm)                                                                  \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(lptr), 16, voff, soff, imm, 0)
-constexpr int XV_RSRC_FLAGS = 0x00020000;              // raw buffer, 32-bit data format (gfx9 family dword 3)
 constexpr int F_SROW = 128;
 constexpr int F_A_BYTES = (BM + MAX_SPAN) * F_SROW;    // 17408
 constexpr int F_B_BYTES = BN * F_SROW;                 // 16384
 constexpr int F_OPER = 2 * F_A_BYTES + 2 * F_B_BYTES;  // 67584 = the epilogue's 128 x 132 fp32 tile
 constexpr size_t F_LDS_BYTES = (size_t)F_OPER + BM;
-
-template <int I, int N, class F>
-__device__ __forceinline__ void f_static_for(F &f)
-{
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        f_static_for<I + 1, N>(f);
-    }
-}
 
 template <int KT>
 __global__ __launch_bounds__(NT, 2) void tdnn_gemm_dma_kernel(const GemmParams p)
@@ -1558,7 +1498,7 @@ __global__ __launch_bounds__(NT, 2) void tdnn_gemm_dma_kernel(const GemmParams p
             pin();
             ++s;
         };
-        f_static_for<0, KT>(tap);
+        static_for<0, KT>(tap);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // (the tail's clamped pieces must have landed before the tile below reuses the LDS)
     __syncthreads();
@@ -1747,24 +1687,12 @@ int launch_gemm(const GemmParams &p0, hipStream_t st)
     const kern_t all[] = {tdnn_gemm_kernel<true, 128>, tdnn_gemm_kernel<false, 128>, tdnn_gemm_kernel<true, 64>,
                           tdnn_gemm_kernel<false, 64>};
     const kern_t dma_all[] = {tdnn_gemm_dma_kernel<1>, tdnn_gemm_dma_kernel<3>, tdnn_gemm_dma_kernel<5>, tdnn_gemm_dma_kernel<7>};
-    static std::atomic<unsigned long long> attr_done{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!((attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-        for (kern_t k : all) {
-            hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEMM_LDS_BYTES);
-            if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");
-        }
-        for (kern_t k : dma_all) {
-            hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES);
-            if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");
-        }
-        for (kern_t k : {tdnn_gemm_k1_kernel<3>, tdnn_gemm_k1_kernel<4>}) {
-            hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G_LDS_BYTES);
-            if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");
-        }
-        attr_done.fetch_or(1ull << (dev & 63), std::memory_order_release);
-    }
+    typedef std::pair<kern_t, size_t> kern_lds;
+    const kern_lds lds[] = {{all[0], GEMM_LDS_BYTES}, {all[1], GEMM_LDS_BYTES}, {all[2], GEMM_LDS_BYTES}, {all[3], GEMM_LDS_BYTES},
+                            {dma_all[0], F_LDS_BYTES}, {dma_all[1], F_LDS_BYTES}, {dma_all[2], F_LDS_BYTES}, {dma_all[3], F_LDS_BYTES},
+                            {tdnn_gemm_k1_kernel<3>, G_LDS_BYTES}, {tdnn_gemm_k1_kernel<4>, G_LDS_BYTES}};
+    static std::atomic<unsigned long long> lds_done{0};
+    if (const int rc = opt_in_dynamic_lds(lds_done, lds, [](const kern_lds &kl) { return kl; })) return rc;
     const dim3 grid((unsigned)(p.n_mt * p.n_nt));
     // the DMA-fed form (128-row tiles): whole 32-channel slabs, 16-byte aligned rows, byte offsets that fit the descriptors' 32 bits
     static const bool dma_env = !(std::getenv("XV_FP32_DMA") != nullptr && std::getenv("XV_FP32_DMA")[0] == '0');
@@ -1777,24 +1705,20 @@ int launch_gemm(const GemmParams &p0, hipStream_t st)
     if (dma_ok && k1_on && p.K == 1 && p.cin >= 2 * G_BK) {
         if (k1_env == 4) hipLaunchKernelGGL(tdnn_gemm_k1_kernel<4>, grid, dim3(NT), G_LDS_BYTES, st, p);
         else hipLaunchKernelGGL(tdnn_gemm_k1_kernel<3>, grid, dim3(NT), G_LDS_BYTES, st, p);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : hip_fail(e, "tdnn_gemm_k1_kernel launch");
+        return launch_status("tdnn_gemm_k1_kernel launch");
     }
     if (dma_ok) {
         const kern_t dk = p.K == 1 ? tdnn_gemm_dma_kernel<1> : p.K == 3 ? tdnn_gemm_dma_kernel<3> : p.K == 5 ? tdnn_gemm_dma_kernel<5>
                                                                                                              : tdnn_gemm_dma_kernel<7>;
         hipLaunchKernelGGL(dk, grid, dim3(NT), F_LDS_BYTES, st, p);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : hip_fail(e, "tdnn_gemm_dma_kernel launch");
+        return launch_status("tdnn_gemm_dma_kernel launch");
     }
     if (p.k_splits > 1) {
         hipLaunchKernelGGL(all[(small ? 2 : 0) + (vec ? 0 : 1)], dim3((unsigned)(p.n_mt * p.n_nt * p.k_splits)), dim3(NT), GEMM_LDS_BYTES, st, p);
-        hipError_t e2 = hipGetLastError();
-        return e2 == hipSuccess ? 0 : hip_fail(e2, "tdnn_gemm_kernel (split-K) launch");
+        return launch_status("tdnn_gemm_kernel (split-K) launch");
     }
     hipLaunchKernelGGL(all[(small ? 2 : 0) + (vec ? 0 : 1)], grid, dim3(NT), GEMM_LDS_BYTES, st, p);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "tdnn_gemm_kernel launch");
+    return launch_status("tdnn_gemm_kernel launch");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2154,12 +2078,6 @@ __global__ void fold_bn_kernel(const float *gamma, const float *beta, const floa
     shift[i] = beta[i] - ms;
 }
 
-int check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, what);
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -2206,7 +2124,7 @@ int xv_pack_weights_f32(const float *w, int kred, int cout, float *wp, void *str
     if (!w || !wp || kred <= 0 || cout <= 0) return fail(XV_ERR_BAD_ARG, "pack_weights: bad argument");
     const size_t n = (size_t)kred * cout;
     hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, kred, cout, wp);
-    return check_launch("pack_weights_kernel");
+    return launch_status("pack_weights_kernel");
 }
 
 int xv_fold_bn_f32(const float *gamma, const float *beta, const float *mean, const float *var, float eps, int c,
@@ -2214,7 +2132,7 @@ int xv_fold_bn_f32(const float *gamma, const float *beta, const float *mean, con
 {
     if (!gamma || !beta || !mean || !var || !scale || !shift || c <= 0) return fail(XV_ERR_BAD_ARG, "fold_bn: bad argument");
     hipLaunchKernelGGL(fold_bn_kernel, dim3((c + 255) / 256), dim3(256), 0, (hipStream_t)stream, gamma, beta, mean, var, eps, c, scale, shift);
-    return check_launch("fold_bn_kernel");
+    return launch_status("fold_bn_kernel");
 }
 
 int xv_tdnn_layer_f32(const float *x, int64_t R, int cin, int ldx, const float *wp, const float *bias,
@@ -2243,7 +2161,7 @@ int xv_pack_weights_rows_f32(const float *w, int K, int cin, int ldx, int cout, 
     if (!w || !wp || n == 0) return fail(XV_ERR_BAD_ARG, "pack_weights_rows: K odd, cin <= ldx, ldx % 4 == 0");
     hipLaunchKernelGGL(pack_weights_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, K, cin, ldx, cout,
                        (int)(n / cout), wp);
-    return check_launch("pack_weights_rows_kernel");
+    return launch_status("pack_weights_rows_kernel");
 }
 
 int xv_tdnn_layer_rows_f32(const float *x, int64_t R, int cin, int ldx, const float *wp, const float *bias, const float *bn_scale,
@@ -2320,7 +2238,7 @@ int xv_fc_splitk_f32(const float *x, int nrows, int in_dim, const float *wp, con
     const size_t n = (size_t)nrows * out_dim;
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float *)workspace,
                        (long)nrows * out_dim, g, nrows, out_dim, bias, bn_scale, bn_shift, act_kind, act_alpha, y, out_dim, y_preact, out_dim);
-    return check_launch("splitk_reduce_kernel");
+    return launch_status("splitk_reduce_kernel");
 }
 
 
@@ -2337,7 +2255,7 @@ int xv_pack_weights_bf16x3(const float *w, int K, int cin, int cout, void *wt, v
     const size_t total = xv_packed_weights_bf16x3_bytes(K, cin, cout) / 4;      // 4 bytes (hi+lo) per element
     hipLaunchKernelGGL(pack_weights_bf16x3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, K,
                        cin, cout, n_chunks, (uint8_t *)wt, total);
-    return check_launch("pack_weights_bf16x3_kernel");
+    return launch_status("pack_weights_bf16x3_kernel");
 }
 
 int xv_pack_weights_bf16x3_many(int n, const float *const *w, const int32_t *K, const int32_t *cin, const int32_t *cin_pad,
@@ -2352,7 +2270,7 @@ int xv_pack_weights_bf16x3_many(int n, const float *const *w, const int32_t *K, 
         hipLaunchKernelGGL(pack_weights_bf16x3_many_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, jobs);
         jobs.n = 0;
         blocks = 0;
-        return check_launch("pack_weights_bf16x3_many_kernel");
+        return launch_status("pack_weights_bf16x3_many_kernel");
     };
     for (int i = 0; i < n; ++i) {
         if (!w[i] || K[i] <= 0 || cin[i] <= 0 || cin_pad[i] < cin[i] || cout[i] <= 0)
@@ -2385,7 +2303,7 @@ int xv_split_encode_f32(const float *x, int64_t R, int c, int ldx, void *xs, voi
     const size_t n = (size_t)R * chunks * 32;
     hipLaunchKernelGGL(split_encode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, (long)R, c, ldx,
                        (uint8_t *)xs, chunks);
-    return check_launch("split_encode_kernel");
+    return launch_status("split_encode_kernel");
 }
 
 int xv_split_decode_f32(const void *xs, int64_t R, int c, float *x, int ldx, void *stream)
@@ -2395,7 +2313,7 @@ int xv_split_decode_f32(const void *xs, int64_t R, int c, float *x, int ldx, voi
     const size_t n = (size_t)R * c;
     hipLaunchKernelGGL(split_decode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const uint8_t *)xs, (long)R, c, (c + 31) / 32, x, ldx);
-    return check_launch("split_decode_kernel");
+    return launch_status("split_decode_kernel");
 }
 
 int xv_tdnn_layer_bf16x3(const void *x, int x_format, int64_t R, int cin, int ldx, const void *wt, const float *bias,
@@ -2485,7 +2403,7 @@ int xv_stats_pool_blocks_f32(const float *block_stats, int c, const int32_t *row
         const int nb = min(65535, nchunks - b0);
         hipLaunchKernelGGL(stats_pool_blocks_kernel, dim3((c + 255) / 256, nb), dim3(256), 0, st, block_stats, c, row_start + b0,
                            row_len + b0, eps, out + (size_t)b0 * 2 * c);
-        int rc = check_launch("stats_pool_blocks_kernel");
+        int rc = launch_status("stats_pool_blocks_kernel");
         if (rc) return rc;
     }
     return 0;
@@ -2524,13 +2442,13 @@ static int stats_pool_impl(const float *h, int64_t ldh, int c, const int32_t *ro
         hipLaunchKernelGGL(stats_pool_kernel, grid, dim3(256), 0, st, h, (long)ldh, c, row_start + b0, row_len + b0,
                            split_rows, max_splits, eps, out + (size_t)b0 * 2 * c,
                            (float *)workspace + (size_t)b0 * max_splits * 2 * c, raw);
-        int rc = check_launch("stats_pool_kernel");
+        int rc = launch_status("stats_pool_kernel");
         if (rc) return rc;
         if (max_splits > 1) {
             hipLaunchKernelGGL(stats_pool_merge_kernel, dim3((c + 255) / 256, nb), dim3(256), 0, st,
                                (const float *)workspace + (size_t)b0 * max_splits * 2 * c, c, row_len + b0, split_rows,
                                max_splits, eps, out + (size_t)b0 * 2 * c, raw);
-            rc = check_launch("stats_pool_merge_kernel");
+            rc = launch_status("stats_pool_merge_kernel");
             if (rc) return rc;
         }
     }
@@ -2561,7 +2479,7 @@ int xv_chunk_average_f32(const float *e, const int32_t *seg_start, const int32_t
         const int nu = min(65535, nutts - u0);
         hipLaunchKernelGGL(chunk_average_kernel, dim3((dim + 255) / 256, nu), dim3(256), 0, st, e, seg_start + u0, chunk_len,
                            dim, out + (size_t)u0 * dim);
-        int rc = check_launch("chunk_average_kernel");
+        int rc = launch_status("chunk_average_kernel");
         if (rc) return rc;
     }
     return 0;

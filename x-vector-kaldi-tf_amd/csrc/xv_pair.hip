@@ -23,27 +23,9 @@
 //     k-step) from the split-format activation buffer of the previous layer.
 // Arithmetic is the bf16x3 scheme of xv_kernels.hip (x = hi + lo, products lo*hi + hi*lo + hi*hi, fp32 accumulate).
 // Per 128-frame workgroup: 4.25 MB global->LDS (the unfused pair: 8 MB), no activation store, no activation reload.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-
-#include <atomic>
-#include <type_traits>
-
-#include "xvector_hip.h"
-
-extern "C" void xv_internal_set_error(const char *msg);
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "xv_device.h"
 
 namespace {
-
-int fail(int code, const char *msg)
-{
-    xv_internal_set_error(msg);
-    return code;
-}
 
 constexpr int CMID = 512;                  // width of the intermediate layer (register budget: CMID/4 VGPRs of operands)
 constexpr int PR_WAVES = 8;
@@ -69,30 +51,9 @@ struct PairParams {
     long n_blocks;
 };
 
-#define XV_GLDS16_OFF(gptr, lptr, imm)                                                                          \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr),                    \
-                                     (__attribute__((address_space(3))) void *)(lptr), 16, imm, 0)
-
 struct Frags {                 // the 4 weight fragments (hi and lo plane) of one sub-step: 8 x 4 VGPRs
     bf16x8 hi[4], lo[4];
 };
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F &f)
-{
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-// MODE 0: max(z,0) + alpha*min(z,0) (identity with alpha = 1, PReLU with per-channel alpha)   1: tf.nn.leaky_relu =
-// max(alpha*z, z)   2: plain ReLU.  A compile-time choice: the epilogues below are straight-line code.
-template <int MODE>
-__device__ __forceinline__ float act_fn(float z, float a)
-{
-    return MODE == 1 ? fmaxf(a * z, z) : MODE == 2 ? fmaxf(z, 0.f) : fmaxf(z, 0.f) + a * fminf(z, 0.f);
-}
 
 template <int MODE>
 __global__ __launch_bounds__(PR_WAVES * 64, 2) void tdnn_pair_pool_kernel(const PairParams p)
@@ -420,9 +381,7 @@ int xv_pack_pair_bf16x3(const float *w1, const float *w2, int cin, int cmid, int
     const size_t total = xv_packed_pair_bf16x3_bytes(cin, cmid, cout) / 4;
     hipLaunchKernelGGL(pack_pair_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w1, w2, cin / 32,
                        cout, cout / 64, (uint8_t *)wt, total);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
-    return 0;
+    return launch_status();
 }
 
 int xv_tdnn_pair_pool_bf16x3(const void *x, int64_t R, int cin, int cmid, int cout, const void *wt, const float *bias1,
@@ -447,22 +406,12 @@ int xv_tdnn_pair_pool_bf16x3(const void *x, int64_t R, int cin, int cmid, int co
     const size_t lds_bytes = (size_t)PR_P2_OFF + (size_t)cout * 16;
     typedef void (*kern_t)(const PairParams);
     const kern_t kerns[3] = {tdnn_pair_pool_kernel<0>, tdnn_pair_pool_kernel<1>, tdnn_pair_pool_kernel<2>};
-    static std::atomic<unsigned long long> attr_done{0};      // dynamic-LDS opt-in: per device, idempotent
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!((attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-        for (kern_t k : kerns) {
-            hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, PR_P2_OFF + 2048 * 16);
-            if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
-        }
-        attr_done.fetch_or(1ull << (dev & 63), std::memory_order_release);
-    }
+    static std::atomic<unsigned long long> lds_done{0};
+    if (const int rc = opt_in_dynamic_lds(lds_done, kerns, PR_P2_OFF + 2048 * 16)) return rc;
     const int mode = act_kind == XV_ACT_LRELU ? 1 : act_kind == XV_ACT_RELU ? 2 : 0;
     hipLaunchKernelGGL(kerns[mode], dim3((unsigned)((R + PR_ROWS - 1) / PR_ROWS)), dim3(PR_WAVES * 64), lds_bytes,
                        (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
-    return 0;
+    return launch_status();
 }
 
 }  // extern "C"

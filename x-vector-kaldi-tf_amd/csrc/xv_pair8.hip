@@ -27,29 +27,10 @@
 // fragment, two 1 KB planes], lane-linear 16-byte fragments; ring of three.  ONE barrier per stage, between its third and
 // fourth unit (the fourth unit's fragments are in registers by then): behind it the slot is refilled with stage s+3, so a
 // DMA has two full stages to land and the barrier's wait is a counted vmcnt(4), never a drain.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-
-#include <atomic>
-#include <type_traits>
-
-#include "xvector_hip.h"
+#include "xv_device.h"
 #include "xv_split8.h"
 
-extern "C" void xv_internal_set_error(const char *msg);
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 namespace {
-
-int fail(int code, const char *msg)
-{
-    xv_internal_set_error(msg);
-    return code;
-}
 
 constexpr int CMID = 512;                  // width of the intermediate layer
 constexpr int P8_WAVES = 8;
@@ -78,29 +59,11 @@ struct Pair8Params {
     int *status;               // bit 0: the intermediate left the fp16 range (clamped)
 };
 
-// One 1 KB LDS-DMA piece: 16 bytes per lane from buffer `rsrc` at byte voff (per lane) + soff (wave-uniform) + imm to LDS
-// lptr + imm + 16 * lane.  The MUBUF form on purpose: the FLAT-encoded global_load_lds marks "a flat access is pending" in the
+// The 1 KB LDS-DMA pieces are XV_BLDS16 (16 bytes per lane from buffer `rsrc` at byte voff (per lane) + soff (wave-uniform) + imm
+// to LDS lptr + imm + 16 * lane).  The MUBUF form on purpose: the FLAT-encoded global_load_lds marks "a flat access is pending" in the
 // compiler's wait-count bookkeeping for as long as any piece is in flight -- here always -- and every s_waitcnt it inserts for an
 // LDS read then degrades to lgkmcnt(0): a step could not start its first MFMA before ALL fragment reads of the previous step
 // had returned.
-#define XV_BLDS16(rsrc, lptr, voff, soff, imm)                                                                  \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(lptr), 16, voff, soff, imm, 0)
-constexpr int XV_RSRC_FLAGS = 0x00020000;              // raw buffer, 32-bit data format (gfx9 family dword 3)
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F &f)
-{
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-template <int MODE>
-__device__ __forceinline__ float act_fn(float z, float a)
-{
-    return MODE == 1 ? fmaxf(a * z, z) : MODE == 2 ? fmaxf(z, 0.f) : fmaxf(z, 0.f) + a * fminf(z, 0.f);
-}
 
 template <int MODE>
 __global__ __launch_bounds__(P8_WAVES * 64, 2) void tdnn_pair_pool_f16bf8_kernel(const Pair8Params p)
@@ -739,9 +702,7 @@ int xv_pack_pair_f16bf8(const float *w1, const float *w2, int cin, int cmid, int
     const size_t total = xv_packed_pair_f16bf8_bytes(cin, cmid, cout) / 64;      // one thread per 64 packed bytes
     hipLaunchKernelGGL(pack_pair8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w1, w2, cin / 32,
                        cout, cout / 64, (uint8_t *)wt, total);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
-    return 0;
+    return launch_status();
 }
 
 int xv_tdnn_pair_pool_f16bf8(const void *x, int64_t R, int cin, int cmid, int cout, const void *wt, const float *bias1,
@@ -765,22 +726,12 @@ int xv_tdnn_pair_pool_f16bf8(const void *x, int64_t R, int cin, int cmid, int co
     p.act = act_kind; p.valid = row_valid; p.blk = block_stats; p.n_blocks = (long)((R + 7) / 8); p.status = (int *)status;
     typedef void (*kern_t)(const Pair8Params);
     const kern_t kerns[3] = {tdnn_pair_pool_f16bf8_kernel<0>, tdnn_pair_pool_f16bf8_kernel<1>, tdnn_pair_pool_f16bf8_kernel<2>};
-    static std::atomic<unsigned long long> attr_done{0};      // dynamic-LDS opt-in: per device, idempotent
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!((attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-        for (kern_t k : kerns) {
-            hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P8_LDS_BYTES);
-            if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
-        }
-        attr_done.fetch_or(1ull << (dev & 63), std::memory_order_release);
-    }
+    static std::atomic<unsigned long long> lds_done{0};
+    if (const int rc = opt_in_dynamic_lds(lds_done, kerns, P8_LDS_BYTES)) return rc;
     const int mode = act_kind == XV_ACT_LRELU ? 1 : act_kind == XV_ACT_RELU ? 2 : 0;
     hipLaunchKernelGGL(kerns[mode], dim3((unsigned)((R + P8_ROWS - 1) / P8_ROWS)), dim3(P8_WAVES * 64), P8_LDS_BYTES,
                        (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
-    return 0;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -34,35 +34,9 @@
 //    back to back.
 // Row pairs are aligned to EVEN global rows; chunks start on even rows (the host lays batches out with align 8), so a chunk's bits
 // do not depend on its batch neighbours.  Gap rows are zero and masked as everywhere else.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-
-#include <atomic>
-#include <type_traits>
-
-#include "xvector_hip.h"
-
-extern "C" void xv_internal_set_error(const char *msg);
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "xv_device.h"
 
 namespace {
-
-int fail(int code, const char *msg)
-{
-    xv_internal_set_error(msg);
-    return code;
-}
-
-int hip_fail(hipError_t e, const char *where)
-{
-    char buf[256];
-    snprintf(buf, sizeof(buf), "%s: %s", where, hipGetErrorString(e));
-    xv_internal_set_error(buf);
-    return (int)e;
-}
 
 // ---- F(2, K) matrices (tools/experiments/toomcook_gen.py prints BT / G / AT and checks them in exact rationals).  Here per
 // product j: the scale SC[j] its row of BT is divided by (G's row is multiplied by it), AT[1][j] (AT[0][j] is 1 except for the
@@ -130,10 +104,6 @@ constexpr int OPER = 2 * A_BYTES + 2 * B_BYTES;   // 69632
 constexpr int TLD = BN + 4;                  // epilogue fp32 tile row (floats)
 static_assert(BM * TLD * 4 <= OPER, "the epilogue tile must fit the operand buffers");
 constexpr size_t LDS_BYTES = (size_t)OPER + BM;
-constexpr int RSRC_FLAGS = 0x00020000;       // raw buffer, 32-bit data format (gfx9 family dword 3)
-
-#define XV_BLDS16(rsrc, lptr, voff, soff, imm)                                                                  \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(lptr), 16, voff, soff, imm, 0)
 
 struct ToomParams {
     const float *x;
@@ -151,25 +121,6 @@ struct ToomParams {
     int n_mt, n_nt;
     int dil;                    // dilation d: the launch runs d independent undilated problems, rows sub, sub + d, sub + 2 d, ...
 };
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F &f)
-{
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-// the activation with its kind as a compile-time constant (the same expressions as apply_act of xv_kernels.hip: same bits)
-template <int ACT>
-__device__ __forceinline__ float act_t(float z, float a)
-{
-    if constexpr (ACT == XV_ACT_RELU) return fmaxf(z, 0.0f);
-    else if constexpr (ACT == XV_ACT_LRELU) return z > 0.0f ? z : a * z;
-    else if constexpr (ACT == XV_ACT_PRELU) return fmaxf(z, 0.0f) + a * fminf(z, 0.0f);
-    else return z;
-}
 
 __device__ __forceinline__ f32x4 fma4(float a, f32x4 x, f32x4 y)
 {
@@ -313,8 +264,8 @@ __global__ __launch_bounds__(NT, 2) void tdnn_gemm_toom_kernel(const ToomParams 
     // of (LDS row >> 1) & 7 -- the swizzle of the row a lane moves is a per-lane constant.  Row part of an address in the VGPR
     // offset (range-checked: rows outside [0, R) come back as zeros), slab part in the scalar offset.
     const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.x) + (size_t)sub * p.ldx, 0,
-                                                                         (int)((p.R - sub) * p.ldx * 4), RSRC_FLAGS);
-    const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.wp), 0, (int)((long)p.cout * p.kred * 4), RSRC_FLAGS);
+                                                                         (int)((p.R - sub) * p.ldx * 4), XV_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.wp), 0, (int)((long)p.cout * p.kred * 4), XV_RSRC_FLAGS);
     const int slotb = ((lane & 7) ^ (((wave & 1) * 4 + (lane >> 4)) & 7)) << 4;
     const int arow_bytes = p.dil * p.ldx * 4, brow_bytes = p.kred * 4;
     const int va0 = (int)(m0 - left + 2 * (lane >> 3)) * arow_bytes + slotb;
@@ -569,8 +520,7 @@ int xv_pack_weights_toom_f32(const float *w, int K, int cin, int cout, float *wp
     if (K == 3) hipLaunchKernelGGL(pack_weights_toom_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, w, cin, cout, wp);
     else if (K == 5) hipLaunchKernelGGL(pack_weights_toom_kernel<5>, grid, dim3(256), 0, (hipStream_t)stream, w, cin, cout, wp);
     else hipLaunchKernelGGL(pack_weights_toom_kernel<7>, grid, dim3(256), 0, (hipStream_t)stream, w, cin, cout, wp);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "pack_weights_toom_kernel launch");
+    return launch_status("pack_weights_toom_kernel launch");
 }
 
 int xv_tdnn_layer_toom_dilated_f32(const float *x, int64_t R, int cin, int ldx, const float *wp, const float *bias, const float *bn_scale,
@@ -598,19 +548,11 @@ int xv_tdnn_layer_toom_dilated_f32(const float *x, int64_t R, int cin, int ldx, 
         return fail(XV_ERR_UNSUPPORTED, "tdnn_toom: matrices must stay below 2^31 bytes (32-bit buffer offsets)");
     typedef void (*kern_t)(const ToomParams);
     const kern_t k = K == 3 ? tdnn_gemm_toom_kernel<3> : K == 5 ? tdnn_gemm_toom_kernel<5> : tdnn_gemm_toom_kernel<7>;
-    static std::atomic<unsigned long long> attr_done{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!((attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-        for (kern_t kk : {tdnn_gemm_toom_kernel<3>, tdnn_gemm_toom_kernel<5>, tdnn_gemm_toom_kernel<7>}) {
-            hipError_t e = hipFuncSetAttribute((const void *)kk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-            if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");
-        }
-        attr_done.fetch_or(1ull << (dev & 63), std::memory_order_release);
-    }
+    static std::atomic<unsigned long long> lds_done{0};
+    const kern_t all[] = {tdnn_gemm_toom_kernel<3>, tdnn_gemm_toom_kernel<5>, tdnn_gemm_toom_kernel<7>};
+    if (const int rc = opt_in_dynamic_lds(lds_done, all, LDS_BYTES)) return rc;
     hipLaunchKernelGGL(k, dim3((unsigned)(p.n_mt * p.n_nt * dilation)), dim3(NT), LDS_BYTES, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "tdnn_gemm_toom_kernel launch");
+    return launch_status("tdnn_gemm_toom_kernel launch");
 }
 
 int xv_tdnn_layer_toom_f32(const float *x, int64_t R, int cin, int ldx, const float *wp, const float *bias, const float *bn_scale,

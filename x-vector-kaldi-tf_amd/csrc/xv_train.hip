@@ -12,34 +12,11 @@
 //   softmax_ce_kernel     loss / accuracy / dlogits of tf.nn.softmax_cross_entropy_with_logits + reduce_mean
 //   adam_kernel, ema_kernel
 // Everything is fp32 storage; reductions accumulate in fp64.
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdint.h>
-#include <stdio.h>
 
-#include "xvector_hip.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-extern "C" void xv_internal_set_error(const char *msg);
+#include "xv_device.h"
 
 namespace {
-
-int tfail(int code, const char *msg)
-{
-    xv_internal_set_error(msg);          // shared with xv_last_error() (xv_kernels.hip)
-    return code;
-}
-int tcheck(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    char buf[256];
-    snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-    xv_internal_set_error(buf);
-    return (int)e;
-}
 
 // ------------------------------------------------------------------------------------------------
 // wgrad: D[cin 128][cout 128] per (tap, tile) accumulated over a range of rows
@@ -334,10 +311,9 @@ __global__ __launch_bounds__(64 * MM_GROUPS) void merge_moments_kernel(const flo
 // SPLIT: the same values once more in the bf16 split activation format (include/xvector_hip.h: per row and 32-channel slab 128 bytes =
 // 4 hi slots + 4 lo slots of 8 bf16, slot t at t ^ ((row >> 1) & 7)) -- a thread's 4 channels are half a slot of either plane.  The
 // K = 1 layers of the training step read it: the DMA-fed GEMM instead of the one that splits fp32 rows while staging them.
-typedef __bf16 tbf16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void store_split4(uint8_t *ys, long r, int C, int c, const f32x4 &o)
 {
-    tbf16x4 hi, lo;
+    bf16x4 hi, lo;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         hi[i] = (__bf16)o[i];
@@ -345,8 +321,8 @@ __device__ __forceinline__ void store_split4(uint8_t *ys, long r, int C, int c, 
     }
     const int q = (c & 31) >> 2, sw = (int)(r >> 1) & 7;
     uint8_t *row = ys + ((size_t)r * (C >> 5) + (c >> 5)) * 128 + (q & 1) * 8;
-    *reinterpret_cast<tbf16x4 *>(row + (((q >> 1)) ^ sw) * 16) = hi;
-    *reinterpret_cast<tbf16x4 *>(row + ((4 + (q >> 1)) ^ sw) * 16) = lo;
+    *reinterpret_cast<bf16x4 *>(row + (((q >> 1)) ^ sw) * 16) = hi;
+    *reinterpret_cast<bf16x4 *>(row + ((4 + (q >> 1)) ^ sw) * 16) = lo;
 }
 
 template <bool VEC, bool SPLIT = false>
@@ -954,23 +930,23 @@ int xv_wgrad_f32(const float *x, int ldx, const float *dz, int lddz, int64_t R, 
                  void *workspace, void *stream)
 {
     if (!x || !dz || !dw || R <= 0 || cin <= 0 || cout <= 0 || K <= 0 || !(K & 1) || dilation <= 0)
-        return tfail(XV_ERR_BAD_ARG, "wgrad: bad argument");
+        return fail(XV_ERR_BAD_ARG, "wgrad: bad argument");
     WgradParams p{};
     p.x = x; p.dz = dz; p.R = (long)R; p.cin = cin; p.ldx = ldx; p.cout = cout; p.lddz = lddz; p.K = K; p.dil = dilation;
     p.n_ct = (cin + WT - 1) / WT; p.n_ot = (cout + WT - 1) / WT;
     const long splits = wgrad_splits(R, cin, cout, K);
     p.rows_per_split = ((R + splits - 1) / splits + WR - 1) / WR * WR;
-    if (splits > 1 && !workspace) return tfail(XV_ERR_BAD_ARG, "wgrad: workspace required");
+    if (splits > 1 && !workspace) return fail(XV_ERR_BAD_ARG, "wgrad: workspace required");
     p.out = splits > 1 ? (float *)workspace : dw;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)(K * p.n_ct * p.n_ot), (unsigned)splits), dim3(256), 0, st, p);
-    int rc = tcheck("wgrad_kernel");
+    int rc = launch_status("wgrad_kernel");
     if (rc) return rc;
     if (splits > 1) {
         const size_t n = (size_t)K * cin * cout;
         hipLaunchKernelGGL(sum_splits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float *)workspace, n,
                            (int)splits, dw);
-        rc = tcheck("sum_splits_kernel");
+        rc = launch_status("sum_splits_kernel");
     }
     return rc;
 }
@@ -980,44 +956,44 @@ size_t xv_col_sums_workspace_bytes(int64_t R, int c) { return (size_t)((R + CS_R
 int xv_col_sums_f32(const float *a, int lda, const float *b, int ldb, int64_t R, int c, float *sum_a, float *sum_ab, void *workspace,
                     void *stream)
 {
-    if (!a || !sum_a || !workspace || R <= 0 || c <= 0 || (b && !sum_ab)) return tfail(XV_ERR_BAD_ARG, "col_sums: bad argument");
+    if (!a || !sum_a || !workspace || R <= 0 || c <= 0 || (b && !sum_ab)) return fail(XV_ERR_BAD_ARG, "col_sums: bad argument");
     const int splits = (int)((R + CS_ROWS - 1) / CS_ROWS);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(col_sums_kernel, dim3((c + 255) / 256, splits), dim3(256), 0, st, a, b, (long)R, c, lda, ldb, CS_ROWS,
                        (double *)workspace);
-    int rc = tcheck("col_sums_kernel");
+    int rc = launch_status("col_sums_kernel");
     if (rc) return rc;
     hipLaunchKernelGGL(col_sums_merge_kernel, dim3((c + 63) / 64), dim3(64 * CSM_GROUPS), 0, st, (const double *)workspace, c, splits, sum_a,
                        b ? sum_ab : nullptr);
-    return tcheck("col_sums_merge_kernel");
+    return launch_status("col_sums_merge_kernel");
 }
 
 int xv_col_sums_merge_f32(const void *workspace, int64_t R, int c, float *sum_a, float *sum_ab, void *stream)
 {
-    if (!workspace || !sum_a || R <= 0 || c <= 0) return tfail(XV_ERR_BAD_ARG, "col_sums_merge: bad argument");
+    if (!workspace || !sum_a || R <= 0 || c <= 0) return fail(XV_ERR_BAD_ARG, "col_sums_merge: bad argument");
     const int splits = (int)((R + CS_ROWS - 1) / CS_ROWS);
     hipLaunchKernelGGL(col_sums_merge_kernel, dim3((c + 63) / 64), dim3(64 * CSM_GROUPS), 0, (hipStream_t)stream, (const double *)workspace, c,
                        splits, sum_a, sum_ab);
-    return tcheck("col_sums_merge_kernel");
+    return launch_status("col_sums_merge_kernel");
 }
 
 int xv_bn_moments_fold_f32(const void *sums_workspace, int64_t R, int c, float n_frames, const float *gamma, const float *beta, float eps,
                            float *mean, float *var, float *scale, float *shift, void *stream)
 {
     if (!sums_workspace || !gamma || !beta || !mean || !var || !scale || !shift || R <= 0 || c <= 0 || !(n_frames > 0.f))
-        return tfail(XV_ERR_BAD_ARG, "bn_moments_fold: bad argument");
+        return fail(XV_ERR_BAD_ARG, "bn_moments_fold: bad argument");
     const int splits = (int)((R + CS_ROWS - 1) / CS_ROWS);
     hipLaunchKernelGGL(moments_fold_kernel, dim3((c + 63) / 64), dim3(64 * CSM_GROUPS), 0, (hipStream_t)stream, (const double *)sums_workspace,
                        c, splits, n_frames, gamma, beta, eps, mean, var, scale, shift);
-    return tcheck("moments_fold_kernel");
+    return launch_status("moments_fold_kernel");
 }
 
 int xv_merge_moments_f32(const float *chunk_mean_var, const int32_t *row_len, int nchunks, int c, float *mean, float *var, void *stream)
 {
-    if (!chunk_mean_var || !row_len || !mean || !var || nchunks <= 0 || c <= 0) return tfail(XV_ERR_BAD_ARG, "merge_moments: bad argument");
+    if (!chunk_mean_var || !row_len || !mean || !var || nchunks <= 0 || c <= 0) return fail(XV_ERR_BAD_ARG, "merge_moments: bad argument");
     hipLaunchKernelGGL(merge_moments_kernel, dim3((c + 63) / 64), dim3(64 * MM_GROUPS), 0, (hipStream_t)stream, chunk_mean_var, row_len,
                        nchunks, c, mean, var);
-    return tcheck("merge_moments_kernel");
+    return launch_status("merge_moments_kernel");
 }
 
 int xv_rows_affine_f32(const float *x, int ldx, int64_t R, int c, const float *scale, const float *shift, const uint8_t *row_valid,
@@ -1029,19 +1005,19 @@ int xv_rows_affine_f32(const float *x, int ldx, int64_t R, int c, const float *s
 int xv_rows_affine_split_f32(const float *x, int ldx, int64_t R, int c, const float *scale, const float *shift, const uint8_t *row_valid,
                              float *y, int ldy, void *y_split, void *stream)
 {
-    if (!x || !y || !scale || !shift || R <= 0 || c <= 0) return tfail(XV_ERR_BAD_ARG, "rows_affine: bad argument");
+    if (!x || !y || !scale || !shift || R <= 0 || c <= 0) return fail(XV_ERR_BAD_ARG, "rows_affine: bad argument");
     const bool vec = !(c & 3) && !(ldx & 3) && !(ldy & 3) && !(((uintptr_t)x | (uintptr_t)y) & 15);
     const dim3 grid((unsigned)((c + 1023) / 1024), (unsigned)(R < 4096 ? R : 4096));
     if (y_split) {
         if (!vec || (c & 31) || (((uintptr_t)y_split) & 15))
-            return tfail(XV_ERR_UNSUPPORTED, "rows_affine: the split copy needs c % 32 == 0 and 16-byte aligned fp32 rows");
+            return fail(XV_ERR_UNSUPPORTED, "rows_affine: the split copy needs c % 32 == 0 and 16-byte aligned fp32 rows");
         hipLaunchKernelGGL((rows_affine_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, x, (long)R, c, ldx, scale, shift, row_valid,
                            y, ldy, (uint8_t *)y_split);
-        return tcheck("rows_affine_kernel");
+        return launch_status("rows_affine_kernel");
     }
     if (vec) hipLaunchKernelGGL(rows_affine_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, (long)R, c, ldx, scale, shift, row_valid, y, ldy);
     else hipLaunchKernelGGL(rows_affine_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, (long)R, c, ldx, scale, shift, row_valid, y, ldy);
-    return tcheck("rows_affine_kernel");
+    return launch_status("rows_affine_kernel");
 }
 
 int xv_bn_act_backward_f32(const float *dh, const float *r, int ld, int64_t R, int c, const float *sum_dh, const float *sum_dh_r,
@@ -1058,7 +1034,7 @@ static int bn_act_backward_tail(const float *dh, const float *r, int ld, int64_t
 {
     const bool vec = !(c & 3) && !(ld & 3) && !(((uintptr_t)dh | (uintptr_t)r | (uintptr_t)dz | (uintptr_t)coef_ws) & 15);
     if (dz_split && (!vec || (c & 31) || (((uintptr_t)dz_split) & 15)))
-        return tfail(XV_ERR_UNSUPPORTED, "bn_act_backward: the split copy needs c % 32 == 0 and 16-byte aligned fp32 rows");
+        return fail(XV_ERR_UNSUPPORTED, "bn_act_backward: the split copy needs c % 32 == 0 and 16-byte aligned fp32 rows");
     if (vec) {
         const dim3 grid((unsigned)((c + 1023) / 1024), (unsigned)(R < 4096 ? R : 4096));
         if (dz_split)
@@ -1067,11 +1043,11 @@ static int bn_act_backward_tail(const float *dh, const float *r, int ld, int64_t
         else
             hipLaunchKernelGGL(bn_act_backward_vec_kernel<false>, grid, dim3(256), 0, st, dh, r, (long)R, c, ld, coef_ws, coef_ws + c,
                                coef_ws + 2 * c, act_kind, act_alpha, row_valid, dz, (uint8_t *)nullptr);
-        return tcheck("bn_act_backward_vec_kernel");
+        return launch_status("bn_act_backward_vec_kernel");
     }
     hipLaunchKernelGGL(bn_act_backward_kernel, dim3(gs_blocks((size_t)R * c)), dim3(256), 0, st, dh, r, (long)R, c, ld, coef_ws,
                        coef_ws + c, coef_ws + 2 * c, act_kind, act_alpha, row_valid, dz);
-    return tcheck("bn_act_backward_kernel");
+    return launch_status("bn_act_backward_kernel");
 }
 
 int xv_bn_act_backward_split_f32(const float *dh, const float *r, int ld, int64_t R, int c, const float *sum_dh, const float *sum_dh_r,
@@ -1080,12 +1056,12 @@ int xv_bn_act_backward_split_f32(const float *dh, const float *r, int ld, int64_
                                  void *dz_split, void *stream)
 {
     if (!dh || !r || !sum_dh || !sum_dh_r || !mean || !var || !gamma || !dgamma || !dbeta || !coef_ws || !dz || R <= 0 || c <= 0)
-        return tfail(XV_ERR_BAD_ARG, "bn_act_backward: bad argument");
-    if (act_kind == XV_ACT_PRELU) return tfail(XV_ERR_UNSUPPORTED, "bn_act_backward: PReLU training is not implemented");
+        return fail(XV_ERR_BAD_ARG, "bn_act_backward: bad argument");
+    if (act_kind == XV_ACT_PRELU) return fail(XV_ERR_UNSUPPORTED, "bn_act_backward: PReLU training is not implemented");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(bn_coeffs_kernel, dim3((c + 255) / 256), dim3(256), 0, st, sum_dh, sum_dh_r, mean, var, gamma, eps, n_frames, c,
                        dgamma, dbeta, coef_ws, coef_ws + c, coef_ws + 2 * c);
-    int rc = tcheck("bn_coeffs_kernel");
+    int rc = launch_status("bn_coeffs_kernel");
     if (rc) return rc;
     return bn_act_backward_tail(dh, r, ld, R, c, act_kind, act_alpha, row_valid, coef_ws, dz, dz_split, st);
 }
@@ -1096,13 +1072,13 @@ int xv_bn_act_backward_parts_f32(const float *dh, const float *r, int ld, int64_
                                  void *stream)
 {
     if (!dh || !r || !sums_workspace || !mean || !var || !gamma || !dgamma || !dbeta || !coef_ws || !dz || R <= 0 || c <= 0)
-        return tfail(XV_ERR_BAD_ARG, "bn_act_backward_parts: bad argument");
-    if (act_kind == XV_ACT_PRELU) return tfail(XV_ERR_UNSUPPORTED, "bn_act_backward: PReLU training is not implemented");
+        return fail(XV_ERR_BAD_ARG, "bn_act_backward_parts: bad argument");
+    if (act_kind == XV_ACT_PRELU) return fail(XV_ERR_UNSUPPORTED, "bn_act_backward: PReLU training is not implemented");
     hipStream_t st = (hipStream_t)stream;
     const int splits = (int)((R + CS_ROWS - 1) / CS_ROWS);
     hipLaunchKernelGGL(col_sums_merge_coeffs_kernel, dim3((c + 63) / 64), dim3(64 * CSM_GROUPS), 0, st, (const double *)sums_workspace, c,
                        splits, mean, var, gamma, eps, n_frames, dgamma, dbeta, coef_ws, coef_ws + c, coef_ws + 2 * c);
-    int rc = tcheck("col_sums_merge_coeffs_kernel");
+    int rc = launch_status("col_sums_merge_coeffs_kernel");
     if (rc) return rc;
     return bn_act_backward_tail(dh, r, ld, R, c, act_kind, act_alpha, row_valid, coef_ws, dz, dz_split, st);
 }
@@ -1111,10 +1087,10 @@ int xv_bn_small_forward_f32(const float *x, int ldx, int nrows, int c, const flo
                             float *var, float *y, int ldy, void *stream)
 {
     if (!x || !gamma || !beta || !mean || !var || !y || nrows <= 0 || nrows > BNS_MAX_ROWS || c <= 0 || ldx < c || ldy < c)
-        return tfail(XV_ERR_BAD_ARG, "bn_small_forward: bad argument (1 .. 1024 rows)");
+        return fail(XV_ERR_BAD_ARG, "bn_small_forward: bad argument (1 .. 1024 rows)");
     hipLaunchKernelGGL(bn_small_forward_kernel, dim3((c + 63) / 64), dim3(64 * BNS_GROUPS), 0, (hipStream_t)stream, x, ldx, nrows, c, gamma, beta,
                        eps, mean, var, y, ldy);
-    return tcheck("bn_small_forward_kernel");
+    return launch_status("bn_small_forward_kernel");
 }
 
 int xv_bn_small_backward_f32(const float *dh, const float *r, int ld, int nrows, int c, const float *mean, const float *var,
@@ -1122,11 +1098,11 @@ int xv_bn_small_backward_f32(const float *dh, const float *r, int ld, int nrows,
                              void *stream)
 {
     if (!dh || !r || !mean || !var || !gamma || !dgamma || !dbeta || !dz || nrows <= 0 || nrows > BNS_MAX_ROWS || c <= 0 || ld < c)
-        return tfail(XV_ERR_BAD_ARG, "bn_small_backward: bad argument (1 .. 1024 rows)");
-    if (act_kind == XV_ACT_PRELU) return tfail(XV_ERR_UNSUPPORTED, "bn_small_backward: PReLU training is not implemented");
+        return fail(XV_ERR_BAD_ARG, "bn_small_backward: bad argument (1 .. 1024 rows)");
+    if (act_kind == XV_ACT_PRELU) return fail(XV_ERR_UNSUPPORTED, "bn_small_backward: PReLU training is not implemented");
     hipLaunchKernelGGL(bn_small_backward_kernel, dim3((c + 63) / 64), dim3(64 * BNS_GROUPS), 0, (hipStream_t)stream, dh, r, ld, nrows, c, mean,
                        var, gamma, eps, act_kind, act_alpha, dgamma, dbeta, dz);
-    return tcheck("bn_small_backward_kernel");
+    return launch_status("bn_small_backward_kernel");
 }
 
 int xv_pool_bn_act_backward_f32(const float *h, const float *r, int ld, int c, const int32_t *row_start, const int32_t *row_len,
@@ -1136,16 +1112,16 @@ int xv_pool_bn_act_backward_f32(const float *h, const float *r, int ld, int c, c
 {
     if (!h || !r || !row_start || !row_len || !pooled || !dpooled || !chunk_moments || !mean || !var || !gamma || !dgamma || !dbeta ||
         !coef_ws || !dz || nchunks <= 0 || nchunks > 65535 || R <= 0 || c <= 0)
-        return tfail(XV_ERR_BAD_ARG, "pool_bn_act_backward: bad argument");
-    if (act_kind == XV_ACT_PRELU) return tfail(XV_ERR_UNSUPPORTED, "pool_bn_act_backward: PReLU training is not implemented");
+        return fail(XV_ERR_BAD_ARG, "pool_bn_act_backward: bad argument");
+    if (act_kind == XV_ACT_PRELU) return fail(XV_ERR_UNSUPPORTED, "pool_bn_act_backward: PReLU training is not implemented");
     if ((c & 3) || (ld & 3) || (((uintptr_t)h | (uintptr_t)r | (uintptr_t)dz | (uintptr_t)coef_ws | (uintptr_t)pooled | (uintptr_t)dpooled) & 15))
-        return tfail(XV_ERR_UNSUPPORTED, "pool_bn_act_backward: needs c % 4 == 0 and 16-byte aligned rows");
+        return fail(XV_ERR_UNSUPPORTED, "pool_bn_act_backward: needs c % 4 == 0 and 16-byte aligned rows");
     if (dz_split && ((c & 31) || (((uintptr_t)dz_split) & 15)))
-        return tfail(XV_ERR_UNSUPPORTED, "pool_bn_act_backward: the split copy needs c % 32 == 0");
+        return fail(XV_ERR_UNSUPPORTED, "pool_bn_act_backward: the split copy needs c % 32 == 0");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(pool_bn_coeffs_kernel, dim3((c + 63) / 64), dim3(64 * CSM_GROUPS), 0, st, pooled, dpooled, chunk_moments, nchunks, mean, var, gamma,
                        eps, n_frames, c, dgamma, dbeta, coef_ws, coef_ws + c, coef_ws + 2 * c);
-    int rc = tcheck("pool_bn_coeffs_kernel");
+    int rc = launch_status("pool_bn_coeffs_kernel");
     if (rc) return rc;
     const int zs = nchunks >= 2048 ? 1 : (2048 + nchunks - 1) / nchunks < 16 ? (2048 + nchunks - 1) / nchunks : 16;
     const dim3 grid((unsigned)((c + 511) / 512), (unsigned)nchunks, (unsigned)zs);
@@ -1155,21 +1131,21 @@ int xv_pool_bn_act_backward_f32(const float *h, const float *r, int ld, int c, c
     else
         hipLaunchKernelGGL(pool_bn_act_backward_kernel<false>, grid, dim3(128), 0, st, h, r, ld, c, row_start, row_len, nchunks, (long)R, pooled,
                            dpooled, coef_ws, coef_ws + c, coef_ws + 2 * c, act_kind, act_alpha, dz, (uint8_t *)nullptr);
-    return tcheck("pool_bn_act_backward_kernel");
+    return launch_status("pool_bn_act_backward_kernel");
 }
 
 int xv_pool_backward_f32(const float *h, int ldh, int c, const int32_t *row_start, const int32_t *row_len, int nchunks, int64_t R,
                          const float *pooled, const float *dpooled, float *dh, void *stream)
 {
-    if (!h || !row_start || !row_len || !pooled || !dpooled || !dh || nchunks <= 0 || c <= 0) return tfail(XV_ERR_BAD_ARG, "pool_backward: bad argument");
+    if (!h || !row_start || !row_len || !pooled || !dpooled || !dh || nchunks <= 0 || c <= 0) return fail(XV_ERR_BAD_ARG, "pool_backward: bad argument");
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(dh, 0, (size_t)R * ldh * sizeof(float), st);      // gap rows carry no gradient
-    if (e != hipSuccess) return tfail((int)e, "pool_backward: memset failed");
+    if (e != hipSuccess) return fail((int)e, "pool_backward: memset failed");
     for (int b0 = 0; b0 < nchunks; b0 += 65535) {
         const int nb = nchunks - b0 < 65535 ? nchunks - b0 : 65535;
         hipLaunchKernelGGL(pool_backward_kernel, dim3(64, nb), dim3(256), 0, st, h, ldh, c, row_start + b0, row_len + b0,
                            pooled + (size_t)b0 * 2 * c, dpooled + (size_t)b0 * 2 * c, dh);
-        int rc = tcheck("pool_backward_kernel");
+        int rc = launch_status("pool_backward_kernel");
         if (rc) return rc;
     }
     return 0;
@@ -1178,29 +1154,29 @@ int xv_pool_backward_f32(const float *h, int ldh, int c, const int32_t *row_star
 int xv_softmax_ce_f32(const float *logits, const int32_t *labels, int nrows, int nclasses, float *loss_acc, float *row_ws,
                       float *dlogits, void *stream)
 {
-    if (!logits || !labels || !loss_acc || !row_ws || nrows <= 0 || nclasses <= 0) return tfail(XV_ERR_BAD_ARG, "softmax_ce: bad argument");
+    if (!logits || !labels || !loss_acc || !row_ws || nrows <= 0 || nclasses <= 0) return fail(XV_ERR_BAD_ARG, "softmax_ce: bad argument");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(softmax_ce_kernel, dim3(nrows), dim3(64), 0, st, logits, labels, nrows, nclasses, row_ws, row_ws + nrows, dlogits);
-    int rc = tcheck("softmax_ce_kernel");
+    int rc = launch_status("softmax_ce_kernel");
     if (rc) return rc;
     hipLaunchKernelGGL(mean2_kernel, dim3(1), dim3(64), 0, st, (const float *)row_ws, (const float *)(row_ws + nrows), nrows, loss_acc);
-    return tcheck("mean2_kernel");
+    return launch_status("mean2_kernel");
 }
 
 int xv_adam_f32(float *param, const float *grad, float *m, float *v, int64_t n, float lr_t, float beta1, float beta2, float eps,
                 void *stream)
 {
-    if (!param || !grad || !m || !v || n <= 0) return tfail(XV_ERR_BAD_ARG, "adam: bad argument");
+    if (!param || !grad || !m || !v || n <= 0) return fail(XV_ERR_BAD_ARG, "adam: bad argument");
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad, m, v, (size_t)n,
                        lr_t, beta1, beta2, eps);
-    return tcheck("adam_kernel");
+    return launch_status("adam_kernel");
 }
 
 int xv_axpy_f32(float *y, const float *x, float a, int64_t n, void *stream)
 {
-    if (!y || !x || n <= 0) return tfail(XV_ERR_BAD_ARG, "axpy: bad argument");
+    if (!y || !x || n <= 0) return fail(XV_ERR_BAD_ARG, "axpy: bad argument");
     hipLaunchKernelGGL(axpy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, x, a, (size_t)n);
-    return tcheck("axpy_kernel");
+    return launch_status("axpy_kernel");
 }
 
 static int sumsq_blocks(int64_t n)
@@ -1213,13 +1189,13 @@ size_t xv_sumsq_workspace_bytes(int64_t n) { return (size_t)sumsq_blocks(n) * si
 
 int xv_sumsq_f32(const float *x, int64_t n, float *out, void *workspace, void *stream)
 {
-    if (!x || !out || n <= 0 || !workspace || (((uintptr_t)workspace) & 7)) return tfail(XV_ERR_BAD_ARG, "sumsq: bad argument");
+    if (!x || !out || n <= 0 || !workspace || (((uintptr_t)workspace) & 7)) return fail(XV_ERR_BAD_ARG, "sumsq: bad argument");
     const int nb = sumsq_blocks(n);
     hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, (size_t)n, (double *)workspace);
-    int rc = tcheck("sumsq_partial_kernel");
+    int rc = launch_status("sumsq_partial_kernel");
     if (rc) return rc;
     hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double *)workspace, nb, out);
-    return tcheck("sumsq_final_kernel");
+    return launch_status("sumsq_final_kernel");
 }
 
 // the three index arrays of a minibatch of B equal chunks of T frames with `gap` zero rows in front of, between and behind them
@@ -1241,17 +1217,17 @@ __global__ void minibatch_layout_kernel(int B, int T, int gap, long rows, int *_
 int xv_minibatch_layout(int B, int T, int gap, int64_t rows, int32_t *row_start, int32_t *row_len, uint8_t *row_valid, void *stream)
 {
     if (!row_start || !row_len || !row_valid || B <= 0 || T <= 0 || gap < 0 || rows < (int64_t)gap + (int64_t)B * (T + gap) || rows < B)
-        return tfail(XV_ERR_BAD_ARG, "minibatch_layout: bad argument");
+        return fail(XV_ERR_BAD_ARG, "minibatch_layout: bad argument");
     hipLaunchKernelGGL(minibatch_layout_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B, T, gap, (long)rows,
                        row_start, row_len, row_valid);
-    return tcheck("minibatch_layout_kernel");
+    return launch_status("minibatch_layout_kernel");
 }
 
 int xv_pack_minibatch_f32(const void *src, int src_is_f16, int B, int T, int F, int gap, int in_dim, float *dst, int64_t rows,
                           void *stream)
 {
     if (!src || !dst || B <= 0 || T <= 0 || F <= 0 || gap < 0 || in_dim < F || rows < (int64_t)gap + (int64_t)B * (T + gap))
-        return tfail(XV_ERR_BAD_ARG, "pack_minibatch: bad argument");
+        return fail(XV_ERR_BAD_ARG, "pack_minibatch: bad argument");
     const size_t n = (size_t)rows * in_dim;
     const dim3 grid((unsigned)std::min<size_t>((n + 255) / 256, 4096));
     if (src_is_f16)
@@ -1260,63 +1236,63 @@ int xv_pack_minibatch_f32(const void *src, int src_is_f16, int B, int T, int F, 
     else
         hipLaunchKernelGGL(pack_minibatch_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float *)src, B, T, F, gap, in_dim,
                            (long)rows, dst);
-    return tcheck("pack_minibatch_kernel");
+    return launch_status("pack_minibatch_kernel");
 }
 
 int xv_dropout_f32(float *x, int ldx, int64_t R, int c, uint64_t seed, float keep_prob, void *stream)
 {
     if (R <= 0 || c <= 0) return 0;
-    if (!x || ldx < c) return tfail(XV_ERR_BAD_ARG, "dropout: bad argument");
-    if (!(keep_prob > 0.f) || keep_prob > 1.f) return tfail(XV_ERR_BAD_ARG, "dropout: keep_prob must be in (0, 1]");
+    if (!x || ldx < c) return fail(XV_ERR_BAD_ARG, "dropout: bad argument");
+    if (!(keep_prob > 0.f) || keep_prob > 1.f) return fail(XV_ERR_BAD_ARG, "dropout: keep_prob must be in (0, 1]");
     if (keep_prob == 1.f) return 0;
     const double thr = (double)keep_prob * 4294967296.0;
     const size_t n = (size_t)R * c;
     hipLaunchKernelGGL(dropout_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65536)), dim3(256), 0, (hipStream_t)stream, x,
                        (long)R, c, ldx, seed, (uint32_t)std::min(thr, 4294967295.0), 1.f / keep_prob);
-    return tcheck("dropout_kernel");
+    return launch_status("dropout_kernel");
 }
 
 int xv_prelu_backward_f32(float *dr, float *z, int ld, int64_t R, int c, const float *alpha, void *stream)
 {
     if (R <= 0 || c <= 0) return 0;
-    if (!dr || !z || !alpha || ld < c) return tfail(XV_ERR_BAD_ARG, "prelu_backward: bad argument");
+    if (!dr || !z || !alpha || ld < c) return fail(XV_ERR_BAD_ARG, "prelu_backward: bad argument");
     const size_t n = (size_t)R * c;
     hipLaunchKernelGGL(prelu_backward_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65536)), dim3(256), 0,
                        (hipStream_t)stream, dr, z, (long)R, c, ld, alpha);
-    return tcheck("prelu_backward_kernel");
+    return launch_status("prelu_backward_kernel");
 }
 
 int xv_l2_normalize_rows_f32(const float *x, int ldx, int nrows, int c, float *y, int ldy, float *norm, void *stream)
 {
     if (nrows <= 0) return 0;
-    if (!x || !y || !norm || c <= 0 || ldx < c || ldy < c) return tfail(XV_ERR_BAD_ARG, "l2_normalize_rows: bad argument");
+    if (!x || !y || !norm || c <= 0 || ldx < c || ldy < c) return fail(XV_ERR_BAD_ARG, "l2_normalize_rows: bad argument");
     hipLaunchKernelGGL(l2_normalize_rows_kernel, dim3(nrows), dim3(64), 0, (hipStream_t)stream, x, ldx, c, y, ldy, norm);
-    return tcheck("l2_normalize_rows_kernel");
+    return launch_status("l2_normalize_rows_kernel");
 }
 
 int xv_l2_normalize_backward_f32(const float *dy, const float *y, const float *norm, int nrows, int c, float *dx, void *stream)
 {
     if (nrows <= 0) return 0;
-    if (!dy || !y || !norm || !dx || c <= 0) return tfail(XV_ERR_BAD_ARG, "l2_normalize_backward: bad argument");
+    if (!dy || !y || !norm || !dx || c <= 0) return fail(XV_ERR_BAD_ARG, "l2_normalize_backward: bad argument");
     hipLaunchKernelGGL(l2_normalize_backward_kernel, dim3(nrows), dim3(64), 0, (hipStream_t)stream, dy, y, norm, c, dx);
-    return tcheck("l2_normalize_backward_kernel");
+    return launch_status("l2_normalize_backward_kernel");
 }
 
 int xv_am_margin_f32(float *cosines, const int32_t *labels, int nrows, int nclasses, float scale, float margin, void *stream)
 {
     if (nrows <= 0 || nclasses <= 0) return 0;
-    if (!cosines || !labels) return tfail(XV_ERR_BAD_ARG, "am_margin: bad argument");
+    if (!cosines || !labels) return fail(XV_ERR_BAD_ARG, "am_margin: bad argument");
     const size_t n = (size_t)nrows * nclasses;
     hipLaunchKernelGGL(am_margin_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream,
                        cosines, labels, nrows, nclasses, scale, margin);
-    return tcheck("am_margin_kernel");
+    return launch_status("am_margin_kernel");
 }
 
 int xv_ema_f32(float *moving, const float *batch, int n, float decay, void *stream)
 {
-    if (!moving || !batch || n <= 0) return tfail(XV_ERR_BAD_ARG, "ema: bad argument");
+    if (!moving || !batch || n <= 0) return fail(XV_ERR_BAD_ARG, "ema: bad argument");
     hipLaunchKernelGGL(ema_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, moving, batch, n, decay);
-    return tcheck("ema_kernel");
+    return launch_status("ema_kernel");
 }
 
 }  // extern "C"

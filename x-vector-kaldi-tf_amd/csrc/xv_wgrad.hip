@@ -19,15 +19,7 @@
 //     (80-byte channel stride: both the writes' 8-lane groups and the reads' 16-lane groups touch distinct 16-byte slots);
 //   * a fragment is then ONE ds_read_b128 per (32-channel tile, k-step, plane): 16 reads for the 24 MFMAs of a step and wave.
 // Workgroup = 4 waves as 2 x 2, 128 x 128 tile, 64 x 64 per wave; next step's 32 loads per thread are in flight under the MFMAs.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "xvector_hip.h"
-
-extern "C" void xv_internal_set_error(const char *msg);
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "xv_device.h"
 
 namespace {
 
@@ -35,7 +27,6 @@ constexpr int WT = 128;           // tile edge (channels)
 constexpr int WR = 32;            // rows per step = two MFMA k-steps
 constexpr int CH_STRIDE = 80;     // bytes per channel in the LDS image: 32 rows x 2 bytes + 16 (see above)
 constexpr int PLANE = WT * CH_STRIDE;                  // 10240: one operand, one of hi / lo
-constexpr int RSRC_FLAGS = 0x00020000;                 // raw buffer, 32-bit data format (gfx9 family dword 3)
 
 struct WgradParams {
     const float *x;
@@ -68,8 +59,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16x3_kernel(const WgradParams 
 
     // operands through buffer descriptors of exactly R rows: a row index outside [0, R) -- before the first row the byte offset
     // wraps to > 2^31 -- is out of range and loads as zero (the host checks R * ld * 4 < 2^31)
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.x), 0, (int)(p.R * p.ldx * 4), RSRC_FLAGS);
-    const __amdgpu_buffer_rsrc_t zrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.dz), 0, (int)(p.R * p.lddz * 4), RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.x), 0, (int)(p.R * p.ldx * 4), XV_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t zrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.dz), 0, (int)(p.R * p.lddz * 4), XV_RSRC_FLAGS);
     const int ch = tid & 127, half = tid >> 7;
     const bool xc_ok = c0 + ch < p.cin, zc_ok = o0 + ch < p.cout;      // a ragged last tile: the column would alias the next row
     const int xcol = (c0 + ch) * 4, zcol = (o0 + ch) * 4;
@@ -217,25 +208,19 @@ size_t xv_wgrad_bias_workspace_bytes(int64_t R, int cin, int cout, int K)
 int xv_wgrad_bias_bf16x3(const float *x, int ldx, const float *dz, int lddz, int64_t R, int cin, int cout, int K, int dilation, float *dw,
                          float *db, void *workspace, void *stream)
 {
-    if (!db || !workspace) {
-        xv_internal_set_error("wgrad_bias_bf16x3: db and the workspace of xv_wgrad_bias_workspace_bytes are required");
-        return XV_ERR_BAD_ARG;
-    }
+    if (!db || !workspace)
+        return fail(XV_ERR_BAD_ARG, "wgrad_bias_bf16x3: db and the workspace of xv_wgrad_bias_workspace_bytes are required");
     return wgrad_bf16x3_impl(x, ldx, dz, lddz, R, cin, cout, K, dilation, dw, db, workspace, stream);
 }
 
 static int wgrad_bf16x3_impl(const float *x, int ldx, const float *dz, int lddz, int64_t R, int cin, int cout, int K, int dilation, float *dw,
                              float *db, void *workspace, void *stream)
 {
-    if (!x || !dz || !dw || R <= 0 || cin <= 0 || cout <= 0 || K <= 0 || !(K & 1) || dilation <= 0 || ldx < cin || lddz < cout) {
-        xv_internal_set_error("wgrad_bf16x3: bad argument");
-        return XV_ERR_BAD_ARG;
-    }
+    if (!x || !dz || !dw || R <= 0 || cin <= 0 || cout <= 0 || K <= 0 || !(K & 1) || dilation <= 0 || ldx < cin || lddz < cout)
+        return fail(XV_ERR_BAD_ARG, "wgrad_bf16x3: bad argument");
     if ((double)R * ldx * 4 >= 2147483648.0 || (double)R * lddz * 4 >= 2147483648.0) {   // 32-bit buffer offsets
-        if (db) {
-            xv_internal_set_error("wgrad_bias_bf16x3: matrices must stay below 2^31 bytes (use xv_wgrad_bf16x3 + xv_col_sums_f32)");
-            return XV_ERR_UNSUPPORTED;
-        }
+        if (db)
+            return fail(XV_ERR_UNSUPPORTED, "wgrad_bias_bf16x3: matrices must stay below 2^31 bytes (use xv_wgrad_bf16x3 + xv_col_sums_f32)");
         return xv_wgrad_f32(x, ldx, dz, lddz, R, cin, cout, K, dilation, dw, workspace, stream);
     }
     WgradParams p{};
@@ -244,31 +229,25 @@ static int wgrad_bf16x3_impl(const float *x, int ldx, const float *dz, int lddz,
     const size_t ws_bytes = xv_wgrad_workspace_bytes(R, cin, cout, K);
     const long splits = ws_bytes ? (long)(ws_bytes / ((size_t)K * cin * (size_t)cout * sizeof(float))) : 1;
     p.rows_per_split = ((R + splits - 1) / splits + WR - 1) / WR * WR;
-    if (splits > 1 && !workspace) {
-        xv_internal_set_error("wgrad_bf16x3: workspace required");
-        return XV_ERR_BAD_ARG;
-    }
+    if (splits > 1 && !workspace)
+        return fail(XV_ERR_BAD_ARG, "wgrad_bf16x3: workspace required");
     p.out = splits > 1 ? (float *)workspace : dw;
     p.db_part = db ? reinterpret_cast<double *>((char *)workspace + (ws_bytes + 7) / 8 * 8) : nullptr;
     hipStream_t st = (hipStream_t)stream;
     if (db) hipLaunchKernelGGL(wgrad_bf16x3_kernel<true>, dim3((unsigned)(K * p.n_ct * p.n_ot), (unsigned)splits), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(wgrad_bf16x3_kernel<false>, dim3((unsigned)(K * p.n_ct * p.n_ot), (unsigned)splits), dim3(256), 0, st, p);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && db) {
+    int rc = launch_status();
+    if (rc == 0 && db) {
         hipLaunchKernelGGL(bias_splits_kernel, dim3((unsigned)((cout + 255) / 256)), dim3(256), 0, st, (const double *)p.db_part, cout, (int)splits, db);
-        e = hipGetLastError();
+        rc = launch_status();
     }
-    if (e == hipSuccess && splits > 1) {
+    if (rc == 0 && splits > 1) {
         const size_t n = (size_t)K * cin * cout;
         hipLaunchKernelGGL(sum_splits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float *)workspace, n,
                            (int)splits, dw);
-        e = hipGetLastError();
+        rc = launch_status();
     }
-    if (e != hipSuccess) {
-        xv_internal_set_error(hipGetErrorString(e));
-        return (int)e;
-    }
-    return 0;
+    return rc;
 }
 
 }  // extern "C"

@@ -12,31 +12,109 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
 ABI_VERSION = 23
 
-# every symbol include/xvector_hip.h declares (tests check the .so exports all of them)
-SYMBOLS = ("xv_version", "xv_last_error", "xv_set_tuning", "xv_pack_weights_f32", "xv_fold_bn_f32", "xv_tdnn_layer_f32",
-           "xv_stats_pool_workspace_bytes", "xv_stats_pool_f32", "xv_fc_f32", "xv_fc_splitk_workspace_bytes", "xv_fc_splitk_f32", "xv_chunk_average_f32",
-           "xv_packed_weights_bf16x3_bytes", "xv_pack_weights_bf16x3", "xv_pack_weights_bf16x3_many", "xv_split_row_bytes", "xv_split_encode_f32",
-           "xv_split_decode_f32", "xv_tdnn_layer_bf16x3", "xv_tdnn_layer_bf16x3_sums", "xv_tdnn_layer_bf16x3_moments", "xv_fc_bf16x3",
-           "xv_block_stats_bytes", "xv_tdnn_layer_pool_bf16x3", "xv_stats_pool_blocks_f32", "xv_tdnn_layer_pool_f32",
-           "xv_packed_weights_rows_f32_floats", "xv_pack_weights_rows_f32", "xv_tdnn_layer_rows_f32",
-           "xv_toom_supported", "xv_packed_weights_toom_f32_floats", "xv_pack_weights_toom_f32", "xv_tdnn_layer_toom_f32", "xv_tdnn_layer_toom_dilated_f32",
-           "xv_packed_pair_bf16x3_bytes", "xv_pack_pair_bf16x3", "xv_tdnn_pair_pool_bf16x3",
-           "xv_packed_first_bf16x3_bytes", "xv_pack_first_bf16x3", "xv_tdnn_first_bf16x3",
-           "xv_packed_weights_f16bf8_bytes", "xv_pack_weights_f16bf8", "xv_split8_encode_f32", "xv_split8_decode_f32",
-           "xv_tdnn_layer_f16bf8", "xv_tdnn_layer_pool_f16bf8", "xv_tdnn_first_f16bf8",
-           "xv_packed_pair_f16bf8_bytes", "xv_pack_pair_f16bf8", "xv_tdnn_pair_pool_f16bf8",
-           # training step
-           "xv_chunk_moments_f32", "xv_merge_moments_f32", "xv_rows_affine_f32", "xv_rows_affine_split_f32", "xv_wgrad_workspace_bytes", "xv_wgrad_f32", "xv_wgrad_bf16x3",
-           "xv_wgrad_bias_workspace_bytes", "xv_wgrad_bias_bf16x3",
-           "xv_col_sums_workspace_bytes", "xv_col_sums_f32", "xv_bn_act_backward_f32", "xv_bn_act_backward_split_f32", "xv_pool_backward_f32",
-           "xv_bn_act_backward_parts_f32", "xv_col_sums_merge_f32", "xv_pool_bn_act_backward_f32", "xv_bn_moments_fold_f32", "xv_bn_small_forward_f32", "xv_bn_small_backward_f32",
-           "xv_softmax_ce_f32", "xv_adam_f32", "xv_ema_f32", "xv_axpy_f32", "xv_sumsq_workspace_bytes", "xv_sumsq_f32", "xv_dropout_f32", "xv_pack_minibatch_f32", "xv_minibatch_layout",
-           "xv_prelu_backward_f32", "xv_l2_normalize_rows_f32", "xv_l2_normalize_backward_f32", "xv_am_margin_f32",
-           # feature front-end
-           "xv_cmn_sliding_scatter_f32",
-           # self-attentive pooling
-           "xv_attention_scores_f32", "xv_attention_softmax_f32", "xv_attention_pool_workspace_bytes", "xv_attention_pool_f32",
-           "xv_attention_pool_backward_f32", "xv_attention_softmax_backward_f32", "xv_attention_scores_backward_f32")
+# every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
+_vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
+_SIGNATURES = {
+    "xv_version": (_ci, []),
+    "xv_last_error": (ctypes.c_char_p, []),
+    "xv_set_tuning": (_ci, [_ci, _ci]),
+    "xv_pack_weights_f32": (_ci, [_vp, _ci, _ci, _vp, _vp]),
+    "xv_fold_bn_f32": (_ci, [_vp, _vp, _vp, _vp, _cf, _ci, _vp, _vp, _vp]),
+    "xv_tdnn_layer_f32": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _vp]),
+    "xv_packed_weights_rows_f32_floats": (_sz, [_ci, _ci, _ci, _ci]),
+    "xv_pack_weights_rows_f32": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp, _vp]),
+    "xv_tdnn_layer_rows_f32": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _vp, _vp, _ci, _vp]),
+    # "fp32tc": the wide-context layers with fewer multiplications (Toom-Cook F(2, K) over time)
+    "xv_toom_supported": (_ci, [_ci, _ci, _ci, _ci]),
+    "xv_packed_weights_toom_f32_floats": (_sz, [_ci, _ci, _ci]),
+    "xv_pack_weights_toom_f32": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp]),
+    "xv_tdnn_layer_toom_f32": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _vp, _vp, _ci, _vp]),
+    "xv_tdnn_layer_toom_dilated_f32": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _ci, _vp]),
+    # bf16x3 split-precision twins
+    "xv_packed_weights_bf16x3_bytes": (_sz, [_ci, _ci, _ci]),
+    "xv_pack_weights_bf16x3": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp]),
+    "xv_pack_weights_bf16x3_many": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "xv_split_row_bytes": (_sz, [_ci]),
+    "xv_split_encode_f32": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp]),
+    "xv_split_decode_f32": (_ci, [_vp, _i64, _ci, _vp, _ci, _vp]),
+    "xv_tdnn_layer_bf16x3": (_ci, [_vp, _ci, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _vp, _ci, _vp]),
+    "xv_tdnn_layer_bf16x3_sums": (_ci, [_vp, _ci, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _ci, _vp, _vp]),
+    "xv_tdnn_layer_bf16x3_moments": (_ci, [_vp, _ci, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _ci, _vp, _vp]),
+    "xv_block_stats_bytes": (_sz, [_i64, _ci]),
+    "xv_tdnn_layer_pool_bf16x3": (_ci, [_vp, _ci, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "xv_stats_pool_blocks_f32": (_ci, [_vp, _ci, _vp, _vp, _ci, _cf, _vp, _vp]),
+    "xv_tdnn_layer_pool_f32": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "xv_packed_first_bf16x3_bytes": (_sz, [_ci, _ci, _ci]),
+    "xv_pack_first_bf16x3": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp]),
+    "xv_tdnn_first_bf16x3": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "xv_packed_pair_bf16x3_bytes": (_sz, [_ci, _ci, _ci]),
+    "xv_pack_pair_bf16x3": (_ci, [_vp, _vp, _ci, _ci, _ci, _vp, _vp]),
+    "xv_tdnn_pair_pool_bf16x3": (_ci, [_vp, _i64, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp]),
+    # f16bf8 split-precision twins of the hidden frame-level layers
+    "xv_packed_weights_f16bf8_bytes": (_sz, [_ci, _ci, _ci]),
+    "xv_pack_weights_f16bf8": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp]),
+    "xv_split8_encode_f32": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp, _vp]),
+    "xv_split8_decode_f32": (_ci, [_vp, _i64, _ci, _vp, _ci, _vp]),
+    "xv_tdnn_layer_f16bf8": (_ci, [_vp, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _vp, _vp]),
+    "xv_tdnn_layer_pool_f16bf8": (_ci, [_vp, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "xv_tdnn_first_f16bf8": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
+    "xv_packed_pair_f16bf8_bytes": (_sz, [_ci, _ci, _ci]),
+    "xv_pack_pair_f16bf8": (_ci, [_vp, _vp, _ci, _ci, _ci, _vp, _vp]),
+    "xv_tdnn_pair_pool_f16bf8": (_ci, [_vp, _i64, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp]),
+    "xv_fc_bf16x3": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp]),
+    "xv_stats_pool_workspace_bytes": (_sz, [_ci, _ci, _ci, _ci]),
+    "xv_stats_pool_f32": (_ci, [_vp, _i64, _ci, _vp, _vp, _ci, _ci, _ci, _cf, _vp, _vp, _vp]),
+    "xv_fc_f32": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp]),
+    "xv_fc_splitk_workspace_bytes": (_sz, [_ci, _ci, _ci]),
+    "xv_fc_splitk_f32": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp]),
+    "xv_chunk_average_f32": (_ci, [_vp, _vp, _vp, _ci, _ci, _vp, _vp]),
+    # training step
+    "xv_chunk_moments_f32": (_ci, [_vp, _i64, _ci, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "xv_merge_moments_f32": (_ci, [_vp, _vp, _ci, _ci, _vp, _vp, _vp]),
+    "xv_rows_affine_f32": (_ci, [_vp, _ci, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _vp]),
+    "xv_rows_affine_split_f32": (_ci, [_vp, _ci, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _vp]),
+    "xv_wgrad_workspace_bytes": (_sz, [_i64, _ci, _ci, _ci]),
+    "xv_wgrad_f32": (_ci, [_vp, _ci, _vp, _ci, _i64, _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "xv_wgrad_bf16x3": (_ci, [_vp, _ci, _vp, _ci, _i64, _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "xv_wgrad_bias_workspace_bytes": (_sz, [_i64, _ci, _ci, _ci]),
+    "xv_wgrad_bias_bf16x3": (_ci, [_vp, _ci, _vp, _ci, _i64, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
+    "xv_col_sums_workspace_bytes": (_sz, [_i64, _ci]),
+    "xv_col_sums_f32": (_ci, [_vp, _ci, _vp, _ci, _i64, _ci, _vp, _vp, _vp, _vp]),
+    "xv_bn_act_backward_f32": (_ci, [_vp, _vp, _ci, _i64, _ci, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _ci, _cf, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "xv_bn_act_backward_split_f32": (_ci, [_vp, _vp, _ci, _i64, _ci, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _ci, _cf, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "xv_bn_act_backward_parts_f32": (_ci, [_vp, _vp, _ci, _i64, _ci, _vp, _vp, _vp, _vp, _cf, _cf, _ci, _cf, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "xv_bn_moments_fold_f32": (_ci, [_vp, _i64, _ci, _cf, _vp, _vp, _cf, _vp, _vp, _vp, _vp, _vp]),
+    "xv_col_sums_merge_f32": (_ci, [_vp, _i64, _ci, _vp, _vp, _vp]),
+    "xv_pool_bn_act_backward_f32": (_ci, [_vp, _vp, _ci, _ci, _vp, _vp, _ci, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _ci, _cf, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "xv_bn_small_forward_f32": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp, _cf, _vp, _vp, _vp, _ci, _vp]),
+    "xv_bn_small_backward_f32": (_ci, [_vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _cf, _ci, _cf, _vp, _vp, _vp, _vp]),
+    "xv_pool_backward_f32": (_ci, [_vp, _ci, _ci, _vp, _vp, _ci, _i64, _vp, _vp, _vp, _vp]),
+    "xv_softmax_ce_f32": (_ci, [_vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp]),
+    "xv_adam_f32": (_ci, [_vp, _vp, _vp, _vp, _i64, _cf, _cf, _cf, _cf, _vp]),
+    "xv_axpy_f32": (_ci, [_vp, _vp, _cf, _i64, _vp]),
+    "xv_sumsq_workspace_bytes": (_sz, [_i64]),
+    "xv_sumsq_f32": (_ci, [_vp, _i64, _vp, _vp, _vp]),
+    "xv_dropout_f32": (_ci, [_vp, _ci, _i64, _ci, ctypes.c_uint64, _cf, _vp]),
+    "xv_minibatch_layout": (_ci, [_ci, _ci, _ci, _i64, _vp, _vp, _vp, _vp]),
+    "xv_pack_minibatch_f32": (_ci, [_vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _i64, _vp]),
+    "xv_prelu_backward_f32": (_ci, [_vp, _vp, _ci, _i64, _ci, _vp, _vp]),
+    "xv_ema_f32": (_ci, [_vp, _vp, _ci, _cf, _vp]),
+    # additive-margin softmax head
+    "xv_l2_normalize_rows_f32": (_ci, [_vp, _ci, _ci, _ci, _vp, _ci, _vp, _vp]),
+    "xv_l2_normalize_backward_f32": (_ci, [_vp, _vp, _vp, _ci, _ci, _vp, _vp]),
+    "xv_am_margin_f32": (_ci, [_vp, _vp, _ci, _ci, _cf, _cf, _vp]),
+    # self-attentive statistics pooling
+    "xv_attention_scores_f32": (_ci, [_vp, _i64, _i64, _ci, _vp, _vp, _vp, _i64, _vp]),
+    "xv_attention_softmax_f32": (_ci, [_vp, _vp, _vp, _ci, _vp, _vp]),
+    "xv_attention_pool_workspace_bytes": (_sz, [_ci, _ci, _ci, _ci]),
+    "xv_attention_pool_f32": (_ci, [_vp, _i64, _ci, _vp, _vp, _vp, _ci, _ci, _ci, _cf, _vp, _vp, _vp]),
+    "xv_attention_pool_backward_f32": (_ci, [_vp, _i64, _ci, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "xv_attention_softmax_backward_f32": (_ci, [_vp, _vp, _vp, _vp, _ci, _vp, _vp]),
+    "xv_attention_scores_backward_f32": (_ci, [_vp, _i64, _vp, _vp, _i64, _ci, _vp, _i64, _vp]),
+    # feature front-end
+    "xv_cmn_sliding_scatter_f32": (_ci, [_vp, _ci, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _vp]),
+}
+SYMBOLS = tuple(_SIGNATURES)      # tests check the header declares exactly these and the .so exports all of them
 
 FMT_F32, FMT_SPLIT, FMT_SPLIT8 = 0, 1, 2
 SPLIT_PAD_BEFORE, SPLIT_PAD_AFTER = 8, 264
@@ -64,189 +142,9 @@ def load():
                               "g.build()'` or `make -C x-vector-kaldi-tf_amd/csrc`)" % SO_PATH)
     import torch  # noqa: F401  (loads torch's libamdhip64 first; see module docstring)
     lib = ctypes.CDLL(SO_PATH)
-    vp, ci, cf, i64, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
-    lib.xv_version.restype = ci
-    lib.xv_version.argtypes = []
-    lib.xv_last_error.restype = ctypes.c_char_p
-    lib.xv_last_error.argtypes = []
-    lib.xv_set_tuning.restype = ci
-    lib.xv_set_tuning.argtypes = [ci, ci]
-    lib.xv_pack_weights_f32.restype = ci
-    lib.xv_pack_weights_f32.argtypes = [vp, ci, ci, vp, vp]
-    lib.xv_fold_bn_f32.restype = ci
-    lib.xv_fold_bn_f32.argtypes = [vp, vp, vp, vp, cf, ci, vp, vp, vp]
-    lib.xv_tdnn_layer_f32.restype = ci
-    lib.xv_tdnn_layer_f32.argtypes = [vp, i64, ci, ci, vp, vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci, vp, vp]
-    lib.xv_packed_weights_rows_f32_floats.restype = sz
-    lib.xv_packed_weights_rows_f32_floats.argtypes = [ci, ci, ci, ci]
-    lib.xv_pack_weights_rows_f32.restype = ci
-    lib.xv_pack_weights_rows_f32.argtypes = [vp, ci, ci, ci, ci, vp, vp]
-    lib.xv_tdnn_layer_rows_f32.restype = ci
-    lib.xv_tdnn_layer_rows_f32.argtypes = [vp, i64, ci, ci, vp, vp, vp, vp, ci, vp, ci, ci, vp, vp, ci, vp]
-    lib.xv_toom_supported.restype = ci
-    lib.xv_toom_supported.argtypes = [ci, ci, ci, ci]
-    lib.xv_packed_weights_toom_f32_floats.restype = sz
-    lib.xv_packed_weights_toom_f32_floats.argtypes = [ci, ci, ci]
-    lib.xv_pack_weights_toom_f32.restype = ci
-    lib.xv_pack_weights_toom_f32.argtypes = [vp, ci, ci, ci, vp, vp]
-    lib.xv_tdnn_layer_toom_f32.restype = ci
-    lib.xv_tdnn_layer_toom_f32.argtypes = [vp, i64, ci, ci, vp, vp, vp, vp, ci, vp, ci, ci, vp, vp, ci, vp]
-    lib.xv_tdnn_layer_toom_dilated_f32.restype = ci
-    lib.xv_tdnn_layer_toom_dilated_f32.argtypes = [vp, i64, ci, ci, vp, vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci, vp]
-    lib.xv_stats_pool_workspace_bytes.restype = sz
-    lib.xv_stats_pool_workspace_bytes.argtypes = [ci, ci, ci, ci]
-    lib.xv_stats_pool_f32.restype = ci
-    lib.xv_stats_pool_f32.argtypes = [vp, i64, ci, vp, vp, ci, ci, ci, cf, vp, vp, vp]
-    lib.xv_fc_f32.restype = ci
-    lib.xv_fc_f32.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp]
-    lib.xv_fc_splitk_workspace_bytes.restype = sz
-    lib.xv_fc_splitk_workspace_bytes.argtypes = [ci, ci, ci]
-    lib.xv_fc_splitk_f32.restype = ci
-    lib.xv_fc_splitk_f32.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp]
-    lib.xv_packed_weights_bf16x3_bytes.restype = sz
-    lib.xv_packed_weights_bf16x3_bytes.argtypes = [ci, ci, ci]
-    lib.xv_pack_weights_bf16x3.restype = ci
-    lib.xv_pack_weights_bf16x3.argtypes = [vp, ci, ci, ci, vp, vp]
-    lib.xv_pack_weights_bf16x3_many.restype = ci
-    lib.xv_pack_weights_bf16x3_many.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.xv_split_row_bytes.restype = sz
-    lib.xv_split_row_bytes.argtypes = [ci]
-    lib.xv_split_encode_f32.restype = ci
-    lib.xv_split_encode_f32.argtypes = [vp, i64, ci, ci, vp, vp]
-    lib.xv_split_decode_f32.restype = ci
-    lib.xv_split_decode_f32.argtypes = [vp, i64, ci, vp, ci, vp]
-    lib.xv_tdnn_layer_bf16x3.restype = ci
-    lib.xv_tdnn_layer_bf16x3.argtypes = [vp, ci, i64, ci, ci, vp, vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci, ci, vp, ci, vp]
-    lib.xv_fc_bf16x3.restype = ci
-    lib.xv_fc_bf16x3.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp]
-    lib.xv_block_stats_bytes.restype = ctypes.c_size_t
-    lib.xv_block_stats_bytes.argtypes = [i64, ci]
-    lib.xv_tdnn_layer_pool_f32.restype = ci
-    lib.xv_tdnn_layer_pool_f32.argtypes = [vp, i64, ci, ci, vp, vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, vp]
-    lib.xv_tdnn_layer_pool_bf16x3.restype = ci
-    lib.xv_tdnn_layer_pool_bf16x3.argtypes = [vp, ci, i64, ci, ci, vp, vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, vp]
-    lib.xv_packed_first_bf16x3_bytes.restype = sz
-    lib.xv_packed_first_bf16x3_bytes.argtypes = [ci, ci, ci]
-    lib.xv_pack_first_bf16x3.restype = ci
-    lib.xv_pack_first_bf16x3.argtypes = [vp, ci, ci, ci, vp, vp]
-    lib.xv_tdnn_first_bf16x3.restype = ci
-    lib.xv_tdnn_first_bf16x3.argtypes = [vp, i64, ci, ci, vp, vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, vp]
-    lib.xv_packed_weights_f16bf8_bytes.restype = sz
-    lib.xv_packed_weights_f16bf8_bytes.argtypes = [ci, ci, ci]
-    lib.xv_pack_weights_f16bf8.restype = ci
-    lib.xv_pack_weights_f16bf8.argtypes = [vp, ci, ci, ci, vp, vp]
-    lib.xv_split8_encode_f32.restype = ci
-    lib.xv_split8_encode_f32.argtypes = [vp, i64, ci, ci, vp, vp, vp]
-    lib.xv_split8_decode_f32.restype = ci
-    lib.xv_split8_decode_f32.argtypes = [vp, i64, ci, vp, ci, vp]
-    lib.xv_tdnn_layer_f16bf8.restype = ci
-    lib.xv_tdnn_layer_f16bf8.argtypes = [vp, i64, ci, vp, vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci, ci, vp, vp]
-    lib.xv_tdnn_layer_pool_f16bf8.restype = ci
-    lib.xv_tdnn_layer_pool_f16bf8.argtypes = [vp, i64, ci, vp, vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, vp]
-    lib.xv_tdnn_first_f16bf8.restype = ci
-    lib.xv_tdnn_first_f16bf8.argtypes = [vp, i64, ci, ci, vp, vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp]
-    lib.xv_packed_pair_f16bf8_bytes.restype = sz
-    lib.xv_packed_pair_f16bf8_bytes.argtypes = [ci, ci, ci]
-    lib.xv_pack_pair_f16bf8.restype = ci
-    lib.xv_pack_pair_f16bf8.argtypes = [vp, vp, ci, ci, ci, vp, vp]
-    lib.xv_tdnn_pair_pool_f16bf8.restype = ci
-    lib.xv_tdnn_pair_pool_f16bf8.argtypes = [vp, i64, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]
-    lib.xv_packed_pair_bf16x3_bytes.restype = sz
-    lib.xv_packed_pair_bf16x3_bytes.argtypes = [ci, ci, ci]
-    lib.xv_pack_pair_bf16x3.restype = ci
-    lib.xv_pack_pair_bf16x3.argtypes = [vp, vp, ci, ci, ci, vp, vp]
-    lib.xv_tdnn_pair_pool_bf16x3.restype = ci
-    lib.xv_tdnn_pair_pool_bf16x3.argtypes = [vp, i64, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]
-    lib.xv_stats_pool_blocks_f32.restype = ci
-    lib.xv_stats_pool_blocks_f32.argtypes = [vp, ci, vp, vp, ci, cf, vp, vp]
-    lib.xv_chunk_average_f32.restype = ci
-    lib.xv_chunk_average_f32.argtypes = [vp, vp, vp, ci, ci, vp, vp]
-    lib.xv_chunk_moments_f32.restype = ci
-    lib.xv_chunk_moments_f32.argtypes = [vp, i64, ci, vp, vp, ci, ci, ci, vp, vp, vp]
-    lib.xv_merge_moments_f32.restype = ci
-    lib.xv_merge_moments_f32.argtypes = [vp, vp, ci, ci, vp, vp, vp]
-    lib.xv_rows_affine_f32.restype = ci
-    lib.xv_rows_affine_f32.argtypes = [vp, ci, i64, ci, vp, vp, vp, vp, ci, vp]
-    lib.xv_rows_affine_split_f32.restype = ci
-    lib.xv_rows_affine_split_f32.argtypes = [vp, ci, i64, ci, vp, vp, vp, vp, ci, vp, vp]
-    lib.xv_wgrad_workspace_bytes.restype = sz
-    lib.xv_wgrad_workspace_bytes.argtypes = [i64, ci, ci, ci]
-    lib.xv_wgrad_f32.restype = ci
-    lib.xv_wgrad_f32.argtypes = [vp, ci, vp, ci, i64, ci, ci, ci, ci, vp, vp, vp]
-    lib.xv_wgrad_bf16x3.restype = ci
-    lib.xv_wgrad_bf16x3.argtypes = lib.xv_wgrad_f32.argtypes
-    lib.xv_wgrad_bias_workspace_bytes.restype = sz
-    lib.xv_wgrad_bias_workspace_bytes.argtypes = [i64, ci, ci, ci]
-    lib.xv_wgrad_bias_bf16x3.restype = ci
-    lib.xv_wgrad_bias_bf16x3.argtypes = [vp, ci, vp, ci, i64, ci, ci, ci, ci, vp, vp, vp, vp]
-    lib.xv_col_sums_workspace_bytes.restype = sz
-    lib.xv_col_sums_workspace_bytes.argtypes = [i64, ci]
-    lib.xv_col_sums_f32.restype = ci
-    lib.xv_col_sums_f32.argtypes = [vp, ci, vp, ci, i64, ci, vp, vp, vp, vp]
-    lib.xv_bn_act_backward_f32.restype = ci
-    lib.xv_bn_act_backward_f32.argtypes = [vp, vp, ci, i64, ci, vp, vp, vp, vp, vp, cf, cf, ci, cf, vp, vp, vp, vp, vp, vp]
-    lib.xv_bn_act_backward_split_f32.restype = ci
-    lib.xv_bn_act_backward_split_f32.argtypes = [vp, vp, ci, i64, ci, vp, vp, vp, vp, vp, cf, cf, ci, cf, vp, vp, vp, vp, vp, vp, vp]
-    lib.xv_tdnn_layer_bf16x3_sums.restype = ci
-    lib.xv_tdnn_layer_bf16x3_sums.argtypes = [vp, ci, i64, ci, ci, vp, vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci, vp, ci, vp, vp]
-    lib.xv_tdnn_layer_bf16x3_moments.restype = ci
-    lib.xv_tdnn_layer_bf16x3_moments.argtypes = [vp, ci, i64, ci, ci, vp, vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci, vp, ci, vp, vp]
-    lib.xv_bn_moments_fold_f32.restype = ci
-    lib.xv_bn_moments_fold_f32.argtypes = [vp, i64, ci, cf, vp, vp, cf, vp, vp, vp, vp, vp]
-    lib.xv_bn_small_forward_f32.restype = ci
-    lib.xv_bn_small_forward_f32.argtypes = [vp, ci, ci, ci, vp, vp, cf, vp, vp, vp, ci, vp]
-    lib.xv_bn_small_backward_f32.restype = ci
-    lib.xv_bn_small_backward_f32.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, cf, ci, cf, vp, vp, vp, vp]
-    lib.xv_bn_act_backward_parts_f32.restype = ci
-    lib.xv_bn_act_backward_parts_f32.argtypes = [vp, vp, ci, i64, ci, vp, vp, vp, vp, cf, cf, ci, cf, vp, vp, vp, vp, vp, vp, vp]
-    lib.xv_col_sums_merge_f32.restype = ci
-    lib.xv_col_sums_merge_f32.argtypes = [vp, i64, ci, vp, vp, vp]
-    lib.xv_pool_bn_act_backward_f32.restype = ci
-    lib.xv_pool_bn_act_backward_f32.argtypes = [vp, vp, ci, ci, vp, vp, ci, i64, vp, vp, vp, vp, vp, vp, cf, cf, ci, cf, vp, vp, vp, vp, vp, vp]
-    lib.xv_pool_backward_f32.restype = ci
-    lib.xv_pool_backward_f32.argtypes = [vp, ci, ci, vp, vp, ci, i64, vp, vp, vp, vp]
-    lib.xv_softmax_ce_f32.restype = ci
-    lib.xv_softmax_ce_f32.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp]
-    lib.xv_adam_f32.restype = ci
-    lib.xv_adam_f32.argtypes = [vp, vp, vp, vp, i64, cf, cf, cf, cf, vp]
-    lib.xv_ema_f32.restype = ci
-    lib.xv_ema_f32.argtypes = [vp, vp, ci, cf, vp]
-    lib.xv_axpy_f32.restype = ci
-    lib.xv_axpy_f32.argtypes = [vp, vp, cf, i64, vp]
-    lib.xv_sumsq_workspace_bytes.restype = sz
-    lib.xv_sumsq_workspace_bytes.argtypes = [i64]
-    lib.xv_sumsq_f32.restype = ci
-    lib.xv_sumsq_f32.argtypes = [vp, i64, vp, vp, vp]
-    lib.xv_dropout_f32.restype = ci
-    lib.xv_dropout_f32.argtypes = [vp, ci, i64, ci, ctypes.c_uint64, cf, vp]
-    lib.xv_minibatch_layout.restype = ci
-    lib.xv_minibatch_layout.argtypes = [ci, ci, ci, i64, vp, vp, vp, vp]
-    lib.xv_pack_minibatch_f32.restype = ci
-    lib.xv_pack_minibatch_f32.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, i64, vp]
-    lib.xv_prelu_backward_f32.restype = ci
-    lib.xv_prelu_backward_f32.argtypes = [vp, vp, ci, i64, ci, vp, vp]
-    lib.xv_l2_normalize_rows_f32.restype = ci
-    lib.xv_l2_normalize_rows_f32.argtypes = [vp, ci, ci, ci, vp, ci, vp, vp]
-    lib.xv_l2_normalize_backward_f32.restype = ci
-    lib.xv_l2_normalize_backward_f32.argtypes = [vp, vp, vp, ci, ci, vp, vp]
-    lib.xv_am_margin_f32.restype = ci
-    lib.xv_am_margin_f32.argtypes = [vp, vp, ci, ci, cf, cf, vp]
-    lib.xv_cmn_sliding_scatter_f32.restype = ci
-    lib.xv_cmn_sliding_scatter_f32.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, vp]
-    lib.xv_attention_scores_f32.restype = ci
-    lib.xv_attention_scores_f32.argtypes = [vp, i64, i64, ci, vp, vp, vp, i64, vp]
-    lib.xv_attention_softmax_f32.restype = ci
-    lib.xv_attention_softmax_f32.argtypes = [vp, vp, vp, ci, vp, vp]
-    lib.xv_attention_pool_workspace_bytes.restype = sz
-    lib.xv_attention_pool_workspace_bytes.argtypes = [ci, ci, ci, ci]
-    lib.xv_attention_pool_f32.restype = ci
-    lib.xv_attention_pool_f32.argtypes = [vp, i64, ci, vp, vp, vp, ci, ci, ci, cf, vp, vp, vp]
-    lib.xv_attention_pool_backward_f32.restype = ci
-    lib.xv_attention_pool_backward_f32.argtypes = [vp, i64, ci, vp, vp, vp, ci, ci, vp, vp, vp, i64, vp, vp]
-    lib.xv_attention_softmax_backward_f32.restype = ci
-    lib.xv_attention_softmax_backward_f32.argtypes = [vp, vp, vp, vp, ci, vp, vp]
-    lib.xv_attention_scores_backward_f32.restype = ci
-    lib.xv_attention_scores_backward_f32.argtypes = [vp, i64, vp, vp, i64, ci, vp, i64, vp]
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.xv_version() != ABI_VERSION:
         raise XvectorHipError("libxvector_hip.so ABI version %d != expected %d" % (lib.xv_version(), ABI_VERSION))
     _lib = lib
