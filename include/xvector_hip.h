@@ -52,7 +52,7 @@ extern "C" {
 #define XV_ERR_BAD_ARG (-1)
 #define XV_ERR_UNSUPPORTED (-2)
 
-/* Library / ABI version (increments whenever an entry point is added or changed; currently 23). */
+/* Library / ABI version (increments whenever an entry point is added or changed; currently 24). */
 int xv_version(void);
 /* Thread-local description of the last non-zero return. */
 const char *xv_last_error(void);
@@ -504,6 +504,44 @@ int xv_attention_scores_backward_f32(float *nonlin, int64_t ldn, const float *ds
 int xv_cmn_sliding_scatter_f32(const float *x, int ldx, int feat_dim, const int32_t *utt_start, const int32_t *utt_len,
                                int n_utts, int max_len, int cmn_window, int center, int min_window, const int32_t *dst_row,
                                float *y, int ldy, void *stream);
+
+/* ---- PLDA / cosine scoring back-end ------------------------------------------------------------
+ * What stage 9 of the recipe does with ivector-subtract-global-mean | transform-vec | ivector-normalize-length |
+ * ivector-plda-scoring, for the part that scales with the data.  The PLDA log-likelihood ratio (Kaldi Plda::LogLikelihoodRatio)
+ * is a dot product of length K = 2d plus a per-enrolment constant r:
+ *   enrolment row [ (a/v) z , 1/v - 1/w ],  test row [ t , -t^2/2 ],  r = -1/2 sum a^2 z^2/v + 1/2 sum (log w - log v),
+ *   a = n psi/(n psi + 1), v = 1 + psi/(n psi + 1), w = 1 + psi   (n = the enrolment vector's utterance count).
+ * xv_backend_prepare_f32  operand rows out[N, ldo] (and r[N]) from raw vectors x[N, D] (ldx):
+ *     y = lda (x - mean) + lda_offset        lda [dim, D] (ld_lda) exact-fp32 MFMA; NULL: y = x - mean (dim == D); mean NULL: 0;
+ *                                            lda_offset NULL: 0
+ *     length_norm: y *= sqrt(dim) / |y|      (ivector-normalize-length; a zero vector is left as it is)
+ *     z = P (y - m), z *= sqrt(dim / sum_k z_k^2 / (psi_k + 1/n))    (Plda::TransformIvector; n = num_utts[row], NULL: 1);
+ *                                            plda_transform [dim, dim] row-major, plda_mean [dim], plda_psi [dim]: all three
+ *                                            or none (NULL: z = y)
+ *     side XV_SIDE_PLAIN   out = z (K = dim)            XV_SIDE_ENROL  out = enrolment row (K = 2 dim), r written
+ *          XV_SIDE_TEST    out = test row (K = 2 dim)   XV_SIDE_COSINE out = z / |z| (K = dim)
+ *   Columns [K, ldo) are written with zeros: ldo is the operand width Kpad of the scorers, a multiple of XV_BACKEND_KSTEP.
+ *   r (may be NULL) receives the row's constant (0 except on the enrolment side).  ENROL / TEST need the PLDA.
+ *   D <= 2048 and dim <= 256, else XV_ERR_UNSUPPORTED.
+ * xv_score_matrix_f32  scores[e, t] (ld_scores) = sum_{k < kpad} E[e, k] T[t, k] + r[e]   (r NULL: + 0) for every
+ *   e < n_enrol, t < n_test, on the exact-fp32 MFMA.  Fixed summation order: one fp32 accumulator per score, k ascending from 0,
+ *   no split-K, r added after the dot product.  E, T: row stride ldk (a multiple of 4 floats, 16-byte aligned), kpad a multiple
+ *   of XV_BACKEND_KSTEP, <= 1024 (else XV_ERR_UNSUPPORTED).
+ * xv_score_pairs_f32  scores[i] = the same expression for the trial (e_idx[i], t_idx[i]), as an fmaf chain k ascending from 0:
+ *   bit-identical to the cell of xv_score_matrix_f32, whatever the other trials of the list. */
+#define XV_BACKEND_KSTEP 8
+#define XV_SIDE_PLAIN 0
+#define XV_SIDE_ENROL 1
+#define XV_SIDE_TEST 2
+#define XV_SIDE_COSINE 3
+int xv_backend_prepare_f32(const float *x, int64_t ldx, int n_rows, int dim_in, const int32_t *num_utts, const float *mean,
+                           const float *lda, int64_t ld_lda, const float *lda_offset, int dim, int length_norm,
+                           const float *plda_transform, const float *plda_mean, const float *plda_psi, int side, float *out,
+                           int64_t ldo, float *r, void *stream);
+int xv_score_matrix_f32(const float *e, const float *t, int64_t ldk, int kpad, int n_enrol, int n_test, const float *r,
+                        float *scores, int64_t ld_scores, void *stream);
+int xv_score_pairs_f32(const float *e, const float *t, int64_t ldk, int kpad, const int32_t *e_idx, const int32_t *t_idx,
+                       int64_t n_trials, const float *r, float *scores, void *stream);
 
 #ifdef __cplusplus
 }

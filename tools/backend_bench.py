@@ -1,0 +1,153 @@
+"""Timings of the scoring back-end: prepare at N = 100 k, D = 512; the dense scorer at Ne = Nt = 16384 against the
+157.3 TF fp32-MFMA peak; the trial scorer at 2 M trials; the `plda_backend.py score` CLI on an SRE16-sized synthetic job with a
+read / prepare / score / write breakdown.  Device events after warm-up.   python tools/backend_bench.py [--fit]
+(--fit: also time the host fp64 LDA + PLDA fits at N = 100 k, D = 512; needs no GPU)."""
+import os, shutil, sys, tempfile, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TWIN = os.path.join(ROOT, "x-vector-kaldi-tf_amd", "local", "tf")
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "x-vector-kaldi-tf_amd")); sys.path.insert(0, TWIN)
+import numpy as np
+
+PEAK_TF = 157.3
+
+
+def fit_timing():
+    from xvector_amd import backend
+    rng = np.random.default_rng(0)
+    N, D, S = 100000, 512, 5000
+    lab = rng.integers(0, S, N)
+    x = rng.standard_normal((S, D))[lab] + rng.standard_normal((N, D))
+    t0 = time.perf_counter()
+    lda = backend.fit_lda(x, lab, 200)
+    t1 = time.perf_counter()
+    y = x @ lda[:, :D].T + lda[:, D]
+    groups = [np.flatnonzero(lab == s) for s in range(S)]
+    t2 = time.perf_counter()
+    backend.fit_plda(y, groups)
+    t3 = time.perf_counter()
+    print("host fp64 fits, N = %d, D = %d, %d speakers: fit_lda (d = 200) %.2f s, fit_plda (d = 200, 10 EM iterations) %.2f s" %
+          (N, D, S, t1 - t0, t3 - t2))
+
+
+def timed(fn, reps):
+    import torch
+    for _ in range(3):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record(); torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def gpu_timing():
+    import torch
+    from xvector_amd import backend, hiplib
+    dev = "cuda:0"
+    rng = np.random.default_rng(1)
+    N, D = 100000, 512
+    x = torch.randn((N, D), device=dev)
+    nu = torch.randint(1, 10, (N,), dtype=torch.int32, device=dev)
+    mean = torch.randn(D, device=dev) * 0.1
+    for d in (100, 200):
+        lda = torch.randn((d, D), device=dev) / D ** 0.5
+        a0 = torch.randn(d, device=dev)
+        q, _ = np.linalg.qr(rng.standard_normal((d, d)))
+        P = torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)).to(dev)
+        m = torch.zeros(d, device=dev)
+        psi = torch.from_numpy(np.sort(rng.uniform(0.1, 5, d))[::-1].astype(np.float32).copy()).to(dev)
+        out = torch.empty((N, backend.kpad_for(2 * d)), device=dev)
+        r = torch.empty(N, device=dev)
+        ms = timed(lambda: hiplib.backend_prepare(x, out, hiplib.SIDE_ENROL, nu, mean, lda, a0, True, P, m, psi, r), 20)
+        fl = 2.0 * N * d * (D + d)
+        print("prepare (enrolment side) N = %d, D = %d, d = %d: %.3f ms = %.1f M vectors/s, %.1f TF/s algorithmic (%.0f GB/s of x)" %
+              (N, D, d, ms, N / ms / 1e3, fl / ms / 1e9, N * D * 4 / ms / 1e6))
+    n = 16384
+    for K in (200, 400):
+        E = torch.randn((n, K), device=dev)
+        T = torch.randn((n, K), device=dev)
+        r = torch.randn(n, device=dev)
+        S = torch.empty((n, n), device=dev)
+        ms = timed(lambda: hiplib.score_matrix(E, T, r, S), 10)
+        tf = 2.0 * n * n * K / ms / 1e9
+        print("score_matrix Ne = Nt = %d, K = %d: %.3f ms = %.1f TF/s algorithmic = %.2f of the %.1f TF fp32-MFMA peak "
+              "(%.0f GB/s of scores written)" % (n, K, ms, tf, tf / PEAK_TF, PEAK_TF, n * n * 4 / ms / 1e6))
+    ne, nt, M, K = 800, 9300, 2000000, 200
+    E = torch.randn((ne, K), device=dev)
+    T = torch.randn((nt, K), device=dev)
+    r = torch.randn(ne, device=dev)
+    ei = torch.randint(0, ne, (M,), dtype=torch.int32, device=dev)
+    ti = torch.randint(0, nt, (M,), dtype=torch.int32, device=dev)
+    out = torch.empty(M, device=dev)
+    lib = hiplib.require_gpu()
+    stream = hiplib._stream()
+    call = lambda: lib.xv_score_pairs_f32(hiplib._ptr(E), hiplib._ptr(T), K, K, hiplib._ptr(ei), hiplib._ptr(ti), M, hiplib._ptr(r),
+                                          hiplib._ptr(out), stream)
+    ms = timed(call, 20)
+    print("score_pairs %d trials (Ne = %d, Nt = %d, K = %d): %.3f ms = %.0f M trials/s" % (M, ne, nt, K, ms, M / ms / 1e3))
+    Sd = torch.empty((ne, nt), device=dev)
+    ms = timed(lambda: hiplib.score_matrix(E, T, r, Sd), 20)
+    print("score_matrix on the same job (all %d cells): %.3f ms" % (ne * nt, ms))
+
+
+def cli_job():
+    """SRE16-sized: 800 enrolment speakers, 9.3 k test segments, 2 M trials, D = 512, LDA d = 100."""
+    import torch
+    import kaldi_io
+    import plda_backend
+    from xvector_amd import backend
+    rng = np.random.default_rng(2)
+    D, d, ne, nt, M = 512, 100, 800, 9300, 2000000
+    tmp = tempfile.mkdtemp(prefix="backend_bench_")
+    ek = ["spk%04d" % i for i in range(ne)]
+    tk = ["seg%05d" % i for i in range(nt)]
+    with kaldi_io.TableWriter(tmp + "/enrol.ark", tmp + "/enrol.scp") as w:
+        kaldi_io.write_vec_flt_batch(w, ek, list(rng.standard_normal((ne, D)).astype(np.float32)))
+    with kaldi_io.TableWriter(tmp + "/test.ark", tmp + "/test.scp") as w:
+        kaldi_io.write_vec_flt_batch(w, tk, list(rng.standard_normal((nt, D)).astype(np.float32)))
+    open(tmp + "/num_utts.ark", "w").writelines("%s %d\n" % (k, rng.integers(1, 6)) for k in ek)
+    ei = rng.integers(0, ne, M); ti = rng.integers(0, nt, M)
+    open(tmp + "/trials", "w").writelines("%s %s target\n" % (ek[a], tk[b]) for a, b in zip(ei, ti))
+    kaldi_io.write_vec_flt(tmp + "/mean.vec", (rng.standard_normal(D) * 0.1).astype(np.float32))
+    backend.write_transform(tmp + "/transform.mat", rng.standard_normal((d, D + 1)) / D ** 0.5)
+    q, _ = np.linalg.qr(rng.standard_normal((d, d)))
+    backend.write_plda(tmp + "/plda", backend.Plda(np.zeros(d), q, np.sort(rng.uniform(0.1, 5, d))[::-1]))
+    args = ["score", "--num-utts=ark:%s/num_utts.ark" % tmp, "--mean", tmp + "/mean.vec", "--lda", tmp + "/transform.mat",
+            tmp + "/plda", "scp:%s/enrol.scp" % tmp, "scp:%s/test.scp" % tmp, tmp + "/trials", tmp + "/scores"]
+    plda_backend.main(args)                                   # warm-up (library load, kernels)
+    # the same steps as cmd_score, timed one by one
+    t = [time.perf_counter()]
+    plda = backend.read_plda(tmp + "/plda")
+    enrol = plda_backend.read_vectors("scp:%s/enrol.scp" % tmp)
+    test = plda_backend.read_vectors("scp:%s/test.scp" % tmp)
+    nu = {k: int(v[0]) for k, v in plda_backend.read_table(tmp + "/num_utts.ark").items()}
+    epos = {k: i for i, k in enumerate(enrol)}; tpos = {k: i for i, k in enumerate(test)}
+    k1, k2, a, b = [], [], [], []
+    for line in open(tmp + "/trials"):
+        p = line.split()
+        k1.append(p[0]); k2.append(p[1]); a.append(epos[p[0]]); b.append(tpos[p[1]])
+    mean = kaldi_io.read_vec_flt(tmp + "/mean.vec").astype(np.float32)
+    lda = backend.read_transform(tmp + "/transform.mat")
+    t.append(time.perf_counter())
+    sc = backend.Scorer(np.stack(list(enrol.values())), np.stack(list(test.values())), plda,
+                        np.array([nu[k] for k in enrol], np.int32), mean, lda)
+    torch.cuda.synchronize(); t.append(time.perf_counter())
+    s = sc.score_trials(a, b)
+    t.append(time.perf_counter())
+    plda_backend.write_scores(tmp + "/scores", k1, k2, s)
+    t.append(time.perf_counter())
+    w0 = time.perf_counter(); plda_backend.main(args); w1 = time.perf_counter()
+    dt = np.diff(t)
+    print("score CLI, %d enrolment speakers x %d test segments, %d trials, D = %d, d = %d: whole command %.2f s; steps: read %.2f s, "
+          "prepare %.3f s, score %.3f s (%s, incl. copy back), write %.2f s" %
+          (ne, nt, M, D, d, w1 - w0, dt[0], dt[1], dt[2], "dense-then-gather" if sc.use_dense(M) else "pairs", dt[3]))
+    shutil.rmtree(tmp)
+
+
+if __name__ == "__main__":
+    if "--fit" in sys.argv:
+        fit_timing()
+    else:
+        gpu_timing()
+        cli_job()

@@ -1,0 +1,225 @@
+#!/usr/bin/env python
+"""The recipe's back-end (stages 8-9 of run.sh) without Kaldi binaries.  Each subcommand is named after the binary it replaces:
+
+  mean         ivector-mean scp:xvector.scp mean.vec
+  compute-lda  ivector-subtract-global-mean scp:xvector.scp ark:- | ivector-compute-lda --total-covariance-factor=f --dim=d
+               ark:- utt2spk transform.mat
+  compute-plda ivector-compute-plda [--num-em-iters n] ark:spk2utt <vectors> plda; with --lda transform.mat the vectors first
+               go through stage 8's chain on the GPU (subtract the set's own mean | transform-vec | ivector-normalize-length)
+  score        ivector-plda-scoring [--num-utts=ark:num_utts.ark] plda <enrol> <test> trials scores; with --mean / --lda the
+               stage-9 chain (ivector-subtract-global-mean mean.vec | transform-vec | ivector-normalize-length) runs on the GPU
+               instead of Kaldi pipes; --scoring cosine scores the cosine of the same chain's vectors instead of the PLDA LLR
+  compute-eer  compute-eer <file of "score target|nontarget" lines, or ->   (prints the EER in percent)
+
+Vector tables are ``scp:<file>`` or ``ark:<file>`` (options before the colon, e.g. ``ark,s,cs:``, are accepted and ignored).
+The fits run on the host in float64 (xvector_amd/backend.py), preparing and scoring on the MI355X: there is no CPU fallback.
+"""
+from __future__ import print_function
+
+import argparse
+import logging
+import os
+import sys
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+if _HERE not in sys.path:
+    sys.path.insert(0, _HERE)
+sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))
+
+import kaldi_io  # noqa: E402
+
+logger = logging.getLogger('plda_backend')
+logger.addHandler(logging.StreamHandler())
+logger.setLevel(logging.INFO)
+
+
+def read_vectors(rspec):
+    """{key: float32 vector} of an ``scp:`` / ``ark:`` table (insertion order kept)."""
+    kind, _, path = rspec.partition(":")
+    if not path:
+        raise SystemExit("expected scp:<file> or ark:<file>, got %r" % rspec)
+    kind = kind.split(",")[0]
+    if kind == "scp":
+        it = kaldi_io.read_vec_flt_scp(path)
+    elif kind == "ark":
+        it = kaldi_io.read_vec_flt_ark(path)
+    else:
+        raise SystemExit("unsupported table %r (scp: or ark: files only, no pipes)" % rspec)
+    return {k: np.asarray(v, dtype=np.float32) for k, v in it}
+
+
+def read_table(path):
+    """Lines ``key value...`` -> {key: [values]}; ``ark:``/``ark,t:`` prefixes are stripped."""
+    if ":" in path and path.split(":", 1)[0].split(",")[0] == "ark":
+        path = path.split(":", 1)[1]
+    out = {}
+    with open(path, "rt") as f:
+        for line in f:
+            parts = line.split()
+            if parts:
+                out[parts[0]] = parts[1:]
+    return out
+
+
+def _stack(vectors, keys):
+    return np.stack([vectors[k] for k in keys]).astype(np.float32)
+
+
+def cmd_mean(args):
+    vectors = read_vectors(args.vectors)
+    x = _stack(vectors, list(vectors)).astype(np.float64)
+    mean = x.mean(axis=0).astype(np.float32)
+    kaldi_io.write_vec_flt(args.mean_vec, mean)
+    logger.info("Wrote mean of %d vectors of dimension %d" % (x.shape[0], x.shape[1]))
+
+
+def cmd_compute_lda(args):
+    from xvector_amd import backend
+    vectors = read_vectors(args.vectors)
+    utt2spk = {u: v[0] for u, v in read_table(args.utt2spk).items()}
+    keys = [k for k in vectors if k in utt2spk]
+    for k in vectors:
+        if k not in utt2spk:
+            logger.warning("No speaker for utterance %s" % k)
+    x = _stack(vectors, keys).astype(np.float64)
+    x -= x.mean(axis=0)                                  # ivector-subtract-global-mean without a mean argument
+    t = backend.fit_lda(x, [utt2spk[k] for k in keys], args.dim, args.total_covariance_factor)
+    backend.write_transform(args.transform, t, binary=args.binary)
+    logger.info("Wrote LDA transform of dimension %d x %d" % t.shape)
+
+
+def cmd_compute_plda(args):
+    from xvector_amd import backend, hiplib
+    vectors = read_vectors(args.vectors)
+    spk2utt = read_table(args.spk2utt)
+    keys = list(vectors)
+    x = _stack(vectors, keys)
+    if args.lda:
+        # stage 8's chain: subtract the set's own mean, transform-vec, ivector-normalize-length -- on the device
+        t = backend.read_transform(args.lda)
+        mean = x.astype(np.float64).mean(axis=0).astype(np.float32)
+        rows, _ = backend.prepare(x, hiplib.SIDE_PLAIN, mean=mean, transform=t, length_norm=True)
+        x = rows[:, :t.shape[0]].cpu().numpy()
+    pos = {k: i for i, k in enumerate(keys)}
+    groups, missing = [], 0
+    for spk, utts in spk2utt.items():
+        have = [pos[u] for u in utts if u in pos]
+        missing += len(utts) - len(have)
+        if not have:
+            logger.warning("Not producing output for speaker %s since no utterances had iVectors" % spk)
+            continue
+        groups.append(have)
+    if missing:
+        logger.warning("%d utterances of spk2utt absent from input" % missing)
+    plda = backend.fit_plda(x, groups, num_em_iters=args.num_em_iters)
+    backend.write_plda(args.plda, plda, binary=args.binary)
+
+
+def cmd_score(args):
+    from xvector_amd import backend, hiplib
+    hiplib.require_gpu()                                 # no CPU fallback: fail before reading anything
+    if args.smoothing != 0:
+        raise SystemExit("only --smoothing 0 is supported (what run.sh uses)")
+    plda = backend.read_plda(args.plda) if args.scoring == "plda" else None
+    enrol = read_vectors(args.enrol)
+    test = read_vectors(args.test)
+    num_utts = None
+    if args.num_utts:
+        num_utts = {k: int(v[0]) for k, v in read_table(args.num_utts).items()}
+    ekeys, tkeys = list(enrol), list(test)
+    if num_utts is not None:
+        for k in ekeys:
+            if k not in num_utts:
+                raise SystemExit("Number of utterances not given for speaker %s" % k)
+    epos = {k: i for i, k in enumerate(ekeys)}
+    tpos = {k: i for i, k in enumerate(tkeys)}
+    k1s, k2s, ei, ti = [], [], [], []
+    n_train_err = n_test_err = 0
+    with open(args.trials, "rt") as f:
+        for line in f:
+            parts = line.split()
+            if len(parts) < 2:
+                continue
+            a, b = parts[0], parts[1]
+            if a not in epos:
+                logger.warning("Key %s not present in training iVectors." % a)
+                n_train_err += 1
+                continue
+            if b not in tpos:
+                logger.warning("Key %s not present in test iVectors." % b)
+                n_test_err += 1
+                continue
+            k1s.append(a); k2s.append(b); ei.append(epos[a]); ti.append(tpos[b])
+    mean = kaldi_io.read_vec_flt(args.mean).astype(np.float32) if args.mean else None
+    lda = backend.read_transform(args.lda) if args.lda else None
+    counts = None if num_utts is None else np.array([num_utts[k] for k in ekeys], np.int32)
+    scorer = backend.Scorer(_stack(enrol, ekeys), _stack(test, tkeys), plda, counts, mean, lda, args.scoring)
+    scores = scorer.score_trials(ei, ti)
+    write_scores(args.scores, k1s, k2s, scores)
+    logger.info("Processed %d trials, %d had errors." % (len(k1s) + n_train_err + n_test_err, n_train_err + n_test_err))
+    return n_train_err + n_test_err
+
+
+def write_scores(path, k1s, k2s, scores):
+    """``key1 key2 score`` lines, the score as %g (C++ ostream default precision, what ivector-plda-scoring prints)."""
+    with open(path, "wt") as f:
+        f.write("".join("%s %s %g\n" % (a, b, s) for a, b, s in zip(k1s, k2s, scores.tolist())))
+
+
+def cmd_compute_eer(args):
+    from xvector_amd import backend
+    fid = sys.stdin if args.scores == "-" else open(args.scores, "rt")
+    tgt, non = [], []
+    for line in fid:
+        parts = line.split()
+        if len(parts) != 2:
+            raise SystemExit("Invalid input line (must have two fields): %s" % line.strip())
+        if parts[1] == "target":
+            tgt.append(float(parts[0]))
+        elif parts[1] == "nontarget":
+            non.append(float(parts[0]))
+        else:
+            raise SystemExit("Invalid input line (second field must be 'target' or 'nontarget'): %s" % line.strip())
+    e, thr = backend.eer(tgt, non)
+    logger.info("Equal error rate is %g%%, at threshold %g" % (100.0 * e, thr))
+    print("%g" % (100.0 * e))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    sub = ap.add_subparsers(dest="cmd")
+    sub.required = True
+    p = sub.add_parser("mean", help="ivector-mean")
+    p.add_argument("vectors"); p.add_argument("mean_vec")
+    p.set_defaults(fn=cmd_mean)
+    p = sub.add_parser("compute-lda", help="ivector-compute-lda")
+    p.add_argument("--dim", type=int, required=True)
+    p.add_argument("--total-covariance-factor", type=float, default=0.0)
+    p.add_argument("--binary", type=lambda s: s.lower() in ("true", "1"), default=True)
+    p.add_argument("vectors"); p.add_argument("utt2spk"); p.add_argument("transform")
+    p.set_defaults(fn=cmd_compute_lda)
+    p = sub.add_parser("compute-plda", help="ivector-compute-plda")
+    p.add_argument("--num-em-iters", type=int, default=10)
+    p.add_argument("--lda", help="transform.mat: apply stage 8's chain to the vectors first (on the GPU)")
+    p.add_argument("--binary", type=lambda s: s.lower() in ("true", "1"), default=True)
+    p.add_argument("spk2utt"); p.add_argument("vectors"); p.add_argument("plda")
+    p.set_defaults(fn=cmd_compute_plda)
+    p = sub.add_parser("score", help="ivector-plda-scoring")
+    p.add_argument("--num-utts", help="ark:num_utts.ark (enrolment utterance counts)")
+    p.add_argument("--mean", help="mean.vec: subtract it first (ivector-subtract-global-mean)")
+    p.add_argument("--lda", help="transform.mat: transform-vec + ivector-normalize-length after the mean")
+    p.add_argument("--scoring", choices=("plda", "cosine"), default="plda")
+    p.add_argument("--smoothing", type=float, default=0.0)
+    p.add_argument("plda"); p.add_argument("enrol"); p.add_argument("test"); p.add_argument("trials"); p.add_argument("scores")
+    p.set_defaults(fn=cmd_score)
+    p = sub.add_parser("compute-eer", help="compute-eer")
+    p.add_argument("scores")
+    p.set_defaults(fn=cmd_compute_eer)
+    args = ap.parse_args(argv)
+    return args.fn(args)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,396 @@
+"""LDA + PLDA scoring back-end: what stages 8-9 of the recipe (run.sh) do with Kaldi binaries.
+
+  fit_lda        ivector-compute-lda --total-covariance-factor f --dim d      (host, fp64)
+  fit_plda       ivector-compute-plda --num-em-iters n  -> Plda (mean, transform, psi)   (host, fp64)
+  read_plda / write_plda, read_transform / write_transform   Kaldi's <Plda> object and transform.mat, binary and text
+  prepare        ivector-subtract-global-mean | transform-vec | ivector-normalize-length | Plda::TransformIvector on the GPU
+                 (xv_backend_prepare_f32)
+  Scorer         ivector-plda-scoring (and cosine scoring): the prepared operands on the device, dense (xv_score_matrix_f32)
+                 or per trial (xv_score_pairs_f32) -- bit-identical, so the choice between them is free
+  eer            compute-eer
+
+The fits run once on the host in float64 NumPy on purpose: they are eigenproblems on scatter matrices, cost O(N D^2) and are
+where precision matters; the GPU carries the part that scales with the data (preparing vectors and scoring trials).
+"""
+import io
+import logging
+import os
+import sys
+
+import numpy as np
+
+from . import hiplib
+
+logger = logging.getLogger("plda_backend")
+
+_TF = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "local", "tf")
+
+
+def _kaldi_io():
+    if _TF not in sys.path:
+        sys.path.insert(0, _TF)
+    import kaldi_io
+    return kaldi_io
+
+
+# ------------------------------------------------------------------------------------------------
+# fits (host, fp64)
+# ------------------------------------------------------------------------------------------------
+def _groups(labels):
+    """labels[N] (any hashable) -> list of index arrays, one per class, in order of first appearance."""
+    order, index = [], {}
+    for i, l in enumerate(labels):
+        if l not in index:
+            index[l] = len(order)
+            order.append([])
+        order[index[l]].append(i)
+    return [np.asarray(g, dtype=np.int64) for g in order]
+
+
+def _eigh_desc(m):
+    s, u = np.linalg.eigh((m + m.T) / 2)
+    o = np.argsort(s)[::-1]
+    return s[o], u[:, o]
+
+
+def scatter_matrices(x, labels):
+    """(mean, Sw, St) of x[N, D] with class labels[N]; both covariances divided by N (Kaldi's CovarianceStats)."""
+    x = np.asarray(x, dtype=np.float64)
+    n = x.shape[0]
+    mean = x.mean(axis=0)
+    xc = x - mean
+    st = xc.T @ xc / n
+    sw = np.zeros_like(st)
+    for g in _groups(labels):
+        d = xc[g] - xc[g].mean(axis=0)
+        sw += d.T @ d
+    return mean, sw / n, st
+
+
+def fit_lda(x, labels, dim, total_covariance_factor=0.0, covariance_floor=1e-6):
+    """ivector-compute-lda: -> transform [dim, D + 1] (float64), the affine map y = A x + a0 with a0 = -A mean in the last column.
+
+    M = f St + (1 - f) Sw is whitened by T = diag(s)^-1/2 U^T (its eigendecomposition, eigenvalues floored at
+    covariance_floor * max, Kaldi's ComputeNormalizingTransform), the top-dim eigenvectors V of T Sb T^T (descending) give
+    A = V^T T.  So A M A^T = I and A Sb A^T is diagonal and descending."""
+    mean, sw, st = scatter_matrices(x, labels)
+    D = sw.shape[0]
+    if not 0 < dim <= D:
+        raise ValueError("LDA dim %d must be in 1..%d" % (dim, D))
+    m = total_covariance_factor * st + (1.0 - total_covariance_factor) * sw
+    s, u = _eigh_desc(m)
+    s = np.maximum(s, s.max() * covariance_floor)
+    t = (u / np.sqrt(s)).T
+    sb = st - sw
+    _, v = _eigh_desc(t @ sb @ t.T)
+    a = v[:, :dim].T @ t
+    return np.hstack([a, -(a @ mean)[:, None]])
+
+
+class Plda(object):
+    """Kaldi's two-covariance PLDA after diagonalisation: mean [d], transform P [d, d] with P W P^T = I, P B P^T = diag(psi),
+    psi [d] descending (all float64)."""
+
+    def __init__(self, mean, transform, psi):
+        self.mean = np.asarray(mean, dtype=np.float64)
+        self.transform = np.asarray(transform, dtype=np.float64)
+        self.psi = np.asarray(psi, dtype=np.float64)
+        d = self.mean.shape[0]
+        assert self.transform.shape == (d, d) and self.psi.shape == (d,)
+
+    @property
+    def dim(self):
+        return self.mean.shape[0]
+
+
+def _spk_stats(x, groups):
+    """(mu = mean of the speaker means, means[S, d], counts[S], within-speaker scatter) over `groups` (index arrays into x)."""
+    means, counts = [], []
+    within = np.zeros((x.shape[1], x.shape[1]))
+    for g in groups:
+        m = x[g].mean(axis=0)
+        d = x[g] - m
+        within += d.T @ d
+        means.append(m)
+        counts.append(len(g))
+    means = np.asarray(means)
+    return means.mean(axis=0), means, np.asarray(counts), within
+
+
+def plda_em_step(means, counts, mu, within_scatter, n_total, B, W):
+    """One EM iteration of the two-covariance model x = mu + y_s + e, y ~ N(0, B), e ~ N(0, W) (Kaldi PldaEstimator).  -> (B, W)."""
+    binv = np.linalg.inv(B)
+    winv = np.linalg.inv(W)
+    b_stats = np.zeros_like(B)
+    w_stats = within_scatter.copy()
+    for n in np.unique(counts):
+        sel = counts == n
+        sigma = np.linalg.inv(binv + n * winv)
+        sigma = (sigma + sigma.T) / 2
+        m = means[sel] - mu                                  # [S_n, d]
+        y = m @ (n * winv) @ sigma                           # rows: Sigma_n n W^-1 (m_s - mu)   (both symmetric)
+        k = int(sel.sum())
+        b_stats += k * sigma + y.T @ y
+        r = m - y
+        w_stats += n * (k * sigma + r.T @ r)
+    return b_stats / len(counts), w_stats / n_total
+
+
+def fit_plda(x, spk_groups, num_em_iters=10, return_history=False):
+    """ivector-compute-plda.  x[N, d] (float64 or float32); spk_groups: list of index arrays (one per speaker).  Speakers with
+    a single utterance are skipped with a warning (they carry no within-speaker information).  -> Plda (and the list of
+    (B, W) after every iteration when return_history)."""
+    x = np.asarray(x, dtype=np.float64)
+    groups = [np.asarray(g) for g in spk_groups]
+    single = sum(1 for g in groups if len(g) == 1)
+    if single:
+        logger.warning("Skipping %d speakers with only one utterance" % single)
+    groups = [g for g in groups if len(g) > 1]
+    if not groups:
+        raise ValueError("fit_plda: no speaker with two or more utterances")
+    mu, means, counts, within = _spk_stats(x, groups)
+    n_total = int(counts.sum())
+    logger.info("Accumulated stats from %d speakers (%d with only one utterance, skipped), consisting of %d utterances." %
+                (len(groups), single, n_total))
+    d = x.shape[1]
+    B, W = np.eye(d), np.eye(d)
+    history = []
+    for _ in range(num_em_iters):
+        B, W = plda_em_step(means, counts, mu, within, n_total, B, W)
+        history.append((B, W))
+    plda = plda_from_covariances(mu, B, W)
+    return (plda, history) if return_history else plda
+
+
+def plda_from_covariances(mu, B, W):
+    """Diagonalise: C = chol(W), T1 = C^-1 (Kaldi's ComputeNormalizingTransform), V = eigenvectors of T1 B T1^T (descending),
+    P = V^T T1, psi = the eigenvalues (floored at 0)."""
+    t1 = np.linalg.inv(np.linalg.cholesky((W + W.T) / 2))
+    s, v = _eigh_desc(t1 @ B @ t1.T)
+    return Plda(mu, v.T @ t1, np.maximum(s, 0.0))
+
+
+# ------------------------------------------------------------------------------------------------
+# Kaldi I/O: <Plda> and transform.mat
+# ------------------------------------------------------------------------------------------------
+def _binary_body(write, a):
+    """The bytes kaldi_io writes for one binary vector / matrix, without the stream's leading \\0B."""
+    bio = io.BytesIO()
+    write(bio, a)
+    b = bio.getvalue()
+    assert b[:2] == b"\x00B"
+    return b[2:]
+
+
+def _text_vector(v):
+    return " [ " + "".join(repr(float(x)) + " " for x in v) + "]\n"
+
+
+def _text_matrix(m):
+    if m.size == 0:
+        return " [ ]\n"
+    return " [" + "".join("\n  " + "".join(repr(float(x)) + " " for x in row) for row in m) + "]\n"
+
+
+def write_plda(path, plda, binary=True):
+    """Kaldi's Plda::Write: <Plda> mean transform psi </Plda> (binary: \\0B, tokens with a trailing space, DV / DM framing)."""
+    kio = _kaldi_io()
+    with open(path, "wb") as f:
+        if binary:
+            f.write(b"\x00B<Plda> ")
+            f.write(_binary_body(kio.write_vec_flt, plda.mean))
+            f.write(_binary_body(kio.write_mat, plda.transform))
+            f.write(_binary_body(kio.write_vec_flt, plda.psi))
+            f.write(b"</Plda> ")
+        else:
+            f.write(("<Plda> " + _text_vector(plda.mean) + _text_matrix(plda.transform) + _text_vector(plda.psi) +
+                     "</Plda> ").encode())
+
+
+def _expect(fd, token):
+    got = fd.read(len(token))
+    if got != token:
+        raise ValueError("expected %r, got %r" % (token, got))
+
+
+def read_plda(path):
+    """A Kaldi <Plda> object, binary or text."""
+    kio = _kaldi_io()
+    with open(path, "rb") as f:
+        head = f.read(2)
+        if head == b"\x00B":
+            _expect(f, b"<Plda> ")
+            mean = np.array(kio._read_vec_flt_binary(f), dtype=np.float64)
+            transform = np.array(kio._read_mat_binary(f), dtype=np.float64)
+            psi = np.array(kio._read_vec_flt_binary(f), dtype=np.float64)
+            _expect(f, b"</Plda>")
+            return Plda(mean, transform, psi)
+        toks = (head + f.read()).decode().split()
+    if not toks or toks[0] != "<Plda>" or toks[-1] != "</Plda>":
+        raise ValueError("%s: not a Kaldi <Plda> object" % path)
+    arrays, cur = [], None
+    for t in toks[1:-1]:
+        if t == "[":
+            cur = []
+        elif t == "]":
+            arrays.append(np.array(cur, dtype=np.float64))
+            cur = None
+        else:
+            cur.append(float(t))
+    mean, transform, psi = arrays
+    d = mean.shape[0]
+    return Plda(mean, transform.reshape(d, d), psi)
+
+
+def write_transform(path, m, binary=True):
+    """transform.mat as ivector-compute-lda writes it (Matrix<BaseFloat>: FM)."""
+    kio = _kaldi_io()
+    m = np.asarray(m, dtype=np.float32)
+    if binary:
+        kio.write_mat(path, m)
+    else:
+        with open(path, "w") as f:
+            f.write(_text_matrix(m))
+
+
+def read_transform(path):
+    """A Kaldi matrix file (binary FM / DM or text) as float32, the precision transform-vec applies it in."""
+    kio = _kaldi_io()
+    with open(path, "rb") as f:
+        head = f.read(2)
+        if head == b"\x00B":
+            return np.array(kio._read_mat_binary(f), dtype=np.float32)
+        toks = (head + f.read()).decode()
+    rows = [l.replace("[", " ").replace("]", " ").split() for l in toks.splitlines()]
+    rows = [r for r in rows if r]
+    return np.array(rows, dtype=np.float32)
+
+
+# ------------------------------------------------------------------------------------------------
+# device side: prepare + score
+# ------------------------------------------------------------------------------------------------
+def kpad_for(k):
+    return (k + hiplib.BACKEND_KSTEP - 1) // hiplib.BACKEND_KSTEP * hiplib.BACKEND_KSTEP
+
+
+def _dev(a, device, dtype=None):
+    import torch
+    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32 if dtype is None else dtype), device=device)
+
+
+def prepare(x, side, num_utts=None, mean=None, transform=None, plda=None, length_norm=True, device="cuda:0"):
+    """Operand rows of the scorers from raw vectors x[N, D] on the device (xv_backend_prepare_f32).
+
+    side: hiplib.SIDE_PLAIN | SIDE_ENROL | SIDE_TEST | SIDE_COSINE;  mean: [D] subtracted first (None: nothing);
+    transform: LDA [d, D] or [d, D + 1] (offset in the last column; None: no LDA); length_norm: scale to norm sqrt(d)
+    (ivector-normalize-length); plda: Plda (None: no PLDA step; then only PLAIN / COSINE).  -> (rows[N, Kpad], r[N]) torch."""
+    import torch
+    hiplib.require_gpu()
+    xt = x if isinstance(x, torch.Tensor) else _dev(x, device)
+    xt = xt.to(device=device, dtype=torch.float32).contiguous()
+    n, D = xt.shape
+    a = a0 = None
+    d = D
+    if transform is not None:
+        transform = np.asarray(transform)
+        if transform.shape[1] not in (D, D + 1):
+            raise ValueError("transform has %d columns, the vectors %d" % (transform.shape[1], D))
+        d = transform.shape[0]
+        a = _dev(transform[:, :D], device)
+        a0 = _dev(transform[:, D], device) if transform.shape[1] == D + 1 else None
+    if plda is not None and plda.dim != d:
+        raise ValueError("PLDA dim %d != vector dim %d" % (plda.dim, d))
+    k = 2 * d if side in (hiplib.SIDE_ENROL, hiplib.SIDE_TEST) else d
+    out = torch.empty((n, kpad_for(k)), dtype=torch.float32, device=device)
+    r = torch.empty(n, dtype=torch.float32, device=device)
+    nu = None
+    if num_utts is not None:
+        nu = torch.as_tensor(np.ascontiguousarray(num_utts, dtype=np.int32), device=device)
+    hiplib.backend_prepare(xt, out, side, num_utts=nu, mean=None if mean is None else _dev(mean, device), lda=a, lda_offset=a0,
+                           length_norm=length_norm,
+                           plda_transform=None if plda is None else _dev(plda.transform, device),
+                           plda_mean=None if plda is None else _dev(plda.mean, device),
+                           plda_psi=None if plda is None else _dev(plda.psi, device), r=r)
+    return out, r
+
+
+DENSE_MAX_BYTES = 1 << 30          # the dense score matrix of one trial list is at most this large
+
+
+class Scorer(object):
+    """Prepared enrolment and test operands on the device.  scoring 'plda' (needs plda) or 'cosine'.  enrol[Ne, D] are speaker
+    means of the raw vectors (num_utts[Ne] their utterance counts), test[Nt, D] raw vectors; mean / transform run the stage-9
+    chain on the device first (None: the vectors are used as they are, e.g. already processed by Kaldi pipes)."""
+
+    def __init__(self, enrol, test, plda=None, num_utts=None, mean=None, transform=None, scoring="plda", device="cuda:0"):
+        hiplib.require_gpu()
+        self.device = device
+        ln = transform is not None
+        if scoring == "plda":
+            if plda is None:
+                raise ValueError("PLDA scoring needs a Plda")
+            self.E, self.r = prepare(enrol, hiplib.SIDE_ENROL, num_utts, mean, transform, plda, ln, device)
+            self.T, _ = prepare(test, hiplib.SIDE_TEST, None, mean, transform, plda, ln, device)
+        elif scoring == "cosine":
+            self.E, _ = prepare(enrol, hiplib.SIDE_COSINE, num_utts, mean, transform, plda, ln, device)
+            self.T, _ = prepare(test, hiplib.SIDE_COSINE, None, mean, transform, plda, ln, device)
+            self.r = None
+        else:
+            raise ValueError("scoring must be 'plda' or 'cosine'")
+        self.scoring = scoring
+
+    @property
+    def shape(self):
+        return self.E.shape[0], self.T.shape[0]
+
+    def score_matrix(self):
+        """S[Ne, Nt] on the device."""
+        import torch
+        s = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+        hiplib.score_matrix(self.E, self.T, self.r, s)
+        return s
+
+    def score_pairs(self, e_idx, t_idx):
+        """score[i] of trial (e_idx[i], t_idx[i]) on the device."""
+        import torch
+        e = torch.as_tensor(np.ascontiguousarray(e_idx, dtype=np.int32), device=self.device)
+        t = torch.as_tensor(np.ascontiguousarray(t_idx, dtype=np.int32), device=self.device)
+        out = torch.empty(e.numel(), dtype=torch.float32, device=self.device)
+        hiplib.score_pairs(self.E, self.T, self.r, e, t, out)
+        return out
+
+    def use_dense(self, n_trials):
+        """Dense-then-gather when the list covers at least 1/8 of the matrix and the matrix fits DENSE_MAX_BYTES."""
+        ne, nt = self.shape
+        return ne * nt * 4 <= DENSE_MAX_BYTES and 8 * n_trials >= ne * nt
+
+    def score_trials(self, e_idx, t_idx):
+        """score[i] of the trial list as a float32 NumPy array: the same bits whichever scorer runs."""
+        e_idx = np.asarray(e_idx, dtype=np.int64)
+        t_idx = np.asarray(t_idx, dtype=np.int64)
+        if e_idx.size == 0:
+            return np.zeros(0, np.float32)
+        if self.use_dense(e_idx.size):
+            import torch
+            s = self.score_matrix()
+            flat = torch.as_tensor(e_idx * self.shape[1] + t_idx, device=self.device)
+            return s.reshape(-1)[flat].cpu().numpy()
+        return self.score_pairs(e_idx, t_idx).cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------------
+# EER (compute-eer)
+# ------------------------------------------------------------------------------------------------
+def eer(target_scores, nontarget_scores):
+    """Kaldi compute-eer: -> (eer as a fraction, threshold).  Walk the sorted target scores upward until the nontarget score at
+    the mirrored rank falls below the target score."""
+    tgt = np.sort(np.asarray(target_scores, dtype=np.float32))
+    non = np.sort(np.asarray(nontarget_scores, dtype=np.float32))
+    if tgt.size == 0 or non.size == 0:
+        raise ValueError("compute-eer needs target and nontarget scores")
+    nt, nn = tgt.size, non.size
+    pos = np.arange(nt - 1, dtype=np.int64)
+    npos = np.maximum(nn - 1 - (nn * pos * 1.0 / nt).astype(np.int64), 0)
+    stop = np.flatnonzero(non[npos] < tgt[pos])
+    pos = int(stop[0]) if stop.size else nt - 1
+    return pos * 1.0 / nt, float(tgt[pos])

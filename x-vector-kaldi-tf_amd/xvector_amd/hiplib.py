@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -113,6 +113,10 @@ _SIGNATURES = {
     "xv_attention_scores_backward_f32": (_ci, [_vp, _i64, _vp, _vp, _i64, _ci, _vp, _i64, _vp]),
     # feature front-end
     "xv_cmn_sliding_scatter_f32": (_ci, [_vp, _ci, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _vp]),
+    # PLDA / cosine scoring back-end
+    "xv_backend_prepare_f32": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp, _vp, _i64, _vp, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _i64, _vp, _vp]),
+    "xv_score_matrix_f32": (_ci, [_vp, _vp, _i64, _ci, _ci, _ci, _vp, _vp, _i64, _vp]),
+    "xv_score_pairs_f32": (_ci, [_vp, _vp, _i64, _ci, _vp, _vp, _i64, _vp, _vp, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)      # tests check the header declares exactly these and the .so exports all of them
 
@@ -124,6 +128,9 @@ TUNE_FP32_GEMM = 3
 TUNE_XCD_COLUMNS = 4
 
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_PRELU = 0, 1, 2, 3
+
+BACKEND_KSTEP = 8
+SIDE_PLAIN, SIDE_ENROL, SIDE_TEST, SIDE_COSINE = 0, 1, 2, 3
 
 _lib = None
 
@@ -1102,6 +1109,63 @@ def cmn_sliding_scatter(x, utt_start, utt_len, n_utts, max_len, cmn_window, cent
     _check(lib.xv_cmn_sliding_scatter_f32(_ptr(x), x.stride(0), x.shape[1], _ptr(utt_start), _ptr(utt_len), int(n_utts), int(max_len),
                                           int(cmn_window), 1 if center else 0, int(min_window), _ptr(dst_row), _ptr(y), y.stride(0),
                                           _stream()), "xv_cmn_sliding_scatter_f32")
+
+
+def backend_prepare(x, out, side, num_utts=None, mean=None, lda=None, lda_offset=None, length_norm=True, plda_transform=None,
+                    plda_mean=None, plda_psi=None, r=None):
+    """Operand rows of the scorers from raw vectors x[N, D] (see include/xvector_hip.h): mean subtraction, LDA, length norm,
+    PLDA transform and length norm, packed for ``side`` into out[N, Kpad] (zeros past K); r[N] the per-row constant."""
+    import torch
+    lib = require_gpu()
+    _f32(x, "x"); _f32(out, "out")
+    n_rows, dim_in = x.shape
+    dim = lda.shape[0] if lda is not None else dim_in
+    assert out.shape[0] >= n_rows and out.shape[1] == out.stride(0)
+    for t, shape in ((mean, (dim_in,)), (lda_offset, (dim,)), (plda_transform, (dim, dim)), (plda_mean, (dim,)), (plda_psi, (dim,)),
+                     (r, (n_rows,))):
+        if t is not None:
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape, shape
+    if lda is not None:
+        _f32(lda, "lda"); assert lda.shape[1] == dim_in
+    if num_utts is not None:
+        assert num_utts.is_cuda and num_utts.dtype == torch.int32 and num_utts.is_contiguous() and num_utts.numel() >= n_rows
+    _check(lib.xv_backend_prepare_f32(_ptr(x), x.stride(0), n_rows, dim_in, _ptr(num_utts), _ptr(mean), _ptr(lda),
+                                      lda.stride(0) if lda is not None else 0, _ptr(lda_offset), dim, 1 if length_norm else 0,
+                                      _ptr(plda_transform), _ptr(plda_mean), _ptr(plda_psi), int(side), _ptr(out), out.stride(0),
+                                      _ptr(r), _stream()), "xv_backend_prepare_f32")
+
+
+def score_matrix(e, t, r, out):
+    """out[Ne, Nt] = e[Ne, Kpad] t[Nt, Kpad]^T + r[Ne] (r may be None), fixed summation order (k ascending)."""
+    import torch
+    lib = require_gpu()
+    _f32(e, "e"); _f32(t, "t"); _f32(out, "out")
+    assert e.shape[1] == t.shape[1] and e.stride(0) == t.stride(0) and out.shape[0] >= e.shape[0] and out.shape[1] >= t.shape[0]
+    if r is not None:
+        assert r.is_cuda and r.dtype == torch.float32 and r.is_contiguous() and r.numel() >= e.shape[0]
+    _check(lib.xv_score_matrix_f32(_ptr(e), _ptr(t), e.stride(0), e.shape[1], e.shape[0], t.shape[0], _ptr(r), _ptr(out), out.stride(0),
+                                   _stream()), "xv_score_matrix_f32")
+
+
+def score_pairs(e, t, r, e_idx, t_idx, out):
+    """out[i] = e[e_idx[i]] . t[t_idx[i]] + r[e_idx[i]]: bit-identical to the cell of score_matrix.  The kernel reads the rows the
+    indices name, so their range is checked here first."""
+    import torch
+    lib = require_gpu()
+    _f32(e, "e"); _f32(t, "t")
+    assert e.shape[1] == t.shape[1] and e.stride(0) == t.stride(0)
+    for ix in (e_idx, t_idx):
+        assert ix.is_cuda and ix.dtype == torch.int32 and ix.is_contiguous()
+    m = e_idx.numel()
+    assert t_idx.numel() == m and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= m
+    if r is not None:
+        assert r.is_cuda and r.dtype == torch.float32 and r.is_contiguous() and r.numel() >= e.shape[0]
+    if m:
+        lo = torch.stack([e_idx.min(), t_idx.min(), e_idx.max() - e.shape[0], t_idx.max() - t.shape[0]]).cpu().tolist()
+        if lo[0] < 0 or lo[1] < 0 or lo[2] >= 0 or lo[3] >= 0:
+            raise XvectorHipError("score_pairs: trial index out of range")
+    _check(lib.xv_score_pairs_f32(_ptr(e), _ptr(t), e.stride(0), e.shape[1], _ptr(e_idx), _ptr(t_idx), m, _ptr(r), _ptr(out), _stream()),
+           "xv_score_pairs_f32")
 
 
 def l2_normalize_rows(x):
