@@ -274,3 +274,33 @@ def test_fp32tc_other_topologies_take_what_the_kernel_covers(net):
     a = net["engine"].Extractor(m, 25, 10000).extract(mats)
     b = net["engine"].Extractor(net["engine"].DeviceModel(w, topo, "cuda:0", precision="fp32"), 25, 10000).extract(mats)
     assert all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("K", [3, 5])
+@pytest.mark.parametrize("dil", [3, 8])
+@pytest.mark.parametrize("rdelta", ["1", "2", "d-1", "d", "d+1"])
+def test_toom_dilated_layer_with_fewer_rows_than_the_dilation(env, K, dil, rdelta):
+    """R < dilation leaves sub-problems without a row (their workgroups must not touch x at all), R = d, d + 1 leave single-row ones.
+    x is a larger buffer whose rows from R on are NaN and y has NaN canary rows behind row R: a load past row R shows up as NaN in
+    the output, a store past it as a changed canary.  Reference: the direct contraction, zero padding outside [0, R)."""
+    torch, hiplib, oracle, dev = env["torch"], env["hiplib"], env["oracle"], env["dev"]
+    R = {"1": 1, "2": 2, "d-1": dil - 1, "d": dil, "d+1": dil + 1}[rdelta]
+    cin, cout = 64, 48
+    rng = np.random.default_rng(100 * K + 10 * dil + R)
+    m = (rng.standard_normal((R, cin)) * 2).astype(np.float32)
+    w = (rng.standard_normal((K, cin, cout)) / np.sqrt(K * cin)).astype(np.float32)
+    b = (0.1 * rng.standard_normal(cout)).astype(np.float32)
+    bn = _rand_bn(rng, cout)
+    host = np.full((R + 64, cin), np.nan, np.float32)
+    host[:R] = m
+    x = torch.from_numpy(host).to(dev)
+    wp = hiplib.pack_weights_toom(torch.from_numpy(np.ascontiguousarray(w)).to(dev))
+    scale, shift = hiplib.fold_bn(*(torch.from_numpy(a).to(dev) for a in bn), 1e-3)
+    y = torch.full((R + 16, cout), float("nan"), dtype=torch.float32, device=dev)
+    hiplib.tdnn_layer_toom(x, wp, torch.from_numpy(b).to(dev), scale, shift, 1, None, None, y, rows=R, dilation=dil)
+    torch.cuda.synchronize()
+    yh = y.cpu().numpy()
+    assert np.isnan(yh[R:]).all()                                    # the canaries behind row R are untouched
+    assert np.isfinite(yh[:R]).all()
+    ref = oracle.tdnn_layer(m, w, b, bn, "relu", None, dil, np.float64)
+    assert oracle.rel_l2(yh[:R], ref) < TOL_GEMM, oracle.rel_l2(yh[:R], ref)

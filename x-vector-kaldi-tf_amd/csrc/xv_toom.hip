@@ -247,6 +247,9 @@ __global__ __launch_bounds__(NT, 2) void tdnn_gemm_toom_kernel(const ToomParams 
     const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
     const int ms = wg / p.n_nt, nt = wg - ms * p.n_nt;
     const int mt = ms / p.dil, sub = ms - mt * p.dil;
+    // R < dilation: sub-problems sub >= R own no row at all, and the record count of their input descriptor below, (R - sub) ldx 4
+    // bytes, would be zero or negative -- a negative one reads as ~4 GB and turns the range check of every load off
+    if (sub >= p.R) return;
     const long m0 = (long)mt * BM;
     const int n0 = nt * BN;
 

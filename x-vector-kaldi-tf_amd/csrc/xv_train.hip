@@ -782,16 +782,19 @@ __global__ __launch_bounds__(64) void l2_normalize_rows_kernel(const float *__re
     if (lane == 0) norm[r] = (float)n;
 }
 
-// dx = (dy - y * <y, dy>) / max(norm, 1e-12)    for y = x / ||x||
+// dx = (dy - y * <y, dy>) / max(norm, 1e-12)    for y = x / ||x||;  dx = dy / 1e-12 below the clamp, where y = x / 1e-12 is linear
 __global__ __launch_bounds__(64) void l2_normalize_backward_kernel(const float *__restrict__ dy, const float *__restrict__ y,
                                                                    const float *__restrict__ norm, int C, float *__restrict__ dx)
 {
     const int r = blockIdx.x, lane = threadIdx.x;
     const float *g = dy + (size_t)r * C, *yr = y + (size_t)r * C;
+    const double nr = norm[r];
     double dot = 0.0;
-    for (int j = lane; j < C; j += 64) dot += (double)g[j] * (double)yr[j];
-    for (int off = 32; off; off >>= 1) dot += __shfl_xor(dot, off, 64);
-    const double inv = 1.0 / fmax((double)norm[r], 1e-12);
+    if (nr >= 1e-12) {
+        for (int j = lane; j < C; j += 64) dot += (double)g[j] * (double)yr[j];
+        for (int off = 32; off; off >>= 1) dot += __shfl_xor(dot, off, 64);
+    }
+    const double inv = 1.0 / fmax(nr, 1e-12);
     for (int j = lane; j < C; j += 64) dx[(size_t)r * C + j] = (float)(((double)g[j] - (double)yr[j] * dot) * inv);
 }
 

@@ -1168,24 +1168,26 @@ def score_pairs(e, t, r, e_idx, t_idx, out):
            "xv_score_pairs_f32")
 
 
-def l2_normalize_rows(x):
-    """-> (y = x / ||x|| per row, norms[R])."""
+def l2_normalize_rows(x, y=None, norm=None):
+    """-> (y = x / ||x|| per row, norms[R]); ``y`` / ``norm`` optional preallocated outputs."""
     import torch
     lib = require_gpu()
     _f32(x, "x")
-    y = torch.empty_like(x)
-    norm = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    y = torch.empty_like(x) if y is None else _f32(y, "y")
+    norm = torch.empty(x.shape[0], dtype=torch.float32, device=x.device) if norm is None else _f32(norm, "norm")
+    assert y.shape == x.shape and norm.numel() == x.shape[0]
     _check(lib.xv_l2_normalize_rows_f32(_ptr(x), x.stride(0), x.shape[0], x.shape[1], _ptr(y), y.stride(0), _ptr(norm), _stream()),
            "xv_l2_normalize_rows_f32")
     return y, norm
 
 
-def l2_normalize_backward(dy, y, norm):
+def l2_normalize_backward(dy, y, norm, dx=None):
     import torch
     lib = require_gpu()
     _f32(dy, "dy"); _f32(y, "y"); _f32(norm, "norm")
     assert dy.shape == y.shape and norm.numel() == y.shape[0]
-    dx = torch.empty_like(y)
+    dx = torch.empty_like(y) if dx is None else _f32(dx, "dx")
+    assert dx.shape == y.shape
     _check(lib.xv_l2_normalize_backward_f32(_ptr(dy), _ptr(y), _ptr(norm), y.shape[0], y.shape[1], _ptr(dx), _stream()),
            "xv_l2_normalize_backward_f32")
     return dx
