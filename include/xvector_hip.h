@@ -52,7 +52,7 @@ extern "C" {
 #define XV_ERR_BAD_ARG (-1)
 #define XV_ERR_UNSUPPORTED (-2)
 
-/* Library / ABI version (increments whenever an entry point is added or changed; currently 24). */
+/* Library / ABI version (increments whenever an entry point is added or changed; currently 25). */
 int xv_version(void);
 /* Thread-local description of the last non-zero return. */
 const char *xv_last_error(void);
@@ -528,7 +528,14 @@ int xv_cmn_sliding_scatter_f32(const float *x, int ldx, int feat_dim, const int3
  *   no split-K, r added after the dot product.  E, T: row stride ldk (a multiple of 4 floats, 16-byte aligned), kpad a multiple
  *   of XV_BACKEND_KSTEP, <= 1024 (else XV_ERR_UNSUPPORTED).
  * xv_score_pairs_f32  scores[i] = the same expression for the trial (e_idx[i], t_idx[i]), as an fmaf chain k ascending from 0:
- *   bit-identical to the cell of xv_score_matrix_f32, whatever the other trials of the list. */
+ *   bit-identical to the cell of xv_score_matrix_f32, whatever the other trials of the list.
+ * xv_topk_row_stats_f32  AS-norm cohort statistics: for each row i < n_rows of scores (row i = scores[i*ld .. i*ld + n_cols)),
+ *   mean[i] and std[i] = the mean and the POPULATION standard deviation (divisor top_n) of the top_n largest values of the row,
+ *   taken as a multiset (ties at the threshold are counted by multiplicity).  Exact selection: an MSB-first radix select on
+ *   order-preserving uint32 keys, no approximation.  Every NaN, of either sign, ranks above +inf, so a row holding a NaN yields
+ *   NaN statistics.  Sums in fp64 (the variance centred on the mean), rounded to fp32 once.  A row's bits depend on its values,
+ *   n_cols and top_n only: not on the other rows, n_rows or ld.  Columns [n_cols, ld) are never read; nothing past n_rows is
+ *   written.  Requires 1 <= top_n <= n_cols <= ld, ld a multiple of 4 and scores 16-byte aligned (else XV_ERR_BAD_ARG). */
 #define XV_BACKEND_KSTEP 8
 #define XV_SIDE_PLAIN 0
 #define XV_SIDE_ENROL 1
@@ -542,6 +549,8 @@ int xv_score_matrix_f32(const float *e, const float *t, int64_t ldk, int kpad, i
                         float *scores, int64_t ld_scores, void *stream);
 int xv_score_pairs_f32(const float *e, const float *t, int64_t ldk, int kpad, const int32_t *e_idx, const int32_t *t_idx,
                        int64_t n_trials, const float *r, float *scores, void *stream);
+int xv_topk_row_stats_f32(const float *scores, int64_t ld, int n_rows, int n_cols, int top_n, float *mean, float *std,
+                          void *stream);
 
 #ifdef __cplusplus
 }

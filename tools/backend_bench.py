@@ -1,7 +1,9 @@
 """Timings of the scoring back-end: prepare at N = 100 k, D = 512; the dense scorer at Ne = Nt = 16384 against the
 157.3 TF fp32-MFMA peak; the trial scorer at 2 M trials; the `plda_backend.py score` CLI on an SRE16-sized synthetic job with a
-read / prepare / score / write breakdown.  Device events after warm-up.   python tools/backend_bench.py [--fit]
-(--fit: also time the host fp64 LDA + PLDA fits at N = 100 k, D = 512; needs no GPU)."""
+read / prepare / score / write breakdown.  Device events after warm-up.   python tools/backend_bench.py [--fit | --asnorm]
+(--fit: instead time the host fp64 LDA + PLDA fits at N = 100 k, D = 512; needs no GPU.  --asnorm: instead time AS-norm --
+cohort scoring and the top-N statistics kernel separately at the recipe shape and at 50 k rows x 50 k cohort in 1 GiB chunks,
+then the `score --cohort` CLI on the SRE16-sized job beside the same job without a cohort)."""
 import os, shutil, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TWIN = os.path.join(ROOT, "x-vector-kaldi-tf_amd", "local", "tf")
@@ -91,8 +93,55 @@ def gpu_timing():
     print("score_matrix on the same job (all %d cells): %.3f ms" % (ne * nt, ms))
 
 
-def cli_job():
-    """SRE16-sized: 800 enrolment speakers, 9.3 k test segments, 2 M trials, D = 512, LDA d = 100."""
+def asnorm_timing(top_n=300):
+    """Cohort scoring (xv_score_matrix_f32) and the top-N statistics (xv_topk_row_stats_f32), each timed on its own with device
+    events: the recipe shape (800 enrolment + 9.3 k test rows against 2,000 cohort vectors, K = 2d = 200) and 50 k rows x
+    50 k cohort in chunks of at most 1 GiB of scores (K = 200 and 400), as Scorer.cohort_stats runs them."""
+    import torch
+    from xvector_amd import backend, hiplib
+    dev = "cuda:0"
+    for name, rows, nc, Ks in (("recipe shape", 800 + 9300, 2000, (200,)), ("large shape", 50000, 50000, (200, 400))):
+        ldc = (nc + 3) // 4 * 4
+        chunk = min(rows, backend.DENSE_MAX_BYTES // (ldc * 4))
+        ws = torch.empty((chunk, ldc), device=dev)
+        mu = torch.empty(rows, device=dev)
+        sd = torch.empty(rows, device=dev)
+        for K in Ks:
+            E = torch.randn((rows, K), device=dev)
+            C = torch.randn((nc, K), device=dev)
+            r = torch.randn(rows, device=dev)
+            ev = []
+
+            def run(record):
+                for i0 in range(0, rows, chunk):
+                    m = min(chunk, rows - i0)
+                    a, b, c = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+                    a.record()
+                    hiplib.score_matrix(E[i0:i0 + m], C, r[i0:i0 + m], ws[:m])
+                    b.record()
+                    hiplib.topk_row_stats(ws[:m, :nc], top_n, mu[i0:i0 + m], sd[i0:i0 + m])
+                    c.record()
+                    if record:
+                        ev.append((a, b, c))
+            run(False)
+            run(False)
+            reps = 5 if rows * nc < 1e9 else 2
+            for _ in range(reps):
+                run(True)
+            torch.cuda.synchronize()
+            t_sc = sum(a.elapsed_time(b) for a, b, _ in ev) / reps
+            t_st = sum(b.elapsed_time(c) for _, b, c in ev) / reps
+            tf = 2.0 * rows * nc * K / t_sc / 1e9
+            print("AS-norm %s: %d rows x %d cohort, K = %d, top-N %d, %d chunk(s) of <= %d rows: cohort scoring %.3f ms (%.1f TF/s = "
+                  "%.2f of the %.1f TF fp32-MFMA peak), top-N stats %.3f ms (%.0f GB/s effective read of the scores) = %.0f %% of "
+                  "the scoring time" % (name, rows, nc, K, top_n, (rows + chunk - 1) // chunk, chunk, t_sc, tf, tf / PEAK_TF, PEAK_TF,
+                                        t_st, 4.0 * rows * nc / t_st / 1e6, 100.0 * t_st / t_sc))
+            del E, C
+
+
+def cli_job(cohort=False):
+    """SRE16-sized: 800 enrolment speakers, 9.3 k test segments, 2 M trials, D = 512, LDA d = 100 (cohort: also the whole
+    command with --cohort of 2,000 vectors, top-N 300, beside the same command without it)."""
     import torch
     import kaldi_io
     import plda_backend
@@ -116,6 +165,19 @@ def cli_job():
     args = ["score", "--num-utts=ark:%s/num_utts.ark" % tmp, "--mean", tmp + "/mean.vec", "--lda", tmp + "/transform.mat",
             tmp + "/plda", "scp:%s/enrol.scp" % tmp, "scp:%s/test.scp" % tmp, tmp + "/trials", tmp + "/scores"]
     plda_backend.main(args)                                   # warm-up (library load, kernels)
+    if cohort:
+        nc = 2000
+        with kaldi_io.TableWriter(tmp + "/cohort.ark", tmp + "/cohort.scp") as w:
+            kaldi_io.write_vec_flt_batch(w, ["coh%04d" % i for i in range(nc)], list(rng.standard_normal((nc, D)).astype(np.float32)))
+        cargs = args[:1] + ["--cohort", "scp:%s/cohort.scp" % tmp, "--cohort-top-n", "300"] + args[1:]
+        plda_backend.main(cargs)                              # warm-up
+        w = []
+        for a in (args, cargs, args, cargs):
+            t0 = time.perf_counter(); plda_backend.main(a); w.append(time.perf_counter() - t0)
+        print("score CLI, %d enrolment speakers x %d test segments, %d trials, D = %d, d = %d: whole command %.2f / %.2f s without a "
+              "cohort, %.2f / %.2f s with --cohort of %d vectors, top-N 300" % (ne, nt, M, D, d, w[0], w[2], w[1], w[3], nc))
+        shutil.rmtree(tmp)
+        return
     # the same steps as cmd_score, timed one by one
     t = [time.perf_counter()]
     plda = backend.read_plda(tmp + "/plda")
@@ -148,6 +210,9 @@ def cli_job():
 if __name__ == "__main__":
     if "--fit" in sys.argv:
         fit_timing()
+    elif "--asnorm" in sys.argv:
+        asnorm_timing()
+        cli_job(cohort=True)
     else:
         gpu_timing()
         cli_job()

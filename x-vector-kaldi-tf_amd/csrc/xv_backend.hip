@@ -6,12 +6,14 @@
 // The PLDA log-likelihood ratio of Kaldi's Plda::LogLikelihoodRatio is one dot product of length K = 2d plus a per-enrolment
 // constant:
 //     enrolment row [ (a/v) z , 1/v - 1/w ]    test row [ t , -t^2/2 ]    r_e = -1/2 sum a^2 z^2 / v + 1/2 sum (log w - log v)
-// with a = n psi / (n psi + 1), v = 1 + psi / (n psi + 1), w = 1 + psi.  Three kernels:
+// with a = n psi / (n psi + 1), v = 1 + psi / (n psi + 1), w = 1 + psi.  Four kernels:
 //   backend_prepare_kernel   x -> operand rows: (x - mu), LDA, length norm, PLDA transform, PLDA length norm, side packing.
 //                            32 rows per workgroup; both products on v_mfma_f32_32x32x2_f32 (exact fp32), the rows stay in LDS
 //                            between the two products and the two norms.
 //   score_matrix_kernel      S = E T^T + r on v_mfma_f32_32x32x2_f32, 128 x 128 tiles, one accumulator per score, k ascending.
 //   score_pairs_kernel       one trial per thread: an fmaf chain over k ascending from 0, then + r.
+//   topk_row_stats_kernel    AS-norm cohort statistics: mean and population std of the top-N scores of each row, by an exact
+//                            MSB-first radix select on order-preserving keys (rows of <= 32768 columns staged in LDS), fp64 sums.
 // The f32-input MFMA is an fmaf chain over its two k values (lanes 0-31 carry k, lanes 32-63 carry k + 1), so the matrix kernel
 // feeds k in ascending pairs (2s, 2s + 1) and the pairs kernel reproduces its bits (tests/test_gpu_backend.py checks it).
 #include "xv_device.h"
@@ -321,6 +323,146 @@ __global__ __launch_bounds__(256) void score_pairs_kernel(const float *__restric
     score[i] = acc + (r ? r[e] : 0.0f);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// top-N row statistics (AS-norm): mean and population std of the top_n largest values of each row, by an exact radix select
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int TK_NT = 256;                   // one workgroup per row; thread t owns bin t of the 8-bit digit in the scan
+constexpr int TK_STAGE_MAX = 32768;          // rows of up to this many columns are staged in LDS as keys (128 KiB)
+constexpr int TK_HDR = 1280;                 // LDS in front of the staged keys: histogram (1 KiB), scan and reduction scratch
+constexpr int TK_LDS_MAX = TK_HDR + 4 * TK_STAGE_MAX;
+
+// order-preserving float -> uint32 (x < y implies key(x) < key(y)); every NaN, of either sign, maps to the largest key
+__device__ __forceinline__ uint32_t tk_key(float x)
+{
+    const uint32_t u = __float_as_uint(x);
+    if (x != x) return 0xffffffffu;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ float tk_value(uint32_t k)
+{
+    if (k == 0xffffffffu) return __uint_as_float(0x7fc00000u);
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// Row blockIdx.x.  Four MSB-first passes over 8-bit digits find tau, the key of the top_n-th largest value, and g, the number
+// of keys above it; the selection is every key above tau plus (top_n - g) copies of tau.  Its sum, then its centred sum of
+// squares, are accumulated in fp64.  Every thread visits its columns in one fixed order (4-column groups tid, tid + NT, ...,
+// then the tail group) and the block sums in one fixed tree, so a row's bits depend on its values, n_cols and top_n alone.
+__global__ __launch_bounds__(TK_NT) void topk_row_stats_kernel(const float *__restrict__ scores, long ld, int n_cols, int top_n,
+                                                               float *__restrict__ mean, float *__restrict__ stdev)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    uint32_t *hist = reinterpret_cast<uint32_t *>(lds);          // [256]
+    uint32_t *wtot = hist + 256;                                  // [4] wave totals of the scan
+    uint32_t *sel = wtot + 4;                                     // [2] the chosen digit, keys above its bin
+    double *dred = reinterpret_cast<double *>(lds + 1088);        // [4] wave partial sums
+    uint32_t *stage = reinterpret_cast<uint32_t *>(lds + TK_HDR);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float *row = scores + (long)blockIdx.x * ld;
+    const bool staged = n_cols <= TK_STAGE_MAX;
+    const int nvec = n_cols >> 2;
+
+    // f(column, key, value) over the thread's columns from global memory (four 16-B loads in flight) or from the staged keys
+    auto visit = [&](bool from_lds, auto &&f) {
+        if (from_lds) {
+            for (int v = tid; v < nvec; v += TK_NT) {
+                const uint4 k = reinterpret_cast<const uint4 *>(stage)[v];
+                f(4 * v, k.x, tk_value(k.x));
+                f(4 * v + 1, k.y, tk_value(k.y));
+                f(4 * v + 2, k.z, tk_value(k.z));
+                f(4 * v + 3, k.w, tk_value(k.w));
+            }
+        } else {
+            const f32x4 *rv = reinterpret_cast<const f32x4 *>(row);
+            int v = tid;
+            for (; v + 3 * TK_NT < nvec; v += 4 * TK_NT) {
+                f32x4 x[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) x[u] = rv[v + u * TK_NT];
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) f(4 * (v + u * TK_NT) + j, tk_key(x[u][j]), x[u][j]);
+            }
+            for (; v < nvec; v += TK_NT) {
+                const f32x4 x = rv[v];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) f(4 * v + j, tk_key(x[j]), x[j]);
+            }
+        }
+        if (tid == nvec % TK_NT)
+            for (int c = 4 * nvec; c < n_cols; ++c) {
+                const uint32_t k = from_lds ? stage[c] : tk_key(row[c]);
+                f(c, k, from_lds ? tk_value(k) : row[c]);
+            }
+    };
+
+    // ---- radix select ----
+    uint32_t prefix = 0, mask = 0;
+    uint32_t k = (uint32_t)top_n;                                 // rank of the target among the keys matching prefix / mask
+    for (int p = 0; p < 4; ++p) {
+        const int shift = 24 - 8 * p;
+        hist[tid] = 0;
+        __syncthreads();
+        auto count = [&](int c, uint32_t key, float) {
+            if (p == 0 && staged) stage[c] = key;
+            if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+        };
+        visit(p > 0 && staged, count);
+        __syncthreads();
+        // inclusive sums from the top bin down: thread t holds bin 255 - t
+        const uint32_t h = hist[255 - tid];
+        uint32_t inc = h;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += y;
+        }
+        if (lane == 63) wtot[wave] = inc;
+        __syncthreads();
+        for (int w = 0; w < wave; ++w) inc += wtot[w];
+        if (inc - h < k && k <= inc) {                           // exactly one bin: the count crosses k inside it
+            sel[0] = 255 - tid;
+            sel[1] = inc - h;
+        }
+        __syncthreads();
+        prefix |= sel[0] << shift;
+        mask |= 255u << shift;
+        k -= sel[1];
+        __syncthreads();
+    }
+    const uint32_t tau = prefix;                                  // k copies of tau complete the selection
+
+    auto block_sum = [&](double v) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        __syncthreads();
+        if (lane == 0) dred[wave] = v;
+        __syncthreads();
+        return (dred[0] + dred[1]) + (dred[2] + dred[3]);
+    };
+    const double tv = (double)tk_value(tau);
+    double s = 0.0;
+    visit(staged, [&](int, uint32_t key, float x) {
+        if (key > tau) s += (double)x;
+    });
+    const double mu = (block_sum(s) + (double)k * tv) / top_n;
+    double q = 0.0;
+    visit(staged, [&](int, uint32_t key, float x) {
+        if (key > tau) {
+            const double d = (double)x - mu;
+            q += d * d;
+        }
+    });
+    const double dt = tv - mu;
+    const double var = (block_sum(q) + (double)k * dt * dt) / top_n;
+    if (tid == 0) {
+        mean[blockIdx.x] = (float)mu;
+        stdev[blockIdx.x] = (float)sqrt(var);
+    }
+}
+
 }  // namespace
 
 extern "C" int xv_backend_prepare_f32(const float *x, int64_t ldx, int n_rows, int dim_in, const int32_t *num_utts, const float *mean,
@@ -373,4 +515,20 @@ extern "C" int xv_score_pairs_f32(const float *e, const float *t, int64_t ldk, i
     hipLaunchKernelGGL(score_pairs_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, e, t, (int)ldk, kpad, e_idx, t_idx,
                        (long)n_trials, r, scores);
     return launch_status("score_pairs_kernel");
+}
+
+extern "C" int xv_topk_row_stats_f32(const float *scores, int64_t ld, int n_rows, int n_cols, int top_n, float *mean, float *std,
+                                     void *stream)
+{
+    if (n_rows <= 0) return 0;
+    if (!scores || !mean || !std || n_cols < 1 || top_n < 1 || top_n > n_cols || ld < n_cols || ld % 4 || ((uintptr_t)scores & 15))
+        return fail(XV_ERR_BAD_ARG, "topk_row_stats: bad argument (1 <= top_n <= n_cols <= ld, ld a multiple of 4, 16-B aligned base)");
+    using tk_t = decltype(&topk_row_stats_kernel);
+    static const tk_t kerns[1] = {topk_row_stats_kernel};
+    static std::atomic<unsigned long long> lds_done{0};
+    if (const int rc = opt_in_dynamic_lds(lds_done, kerns, TK_LDS_MAX)) return rc;
+    const size_t lds = TK_HDR + (n_cols <= TK_STAGE_MAX ? 4 * (size_t)((n_cols + 3) & ~3) : 0);
+    hipLaunchKernelGGL(topk_row_stats_kernel, dim3((unsigned)n_rows), dim3(TK_NT), lds, (hipStream_t)stream, scores, (long)ld, n_cols,
+                       top_n, mean, std);
+    return launch_status("topk_row_stats_kernel");
 }

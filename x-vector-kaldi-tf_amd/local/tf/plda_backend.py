@@ -8,7 +8,9 @@
                go through stage 8's chain on the GPU (subtract the set's own mean | transform-vec | ivector-normalize-length)
   score        ivector-plda-scoring [--num-utts=ark:num_utts.ark] plda <enrol> <test> trials scores; with --mean / --lda the
                stage-9 chain (ivector-subtract-global-mean mean.vec | transform-vec | ivector-normalize-length) runs on the GPU
-               instead of Kaldi pipes; --scoring cosine scores the cosine of the same chain's vectors instead of the PLDA LLR
+               instead of Kaldi pipes; --scoring cosine scores the cosine of the same chain's vectors instead of the PLDA LLR;
+               --cohort <vectors> [--cohort-top-n N] writes AS-norm scores (adaptive symmetric normalisation against the top N
+               cohort scores of each side; the cohort goes through the same --mean / --lda chain as the tests)
   compute-eer  compute-eer <file of "score target|nontarget" lines, or ->   (prints the EER in percent)
 
 Vector tables are ``scp:<file>`` or ``ark:<file>`` (options before the colon, e.g. ``ark,s,cs:``, are accepted and ignored).
@@ -119,6 +121,8 @@ def cmd_compute_plda(args):
 
 def cmd_score(args):
     from xvector_amd import backend, hiplib
+    if args.cohort_top_n < 2:
+        raise SystemExit("--cohort-top-n must be at least 2 (the std of a single cohort score is 0), got %d" % args.cohort_top_n)
     hiplib.require_gpu()                                 # no CPU fallback: fail before reading anything
     if args.smoothing != 0:
         raise SystemExit("only --smoothing 0 is supported (what run.sh uses)")
@@ -155,8 +159,28 @@ def cmd_score(args):
     mean = kaldi_io.read_vec_flt(args.mean).astype(np.float32) if args.mean else None
     lda = backend.read_transform(args.lda) if args.lda else None
     counts = None if num_utts is None else np.array([num_utts[k] for k in ekeys], np.int32)
-    scorer = backend.Scorer(_stack(enrol, ekeys), _stack(test, tkeys), plda, counts, mean, lda, args.scoring)
-    scores = scorer.score_trials(ei, ti)
+    cohort, top_n = None, args.cohort_top_n
+    if args.cohort:
+        cvec = read_vectors(args.cohort)
+        if not cvec:
+            raise SystemExit("the cohort %s is empty" % args.cohort)
+        cohort = _stack(cvec, list(cvec))
+        if top_n > len(cohort):
+            logger.warning("--cohort-top-n %d exceeds the cohort size %d: using %d" % (top_n, len(cohort), len(cohort)))
+            top_n = len(cohort)
+    scorer = backend.Scorer(_stack(enrol, ekeys), _stack(test, tkeys), plda, counts, mean, lda, args.scoring, cohort=cohort,
+                            cohort_top_n=top_n)
+    if cohort is None:
+        scores = scorer.score_trials(ei, ti)
+    else:
+        try:
+            scores = scorer.score_trials(ei, ti, norm="asnorm")
+        except backend.CohortStatsError as e:
+            key = (ekeys if e.side == "enrol" else tkeys)[e.row]
+            raise SystemExit("AS-norm: the cohort scores of %s %s have standard deviation %g; no scores written" %
+                             ("enrolment" if e.side == "enrol" else "test vector", key, e.std))
+        logger.info("AS-norm: cohort of %d vectors, top-N %d, cohort statistics took %.3f s" %
+                    (len(cohort), top_n, scorer.stats_seconds))
     write_scores(args.scores, k1s, k2s, scores)
     logger.info("Processed %d trials, %d had errors." % (len(k1s) + n_train_err + n_test_err, n_train_err + n_test_err))
     return n_train_err + n_test_err
@@ -212,6 +236,9 @@ def main(argv=None):
     p.add_argument("--lda", help="transform.mat: transform-vec + ivector-normalize-length after the mean")
     p.add_argument("--scoring", choices=("plda", "cosine"), default="plda")
     p.add_argument("--smoothing", type=float, default=0.0)
+    p.add_argument("--cohort", help="scp: / ark: cohort vectors: write AS-norm scores (DESIGN.md §8.5)")
+    p.add_argument("--cohort-top-n", type=int, default=300, help="cohort scores per side in the AS-norm statistics (>= 2; "
+                   "clamped to the cohort size)")
     p.add_argument("plda"); p.add_argument("enrol"); p.add_argument("test"); p.add_argument("trials"); p.add_argument("scores")
     p.set_defaults(fn=cmd_score)
     p = sub.add_parser("compute-eer", help="compute-eer")

@@ -6,7 +6,9 @@
   prepare        ivector-subtract-global-mean | transform-vec | ivector-normalize-length | Plda::TransformIvector on the GPU
                  (xv_backend_prepare_f32)
   Scorer         ivector-plda-scoring (and cosine scoring): the prepared operands on the device, dense (xv_score_matrix_f32)
-                 or per trial (xv_score_pairs_f32) -- bit-identical, so the choice between them is free
+                 or per trial (xv_score_pairs_f32) -- bit-identical, so the choice between them is free; with a cohort,
+                 adaptive symmetric score normalisation (AS-norm): cohort scores in chunks, their top-N statistics per row
+                 (xv_topk_row_stats_f32), the normalised score on the device
   eer            compute-eer
 
 The fits run once on the host in float64 NumPy on purpose: they are eigenproblems on scatter matrices, cost O(N D^2) and are
@@ -317,12 +319,27 @@ def prepare(x, side, num_utts=None, mean=None, transform=None, plda=None, length
 DENSE_MAX_BYTES = 1 << 30          # the dense score matrix of one trial list is at most this large
 
 
+class CohortStatsError(ValueError):
+    """A cohort score standard deviation that AS-norm would divide by is 0 or not finite.  side: 'enrol' | 'test'; row: the
+    row of that side's vectors."""
+
+    def __init__(self, side, row, std):
+        ValueError.__init__(self, "AS-norm: the cohort scores of %s row %d have standard deviation %r (0 or not finite)" %
+                            ("enrolment" if side == "enrol" else "test", row, std))
+        self.side, self.row, self.std = side, row, std
+
+
 class Scorer(object):
     """Prepared enrolment and test operands on the device.  scoring 'plda' (needs plda) or 'cosine'.  enrol[Ne, D] are speaker
     means of the raw vectors (num_utts[Ne] their utterance counts), test[Nt, D] raw vectors; mean / transform run the stage-9
-    chain on the device first (None: the vectors are used as they are, e.g. already processed by Kaldi pipes)."""
+    chain on the device first (None: the vectors are used as they are, e.g. already processed by Kaldi pipes).
 
-    def __init__(self, enrol, test, plda=None, num_utts=None, mean=None, transform=None, scoring="plda", device="cuda:0"):
+    cohort[Nc, D] (raw vectors, the same chain as the test vectors) enables AS-norm with the top
+    min(cohort_top_n, Nc) cohort scores of each side.  The cohort is prepared as test rows; for the test-side statistics the test
+    vectors are prepared a second time as one-utterance enrolment rows (cosine: both sides are the cosine rows)."""
+
+    def __init__(self, enrol, test, plda=None, num_utts=None, mean=None, transform=None, scoring="plda", device="cuda:0",
+                 cohort=None, cohort_top_n=300):
         hiplib.require_gpu()
         self.device = device
         ln = transform is not None
@@ -338,6 +355,20 @@ class Scorer(object):
         else:
             raise ValueError("scoring must be 'plda' or 'cosine'")
         self.scoring = scoring
+        self.C = None
+        self.stats_seconds = 0.0
+        if cohort is not None:
+            if len(cohort) == 0:
+                raise ValueError("the cohort is empty")
+            if cohort_top_n < 2:
+                raise ValueError("cohort_top_n must be at least 2 (the std of one score is 0), got %d" % cohort_top_n)
+            self.cohort_top_n = min(int(cohort_top_n), len(cohort))
+            if scoring == "plda":
+                self.C, _ = prepare(cohort, hiplib.SIDE_TEST, None, mean, transform, plda, ln, device)
+                self.TE, self.rT = prepare(test, hiplib.SIDE_ENROL, np.ones(len(test), np.int32), mean, transform, plda, ln, device)
+            else:
+                self.C, _ = prepare(cohort, hiplib.SIDE_COSINE, None, mean, transform, plda, ln, device)
+                self.TE, self.rT = self.T, None
 
     @property
     def shape(self):
@@ -364,18 +395,82 @@ class Scorer(object):
         ne, nt = self.shape
         return ne * nt * 4 <= DENSE_MAX_BYTES and 8 * n_trials >= ne * nt
 
-    def score_trials(self, e_idx, t_idx):
-        """score[i] of the trial list as a float32 NumPy array: the same bits whichever scorer runs."""
-        e_idx = np.asarray(e_idx, dtype=np.int64)
-        t_idx = np.asarray(t_idx, dtype=np.int64)
-        if e_idx.size == 0:
-            return np.zeros(0, np.float32)
+    def _raw_scores(self, e_idx, t_idx):
+        """score[i] of the trial list on the device: the same bits whichever scorer runs."""
         if self.use_dense(e_idx.size):
             import torch
             s = self.score_matrix()
             flat = torch.as_tensor(e_idx * self.shape[1] + t_idx, device=self.device)
-            return s.reshape(-1)[flat].cpu().numpy()
-        return self.score_pairs(e_idx, t_idx).cpu().numpy()
+            return s.reshape(-1)[flat]
+        return self.score_pairs(e_idx, t_idx)
+
+    def cohort_stats(self, side, idx, chunk_rows=None, max_bytes=DENSE_MAX_BYTES):
+        """(mu, sigma) on the device: mean and population std of the top cohort_top_n cohort scores of the rows idx of side
+        'enrol' (the enrolment operands) or 'test' (the test vectors as one-utterance enrolments).  Rows go in chunks of at most
+        chunk_rows (None: no limit) whose cohort score matrix fits max_bytes; a row's result does not depend on the chunking."""
+        import torch
+        if self.C is None:
+            raise ValueError("cohort_stats needs a Scorer built with a cohort")
+        if side == "enrol":
+            ops, r = self.E, self.r
+        elif side == "test":
+            ops, r = self.TE, self.rT
+        else:
+            raise ValueError("side must be 'enrol' or 'test'")
+        idx = torch.as_tensor(np.ascontiguousarray(idx, dtype=np.int64), device=self.device)
+        n, nc = idx.numel(), self.C.shape[0]
+        ldc = (nc + 3) // 4 * 4                                  # xv_topk_row_stats_f32 wants ld % 4 == 0
+        rows = max_bytes // (ldc * 4)
+        if chunk_rows is not None:
+            rows = min(rows, int(chunk_rows))
+        if rows < 1:
+            raise ValueError("max_bytes %d holds no row of %d cohort scores" % (max_bytes, nc))
+        rows = min(rows, max(n, 1), 65535 * 128)               # xv_score_matrix_f32 takes at most 65535 x 128 rows a launch
+        mu = torch.empty(n, dtype=torch.float32, device=self.device)
+        sd = torch.empty(n, dtype=torch.float32, device=self.device)
+        ws = torch.empty((rows, ldc), dtype=torch.float32, device=self.device)
+        for i0 in range(0, n, rows):
+            sel = idx[i0:i0 + rows]
+            m = sel.numel()
+            hiplib.score_matrix(ops.index_select(0, sel), self.C, None if r is None else r.index_select(0, sel), ws[:m])
+            hiplib.topk_row_stats(ws[:m, :nc], self.cohort_top_n, mu[i0:i0 + m], sd[i0:i0 + m])
+        return mu, sd
+
+    def score_trials(self, e_idx, t_idx, norm="none"):
+        """score[i] of the trial list as a float32 NumPy array: the same bits whichever scorer runs.  norm 'asnorm' (needs a
+        cohort): s' = 1/2 ((s - mu_e) / sigma_e + (s - mu_t) / sigma_t) in fp32 on the device, with the statistics of the
+        enrolment and test rows the list references; CohortStatsError if one of their sigma is 0 or not finite."""
+        e_idx = np.asarray(e_idx, dtype=np.int64)
+        t_idx = np.asarray(t_idx, dtype=np.int64)
+        if norm not in ("none", "asnorm"):
+            raise ValueError("norm must be 'none' or 'asnorm'")
+        if norm == "asnorm" and self.C is None:
+            raise ValueError("AS-norm needs a Scorer built with a cohort")
+        if e_idx.size == 0:
+            return np.zeros(0, np.float32)
+        s = self._raw_scores(e_idx, t_idx)
+        if norm == "none":
+            return s.cpu().numpy()
+        import time
+        import torch
+        t0 = time.perf_counter()
+        stats = []
+        for side, ix, n in (("enrol", e_idx, self.shape[0]), ("test", t_idx, self.shape[1])):
+            used = np.zeros(n, bool)                             # the rows the list references, without sorting the list
+            used[ix] = True
+            rows = np.flatnonzero(used)
+            pos = (np.cumsum(used) - 1)[ix]
+            mu, sd = self.cohort_stats(side, rows)
+            bad = ~(torch.isfinite(sd) & (sd > 0))
+            if bool(bad.any()):
+                j = int(torch.nonzero(bad)[0, 0])
+                raise CohortStatsError(side, int(rows[j]), float(sd[j]))
+            p = torch.as_tensor(pos, device=self.device)
+            stats.append((mu[p], sd[p]))
+        torch.cuda.synchronize(self.device)
+        self.stats_seconds = time.perf_counter() - t0
+        (mu_e, sd_e), (mu_t, sd_t) = stats
+        return (((s - mu_e) / sd_e + (s - mu_t) / sd_t) * 0.5).cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------------

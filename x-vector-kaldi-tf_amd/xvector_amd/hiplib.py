@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -117,6 +117,7 @@ _SIGNATURES = {
     "xv_backend_prepare_f32": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp, _vp, _i64, _vp, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _i64, _vp, _vp]),
     "xv_score_matrix_f32": (_ci, [_vp, _vp, _i64, _ci, _ci, _ci, _vp, _vp, _i64, _vp]),
     "xv_score_pairs_f32": (_ci, [_vp, _vp, _i64, _ci, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "xv_topk_row_stats_f32": (_ci, [_vp, _i64, _ci, _ci, _ci, _vp, _vp, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)      # tests check the header declares exactly these and the .so exports all of them
 
@@ -1166,6 +1167,19 @@ def score_pairs(e, t, r, e_idx, t_idx, out):
             raise XvectorHipError("score_pairs: trial index out of range")
     _check(lib.xv_score_pairs_f32(_ptr(e), _ptr(t), e.stride(0), e.shape[1], _ptr(e_idx), _ptr(t_idx), m, _ptr(r), _ptr(out), _stream()),
            "xv_score_pairs_f32")
+
+
+def topk_row_stats(scores, top_n, mean, std):
+    """mean[i], std[i] = mean and population std of the top_n largest values of row i of scores[R, C] (exact selection, fp64 sums;
+    see include/xvector_hip.h).  scores may be a row slice of a wider buffer: its row stride is passed as ld."""
+    import torch
+    lib = require_gpu()
+    assert scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and scores.stride(1) == 1
+    n_rows, n_cols = scores.shape
+    for t in (mean, std):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n_rows
+    _check(lib.xv_topk_row_stats_f32(_ptr(scores), scores.stride(0), n_rows, n_cols, int(top_n), _ptr(mean), _ptr(std), _stream()),
+           "xv_topk_row_stats_f32")
 
 
 def l2_normalize_rows(x, y=None, norm=None):
