@@ -52,7 +52,7 @@ extern "C" {
 #define XV_ERR_BAD_ARG (-1)
 #define XV_ERR_UNSUPPORTED (-2)
 
-/* Library / ABI version (increments whenever an entry point is added or changed; currently 25). */
+/* Library / ABI version (increments whenever an entry point is added or changed; currently 26). */
 int xv_version(void);
 /* Thread-local description of the last non-zero return. */
 const char *xv_last_error(void);
@@ -551,6 +551,40 @@ int xv_score_pairs_f32(const float *e, const float *t, int64_t ldk, int kpad, co
                        int64_t n_trials, const float *r, float *scores, void *stream);
 int xv_topk_row_stats_f32(const float *scores, int64_t ld, int n_rows, int n_cols, int top_n, float *mean, float *std,
                           void *stream);
+
+/* Stage 1 of the recipe: MFCC features and the energy VAD (compute-mfcc-feats / compute-vad; csrc/xv_mfcc.hip).
+ * xv_mfcc_f32  MFCC rows of n_utts utterances in one launch.  samples: every utterance's samples back to back, int16
+ *   (sample_format 0) or fp32 (1); utterance u has utt_samples[u] samples from element utt_offset[u], its frames go to rows
+ *   utt_row0[u] .. utt_row0[u] + frames(u) - 1 of feats [total_rows, ld_feats] (utt_row0 non-decreasing: the prefix sum of the
+ *   frame counts, which the host forms with the geometry below), and utt_key[u] keys its dither noise.
+ *   Geometry: frames(n) = snip_edges ? (n < frame_length ? 0 : 1 + (n - frame_length) / frame_shift)
+ *                                    : (n + frame_shift / 2) / frame_shift;
+ *   frame t starts at t * frame_shift (snip) or t * frame_shift + frame_shift / 2 - frame_length / 2; indices outside [0, n) are
+ *   reflected (s < 0 -> -s - 1, s >= n -> 2n - 1 - s) until they land inside.
+ *   Per frame: + dither * N(0,1) per sample (Philox4x32-10 keyed on utt_key, counter (sample, frame lo, frame hi, 0), Box-Muller),
+ *   - the mean if remove_dc, raw log energy, pre-emphasis, window[frame_length], zero padding to padded_length, power spectrum
+ *   of bins 0 .. padded/2 - 1 (radix-2 FFT with twiddle = exp(-2 pi i k / padded) as (re, im) fp32 pairs, k < padded/2),
+ *   log-mel b = log(max(sum_j mel_w[b * mel_ld + j] * P[mel_first[b] + j], FLT_EPSILON)) for j < mel_len[b],
+ *   feats[c] = sum_b lifter_dct[c * num_bins + b] * logmel[b]; with use_energy, c0 := the log energy (raw_energy: after DC
+ *   removal, else after the window), floored at log(energy_floor) when energy_floor > 0.  logmel (NULL: not written) receives
+ *   the log-mel energies [total_rows, ld_logmel].  Rows that no utterance's frames cover are not written.  A frame's bits depend
+ *   on its utterance's samples, key and the tables only.  padded_length must be a power of two in [128, 1024] and num_bins
+ *   <= 128 (else XV_ERR_UNSUPPORTED); frame_length <= padded_length, num_ceps <= num_bins, mel_first[b] + mel_len[b] <=
+ *   padded_length / 2 (the caller's tables).
+ * xv_vad_energy_f32  compute-vad on ragged utterances: utterance u is rows utt_row0[u] .. + n_frames[u] - 1 of feats (row
+ *   stride ld; column 0 = the log energy is the only one read).  thr = energy_threshold + energy_mean_scale * sum_t c0[t] / T
+ *   with the sum in fp64 in a fixed order; out[utt_row0[u] + t] = 1.0f when #{t2 in [t - ctx, t + ctx] n [0, T) : c0[t2] > thr}
+ *   >= float(den) * proportion_threshold (den = the in-range frames), else 0.0f.  One workgroup per utterance: a decision does not
+ *   depend on the other utterances of the launch. */
+int xv_mfcc_f32(const void *samples, int sample_format, const int64_t *utt_offset, const int64_t *utt_samples,
+                const int64_t *utt_row0, const uint64_t *utt_key, int n_utts, int64_t total_rows, const float *window,
+                const int32_t *mel_first, const int32_t *mel_len, const float *mel_w, int num_bins, int mel_ld,
+                const float *lifter_dct, int num_ceps, const float *twiddle, int frame_length, int frame_shift, int padded_length,
+                int snip_edges, float dither, float preemph_coeff, int remove_dc, int use_energy, int raw_energy,
+                float energy_floor, float *feats, int64_t ld_feats, float *logmel, int64_t ld_logmel, void *stream);
+int xv_vad_energy_f32(const float *feats, int64_t ld, const int64_t *utt_row0, const int32_t *n_frames, int n_utts,
+                      float energy_threshold, float energy_mean_scale, int frames_context, float proportion_threshold, float *out,
+                      void *stream);
 
 #ifdef __cplusplus
 }

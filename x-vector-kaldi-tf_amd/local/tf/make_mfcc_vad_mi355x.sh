@@ -1,0 +1,24 @@
+#!/usr/bin/env bash
+# MFCC features + energy VAD of one Kaldi data directory on the MI355X -- what steps/make_mfcc.sh followed by
+# sid/compute_vad_decision.sh do with nj CPU jobs and Kaldi binaries, as ONE pass (mfcc_vad.py compute-mfcc-vad):
+# writes <out-dir>/raw_mfcc_<name>.{ark,scp}, <out-dir>/vad_<name>.{ark,scp} and puts feats.scp, vad.scp and utt2num_frames
+# into the data dir, as the Kaldi scripts do.  Data dirs with a segments file are refused (not supported).
+# Usage: make_mfcc_vad_mi355x.sh <data-dir> <mfcc.conf> <vad.conf> <out-dir>
+set -euo pipefail
+[[ $# -eq 4 ]] || { sed -n 2,6p "$0"; exit 1; }
+data=$1; mfcc_conf=$2; vad_conf=$3; dir=$4
+here=$(cd "$(dirname "$0")" && pwd)
+for f in "$data/wav.scp" "$mfcc_conf" "$vad_conf"; do [[ -f $f ]] || { echo "$0: no such file $f" >&2; exit 1; }; done
+if [[ -f $data/segments ]]; then
+  echo "$0: $data/segments exists: segmented recordings are not supported (extract the segments into a wav.scp first)" >&2
+  exit 1
+fi
+name=$(basename "$data")
+mkdir -p "$dir/log"
+dir=$(cd "$dir" && pwd)
+python "$here/mfcc_vad.py" compute-mfcc-vad --config="$mfcc_conf" --vad-config="$vad_conf" \
+    --write-num-frames="ark,t:$data/utt2num_frames" "scp:$data/wav.scp" \
+    "ark,scp:$dir/raw_mfcc_$name.ark,$dir/raw_mfcc_$name.scp" "ark,scp:$dir/vad_$name.ark,$dir/vad_$name.scp" \
+    2>&1 | tee "$dir/log/make_mfcc_vad_$name.log"
+cp "$dir/raw_mfcc_$name.scp" "$data/feats.scp"
+cp "$dir/vad_$name.scp" "$data/vad.scp"

@@ -1,0 +1,223 @@
+#!/usr/bin/env python
+"""Stage 1 of run.sh without Kaldi binaries.  Each subcommand is named after the binary it replaces:
+
+  compute-mfcc-feats [--config F] [--name=value ...] [--write-num-frames ark,t:F] scp:wav.scp <wspec>
+  compute-vad        [--config F] [--name=value ...] <feats-rspec> <wspec>
+  compute-mfcc-vad   [--config F] [--vad-config F] [--name=value ...] [--write-num-frames ark,t:F] scp:wav.scp <feats-wspec>
+                     <vad-wspec>       (both in one pass: the VAD reads the features on the device, nothing is re-read)
+
+Options carry Kaldi's names and defaults (xvector_amd/mfcc.py); a ``--config`` file is read first, the command line
+overrides it.  ``--seed`` keys the dither noise with the utterance id.  Outputs are ``ark,scp:A,S`` or
+``ark:A``; features are written as ``FM`` records, VAD decisions as ``FV`` records, ``--write-num-frames`` as ``key N`` lines.
+wav.scp entries are paths or ``cmd |`` pipes; 16-bit PCM WAV only.  The arithmetic runs on the MI355X: no CPU fallback.
+"""
+from __future__ import print_function
+
+import argparse
+import logging
+import os
+import sys
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+if _HERE not in sys.path:
+    sys.path.insert(0, _HERE)
+sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))
+
+import kaldi_io  # noqa: E402
+from xvector_amd import mfcc  # noqa: E402
+
+logger = logging.getLogger('mfcc_vad')
+logger.addHandler(logging.StreamHandler())
+logger.setLevel(logging.INFO)
+logging.getLogger('mfcc').addHandler(logging.StreamHandler())
+
+WINDOW_SAMPLES = 1 << 26          # samples per launch (128 MiB of int16)
+
+
+def _flags(p, cls):
+    for name in cls.names():
+        p.add_argument("--" + name.replace("_", "-"), dest="opt_" + name, nargs="?", const="true", default=None)
+
+
+def _options(cls, config, args):
+    o = cls()
+    if config:
+        o.update(mfcc.read_config(config))
+    o.update((n, getattr(args, "opt_" + n)) for n in cls.names() if getattr(args, "opt_" + n, None) is not None)
+    return o
+
+
+class _Out(object):
+    """A table wspecifier: ``ark,scp:A,S`` (TableWriter) or ``ark[,b]:A``."""
+
+    def __init__(self, wspec):
+        kind, _, path = wspec.partition(":")
+        opts = kind.split(",")
+        if not path or opts[0] != "ark" or any(o not in ("ark", "scp", "b", "t", "f", "nf", "p", "np") for o in opts):
+            raise SystemExit("unsupported wspecifier %r (ark,scp:A,S or ark:A)" % wspec)
+        if "scp" in opts:
+            ark, _, scp = path.partition(",")
+            if not scp:
+                raise SystemExit("wspecifier %r: ark,scp needs A,S" % wspec)
+            self.fd = kaldi_io.TableWriter(ark, scp)
+        else:
+            self.fd = open(path, "wb")
+
+    def close(self):
+        self.fd.close()
+
+
+class _NumFrames(object):
+    def __init__(self, wspec):
+        path = wspec.split(":", 1)[1] if ":" in wspec else wspec
+        self.f = open(path, "wt")
+
+    def write(self, key, n):
+        self.f.write("%s %d\n" % (key, n))
+
+    def close(self):
+        self.f.close()
+
+
+def _wav_scp_path(rspec):
+    kind, _, path = rspec.partition(":")
+    if kind.split(",")[0] != "scp" or not path:
+        raise SystemExit("expected scp:wav.scp, got %r" % rspec)
+    return path
+
+
+def _read_waves(path, opts):
+    """(key, int16 samples) of every usable entry, in order (Kaldi's skip rules applied)."""
+    for key, rx in mfcc.read_wav_scp(path):
+        try:
+            rate, x = mfcc.load_wav(key, rx)
+        except mfcc.WavError as e:
+            raise SystemExit("Failed to read the wave of %s: %s" % (key, e))
+        w = mfcc.select_channel(key, rate, x, opts)
+        if w is not None:
+            yield key, w
+
+
+def _batches(items, max_samples):
+    keys, waves, tot = [], [], 0
+    for k, w in items:
+        if keys and tot + w.shape[0] > max_samples:
+            yield keys, waves
+            keys, waves, tot = [], [], 0
+        keys.append(k)
+        waves.append(w)
+        tot += w.shape[0]
+    if keys:
+        yield keys, waves
+
+
+def cmd_mfcc(args, with_vad):
+    opts = _options(mfcc.MfccOptions, args.config, args)
+    vopts = _options(mfcc.VadOptions, args.vad_config, args) if with_vad else None
+    try:
+        opts.check()
+    except (NotImplementedError, ValueError) as e:
+        raise SystemExit(str(e))
+    path = _wav_scp_path(args.wav_rspecifier)
+    feats_out = _Out(args.feats_wspecifier)
+    vad_out = _Out(args.vad_wspecifier) if with_vad else None
+    nf_out = _NumFrames(args.write_num_frames) if args.write_num_frames else None
+    engine = mfcc.Mfcc(opts, vopts, window_samples=WINDOW_SAMPLES)
+    n_done = n_vad_skipped = 0
+    for keys, waves in _batches(_read_waves(path, opts), WINDOW_SAMPLES):
+        feats, vads, _ = engine.compute(keys, waves)
+        for i, (k, f) in enumerate(zip(keys, feats)):
+            kaldi_io.write_mat(feats_out.fd, f, key=k)
+            if nf_out:
+                nf_out.write(k, f.shape[0])
+            if with_vad:
+                if f.shape[0] == 0:
+                    logger.warning("Empty feature matrix for utterance %s", k)
+                    n_vad_skipped += 1
+                else:
+                    kaldi_io.write_vec_flt(vad_out.fd, vads[i], key=k)
+            n_done += 1
+    feats_out.close()
+    if vad_out:
+        vad_out.close()
+    if nf_out:
+        nf_out.close()
+    logger.info("Done %d utterances (%d frames)%s", n_done, engine.stats["frames"],
+                ", %d without a VAD vector" % n_vad_skipped if with_vad else "")
+
+
+def _read_feats(rspec):
+    kind, _, path = rspec.partition(":")
+    kind = kind.split(",")[0]
+    if kind == "scp":
+        return kaldi_io.read_mat_scp(path)
+    if kind == "ark":
+        return kaldi_io.read_mat_ark(path)
+    raise SystemExit("unsupported rspecifier %r (scp: or ark:)" % rspec)
+
+
+def cmd_vad(args):
+    vopts = _options(mfcc.VadOptions, args.config, args)
+    out = _Out(args.vad_wspecifier)
+    keys, mats = [], []
+    for k, m in _read_feats(args.feats_rspecifier):
+        if m.shape[0] == 0:
+            logger.warning("Empty feature matrix for utterance %s", k)
+            continue
+        keys.append(k)
+        mats.append(np.asarray(m, np.float32))
+    runs = mfcc.compute_vad(mats, vopts)
+    for k, v in zip(keys, runs):
+        kaldi_io.write_vec_flt(out.fd, v, key=k)
+    out.close()
+    logger.info("Applied energy based voice activity detection; processed %d utterances", len(keys))
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
+    sub = p.add_subparsers(dest="cmd")
+    m = sub.add_parser("compute-mfcc-feats")
+    m.add_argument("--config", default=None)
+    m.add_argument("--write-num-frames", default=None)
+    _flags(m, mfcc.MfccOptions)
+    m.add_argument("wav_rspecifier")
+    m.add_argument("feats_wspecifier")
+    v = sub.add_parser("compute-vad")
+    v.add_argument("--config", default=None)
+    _flags(v, mfcc.VadOptions)
+    v.add_argument("feats_rspecifier")
+    v.add_argument("vad_wspecifier")
+    b = sub.add_parser("compute-mfcc-vad")
+    b.add_argument("--config", default=None)
+    b.add_argument("--vad-config", default=None)
+    b.add_argument("--write-num-frames", default=None)
+    _flags(b, mfcc.MfccOptions)
+    _flags(b, mfcc.VadOptions)
+    b.add_argument("wav_rspecifier")
+    b.add_argument("feats_wspecifier")
+    b.add_argument("vad_wspecifier")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    try:
+        if args.cmd == "compute-mfcc-feats":
+            args.vad_config = None
+            cmd_mfcc(args, False)
+        elif args.cmd == "compute-mfcc-vad":
+            cmd_mfcc(args, True)
+        elif args.cmd == "compute-vad":
+            cmd_vad(args)
+        else:
+            build_parser().print_help()
+            return 1
+    except ValueError as e:               # unknown / malformed options in a config file
+        raise SystemExit(str(e))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

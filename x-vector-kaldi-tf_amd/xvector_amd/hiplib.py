@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -118,6 +118,9 @@ _SIGNATURES = {
     "xv_score_matrix_f32": (_ci, [_vp, _vp, _i64, _ci, _ci, _ci, _vp, _vp, _i64, _vp]),
     "xv_score_pairs_f32": (_ci, [_vp, _vp, _i64, _ci, _vp, _vp, _i64, _vp, _vp, _vp]),
     "xv_topk_row_stats_f32": (_ci, [_vp, _i64, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "xv_mfcc_f32": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _ci, _i64, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _ci, _vp, _ci, _ci, _ci, _ci,
+                          _cf, _cf, _ci, _ci, _ci, _cf, _vp, _i64, _vp, _i64, _vp]),
+    "xv_vad_energy_f32": (_ci, [_vp, _i64, _vp, _vp, _ci, _cf, _cf, _ci, _cf, _vp, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)      # tests check the header declares exactly these and the .so exports all of them
 
@@ -1180,6 +1183,44 @@ def topk_row_stats(scores, top_n, mean, std):
         assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n_rows
     _check(lib.xv_topk_row_stats_f32(_ptr(scores), scores.stride(0), n_rows, n_cols, int(top_n), _ptr(mean), _ptr(std), _stream()),
            "xv_topk_row_stats_f32")
+
+
+def mfcc(samples, utt_offset, utt_samples, utt_row0, utt_key, total_rows, tables, opts, feats, logmel=None):
+    """MFCC rows of a window of utterances (xv_mfcc_f32; see include/xvector_hip.h).  samples: int16 or float32 (1-D, device);
+    utt_*: int64 device tensors (utt_key as int64 bit patterns); tables: the device tables of ``mfcc.MfccTables``
+    (window, mel_first, mel_len, mel_w, lifter_dct, twiddle); opts: ``mfcc.MfccOptions``.  feats [rows, ld] float32 (ld >=
+    num_ceps), logmel [rows, ld] or None."""
+    import torch
+    lib = require_gpu()
+    assert samples.is_cuda and samples.dim() == 1 and samples.dtype in (torch.int16, torch.float32)
+    for t in (utt_offset, utt_samples, utt_row0, utt_key):
+        assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == utt_offset.numel()
+    for t in (feats, logmel):
+        if t is not None:
+            assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] >= total_rows
+    tb = tables
+    _check(lib.xv_mfcc_f32(_ptr(samples), 0 if samples.dtype == torch.int16 else 1, _ptr(utt_offset), _ptr(utt_samples),
+                           _ptr(utt_row0), _ptr(utt_key), int(utt_offset.numel()), int(total_rows), _ptr(tb["window"]),
+                           _ptr(tb["mel_first"]), _ptr(tb["mel_len"]), _ptr(tb["mel_w"]), int(tb["mel_w"].shape[0]),
+                           int(tb["mel_w"].shape[1]), _ptr(tb["lifter_dct"]), int(tb["lifter_dct"].shape[0]), _ptr(tb["twiddle"]),
+                           opts.frame_length_samples, opts.frame_shift_samples, opts.padded_length, int(opts.snip_edges),
+                           float(opts.dither), float(opts.preemphasis_coefficient), int(opts.remove_dc_offset),
+                           int(opts.use_energy), int(opts.raw_energy), float(opts.energy_floor), _ptr(feats), feats.stride(0),
+                           _ptr(logmel), 0 if logmel is None else logmel.stride(0), _stream()), "xv_mfcc_f32")
+
+
+def vad_energy(feats, utt_row0, n_frames, vopts, out):
+    """compute-vad over ragged utterances (xv_vad_energy_f32): column 0 of feats [rows, ld] (any row stride), utterance u = rows
+    utt_row0[u] .. + n_frames[u] (int64 / int32 device tensors); out[rows] float32 receives 0.0 / 1.0."""
+    import torch
+    lib = require_gpu()
+    assert feats.is_cuda and feats.dtype == torch.float32 and feats.dim() == 2 and feats.stride(1) == 1
+    assert utt_row0.is_cuda and utt_row0.dtype == torch.int64 and n_frames.is_cuda and n_frames.dtype == torch.int32
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+    _check(lib.xv_vad_energy_f32(_ptr(feats), feats.stride(0), _ptr(utt_row0), _ptr(n_frames), int(utt_row0.numel()),
+                                 float(vopts.vad_energy_threshold), float(vopts.vad_energy_mean_scale),
+                                 int(vopts.vad_frames_context), float(vopts.vad_proportion_threshold), _ptr(out), _stream()),
+           "xv_vad_energy_f32")
 
 
 def l2_normalize_rows(x, y=None, norm=None):

@@ -1,0 +1,520 @@
+"""Stage 1 of the recipe on the MI355X: MFCC features and the energy VAD from wav.scp.
+
+What ``steps/make_mfcc.sh`` (compute-mfcc-feats) and ``sid/compute_vad_decision.sh`` (compute-vad) do with Kaldi binaries:
+
+* ``MfccOptions`` / ``VadOptions`` -- Kaldi's option names and Kaldi's defaults; a recipe's values arrive through a
+  ``--config`` file (``read_config``), not through changed defaults.
+* ``MfccTables`` -- every table the kernel reads, built here: the window and the lifter x DCT-II in fp64 rounded to fp32
+  once, the twiddles exp(-2 pi i k / N) likewise, the sparse mel bank in fp32 the way Kaldi's MelBanks forms it.
+* ``read_wav`` / ``read_wav_scp`` -- RIFF/WAVE 16-bit PCM (plain or WAVE_FORMAT_EXTENSIBLE), paths and ``cmd |`` pipes.
+* ``Mfcc.compute`` -- MFCC rows and VAD decisions of many utterances per launch (csrc/xv_mfcc.hip); the decisions come back as
+  a ``frontend.VadRuns``, so they plug straight into ``FrontEnd.apply``.
+
+There is no CPU path: the arithmetic runs on the GPU, and a missing device is an error.
+"""
+import io
+import logging
+import math
+import struct
+import subprocess
+
+import numpy as np
+
+from . import frontend, hiplib
+
+logger = logging.getLogger("mfcc")
+
+FLT_EPSILON = np.float32(1.1920928955078125e-07)
+WINDOW_TYPES = ("hamming", "hanning", "povey", "rectangular", "sine", "blackman")
+
+
+# ------------------------------------------------------------------------------------------------
+# options and --config files
+# ------------------------------------------------------------------------------------------------
+class _Options(object):
+    """Options as attributes, under Kaldi's names with '-' -> '_'.  ``_FIELDS``: (name, type, Kaldi default)."""
+    _FIELDS = ()
+
+    def __init__(self, **kw):
+        for name, _, default in self._FIELDS:
+            setattr(self, name, default)
+        for k, v in kw.items():
+            self.set(k, v)
+
+    @classmethod
+    def names(cls):
+        return [n for n, _, _ in cls._FIELDS]
+
+    def set(self, name, value):
+        name = name.replace("-", "_")
+        types = {n: t for n, t, _ in self._FIELDS}
+        if name not in types:
+            raise ValueError("unknown option --%s" % name.replace("_", "-"))
+        setattr(self, name, _convert(name, types[name], value))
+
+    def update(self, pairs):
+        for k, v in pairs:
+            self.set(k, v)
+        return self
+
+
+def _convert(name, typ, value):
+    if not isinstance(value, str):
+        return typ(value)
+    if typ is bool:
+        v = value.strip().lower()
+        if v in ("true", "t", "1", ""):
+            return True
+        if v in ("false", "f", "0"):
+            return False
+        raise ValueError("option --%s: invalid boolean %r" % (name.replace("_", "-"), value))
+    try:
+        return typ(value.strip())
+    except ValueError:
+        raise ValueError("option --%s: invalid value %r" % (name.replace("_", "-"), value))
+
+
+class MfccOptions(_Options):
+    """compute-mfcc-feats' options (FrameExtractionOptions + MelBanksOptions + MfccOptions + the binary's own), Kaldi's defaults.
+    ``seed`` is this implementation's: it keys the dither noise together with the utterance id."""
+    _FIELDS = (
+        ("sample_frequency", float, 16000.0), ("frame_length", float, 25.0), ("frame_shift", float, 10.0),
+        ("dither", float, 1.0), ("preemphasis_coefficient", float, 0.97), ("remove_dc_offset", bool, True),
+        ("window_type", str, "povey"), ("round_to_power_of_two", bool, True), ("blackman_coeff", float, 0.42),
+        ("snip_edges", bool, True), ("allow_downsample", bool, False), ("allow_upsample", bool, False),
+        ("max_feature_vectors", int, -1),
+        ("num_mel_bins", int, 23), ("low_freq", float, 20.0), ("high_freq", float, 0.0), ("vtln_low", float, 100.0),
+        ("vtln_high", float, -500.0), ("debug_mel", bool, False),
+        ("num_ceps", int, 13), ("use_energy", bool, True), ("energy_floor", float, 0.0), ("raw_energy", bool, True),
+        ("cepstral_lifter", float, 22.0), ("htk_compat", bool, False),
+        ("channel", int, -1), ("min_duration", float, 0.0), ("vtln_warp", float, 1.0), ("subtract_mean", bool, False),
+        ("output_format", str, "kaldi"), ("seed", int, 0),
+    )
+
+    @property
+    def frame_length_samples(self):
+        return int(self.sample_frequency * 0.001 * self.frame_length)
+
+    @property
+    def frame_shift_samples(self):
+        return int(self.sample_frequency * 0.001 * self.frame_shift)
+
+    @property
+    def padded_length(self):
+        n = self.frame_length_samples
+        return 1 << max(0, (n - 1).bit_length()) if self.round_to_power_of_two else n
+
+    def num_frames(self, n_samples):
+        """Kaldi's NumFrames (flush=true); works on arrays."""
+        n = np.asarray(n_samples, np.int64)
+        L, S = self.frame_length_samples, self.frame_shift_samples
+        if self.snip_edges:
+            return np.where(n < L, 0, 1 + (n - L) // S)
+        return (n + S // 2) // S
+
+    def first_sample(self, t):
+        L, S = self.frame_length_samples, self.frame_shift_samples
+        t = np.asarray(t, np.int64)
+        return t * S if self.snip_edges else t * S + S // 2 - L // 2
+
+    def check(self):
+        """What the kernel does not implement raises (the analogue of XV_ERR_UNSUPPORTED on the host side)."""
+        if not self.round_to_power_of_two:
+            raise NotImplementedError("--round-to-power-of-two=false (non-power-of-two FFT) is not supported")
+        if self.htk_compat:
+            raise NotImplementedError("--htk-compat=true is not supported")
+        if self.vtln_warp != 1.0:
+            raise NotImplementedError("VTLN (--vtln-warp != 1) is not supported")
+        if self.allow_downsample or self.allow_upsample:
+            raise NotImplementedError("resampling (--allow-downsample / --allow-upsample) is not supported")
+        if self.subtract_mean or self.max_feature_vectors != -1 or self.output_format != "kaldi":
+            raise NotImplementedError("--subtract-mean, --max-feature-vectors and --output-format are not supported")
+        if self.window_type not in WINDOW_TYPES:
+            raise ValueError("invalid --window-type %r" % self.window_type)
+        if not 128 <= self.padded_length <= 1024:
+            raise NotImplementedError("padded frame length %d outside [128, 1024]" % self.padded_length)
+        if self.frame_shift_samples < 1 or self.frame_length_samples < 2:
+            raise ValueError("frame length / shift too small for --sample-frequency=%g" % self.sample_frequency)
+        if not 1 <= self.num_ceps <= self.num_mel_bins <= 128:
+            raise ValueError("need 1 <= --num-ceps <= --num-mel-bins <= 128")
+        if self.dither < 0:
+            raise ValueError("--dither must be >= 0")
+        return self
+
+
+class VadOptions(_Options):
+    """compute-vad's options, Kaldi's defaults."""
+    _FIELDS = (
+        ("vad_energy_threshold", float, 5.0), ("vad_energy_mean_scale", float, 0.5), ("vad_frames_context", int, 0),
+        ("vad_proportion_threshold", float, 0.6), ("omit_unvoiced_utts", bool, False),
+    )
+
+
+def parse_config_lines(lines, source="config"):
+    """Kaldi's ``--config`` syntax: one ``--name=value`` (or bare ``--flag``) per line; '#' starts a comment anywhere on a line.
+    Returns [(name, value)] in file order (a later line wins when applied)."""
+    out = []
+    for no, line in enumerate(lines, 1):
+        line = line.split("#", 1)[0].strip()
+        if not line:
+            continue
+        if not line.startswith("--"):
+            raise ValueError("%s:%d: expected --name=value, got %r" % (source, no, line))
+        name, eq, value = line[2:].partition("=")
+        name = name.strip()
+        if not name or " " in name:
+            raise ValueError("%s:%d: malformed option %r" % (source, no, line))
+        out.append((name, value.strip() if eq else ""))
+    return out
+
+
+def read_config(path):
+    with open(path, "rt") as f:
+        return parse_config_lines(f, path)
+
+
+def fnv1a64(key):
+    h = 0xCBF29CE484222325
+    for b in key.encode():
+        h = ((h ^ b) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def dither_key(utt, seed=0):
+    """The 64-bit Philox key of an utterance: FNV-1a of its id XOR the seed."""
+    return fnv1a64(utt) ^ (int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+# ------------------------------------------------------------------------------------------------
+# tables
+# ------------------------------------------------------------------------------------------------
+def window_function(opts):
+    """Kaldi's FeatureWindowFunction, fp64 -> fp32."""
+    L = opts.frame_length_samples
+    i = np.arange(L, dtype=np.float64)
+    a = 2.0 * math.pi / (L - 1)
+    t = opts.window_type
+    if t == "hanning":
+        w = 0.5 - 0.5 * np.cos(a * i)
+    elif t == "sine":
+        w = np.sin(0.5 * a * i)
+    elif t == "hamming":
+        w = 0.54 - 0.46 * np.cos(a * i)
+    elif t == "povey":
+        w = np.power(0.5 - 0.5 * np.cos(a * i), 0.85)
+    elif t == "rectangular":
+        w = np.ones(L)
+    elif t == "blackman":
+        b = opts.blackman_coeff
+        w = b - 0.5 * np.cos(a * i) + (0.5 - b) * np.cos(2 * a * i)
+    else:
+        raise ValueError("invalid --window-type %r" % t)
+    return w.astype(np.float32)
+
+
+def _mel32(f):
+    return np.float32(1127.0) * np.log(np.float32(1.0) + np.asarray(f, np.float32) / np.float32(700.0))
+
+
+def mel_banks(opts):
+    """Kaldi's MelBanks in fp32: -> (first bin [B] int32, weights [B, maxlen] float32, lengths [B] int32).  FFT bin i < N/2 (the
+    Nyquist bin never) at i * fs / N gets a triangular weight when its mel lies strictly inside (left, right)."""
+    f32 = np.float32
+    N = opts.padded_length
+    B = opts.num_mel_bins
+    nyq = f32(0.5) * f32(opts.sample_frequency)
+    lo = f32(opts.low_freq)
+    hi = f32(opts.high_freq) if opts.high_freq > 0 else nyq + f32(opts.high_freq)
+    if not (0 <= lo < nyq and 0 < hi <= nyq and hi > lo):
+        raise ValueError("bad mel frequency range [%g, %g] for sample frequency %g" % (lo, hi, opts.sample_frequency))
+    width = f32(opts.sample_frequency) / f32(N)
+    mlo, mhi = _mel32(lo), _mel32(hi)
+    delta = (mhi - mlo) / f32(B + 1)
+    mel = _mel32(width * np.arange(N // 2, dtype=np.float32))
+    firsts, rows = [], []
+    for b in range(B):
+        left = mlo + f32(b) * delta
+        center = mlo + f32(b + 1) * delta
+        right = mlo + f32(b + 2) * delta
+        inside = (mel > left) & (mel < right)
+        up = (mel - left) / (center - left)
+        down = (right - mel) / (right - center)
+        w = np.where(mel <= center, up, down).astype(np.float32)
+        idx = np.flatnonzero(inside)
+        if len(idx) == 0:
+            raise ValueError("mel band %d has no FFT bin: too many --num-mel-bins for this frame length" % b)
+        firsts.append(int(idx[0]))
+        rows.append(w[idx[0]:idx[-1] + 1] * inside[idx[0]:idx[-1] + 1])
+    maxlen = max(len(r) for r in rows)
+    weights = np.zeros((B, maxlen), np.float32)
+    for b, r in enumerate(rows):
+        weights[b, :len(r)] = r
+    return np.array(firsts, np.int32), weights, np.array([len(r) for r in rows], np.int32)
+
+
+def lifter_dct(opts):
+    """Rows 0 .. num_ceps - 1 of Kaldi's DCT-II matrix times the cepstral lifter, fp64 -> fp32."""
+    B, C = opts.num_mel_bins, opts.num_ceps
+    k = np.arange(C, dtype=np.float64)[:, None]
+    n = np.arange(B, dtype=np.float64)[None, :]
+    d = math.sqrt(2.0 / B) * np.cos(math.pi / B * (n + 0.5) * k)
+    d[0, :] = math.sqrt(1.0 / B)
+    Q = opts.cepstral_lifter
+    if Q != 0:
+        d *= (1.0 + 0.5 * Q * np.sin(math.pi * np.arange(C) / Q))[:, None]
+    return d.astype(np.float32)
+
+
+def twiddles(opts):
+    """exp(-2 pi i k / N) for k < N/2 as (re, im) fp32 pairs, fp64 -> fp32."""
+    N = opts.padded_length
+    ang = -2.0 * math.pi * np.arange(N // 2, dtype=np.float64) / N
+    return np.stack([np.cos(ang), np.sin(ang)], axis=1).astype(np.float32)
+
+
+class MfccTables(object):
+    def __init__(self, opts):
+        opts.check()
+        self.window = window_function(opts)
+        self.mel_first, self.mel_w, self.mel_len = mel_banks(opts)
+        self.lifter_dct = lifter_dct(opts)
+        self.twiddle = twiddles(opts)
+
+    def to_device(self, device):
+        import torch
+        return {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(device)
+                for k in ("window", "mel_first", "mel_len", "mel_w", "lifter_dct", "twiddle")}
+
+
+# ------------------------------------------------------------------------------------------------
+# WAV input
+# ------------------------------------------------------------------------------------------------
+class WavError(ValueError):
+    pass
+
+
+_EXTENSIBLE = 0xFFFE
+_PCM_GUID_TAIL = b"\x00\x00\x00\x00\x10\x00\x80\x00\x00\xaa\x00\x38\x9b\x71"
+
+
+def read_wav(data, name="wav"):
+    """RIFF/WAVE bytes -> (sample rate, int16 [channels, samples]).  16-bit PCM only (format 1, or WAVE_FORMAT_EXTENSIBLE with
+    the PCM sub-format); unknown chunks are skipped (with their pad byte when odd-sized); a ``data`` size of 0 or 0xFFFFFFFF
+    (what piped writers put there) means "to the end of the stream"."""
+    if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WAVE":
+        raise WavError("%s: not a RIFF/WAVE file" % name)
+    pos, fmt = 12, None
+    while pos + 8 <= len(data):
+        cid, size = data[pos:pos + 4], struct.unpack("<I", data[pos + 4:pos + 8])[0]
+        pos += 8
+        if cid == b"fmt ":
+            if size < 16:
+                raise WavError("%s: short fmt chunk" % name)
+            tag, nch, rate, _, align, bits = struct.unpack("<HHIIHH", data[pos:pos + 16])
+            if tag == _EXTENSIBLE:
+                if size < 40 or data[pos + 24 + 2:pos + 40] != _PCM_GUID_TAIL or struct.unpack("<H", data[pos + 24:pos + 26])[0] != 1:
+                    raise WavError("%s: WAVE_FORMAT_EXTENSIBLE with a non-PCM sub-format" % name)
+            elif tag != 1:
+                raise WavError("%s: unsupported WAV format tag %d (16-bit PCM only)" % (name, tag))
+            if bits != 16:
+                raise WavError("%s: %d-bit samples are not supported (16-bit PCM only)" % (name, bits))
+            if nch < 1 or align != 2 * nch:
+                raise WavError("%s: inconsistent fmt chunk" % name)
+            fmt = (nch, rate)
+        elif cid == b"data":
+            if fmt is None:
+                raise WavError("%s: data chunk before fmt chunk" % name)
+            end = len(data) if size in (0, 0xFFFFFFFF) else pos + size
+            if end > len(data):
+                raise WavError("%s: truncated data chunk (%d of %d bytes)" % (name, len(data) - pos, size))
+            nch = fmt[0]
+            n = (end - pos) // (2 * nch)
+            x = np.frombuffer(data, dtype="<i2", count=n * nch, offset=pos).astype(np.int16)
+            return fmt[1], x.reshape(n, nch).T
+        pos += size + (size & 1)
+    raise WavError("%s: no data chunk" % name)
+
+
+def read_wav_scp(path):
+    """Generator of (key, rxfilename) of a wav.scp."""
+    with open(path, "rt") as f:
+        for line in f:
+            line = line.strip()
+            if not line:
+                continue
+            key, _, rx = line.partition(" ")
+            if not rx.strip():
+                raise WavError("%s: no wave for key %s" % (path, key))
+            yield key, rx.strip()
+
+
+def load_wav(key, rx):
+    """The bytes of a wav.scp entry: a path, or a ``cmd |`` pipe whose non-zero exit is an error naming the key."""
+    if rx.endswith("|"):
+        p = subprocess.run(rx[:-1], shell=True, stdout=subprocess.PIPE)
+        if p.returncode != 0:
+            raise WavError("%s: command %r exited with status %d" % (key, rx[:-1], p.returncode))
+        data = p.stdout
+    else:
+        with open(rx, "rb") as f:
+            data = f.read()
+    return read_wav(data, key)
+
+
+def select_channel(key, rate, x, opts):
+    """compute-mfcc-feats' utterance rules: -> int16 [samples], or None (skipped, with Kaldi's warning)."""
+    nch = x.shape[0]
+    ch = opts.channel
+    if ch == -1:
+        if nch > 1:
+            logger.warning("Channel not specified but you have data with %d channels; defaulting to zero (key %s)", nch, key)
+        ch = 0
+    elif ch < 0 or ch >= nch:
+        logger.warning("Invalid channel %d/%d for key %s; skipping", ch, nch, key)
+        return None
+    if rate != opts.sample_frequency:
+        logger.warning("Sample frequency %g of key %s differs from --sample-frequency=%g; skipping (no resampling)",
+                       rate, key, opts.sample_frequency)
+        return None
+    if x.shape[1] < opts.min_duration * rate:
+        logger.warning("File: %s is too short (%g sec): producing no output.", key, x.shape[1] / float(rate))
+        return None
+    return np.ascontiguousarray(x[ch])
+
+
+# ------------------------------------------------------------------------------------------------
+# the device path
+# ------------------------------------------------------------------------------------------------
+class Mfcc(object):
+    """MFCC (+ VAD) of batches of utterances on one GPU.  ``window_samples``: the most samples uploaded per launch."""
+
+    def __init__(self, opts, vad_opts=None, device="cuda:0", window_samples=1 << 26, with_logmel=False):
+        import torch
+        hiplib.require_gpu()
+        self.torch = torch
+        self.opts = opts.check()
+        self.vad_opts = vad_opts
+        self.device = torch.device(device)
+        self.window_samples = int(window_samples)
+        self.with_logmel = with_logmel
+        self.tables = MfccTables(opts)
+        self._dev = self.tables.to_device(self.device)
+        # own stream, as FrontEnd: the results go back to the host, nothing on the compute stream waits for them
+        self._stream = torch.cuda.Stream(device=self.device)
+        self.stats = dict(utterances=0, samples=0, frames=0, launches=0)
+
+    def _windows(self, lens):
+        i, n = 0, len(lens)
+        while i < n:
+            j, tot = i, 0
+            while j < n and (j == i or tot + lens[j] <= self.window_samples):
+                tot += lens[j]
+                j += 1
+            yield i, j
+            i = j
+
+    def compute(self, keys, waves, vad=None):
+        """keys: utterance ids (they key the dither); waves: 1-D int16 (or float32) sample arrays.  Returns
+        ``(feats, vads, logmel)``: float32 [T, num_ceps] per utterance, a ``frontend.VadRuns`` (None unless VAD options were
+        given or ``vad`` is True), and the float32 [T, num_mel_bins] log-mel energies (None unless ``with_logmel``)."""
+        opts = self.opts
+        waves = [np.asarray(w).reshape(-1) for w in waves]
+        assert len(keys) == len(waves)
+        do_vad = self.vad_opts is not None if vad is None else bool(vad)
+        feats, logmels, runs = [], [], frontend.VadRuns() if do_vad else None
+        lens = [w.shape[0] for w in waves]
+        for i, j in self._windows(lens):
+            f, lm, v = self._launch(keys[i:j], waves[i:j], do_vad)
+            feats += f
+            logmels += lm
+            if do_vad:
+                runs.add_run(*v)
+        return feats, runs, (logmels if self.with_logmel else None)
+
+    def _launch(self, keys, waves, do_vad):
+        torch, opts = self.torch, self.opts
+        n = len(waves)
+        ns = np.array([w.shape[0] for w in waves], np.int64)
+        T = opts.num_frames(ns).astype(np.int64)
+        row0 = np.zeros(n, np.int64)
+        np.cumsum(T[:-1], out=row0[1:])
+        rows = int(T.sum())
+        off = np.zeros(n, np.int64)
+        np.cumsum(ns[:-1], out=off[1:])
+        dtype = np.float32 if any(w.dtype != np.int16 for w in waves) else np.int16
+        flat = np.concatenate([w.astype(dtype, copy=False) for w in waves]) if n else np.zeros(0, dtype)
+        keyv = np.array([dither_key(k, opts.seed) for k in keys], np.uint64).view(np.int64)
+        C, B = opts.num_ceps, opts.num_mel_bins
+        with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
+            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device, non_blocking=False)  # noqa: E731
+            x = dev(flat if len(flat) else np.zeros(1, dtype))
+            d_off, d_ns, d_row0, d_key = dev(off), dev(ns), dev(row0), dev(keyv)
+            y = torch.empty((max(rows, 1), C), dtype=torch.float32, device=self.device)
+            lm = torch.empty((max(rows, 1), B), dtype=torch.float32, device=self.device) if self.with_logmel else None
+            hiplib.mfcc(x, d_off, d_ns, d_row0, d_key, rows, self._dev, opts, y, lm)
+            if do_vad:
+                vad = torch.empty(max(rows, 1), dtype=torch.float32, device=self.device)
+                hiplib.vad_energy(y, d_row0, dev(T.astype(np.int32)), self.vad_opts, vad)
+                vad_h = vad[:rows].cpu().numpy()
+            y_h = y[:rows].cpu().numpy()
+            lm_h = lm[:rows].cpu().numpy() if lm is not None else None
+        self.stats["utterances"] += n
+        self.stats["samples"] += int(ns.sum())
+        self.stats["frames"] += rows
+        self.stats["launches"] += 1
+        bounds = list(zip(row0.tolist(), (row0 + T).tolist()))
+        feats = [y_h[a:b] for a, b in bounds]
+        logmel = [lm_h[a:b] for a, b in bounds] if lm_h is not None else []
+        v = None
+        if do_vad:
+            offs = np.concatenate([[0], np.cumsum(T)]).astype(np.int64)
+            v = (vad_h, offs)
+        return feats, logmel, v
+
+
+def compute_vad(mats, vad_opts, device="cuda:0"):
+    """compute-vad on feature matrices already in memory (the kernel reads column 0): -> ``frontend.VadRuns``."""
+    import torch
+    hiplib.require_gpu()
+    dev = torch.device(device)
+    T = np.array([m.shape[0] for m in mats], np.int64)
+    row0 = np.zeros(len(mats), np.int64)
+    np.cumsum(T[:-1], out=row0[1:])
+    rows = int(T.sum())
+    runs = frontend.VadRuns()
+    if not len(mats):
+        return runs
+    c0 = np.zeros((max(rows, 1), 1), np.float32)
+    for m, r in zip(mats, row0.tolist()):
+        if m.shape[0]:
+            c0[r:r + m.shape[0], 0] = m[:, 0]
+    with torch.cuda.device(dev):
+        out = torch.empty(max(rows, 1), dtype=torch.float32, device=dev)
+        hiplib.vad_energy(torch.from_numpy(c0).to(dev), torch.from_numpy(row0).to(dev), torch.from_numpy(T.astype(np.int32)).to(dev),
+                          vad_opts, out)
+        runs.add_run(out[:rows].cpu().numpy(), np.concatenate([[0], np.cumsum(T)]).astype(np.int64))
+    return runs
+
+
+def wav_bytes(x, rate, extensible=False, streaming=False, extra_chunks=()):
+    """int16 [samples] or [channels, samples] -> RIFF/WAVE bytes (tests and the bench tool write their inputs with it).
+    ``streaming``: the RIFF and data sizes are 0xFFFFFFFF, as piped writers leave them; ``extra_chunks``: (id, payload) pairs
+    placed before the data chunk."""
+    x = np.asarray(x, np.int16)
+    if x.ndim == 1:
+        x = x[None]
+    nch = x.shape[0]
+    payload = np.ascontiguousarray(x.T).astype("<i2").tobytes()
+    if extensible:
+        fmt = struct.pack("<HHIIHHHHI", _EXTENSIBLE, nch, int(rate), int(rate) * 2 * nch, 2 * nch, 16, 22, 16, 0) + \
+            struct.pack("<H", 1) + _PCM_GUID_TAIL
+    else:
+        fmt = struct.pack("<HHIIHH", 1, nch, int(rate), int(rate) * 2 * nch, 2 * nch, 16)
+    body = io.BytesIO()
+    body.write(b"WAVE")
+    body.write(b"fmt " + struct.pack("<I", len(fmt)) + fmt)
+    for cid, data in extra_chunks:
+        body.write(cid + struct.pack("<I", len(data)) + data + (b"\x00" if len(data) & 1 else b""))
+    body.write(b"data" + struct.pack("<I", 0xFFFFFFFF if streaming else len(payload)) + payload)
+    b = body.getvalue()
+    return b"RIFF" + struct.pack("<I", 0xFFFFFFFF if streaming else len(b)) + b

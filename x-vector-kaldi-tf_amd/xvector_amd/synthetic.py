@@ -16,6 +16,8 @@ used once to manufacture "trained-like" running statistics; the extractor never 
                              precision arithmetics (tests/test_gpu_hostile.py).
 * ``mfcc_like``           -- utterances with the statistics of real cepstra after CMN: frame-to-frame AR(1) correlation,
                              a spectrum of per-coefficient scales, zero mean per utterance.
+* ``speech_like_wave``    -- int16 audio for the feature front-end: AR-filtered noise bursts of varying level and colour,
+                             separated by near-silence.
 """
 import numpy as np
 
@@ -294,3 +296,27 @@ def trained_checkpoint(topo, feat_dim=23, n_spk=64, steps=300, learning_rate=1e-
             first = last
     out, _ = tr.export()
     return out, dict(first_loss=float(first), last_loss=float(last), accuracy_last=float(acc), seconds=time.time() - t0, steps=steps)
+
+
+
+def speech_like_wave(n_samples, fs=8000, seed=0, level_db=(-35.0, -6.0)):
+    """int16 [n_samples]: bursts of 0.2-1.5 s of noise shaped by two random resonances and a spectral tilt (a crude vowel-like
+    spectrum; filtered in the frequency domain, so NumPy alone does it at any length), levels uniform in ``level_db`` dBFS,
+    separated by 0.1-0.8 s of near-silence (std ~3 LSB)."""
+    rng = np.random.default_rng(seed)
+    out = rng.standard_normal(n_samples) * 3.0
+    pos = int(rng.integers(0, max(1, int(0.3 * fs))))
+    while pos < n_samples:
+        n = min(int(rng.uniform(0.2, 1.5) * fs), n_samples - pos)
+        if n > 1:
+            f = np.fft.rfftfreq(n, 1.0 / fs)
+            env = 1.0 / (1.0 + (f / 500.0) ** 2) ** 0.5
+            for _ in range(2):
+                fc, bw = rng.uniform(200.0, 0.45 * fs), rng.uniform(60.0, 300.0)
+                env = env + 4.0 / (1.0 + ((f - fc) / bw) ** 2)
+            x = np.fft.irfft(np.fft.rfft(rng.standard_normal(n)) * env, n)
+            x *= np.hanning(n) ** 0.25
+            rms = np.sqrt(np.mean(x * x)) or 1.0
+            out[pos:pos + n] += x / rms * 32768.0 * 10.0 ** (rng.uniform(*level_db) / 20.0)
+        pos += n + int(rng.uniform(0.1, 0.8) * fs)
+    return np.clip(np.rint(out), -32768, 32767).astype(np.int16)
