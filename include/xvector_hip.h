@@ -52,7 +52,7 @@ extern "C" {
 #define XV_ERR_BAD_ARG (-1)
 #define XV_ERR_UNSUPPORTED (-2)
 
-/* Library / ABI version (increments whenever an entry point is added or changed; currently 26). */
+/* Library / ABI version (increments whenever an entry point is added or changed; currently 27). */
 int xv_version(void);
 /* Thread-local description of the last non-zero return. */
 const char *xv_last_error(void);
@@ -585,6 +585,66 @@ int xv_mfcc_f32(const void *samples, int sample_format, const int64_t *utt_offse
 int xv_vad_energy_f32(const float *feats, int64_t ld, const int64_t *utt_row0, const int32_t *n_frames, int n_utts,
                       float energy_threshold, float energy_mean_scale, int frames_context, float proportion_threshold, float *out,
                       void *stream);
+
+/* Stage 2 of the recipe: wav-reverberate on the GPU (reverberation, additive noise, level, trim / repeat, the int16 write;
+ * csrc/xv_augment.hip).  One evaluation level of many ragged utterances is six launches in this order:
+ * power, conv, gains, mix, level, write.  sig: an int16 sample pool holding every input and noise; taps: an fp32 pool of
+ * impulse responses (already scaled by 1/32768); y: an fp64 scratch pool (the waveform between the steps).  Utterance u is described by
+ * utt[XV_AUG_UTT_FIELDS * u + XV_AUG_*] (int64), noise reference r by refs[XV_AUG_REF_FIELDS * r + XV_AUG_REF_*].
+ * xv_augment_power_f64  segment s = segments[4s ..] = (off, len, tile0, ntiles), a run of sig; tile t = tiles[2t ..] = (segment,
+ *   i0), i0 a multiple of 16384: tile_sumsq[t] = the fp64 sum of sig[off + i]^2 over i in [i0, min(i0 + 16384, len)); the tiles
+ *   of segment s are tile_sumsq[tile0 .. tile0 + ntiles) in order (ntiles = 0 for an empty segment).
+ * xv_augment_conv_f64  job j = jobs[5j ..] = (x_off, N, h_off, L, y_off): the full linear convolution of x = sig[x_off .. + N)
+ *   with h = taps[h_off .. + L), exact products summed in fp64; output n < N + L - 1 goes to y[y_off + n]
+ *   (y_off < 0: not written).  Tile t = tiles[2t ..] = (job, n0) covers outputs n0 .. n0 + 2047 (n0 a multiple of 2048) and
+ *   writes tile_sumsq[t] = the fp64 sum of their squares.
+ * xv_augment_gains_f32  with S(s) = the sum of power_sumsq over segment s's tiles, in order: per utterance utt_out[4u] = P0 =
+ *   S(X_SEG) / N; utt_out[4u + 1] = E = (sum of conv_sumsq over EARLY_TILE0 .. + EARLY_NTILES) / EARLY_LEN, or P0 when
+ *   EARLY_NTILES = 0; per reference: ref_power[r] = Pn = S(NOISE_SEG) / NOISE_LEN (0 when NOISE_LEN = 0), ref_scale[r] =
+ *   fp32(sqrt(10^(-snr_r / 10) E / Pn)), 0 when Pn = 0.
+ * xv_augment_mix_f64  tile t = (utt, n0), n0 a multiple of 1024: for n < Y_LEN, v = y[Y_OFF + n] (RIR != 0) or sig[X_OFF + n];
+ *   then for each reference in order, v = v + ref_scale * sig[NOISE_OFF + n - OFFSET] where 0 <= n - OFFSET < NOISE_LEN (fp64,
+ *   the product exact); y[Y_OFF + n] = v; tile_sumsq[t] = sum v^2 (fp64).
+ * xv_augment_level_f32  utt_out[4u + 2] = P1 = (sum of mix_sumsq over MIX_TILE0 .. + MIX_NTILES) / Y_LEN; utt_out[4u + 3] =
+ *   the level: utt_param[2u] (volume) when > 0, else fp32(sqrt(P0 / P1)) when utt_param[2u + 1] != 0 and P1 > 0, else 1.
+ * xv_augment_write  tile t = (utt, m0), m0 a multiple of 1024: for m < M, v = trunc(y[Y_OFF + SHIFT + (m mod N)] * level) (fp64),
+ *   saturated to [-32768, 32767] (clipped[u] += 1 when saturated), to out[OUT_OFF + m] as int16 (sample_format 0) or fp32 (1).
+ *   SHIFT + N <= Y_LEN is the caller's.  Nothing outside the described rows is written. */
+#define XV_AUG_UTT_FIELDS 16
+#define XV_AUG_X_OFF 0
+#define XV_AUG_N 1
+#define XV_AUG_Y_OFF 2
+#define XV_AUG_Y_LEN 3
+#define XV_AUG_RIR 4
+#define XV_AUG_EARLY_TILE0 5
+#define XV_AUG_EARLY_NTILES 6
+#define XV_AUG_EARLY_LEN 7
+#define XV_AUG_REF0 8
+#define XV_AUG_NREF 9
+#define XV_AUG_SHIFT 10
+#define XV_AUG_M 11
+#define XV_AUG_OUT_OFF 12
+#define XV_AUG_MIX_TILE0 13
+#define XV_AUG_MIX_NTILES 14
+#define XV_AUG_X_SEG 15
+#define XV_AUG_REF_FIELDS 4
+#define XV_AUG_REF_NOISE_OFF 0
+#define XV_AUG_REF_NOISE_LEN 1
+#define XV_AUG_REF_OFFSET 2
+#define XV_AUG_REF_NOISE_SEG 3
+int xv_augment_power_f64(const int16_t *sig, const int64_t *segments, const int64_t *tiles, int64_t n_tiles, double *tile_sumsq,
+                         void *stream);
+int xv_augment_conv_f64(const int16_t *sig, const float *taps, const int64_t *jobs, const int64_t *tiles, int64_t n_tiles, double *y,
+                        double *tile_sumsq, void *stream);
+int xv_augment_gains_f32(const int64_t *utt, int n_utts, const int64_t *refs, const float *ref_snr, const int64_t *segments,
+                         const double *power_sumsq, const double *conv_sumsq, double *utt_out, double *ref_power, float *ref_scale,
+                         void *stream);
+int xv_augment_mix_f64(const int16_t *sig, const int64_t *utt, const int64_t *refs, const float *ref_scale, const int64_t *tiles,
+                       int64_t n_tiles, double *y, double *tile_sumsq, void *stream);
+int xv_augment_level_f32(const int64_t *utt, int n_utts, const double *utt_param, const double *mix_sumsq, double *utt_out,
+                         void *stream);
+int xv_augment_write(const double *y, const int64_t *utt, const double *utt_out, const int64_t *tiles, int64_t n_tiles, void *out,
+                     int sample_format, unsigned long long *clipped, void *stream);
 
 #ifdef __cplusplus
 }

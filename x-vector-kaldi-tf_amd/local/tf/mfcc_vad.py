@@ -5,11 +5,14 @@
   compute-vad        [--config F] [--name=value ...] <feats-rspec> <wspec>
   compute-mfcc-vad   [--config F] [--vad-config F] [--name=value ...] [--write-num-frames ark,t:F] scp:wav.scp <feats-wspec>
                      <vad-wspec>       (both in one pass: the VAD reads the features on the device, nothing is re-read)
+  wav-to-duration    [--read-entire-file] scp:wav.scp ark,t:utt2dur
 
 Options carry Kaldi's names and defaults (xvector_amd/mfcc.py); a ``--config`` file is read first, the command line
 overrides it.  ``--seed`` keys the dither noise with the utterance id.  Outputs are ``ark,scp:A,S`` or
 ``ark:A``; features are written as ``FM`` records, VAD decisions as ``FV`` records, ``--write-num-frames`` as ``key N`` lines.
-wav.scp entries are paths or ``cmd |`` pipes; 16-bit PCM WAV only.  The arithmetic runs on the MI355X: no CPU fallback.
+wav.scp entries are paths or ``cmd |`` pipes; 16-bit PCM WAV only.  A pipe whose last stage is ``wav-reverberate`` (what
+Kaldi's reverberate_data_dir.py / augment_data_dir.py write) is evaluated in-process on the GPU (xvector_amd/augment.py,
+DESIGN.md §8.7); no wav-reverberate process is started.  The arithmetic runs on the MI355X: no CPU fallback.
 """
 from __future__ import print_function
 
@@ -26,12 +29,13 @@ if _HERE not in sys.path:
 sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))
 
 import kaldi_io  # noqa: E402
-from xvector_amd import mfcc  # noqa: E402
+from xvector_amd import augment, mfcc  # noqa: E402
 
 logger = logging.getLogger('mfcc_vad')
 logger.addHandler(logging.StreamHandler())
 logger.setLevel(logging.INFO)
 logging.getLogger('mfcc').addHandler(logging.StreamHandler())
+logging.getLogger('augment').addHandler(logging.StreamHandler())
 
 WINDOW_SAMPLES = 1 << 26          # samples per launch (128 MiB of int16)
 
@@ -88,9 +92,27 @@ def _wav_scp_path(rspec):
     return path
 
 
-def _read_waves(path, opts):
-    """(key, int16 samples) of every usable entry, in order (Kaldi's skip rules applied)."""
+def _read_waves(path, opts, state=None):
+    """(key, int16 samples) of every usable entry, in order (Kaldi's skip rules applied).  An entry whose last pipeline stage
+    is wav-reverberate comes as (key, augment.Pending) added to ``state['plan']``: only its length is known here, the GPU makes
+    its samples (xvector_amd/augment.py)."""
     for key, rx in mfcc.read_wav_scp(path):
+        node = None
+        if augment.is_augmented(rx):
+            try:
+                node = augment.parse_rx(rx)
+                if isinstance(node, augment.Reverb):
+                    if state is None:
+                        raise augment.AugmentError("augmented entry outside a batch")
+                    if state.get("plan") is None:
+                        state["plan"] = augment.Plan()
+                    top = state["augmenter"].plan([(key, node)], state["plan"]).top[-1]
+                    p = augment.Pending(top, state["plan"])
+                    if _select_pending(key, p, opts):
+                        yield key, p
+                    continue
+            except augment.AugmentError as e:
+                raise SystemExit("Failed to read the wave of %s: %s" % (key, e))
         try:
             rate, x = mfcc.load_wav(key, rx)
         except mfcc.WavError as e:
@@ -98,6 +120,21 @@ def _read_waves(path, opts):
         w = mfcc.select_channel(key, rate, x, opts)
         if w is not None:
             yield key, w
+
+
+def _select_pending(key, p, opts):
+    """mfcc.select_channel's rules for an augmented entry (one channel, p.M samples at p.rate)."""
+    if opts.channel not in (-1, 0):
+        logger.warning("Invalid channel %d/1 for key %s; skipping", opts.channel, key)
+        return False
+    if p.rate != opts.sample_frequency:
+        logger.warning("Sample frequency %g of key %s differs from --sample-frequency=%g; skipping (no resampling)",
+                       p.rate, key, opts.sample_frequency)
+        return False
+    if p.M < opts.min_duration * p.rate:
+        logger.warning("File: %s is too short (%g sec): producing no output.", key, p.M / float(p.rate))
+        return False
+    return True
 
 
 def _batches(items, max_samples):
@@ -113,6 +150,16 @@ def _batches(items, max_samples):
         yield keys, waves
 
 
+def _planned_batches(path, opts, augmenter, max_samples):
+    """_batches over _read_waves.  _batches reads the entry that overflows a batch before it yields the batch, so that entry is
+    already planned into the current plan: it keeps that plan (augment.Pending.plan), and the entries read after the yield start a
+    plan of their own, so no plan (and no decoded RIR or noise) outlives the batches that use it."""
+    state = dict(augmenter=augmenter, plan=None)
+    for keys, waves in _batches(_read_waves(path, opts, state), max_samples):
+        state["plan"] = None
+        yield keys, waves
+
+
 def cmd_mfcc(args, with_vad):
     opts = _options(mfcc.MfccOptions, args.config, args)
     vopts = _options(mfcc.VadOptions, args.vad_config, args) if with_vad else None
@@ -125,9 +172,13 @@ def cmd_mfcc(args, with_vad):
     vad_out = _Out(args.vad_wspecifier) if with_vad else None
     nf_out = _NumFrames(args.write_num_frames) if args.write_num_frames else None
     engine = mfcc.Mfcc(opts, vopts, window_samples=WINDOW_SAMPLES)
+    augmenter = augment.Augmenter()
     n_done = n_vad_skipped = 0
-    for keys, waves in _batches(_read_waves(path, opts), WINDOW_SAMPLES):
-        feats, vads, _ = engine.compute(keys, waves)
+    for keys, waves in _planned_batches(path, opts, augmenter, WINDOW_SAMPLES):
+        if any(isinstance(w, augment.Pending) for w in waves):
+            feats, vads, _ = augment.mfcc_compute(engine, augmenter, keys, waves)
+        else:
+            feats, vads, _ = engine.compute(keys, waves)
         for i, (k, f) in enumerate(zip(keys, feats)):
             kaldi_io.write_mat(feats_out.fd, f, key=k)
             if nf_out:
@@ -175,6 +226,26 @@ def cmd_vad(args):
     logger.info("Applied energy based voice activity detection; processed %d utterances", len(keys))
 
 
+def cmd_wav_to_duration(args):
+    """key + samples / rate per entry (Kaldi's wav-to-duration); an augmented entry's length comes from its options and the
+    header of its input, without evaluating it."""
+    path = _wav_scp_path(args.wav_rspecifier)
+    kind, _, out = args.duration_wspecifier.partition(":")
+    if kind.split(",")[0] != "ark" or not out:
+        raise SystemExit("unsupported wspecifier %r (ark,t:F)" % args.duration_wspecifier)
+    aug = augment.Augmenter()
+    n = 0
+    with open(out, "wt") as f:
+        for key, rx in mfcc.read_wav_scp(path):
+            try:
+                samples, rate = augment.duration_samples(key, rx, aug)
+            except (mfcc.WavError, augment.AugmentError) as e:
+                raise SystemExit("Failed to read the wave of %s: %s" % (key, e))
+            f.write("%s %.7g\n" % (key, np.float32(samples) / np.float32(rate)))
+            n += 1
+    logger.info("Printed duration for %d audio files.", n)
+
+
 def build_parser():
     p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = p.add_subparsers(dest="cmd")
@@ -198,10 +269,17 @@ def build_parser():
     b.add_argument("wav_rspecifier")
     b.add_argument("feats_wspecifier")
     b.add_argument("vad_wspecifier")
+    d = sub.add_parser("wav-to-duration")
+    d.add_argument("--read-entire-file", action="store_true", help="accepted for Kaldi compatibility: every file is read whole")
+    d.add_argument("wav_rspecifier")
+    d.add_argument("duration_wspecifier")
     return p
 
 
 def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if argv[:1] == ["wav-to-duration"]:               # Kaldi's --read-entire-file=true|false form
+        argv = [a.split("=")[0] if a.startswith("--read-entire-file=") else a for a in argv]
     args = build_parser().parse_args(argv)
     try:
         if args.cmd == "compute-mfcc-feats":
@@ -211,6 +289,8 @@ def main(argv=None):
             cmd_mfcc(args, True)
         elif args.cmd == "compute-vad":
             cmd_vad(args)
+        elif args.cmd == "wav-to-duration":
+            cmd_wav_to_duration(args)
         else:
             build_parser().print_help()
             return 1

@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -121,6 +121,13 @@ _SIGNATURES = {
     "xv_mfcc_f32": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _ci, _i64, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _ci, _vp, _ci, _ci, _ci, _ci,
                           _cf, _cf, _ci, _ci, _ci, _cf, _vp, _i64, _vp, _i64, _vp]),
     "xv_vad_energy_f32": (_ci, [_vp, _i64, _vp, _vp, _ci, _cf, _cf, _ci, _cf, _vp, _vp]),
+    # stage 2: wav-reverberate
+    "xv_augment_power_f64": (_ci, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "xv_augment_conv_f64": (_ci, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "xv_augment_gains_f32": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "xv_augment_mix_f64": (_ci, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "xv_augment_level_f32": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp]),
+    "xv_augment_write": (_ci, [_vp, _vp, _vp, _vp, _i64, _vp, _ci, _vp, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)      # tests check the header declares exactly these and the .so exports all of them
 
@@ -1221,6 +1228,75 @@ def vad_energy(feats, utt_row0, n_frames, vopts, out):
                                  float(vopts.vad_energy_threshold), float(vopts.vad_energy_mean_scale),
                                  int(vopts.vad_frames_context), float(vopts.vad_proportion_threshold), _ptr(out), _stream()),
            "xv_vad_energy_f32")
+
+
+def _dev(t, dtype, name):
+    assert t.is_cuda and t.dtype == dtype and t.is_contiguous(), "%s must be a contiguous cuda %s tensor" % (name, dtype)
+    return _ptr(t)
+
+
+def augment_power(sig, segments, tiles, tile_sumsq):
+    """wav-reverberate, step 1 (xv_augment_power_f64): fp64 sums of squares of int16 segments [S, 4] = (off, len, tile0,
+    ntiles), per tile [T, 2] = (segment, first sample)."""
+    import torch
+    lib = require_gpu()
+    assert segments.shape[1] == 4 and tiles.shape[1] == 2 and tile_sumsq.numel() >= tiles.shape[0]
+    _check(lib.xv_augment_power_f64(_dev(sig, torch.int16, "sig"), _dev(segments, torch.int64, "segments"),
+                                    _dev(tiles, torch.int64, "tiles"), int(tiles.shape[0]), _dev(tile_sumsq, torch.float64, "tile_sumsq"),
+                                    _stream()), "xv_augment_power_f64")
+
+
+def augment_conv(sig, taps, jobs, tiles, y, tile_sumsq):
+    """Step 2 (xv_augment_conv_f64): jobs [J, 5], tiles [T, 2] int64; y, tile_sumsq float64 [>= T]."""
+    import torch
+    lib = require_gpu()
+    assert jobs.shape[1] == 5 and tiles.shape[1] == 2 and tile_sumsq.numel() >= tiles.shape[0]
+    _check(lib.xv_augment_conv_f64(_dev(sig, torch.int16, "sig"), _dev(taps, torch.float32, "taps"), _dev(jobs, torch.int64, "jobs"),
+                                   _dev(tiles, torch.int64, "tiles"), int(tiles.shape[0]), _dev(y, torch.float64, "y"),
+                                   _dev(tile_sumsq, torch.float64, "tile_sumsq"), _stream()), "xv_augment_conv_f64")
+
+
+def augment_gains(utt, refs, ref_snr, segments, power_sumsq, conv_sumsq, utt_out, ref_power, ref_scale):
+    """Step 3 (xv_augment_gains_f32): utt [U, 16], refs [R, 4], segments [S, 4] int64 descriptors; utt_out [U, 4] float64."""
+    import torch
+    lib = require_gpu()
+    assert utt.shape[1] == 16 and refs.shape[1] == 4 and segments.shape[1] == 4 and utt_out.shape == (utt.shape[0], 4)
+    _check(lib.xv_augment_gains_f32(_dev(utt, torch.int64, "utt"), int(utt.shape[0]), _dev(refs, torch.int64, "refs"),
+                                    _dev(ref_snr, torch.float32, "ref_snr"), _dev(segments, torch.int64, "segments"),
+                                    _dev(power_sumsq, torch.float64, "power_sumsq"), _dev(conv_sumsq, torch.float64, "conv_sumsq"),
+                                    _dev(utt_out, torch.float64, "utt_out"), _dev(ref_power, torch.float64, "ref_power"),
+                                    _dev(ref_scale, torch.float32, "ref_scale"), _stream()), "xv_augment_gains_f32")
+
+
+def augment_mix(sig, utt, refs, ref_scale, tiles, y, tile_sumsq):
+    """Step 4 (xv_augment_mix_f64): tiles [T, 2] = (utterance, first sample) int64."""
+    import torch
+    lib = require_gpu()
+    assert tiles.shape[1] == 2 and tile_sumsq.numel() >= tiles.shape[0]
+    _check(lib.xv_augment_mix_f64(_dev(sig, torch.int16, "sig"), _dev(utt, torch.int64, "utt"), _dev(refs, torch.int64, "refs"),
+                                  _dev(ref_scale, torch.float32, "ref_scale"), _dev(tiles, torch.int64, "tiles"), int(tiles.shape[0]),
+                                  _dev(y, torch.float64, "y"), _dev(tile_sumsq, torch.float64, "tile_sumsq"), _stream()),
+           "xv_augment_mix_f64")
+
+
+def augment_level(utt, utt_param, mix_sumsq, utt_out):
+    """Step 5 (xv_augment_level_f32): utt_param [U, 2] float64 = (volume, normalize)."""
+    import torch
+    lib = require_gpu()
+    assert utt_param.shape == (utt.shape[0], 2)
+    _check(lib.xv_augment_level_f32(_dev(utt, torch.int64, "utt"), int(utt.shape[0]), _dev(utt_param, torch.float64, "utt_param"),
+                                    _dev(mix_sumsq, torch.float64, "mix_sumsq"), _dev(utt_out, torch.float64, "utt_out"), _stream()),
+           "xv_augment_level_f32")
+
+
+def augment_write(y, utt, utt_out, tiles, out, sample_format, clipped):
+    """Step 6 (xv_augment_write): out int16 (sample_format 0) or float32 (1), 1-D; clipped [U] int64 counters."""
+    import torch
+    lib = require_gpu()
+    assert tiles.shape[1] == 2 and out.dim() == 1 and out.dtype == (torch.int16 if sample_format == 0 else torch.float32)
+    _check(lib.xv_augment_write(_dev(y, torch.float64, "y"), _dev(utt, torch.int64, "utt"), _dev(utt_out, torch.float64, "utt_out"),
+                                _dev(tiles, torch.int64, "tiles"), int(tiles.shape[0]), _ptr(out), int(sample_format),
+                                _dev(clipped, torch.int64, "clipped"), _stream()), "xv_augment_write")
 
 
 def l2_normalize_rows(x, y=None, norm=None):

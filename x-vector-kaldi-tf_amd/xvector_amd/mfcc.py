@@ -413,10 +413,12 @@ class Mfcc(object):
             yield i, j
             i = j
 
-    def compute(self, keys, waves, vad=None):
+    def compute(self, keys, waves, vad=None, fill=None):
         """keys: utterance ids (they key the dither); waves: 1-D int16 (or float32) sample arrays.  Returns
         ``(feats, vads, logmel)``: float32 [T, num_ceps] per utterance, a ``frontend.VadRuns`` (None unless VAD options were
-        given or ``vad`` is True), and the float32 [T, num_mel_bins] log-mel energies (None unless ``with_logmel``)."""
+        given or ``vad`` is True), and the float32 [T, num_mel_bins] log-mel energies (None unless ``with_logmel``).
+        ``fill(x, i, j, offsets)``: called with each window's device sample buffer after the upload, before the MFCC launch, for
+        utterances i .. j - 1 at ``offsets`` (the augmented entries of xvector_amd/augment.py write their samples there)."""
         opts = self.opts
         waves = [np.asarray(w).reshape(-1) for w in waves]
         assert len(keys) == len(waves)
@@ -424,14 +426,15 @@ class Mfcc(object):
         feats, logmels, runs = [], [], frontend.VadRuns() if do_vad else None
         lens = [w.shape[0] for w in waves]
         for i, j in self._windows(lens):
-            f, lm, v = self._launch(keys[i:j], waves[i:j], do_vad)
+            f, lm, v = self._launch(keys[i:j], waves[i:j], do_vad,
+                                    None if fill is None else (lambda x, off, i=i, j=j: fill(x, i, j, off)))
             feats += f
             logmels += lm
             if do_vad:
                 runs.add_run(*v)
         return feats, runs, (logmels if self.with_logmel else None)
 
-    def _launch(self, keys, waves, do_vad):
+    def _launch(self, keys, waves, do_vad, fill=None):
         torch, opts = self.torch, self.opts
         n = len(waves)
         ns = np.array([w.shape[0] for w in waves], np.int64)
@@ -448,6 +451,8 @@ class Mfcc(object):
         with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
             dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device, non_blocking=False)  # noqa: E731
             x = dev(flat if len(flat) else np.zeros(1, dtype))
+            if fill is not None:
+                fill(x, off)
             d_off, d_ns, d_row0, d_key = dev(off), dev(ns), dev(row0), dev(keyv)
             y = torch.empty((max(rows, 1), C), dtype=torch.float32, device=self.device)
             lm = torch.empty((max(rows, 1), B), dtype=torch.float32, device=self.device) if self.with_logmel else None
