@@ -13,17 +13,23 @@ for every ragged batch 5x TDNN GEMM -> statistics pooling -> segment FC, then th
 average, then (N > 1) the single RCCL gather of the [10000, 512] blocks to rank 0.  Inputs (packed
 feature batches) are resident in HBM before the timed region starts; nothing is skipped or cached.
 
-Rank 0 prints ONE JSON line.  ``roofline`` is for the GEMM kernels of the step (bf16x3 split-precision MFMA by default:
-tdnn_gemm_bf16x3_kernel for layers 0-2, tdnn_pair_pool_kernel for layers 3+4 + pooling statistics, the FC) from
-algorithmic FLOPs / HIP-event time measured inside the timed region; ``roofline_pool`` is the same for the HBM-bound
-pooling kernel; ``cpu_baseline`` is a torch-CPU fp32 port of the reference forward (batch 1, like the reference) timed on
-this box's host cores on a bounded sample: the faithful 2-thread figure, a thread sweep, and ``all_cores`` = the
-reference's deployment shape (nj processes x 2 threads).  At N = 1 the line also carries ``fp32_exact`` (the same step on
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, writes ``--dump-outputs`` and prints the line
+with what its own timed region measured: ``value`` / ``ms_per_step``, ``roofline`` for the GEMM kernels of the step (bf16x3
+split-precision MFMA by default: tdnn_gemm_bf16x3_kernel for layers 0-2, tdnn_pair_pool_kernel for layers 3+4 + pooling
+statistics, the FC) from algorithmic FLOPs / HIP-event time measured inside the timed region, the pooling launches' figure
+(``pool_blocks`` behind the fused epilogue, ``roofline_pool`` without it) and ``accuracy_probe`` (what ``engine.select_model``
+measured when it admitted the arithmetic for these weights).
+
+``--full`` adds everything that takes runs or checks of its own, after the timed region: ``roofline.by_launch`` (extra passes
+over the largest batch), ``roofline_pool`` of the standalone pooling kernel, the parity of sampled utterances against the fp64
+oracle, ``with_ark_write`` and ``cpu_baseline``, a torch-CPU fp32 port of the reference forward (batch 1, like the reference)
+timed on this box's host cores on a bounded sample: the faithful 2-thread figure, a thread sweep, and ``all_cores`` = the
+reference's deployment shape (nj processes x 2 threads).  At N = 1 the full line also carries ``fp32_exact`` (the same step on
 the exact-fp32 MFMA path), ``bf16x3`` (all layers in the bf16x3 arithmetic), ``e2e_ark_to_ark`` (ark bytes ->
 Model.make_embedding -> ark bytes, PCIe and Kaldi parsing included; never ``value``), ``cli_job`` (the wall clock of one
 ``extract_embedding.py`` worker job from process birth to renamed ark,scp), ``config2_varlen`` (BASELINE configs[2]:
-T in [25, 10000], length-bucketed) and ``train_step`` (BASELINE configs[4]: one rank's share).  ``accuracy_probe`` is what
-``engine.select_model`` measured when it admitted the arithmetic for these weights.
+T in [25, 10000], length-bucketed), ``train_step`` (BASELINE configs[4]: one rank's share) and ``trained_checkpoint``.
+``--mode train`` has nothing beyond its headline: ``--full`` changes nothing there.
 
 ``python bench.py --gpus N`` with N > 1 starts its own N ranks (xvector_amd/launch.py) when it is not already one.
 ``--dump-outputs DIR`` writes what the last timed step computed (``xvectors.npy``: [N x utts, 512] float32 in utterance order; in
@@ -55,13 +61,18 @@ def parse():
     ap.add_argument("--tmin", type=int, default=200)
     ap.add_argument("--tmax", type=int, default=400)
     ap.add_argument("--batch-rows", type=int, default=262144)
-    ap.add_argument("--cpu-budget", type=float, default=18.0, help="seconds of CPU-baseline timing (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also run every other measurement and check of the line (per-launch and "
+                         "standalone pooling figures, parity against the fp64 oracle, ark write, CPU baseline, the other arithmetics, "
+                         "ark -> ark, CLI job, configs[2] and configs[4] legs); a plain run measures the headline alone")
+    ap.add_argument("--cpu-budget", type=float, default=18.0, help="--full: seconds of CPU-baseline timing (0 = skip it and the parity check)")
     ap.add_argument("--e2e-utts", type=int, default=50000,
-                    help="N = 1 only: utterances of the ark -> ark sub-measurement through Model.make_embedding (0 = skip)")
-    ap.add_argument("--no-fp32-leg", action="store_true", help="skip the exact-fp32 sub-measurement (fp32_exact)")
-    ap.add_argument("--parity-utts", type=int, default=40, help="utterances, spread over ALL batches of the step, checked against the fp64 oracle")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip config2_varlen, train_step and cli_job")
-    ap.add_argument("--no-job-rehearsal", action="store_true", help="skip cli_job.rehearsal_8x125k (the 1 M-utterance job's counts on this box)")
+                    help="--full, N = 1 only: utterances of the ark -> ark sub-measurement through Model.make_embedding (0 = skip)")
+    ap.add_argument("--no-fp32-leg", action="store_true", help="--full: skip the exact-fp32 sub-measurement (fp32_exact)")
+    ap.add_argument("--parity-utts", type=int, default=40,
+                    help="--full: utterances, spread over ALL batches of the step, checked against the fp64 oracle")
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full: skip config2_varlen, train_step and cli_job")
+    ap.add_argument("--no-job-rehearsal", action="store_true", help="--full: skip cli_job.rehearsal_8x125k (the 1 M-utterance job's counts)")
     ap.add_argument("--no-fused-pool", action="store_true",
                     help="bf16x3: store the last layer and run the standalone pooling kernel (A/B against the fused epilogue)")
     ap.add_argument("--mode", choices=["extract", "train"], default="extract",
@@ -878,8 +889,9 @@ def main():
     n_gemm_launch = (launches_per_batch * len(batches) + 1) * args.steps
     C = topo["layer_sizes"][-1]
     by_pool = (4 * C * frames + 4 * 2 * C * n_utts) * args.steps
-    pool_kernel = "stats_pool_kernel"
-    if model.fused_pool:
+    pool_kernel, pool_launches = "stats_pool_kernel", len(batches) * args.steps
+    t_blocks = t_pool
+    if model.fused_pool and args.full:
         # the timed path reduces the last layer inside the GEMM epilogue; the standalone pooling kernel (attention-free models without the fused epilogue, training)
         # is timed here, outside the timed region, on a materialised [rows, 1536] fp32 activation of the largest batch
         pool_kernel = "stats_pool_kernel (standalone, measured outside the timed region: the timed path reduces the last layer " \
@@ -897,13 +909,10 @@ def main():
             hiplib.stats_pool(hbuf, big["rs"], big["rl"], big["n"], big["max_len"], 512, tp.VAR2STD_EPSILON, pout, ws)
         e1.record()
         torch.cuda.synchronize()
-        t_blocks = t_pool
         t_pool = e0.elapsed_time(e1) * 1e-3
         by_pool = (4 * C * big["frames"] + 4 * 2 * C * big["n"]) * reps
         pool_launches = reps
         del hbuf
-    else:
-        pool_launches = len(batches) * args.steps
     fl_total = (tp.flops_per_frame(topo, feat) * frames + tp.flops_per_utt(topo) * n_utts)
 
     if rank != 0:
@@ -940,7 +949,7 @@ def main():
                 "executed_bf16_tflops": 3 * fl_gemm / t_gemm / 1e12,
                 "peak_note": "achieved = ALGORITHMIC (fp32-contraction) FLOPs; every product costs 3 bf16 MFMAs, so "
                              "peak = 2.5 PFLOP/s dense bf16 MFMA / 3 and frac = executed bf16 FLOPs / 2.5 PF"}
-    if getattr(model, "f16bf8", False):
+    if args.full and getattr(model, "f16bf8", False):
         # per-launch breakdown from a few more (untimed) passes over the largest batch: HIP events between the launches
         big = max(batches, key=lambda b: b["rows"])
         passes = []
@@ -996,11 +1005,12 @@ def main():
                           # how many times the fp32-MFMA ceiling (157.3 TF: what exact fp32 products could reach at most) the
                           # algorithmic rate is -- a speed-up over that ceiling, not a roofline fraction
                           "algorithmic_rate_over_fp32_mfma_ceiling": fl_gemm / t_gemm / MFMA_F32_PEAK}, **kern),
-        "roofline_pool": {"kernel": pool_kernel, "bound": "hbm", "achieved": by_pool / t_pool / 1e9,
-                          "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": by_pool / t_pool / HBM_PEAK,
-                          "avg_launch_ms": t_pool / pool_launches * 1e3,
-                          "algorithmic_mb_per_launch": by_pool / pool_launches / 1e6},
     }
+    if not model.fused_pool or args.full:                   # (behind the fused epilogue the standalone kernel is timed by --full alone)
+        out["roofline_pool"] = {"kernel": pool_kernel, "bound": "hbm", "achieved": by_pool / t_pool / 1e9,
+                                "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": by_pool / t_pool / HBM_PEAK,
+                                "avg_launch_ms": t_pool / pool_launches * 1e3,
+                                "algorithmic_mb_per_launch": by_pool / pool_launches / 1e6}
     out["accuracy_probe"] = dict(selection, note="engine.select_model: x-vectors of a fixed MFCC-like batch through these weights in "
                                  "f16bf8 vs bf16x3 (kept when <= f16bf8_limit), then bf16x3 vs exact fp32 if that failed")
     out["rccl_ranks"] = dist.get_world_size() if dist.is_initialized() else 0
@@ -1015,6 +1025,12 @@ def main():
         out["pool_blocks"] = {"kernel": "stats_pool_blocks_kernel", "bound": "hbm", "achieved": by_blk / t_blocks / 1e9,
                               "unit": "GB/s", "frac": by_blk / t_blocks / HBM_PEAK,
                               "avg_launch_ms": t_blocks / (len(batches) * args.steps) * 1e3}
+    if not args.full:
+        # a plain run ends here: the headline and what its own timed region measured
+        print(json.dumps(out))
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
 
     if args.cpu_budget > 0:
         from oracle import oracle

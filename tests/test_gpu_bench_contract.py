@@ -1,4 +1,5 @@
-"""bench.py's output contract (one JSON line on stdout with the driver's keys + roofline + cpu_baseline) on a tiny workload."""
+"""bench.py's output contract (one JSON line on stdout with the driver's keys + roofline; with --full also cpu_baseline and the
+sub-records) on a tiny workload."""
 import json
 import os
 import subprocess
@@ -19,7 +20,7 @@ def _run(*flags, **env):
 
 
 def test_extraction_bench_line():
-    d = _run("--utts", "600", "--steps", "2", "--warmup", "1", "--cpu-budget", "6", "--parity-utts", "2", "--e2e-utts", "700",
+    d = _run("--full", "--utts", "600", "--steps", "2", "--warmup", "1", "--cpu-budget", "6", "--parity-utts", "2", "--e2e-utts", "700",
              XV_BENCH_REHEARSAL_UTTS="3000")                        # (the job rehearsal at 4 x 3000 instead of 4 x 250 k utterances)
     for k, t in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
                  ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str), ("config", dict)):
@@ -88,6 +89,21 @@ def test_extraction_bench_line():
     assert "no exchange at N = 1" in d["config"]["parallelism"]
 
 
+def test_plain_line_is_the_headline_alone():
+    """Without --full the line carries the headline and the figures of its own timed region, and nothing that needs runs or
+    checks of its own."""
+    d = _run("--utts", "600", "--steps", "2", "--warmup", "1")
+    assert d["unit"] == "utt/s" and d["higher_is_better"] is True and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
+    assert abs(d["value"] - 600 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"] and isinstance(d["dtype"], str)
+    r = d["roofline"]
+    assert r["bound"] == "mfma" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9 and "by_launch" not in r
+    assert d["config"]["fused_pool"] is True and 0 < d["pool_blocks"]["frac"] < 1.2 and "roofline_pool" not in d
+    assert d["accuracy_probe"]["selected"] == "f16bf8" and d["rccl_ranks"] == 0
+    for k in ("cpu_baseline", "parity_rel_l2_max_vs_fp64_oracle", "with_ark_write", "fp32_exact", "fp32_toomcook", "bf16x3",
+              "config2_varlen", "e2e_ark_to_ark", "cli_job", "train_step", "trained_checkpoint"):
+        assert k not in d, k
+
+
 def test_dump_outputs_holds_the_last_step_and_repeats(tmp_path):
     """--dump-outputs: the x-vectors of the timed path's last step, one row per utterance in utterance order, and the same
     arguments give the same inputs -- two runs (with different step counts) write the same vectors."""
@@ -109,7 +125,7 @@ def test_two_ranks_through_the_self_launcher_on_one_gpu():
     env = dict(os.environ, XV_BENCH_SHARE_GPU="1", XVECTOR_DIST_BACKEND="gloo")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--utts", "600", "--steps", "2", "--warmup", "1",
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--utts", "600", "--steps", "2", "--warmup", "1",
                           "--cpu-budget", "4", "--parity-utts", "4", "--e2e-utts", "0"], cwd=ROOT, env=env, stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, timeout=600)
     assert run.returncode == 0, run.stderr.decode()[-2000:]
@@ -142,7 +158,7 @@ def test_two_training_ranks_through_the_self_launcher_on_one_gpu():
 def test_bench_at_the_per_rank_size_of_the_million_utterance_job():
     """BASELINE configs[3] gives every one of 8 ranks 125 k utterances: the resident-input step at that size (37.5 M frames,
     ~145 batches) on one GPU."""
-    d = _run("--utts", "125000", "--steps", "1", "--warmup", "0", "--cpu-budget", "0", "--e2e-utts", "0", "--no-fp32-leg", "--no-extra-legs")
+    d = _run("--full", "--utts", "125000", "--steps", "1", "--warmup", "0", "--cpu-budget", "0", "--e2e-utts", "0", "--no-fp32-leg", "--no-extra-legs")
     assert d["config"]["utts_per_gpu"] == 125000 and d["config"]["batches_per_step"] > 100
     assert 36e6 < d["config"]["frames_per_gpu"] < 39e6 and d["value"] > 20000 and "fp32_exact" not in d and "e2e_ark_to_ark" not in d
     assert d["with_ark_write"]["ark_mb"] > 250

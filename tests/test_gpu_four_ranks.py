@@ -30,7 +30,7 @@ def _clean_env(**extra):
 def test_bench_at_four_ranks_prints_one_line():
     """`python bench.py --gpus N`, the driver's command form for SCALE_rNN.json."""
     env = _clean_env(XV_BENCH_SHARE_GPU="1", XVECTOR_DIST_BACKEND="gloo")
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(RANKS), "--utts", "400", "--steps", "2", "--warmup", "1",
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(RANKS), "--full", "--utts", "400", "--steps", "2", "--warmup", "1",
                           "--cpu-budget", "4", "--parity-utts", "4", "--e2e-utts", "0"], cwd=ROOT, env=env, stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, timeout=900)
     assert run.returncode == 0, run.stderr.decode()[-3000:]

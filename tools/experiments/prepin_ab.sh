@@ -1,6 +1,6 @@
 mkdir -p gpurun_out
 for rep in 1 2; do for m in 0 1; do
-XVECTOR_PREPIN=$m timeout 300 python bench.py --no-fp32-leg --cpu-budget 0 --steps 3 --warmup 1 2>/dev/null | python -c "
+XVECTOR_PREPIN=$m timeout 300 python bench.py --full --no-fp32-leg --cpu-budget 0 --steps 3 --warmup 1 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); cj=d['cli_job']; rh=cj.get('rehearsal_8x125k',{})
 b=cj['breakdown_s']
