@@ -7,6 +7,8 @@ the whole network is 1e-4 (checked in test_gpu_forward.py for this precision as 
 import numpy as np
 import pytest
 
+import arith_emul as em
+
 pytestmark = pytest.mark.gpu
 
 TOL_GEMM8 = 4e-5
@@ -41,6 +43,8 @@ def test_split8_roundtrip_layout_and_overflow_flag(env):
     x = (rng.standard_normal((R, C)) * np.exp(1.5 * rng.standard_normal((R, C)))).astype(np.float32)   # |x| up to ~1e3
     x[3, 5] = 0.0
     x[4, 6] = 1e-7                                  # below fp16's normal range: kept to an absolute 2^-25
+    x[5, :14] = [1 + 2 ** -11, 1 + 3 * 2 ** -11, -1 - 3 * 2 ** -11, 2 ** -24, 2 ** -25, 1.5 * 2 ** -14, 6e-5, 3e-6, 1.375, 1.125,
+                 2 ** -17, 3 * 2 ** -17, 0.0, -0.0]          # fp16 / e5m2 ties, fp16 and e5m2 subnormals, zeros
     xd = torch.from_numpy(x).to(dev)
     buf = hiplib.SplitBuf(R, C, dev, hiplib.FMT_SPLIT8)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -61,6 +65,7 @@ def test_split8_roundtrip_layout_and_overflow_flag(env):
     assert abs(float(h8) - x[r, c]) <= abs(x[r, c]) * 0.125
     l8 = (cross[e:e + 1].astype(np.uint16) << 8).view(np.float16)[0]
     assert abs(float(hi) + float(l8) / 2048 - x[r, c]) <= abs(x[r, c]) * 2.0 ** -13
+    _split8_bytes_are_the_emulators(raw, x, R, C)
     # the padding channels of the last slab (80..95: groups 2 and 3 of slab 2) are zeros
     for r in range(R):
         sw = (r >> 1) & 7
@@ -72,6 +77,22 @@ def test_split8_roundtrip_layout_and_overflow_flag(env):
     hiplib.split_encode(torch.from_numpy(x).to(dev), buf, status=status)
     back = hiplib.split_decode(buf, R).cpu().numpy()
     assert int(status.item()) == 1 and back[7, 7] == 57344.0 and back[8, 1] == -57344.0
+    _split8_bytes_are_the_emulators(buf.base.cpu().numpy()[hiplib.SPLIT_PAD_BEFORE * buf.row_bytes:].reshape(-1, buf.row_bytes), x, R, C)
+
+
+def _split8_bytes_are_the_emulators(raw, x, R, C):
+    """Every byte of a split8 buffer (fp16 hi, l8, h8 of every element) against tests/arith_emul.py."""
+    hi, l8, h8 = em.split8_bytes(x)
+    r, c = np.arange(R)[:, None], np.arange(C)[None, :]
+    slab, g, e = c // 32, (c % 32) // 8, c % 8
+    sw = (r >> 1) & 7
+    rows = np.broadcast_to(r, (R, C))
+    hoff = slab * 128 + ((g ^ sw) << 4) + 2 * e
+    got_hi = raw[rows, hoff].astype(np.uint16) | (raw[rows, hoff + 1].astype(np.uint16) << 8)
+    xoff = slab * 128 + (((4 + g) ^ sw) << 4) + e
+    assert np.array_equal(got_hi, hi)
+    assert np.array_equal(raw[rows, xoff], l8)
+    assert np.array_equal(raw[rows, xoff + 8], h8)
 
 
 @pytest.mark.parametrize("tile_rows", [128, 256, 512, 1024])      # 512 / 1024 = the 256 x 256 tile on the 32 x 32 / 16 x 16 MFMA shapes

@@ -7,6 +7,8 @@ oracle for the GEMM kernels, 2e-6 for pooling, bit-exact for the chunk average.
 import numpy as np
 import pytest
 
+import arith_emul as em
+
 pytestmark = pytest.mark.gpu
 
 TOL_GEMM = 2e-6          # exact-fp32 MFMA path
@@ -242,18 +244,16 @@ def test_split_format_roundtrip_and_layout(env):
     rng = np.random.default_rng(21)
     R, C = 37, 72                                   # 3 slabs, last one ragged
     x = (rng.standard_normal((R, C)) * 5).astype(np.float32)
+    x[5, :10] = [1 + 2 ** -8, 1 + 3 * 2 ** -8, -1 - 2 ** -8, 0.0, -0.0, 1e-30, 2 ** -120, 1 + 2 ** -8 + 2 ** -20, 3e38, 1 - 2 ** -9]
     buf = hiplib.SplitBuf(R, C, dev)
     hiplib.split_encode(torch.from_numpy(x).to(dev), buf)
     back = hiplib.split_decode(buf, R).cpu().numpy()
     assert np.abs(back - x).max() <= np.abs(x).max() * 2.0 ** -16
+    assert (np.abs(back - x) <= np.abs(x) * 2.0 ** -16).all()                      # per element: the sweep's 3e38 widens nothing
     raw = buf.base.cpu().numpy()[hiplib.SPLIT_PAD_BEFORE * buf.row_bytes:].view(np.uint16)
 
-    def bf16_rne(a):
-        u = a.astype(np.float32).view(np.uint32).astype(np.uint64)
-        return (((u + 0x7FFF + ((u >> 16) & 1)) >> 16) & 0xFFFF).astype(np.uint16)
-
-    hi = bf16_rne(x)
-    lo = bf16_rne(x - (hi.astype(np.uint32) << 16).view(np.float32))
+    hi = em.bf16_rne(x)
+    lo = em.bf16_rne(x - em.bf16_value(hi))
     for r in (0, 1, 2, 9, 36):
         for c in (0, 7, 8, 31, 32, 71):
             s, k = c >> 5, c & 31
@@ -261,6 +261,12 @@ def test_split_format_roundtrip_and_layout(env):
                 phys = (plane * 4 + (k >> 3)) ^ ((r >> 1) & 7)
                 got = raw[((r * 3 + s) * 128 + phys * 16) // 2 + (k & 7)]
                 assert got == want, (r, c, plane)
+    # every byte: both planes of every element are the emulator's encoding (ties, signed zeros, tiny and huge normals in the sweep)
+    r, c = np.arange(R)[:, None], np.arange(C)[None, :]
+    s, k = c >> 5, c & 31
+    for plane, want in ((0, hi), (1, lo)):
+        phys = (plane * 4 + (k >> 3)) ^ ((r >> 1) & 7)
+        assert np.array_equal(raw[((r * 3 + s) * 128 + phys * 16) // 2 + (k & 7)], want), plane
     assert not buf.base[:hiplib.SPLIT_PAD_BEFORE * buf.row_bytes].any()          # padding rows stay zero
 
 

@@ -21,6 +21,7 @@ def _tables(K):
     def arr(name):
         m = re.search(r"%s(?:\[\d+\])+ = (\{.*?\});" % name, body, re.S)
         text = re.sub(r"(\d+)\.(?=[^\d])", r"\1", m.group(1))            # "1. / 6" -> "1 / 6"
+        text = re.sub(r"(?<![\d.])\.(\d)", r"0.\1", text)                   # ".5f" -> "0.5f"
         text = text.replace("f", "").replace("{", "[").replace("}", "]")
         return eval(re.sub(r"(-?\d+(?:\.\d+)?)", r"Fr('\1')", text))
     G, SC, A1, ORDER = arr("G"), arr("SC"), arr("A1"), arr("ORDER")
