@@ -52,7 +52,7 @@ extern "C" {
 #define XV_ERR_BAD_ARG (-1)
 #define XV_ERR_UNSUPPORTED (-2)
 
-/* Library / ABI version (increments whenever an entry point is added or changed; currently 27). */
+/* Library / ABI version (increments whenever an entry point is added or changed; currently 28). */
 int xv_version(void);
 /* Thread-local description of the last non-zero return. */
 const char *xv_last_error(void);
@@ -63,16 +63,12 @@ const char *xv_last_error(void);
  *                      16 x 16 MFMA shapes where the shape allows it, else as 0; bf16x3: as 256), 0 = built-in choice.
  *   XV_TUNE_FP32_GEMM  form of the exact-fp32 GEMM where several exist (bit-identical results): 1 = register-staged (tdnn_gemm_kernel),
  *                      2 = fed by LDS-DMA on 32-channel slabs (tdnn_gemm_dma_kernel), 3 = as 2 with the K = 1 layers on 16-channel
- *                      slabs, three workgroups per CU (tdnn_gemm_k1_kernel), 0 = built-in choice (3 unless XV_FP32_K1=0 / XV_FP32_DMA=0).
- *   XV_TUNE_XCD_COLUMNS  the 256 x 256-tile f16bf8 GEMM on two column tiles (Cout = 512): 1 = XCDs 0-3 work on column tile 0 and
- *                      XCDs 4-7 on tile 1 (each L2 holds one tile's weights, operand rows are fetched by two XCDs), 0 = every XCD
- *                      works on both column tiles of a contiguous run of row tiles (built-in).
+ *                      slabs, three workgroups per CU (tdnn_gemm_k1_kernel), 0 = built-in choice (3).
  *   XV_TUNE_FIRST_TILES  16-frame tiles per wave of the first-layer kernel (xv_tdnn_first_*): 1..4096, 0 = spread the rows evenly
  *                      over one workgroup per CU (tests use small values to walk through several groups of tiles on small inputs). */
 #define XV_TUNE_TILE_ROWS 1
 #define XV_TUNE_FIRST_TILES 2
 #define XV_TUNE_FP32_GEMM 3
-#define XV_TUNE_XCD_COLUMNS 4
 int xv_set_tuning(int key, int value);
 
 /* One-off weight re-layout.  TF stores a conv kernel as w[K, Cin, Cout] == row-major [K*Cin, Cout]

@@ -47,7 +47,6 @@ def test_random_topologies_through_the_first_layer_and_pair_kernels(oracle_mod, 
     multiple of 32; last two layers K = 1 around a 512-wide intermediate -- through DeviceModel + Extractor (bf16x3) against
     the fp64 oracle, with the kernels asserted to be the ones that ran; the same model with both switched off must agree to
     fp32 summation order."""
-    import os
     from xvector_amd import engine, hiplib, synthetic
     hiplib.require_gpu()
     rng = np.random.default_rng(seed)
@@ -69,11 +68,7 @@ def test_random_topologies_through_the_first_layer_and_pair_kernels(oracle_mod, 
         model = engine.DeviceModel(w, topo, "cuda:0")
         assert model.pair is not None and model.first is not None, topo
         got = engine.Extractor(model, mn, cs, max_batch_rows=int(rng.choice([700, 262144]))).extract(mats)
-        os.environ["XVECTOR_PAIR_KERNEL"] = os.environ["XVECTOR_FIRST_KERNEL"] = "0"
-        try:
-            plain = engine.DeviceModel(w, topo, "cuda:0")
-        finally:
-            del os.environ["XVECTOR_PAIR_KERNEL"], os.environ["XVECTOR_FIRST_KERNEL"]
+        plain = engine.DeviceModel(w, topo, "cuda:0", pair_kernel=False, first_kernel=False)
         assert plain.pair is None and plain.first is None
         base = engine.Extractor(plain, mn, cs).extract(mats)
         for g, b, r in zip(got, base, refs):

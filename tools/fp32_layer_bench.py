@@ -34,6 +34,6 @@ for (cin, cout, K) in (SHAPES if len(sys.argv) < 3 else SHAPES[int(sys.argv[2]):
     ts.sort(); ms = ts[len(ts) // 2]
     fl = 2.0 * R * cin * cout * K
     tot_ms += ms; tot_fl += fl
-    bits = int(y.view(torch.int32).to(torch.int64).sum().item())      # (a checksum of the bit patterns: XV_FP32_DMA=0 / 1 must agree)
+    bits = int(y.view(torch.int32).to(torch.int64).sum().item())      # (a checksum of the bit patterns: every XV_BENCH_FORM must agree)
     print("%4d -> %4d K=%d: %.3f ms  %.1f TF = %.3f of 157.3   (output %.2f GB at %.2f TB/s)  bits %d" % (cin, cout, K, ms, fl / ms / 1e9, fl / ms / 1e9 / 157.3, R * cout * 4 / 1e9, R * cout * 4 / ms / 1e9, bits))
 print("all five: %.3f ms, %.1f TF = %.3f" % (tot_ms, tot_fl / tot_ms / 1e9, tot_fl / tot_ms / 1e9 / 157.3))

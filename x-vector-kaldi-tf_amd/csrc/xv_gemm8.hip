@@ -67,7 +67,6 @@ struct Gemm8Params {
     float *blk;           // POOL: per-8-row-block (mean, M2) planes
     int *status;          // bit 0 is set when a split8 output had to be clamped (may be NULL)
     int n_mt, n_nt, n_chunks;
-    int colmap;           // wide16, two column tiles: 1 = XCDs 0-3 work on column tile 0, XCDs 4-7 on tile 1 (XV_TUNE_XCD_COLUMNS)
 };
 
 #define XV_BLDS16_X4(rsrc, lptr, voff, soff, imm)                                                               \
@@ -979,17 +978,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_f16bf8_wide16_kernel(const G
     const int xcd = bid & 7, idx = bid >> 3;
     const int q_ = nwg >> 3, r_ = nwg & 7;
     const int wg = (xcd < r_ ? xcd * (q_ + 1) : r_ * (q_ + 1) + (xcd - r_) * q_) + idx;
-    int mt = wg / p.n_nt, nt = wg - mt * p.n_nt;
-    if (p.colmap) {
-        // XCD-aware column placement (two column tiles): an XCD's L2 then holds ONE column tile's weights (3.7 MB of the K = 7
-        // layer's 7.3 MB) and every row tile's operand rows are fetched by two XCDs.  Slot (column tile, quarter x4 of the row tiles)
-        // = XCD 4 nt + x4; the <= 6 blocks the round-robin deals to other XCDs than the slots need take the slots' last tiles.
-        const int q4 = p.n_mt >> 2, r4 = p.n_mt & 3;
-        int x4 = xcd & 3;
-        nt = xcd >> 2;
-        if (idx >= q4) { nt = xcd / r4; x4 = xcd - nt * r4; }
-        mt = x4 * q4 + (x4 < r4 ? x4 : r4) + idx;
-    }
+    const int mt = wg / p.n_nt, nt = wg - mt * p.n_nt;
     const long m0 = (long)mt * W_BM;
     const int n0 = nt * W_BN;
 
@@ -1308,21 +1297,11 @@ const Gemm8Kernel GEMM8_KERNELS[] = {
 size_t g8_kernel_lds(const Gemm8Kernel &e) { return e.wm >= 8 ? W_LDS_BYTES : g8_lds_bytes(e.kt, e.wm); }
 
 std::atomic<int> g_tile_rows8{0};
-std::atomic<int> g_wide16{1};          // XV_F16BF8_S16=0: the built-in choice keeps the 32 x 32 form of the 256 x 256 tile
-std::atomic<int> g_xcd_columns{0};     // XV_TUNE_XCD_COLUMNS
 
 int launch_gemm8(const Gemm8Params &p0, hipStream_t st)
 {
     Gemm8Params p = p0;
     if (p.R <= 0 || p.cout <= 0) return 0;
-    static const bool env_once = [] {
-        const char *e = std::getenv("XV_F16BF8_S16");
-        if (e && e[0] == '0') g_wide16.store(0, std::memory_order_relaxed);
-        const char *x = std::getenv("XV_XCD_COLUMNS");                 // (counter runs: the knob of XV_TUNE_XCD_COLUMNS from outside)
-        if (x && (x[0] == '0' || x[0] == '1')) g_xcd_columns.store(x[0] - '0', std::memory_order_relaxed);
-        return true;
-    }();
-    (void)env_once;
     if (p.cin <= 0 || p.dil <= 0) return fail(XV_ERR_BAD_ARG, "tdnn_f16bf8: dims > 0");
     const int span = (p.K - 1) * p.dil;
     if ((p.K != 1 && p.K != 3 && p.K != 5 && p.K != 7) || (p.K > 1 && (span < 2 || span > MAX_SPAN)))
@@ -1355,7 +1334,7 @@ int launch_gemm8(const Gemm8Params &p0, hipStream_t st)
         // bit), so a shape that can take it ALWAYS takes it, whatever the number of rows: an utterance's x-vector must not depend on
         // how many utterances share its batch -- on the sharding of a job over ranks, say (tests/test_gpu_eight_ranks.py: 8 ranks
         // write the single process's bytes).  A batch too small to fill the chip twice with 256 x 256 tiles loses a few per cent.
-        if (w16_ok && (want == 1024 || (want == 0 && g_wide16.load(std::memory_order_relaxed)))) wm = 16;
+        if (w16_ok && (want == 1024 || want == 0)) wm = 16;
         else if (wide_ok && (want == 512 || want == 1024 || (want == 0 && wide_pays))) wm = 8;
         else if (want == 256 || (want == 0 && p.K >= 5 && big_enough)) wm = 4;
     }
@@ -1372,7 +1351,6 @@ int launch_gemm8(const Gemm8Params &p0, hipStream_t st)
     static std::atomic<unsigned long long> lds_done{0};
     if (const int rc = opt_in_dynamic_lds(lds_done, GEMM8_KERNELS, [](const Gemm8Kernel &e) { return std::make_pair(e.fn, g8_kernel_lds(e)); }))
         return rc;
-    p.colmap = (wm == 16 && p.n_nt == 2 && p.n_mt >= 8 && g_xcd_columns.load(std::memory_order_relaxed)) ? 1 : 0;
     hipLaunchKernelGGL(k->fn, dim3((unsigned)(p.n_mt * p.n_nt)), dim3(wm >= 8 ? 512 : wm * 128), g8_kernel_lds(*k), st, p);
     return launch_status("tdnn_gemm_f16bf8_kernel launch");
 }
@@ -1450,7 +1428,6 @@ __global__ void split8_decode_kernel(const uint8_t *__restrict__ xs, long R, int
 extern "C" {
 
 void xv_internal_gemm8_tile_rows(int value) { g_tile_rows8.store(value, std::memory_order_relaxed); }
-void xv_internal_gemm8_xcd_columns(int value) { g_xcd_columns.store(value, std::memory_order_relaxed); }
 
 size_t xv_packed_weights_f16bf8_bytes(int K, int cin, int cout)
 {

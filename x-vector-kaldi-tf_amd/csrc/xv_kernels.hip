@@ -1310,9 +1310,8 @@ int launch_gemm3(const Gemm3Params &p0, hipStream_t st)
     // workgroup tile: 256 rows (8 waves, one workgroup per CU) for the wide-context layers when the input is in the split
     // format and there are enough rows to fill the chip with such tiles, else 128 rows (4 waves, two per CU);
     // xv_set_tuning(XV_TUNE_TILE_ROWS) overrides
-    // the 16 x 16 MFMA form where it exists: split input, K > 1, an even number of 32-channel slabs (XV_BF16X3_S16=0: off)
-    static const bool s16_on = !(std::getenv("XV_BF16X3_S16") != nullptr && std::getenv("XV_BF16X3_S16")[0] == '0');
-    const bool s16 = s16_on && p.x_split && kt > 1 && (p.n_chunks & 1) == 0;
+    // the 16 x 16 MFMA form where it exists: split input, K > 1, an even number of 32-channel slabs
+    const bool s16 = p.x_split && kt > 1 && (p.n_chunks & 1) == 0;
     int wm = 2;
     if (p.x_split) {
         const int want = g_tile_rows.load(std::memory_order_relaxed);
@@ -1553,8 +1552,8 @@ __device__ __forceinline__ void k1_epilogue(const GemmParams &p, char *lds, cons
     }
 }
 
-template <int OCC>                                     // workgroups per CU the register budget is cut for (3: 168 VGPRs, no spills; 4: 128, the epilogue spills)
-__global__ __launch_bounds__(NT, OCC) void tdnn_gemm_k1_kernel(const GemmParams p)
+// three workgroups per CU: 168 VGPRs, no spills (a build for four, at 128 VGPRs, spills in the epilogue)
+__global__ __launch_bounds__(NT, 3) void tdnn_gemm_k1_kernel(const GemmParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char glds[];
     char *Abuf = glds;                                 // [2][BM rows][64 B]
@@ -1660,7 +1659,6 @@ __global__ __launch_bounds__(NT, OCC) void tdnn_gemm_k1_kernel(const GemmParams 
     }
 }
 
-constexpr bool FP32_K1_DEFAULT = true;                // (profiles/r06_fp32_k1_slab16.txt: 1.03 -> 0.98 ms, 3.06 -> 2.90 ms; XV_FP32_K1=0 turns it off)
 std::atomic<int> g_fp32_form{0};
 
 int launch_gemm(const GemmParams &p0, hipStream_t st)
@@ -1681,7 +1679,7 @@ int launch_gemm(const GemmParams &p0, hipStream_t st)
     if (p.lead && (!vec || p.K != 1 || p.ypre)) return fail(XV_ERR_UNSUPPORTED, "tdnn_rows: needs 16-byte aligned rows of a multiple of 4 floats");
     const uintptr_t out_bits = (uintptr_t)p.y | (uintptr_t)p.ypre | (uintptr_t)p.bias | (uintptr_t)p.scale | (uintptr_t)p.shift |
                                (p.act == XV_ACT_PRELU ? (uintptr_t)p.alpha : 0);
-    p.vec_out = (p.cout % 4 == 0) && (p.ldy % 4 == 0) && (out_bits % 16 == 0) && (p.blk || std::getenv("XV_FP32_SCALAR_EPILOGUE") == nullptr);
+    p.vec_out = (p.cout % 4 == 0) && (p.ldy % 4 == 0) && (out_bits % 16 == 0);
     if (p.blk && !p.vec_out) return fail(XV_ERR_UNSUPPORTED, "tdnn_pool: needs cout % 4 == 0 and 16-byte aligned per-column parameters");
     typedef void (*kern_t)(const GemmParams);
     const kern_t all[] = {tdnn_gemm_kernel<true, 128>, tdnn_gemm_kernel<false, 128>, tdnn_gemm_kernel<true, 64>,
@@ -1690,21 +1688,19 @@ int launch_gemm(const GemmParams &p0, hipStream_t st)
     typedef std::pair<kern_t, size_t> kern_lds;
     const kern_lds lds[] = {{all[0], GEMM_LDS_BYTES}, {all[1], GEMM_LDS_BYTES}, {all[2], GEMM_LDS_BYTES}, {all[3], GEMM_LDS_BYTES},
                             {dma_all[0], F_LDS_BYTES}, {dma_all[1], F_LDS_BYTES}, {dma_all[2], F_LDS_BYTES}, {dma_all[3], F_LDS_BYTES},
-                            {tdnn_gemm_k1_kernel<3>, G_LDS_BYTES}, {tdnn_gemm_k1_kernel<4>, G_LDS_BYTES}};
+                            {tdnn_gemm_k1_kernel, G_LDS_BYTES}};
     static std::atomic<unsigned long long> lds_done{0};
     if (const int rc = opt_in_dynamic_lds(lds_done, lds, [](const kern_lds &kl) { return kl; })) return rc;
     const dim3 grid((unsigned)(p.n_mt * p.n_nt));
     // the DMA-fed form (128-row tiles): whole 32-channel slabs, 16-byte aligned rows, byte offsets that fit the descriptors' 32 bits
-    static const bool dma_env = !(std::getenv("XV_FP32_DMA") != nullptr && std::getenv("XV_FP32_DMA")[0] == '0');
-    const int form = g_fp32_form.load(std::memory_order_relaxed);       // XV_TUNE_FP32_GEMM: 0 built-in, 1 register-staged, 2 DMA-fed, 3 DMA-fed with the K = 1 layers on 16-channel slabs
-    const bool dma_on = form >= 2 || (form == 0 && dma_env);
-    static const int k1_env = std::getenv("XV_FP32_K1") ? atoi(std::getenv("XV_FP32_K1")) : -1;
-    const bool k1_on = form == 3 || (form == 0 && (k1_env < 0 ? FP32_K1_DEFAULT : k1_env != 0));
+    const int form = g_fp32_form.load(std::memory_order_relaxed);       // XV_TUNE_FP32_GEMM: 0 built-in (= 3), 1 register-staged, 2 DMA-fed, 3 DMA-fed with the K = 1 layers on 16-channel slabs
+    const bool dma_on = form != 1;
+    // K = 1 on 16-channel slabs: profiles/r06_fp32_k1_slab16.txt, 1.03 -> 0.98 ms, 3.06 -> 2.90 ms
+    const bool k1_on = form == 0 || form == 3;
     const bool dma_ok = dma_on && !small && p.k_splits <= 1 && vec && p.vec_out && (p.cin % BK) == 0 && (p.K == 1 || p.K == 3 || p.K == 5 || p.K == 7) &&
                         (p.R + BM + MAX_SPAN) * (long)p.ldx * 4 < (1l << 31) && (long)(p.cout + BN) * p.kred * 4 < (1l << 31);
     if (dma_ok && k1_on && p.K == 1 && p.cin >= 2 * G_BK) {
-        if (k1_env == 4) hipLaunchKernelGGL(tdnn_gemm_k1_kernel<4>, grid, dim3(NT), G_LDS_BYTES, st, p);
-        else hipLaunchKernelGGL(tdnn_gemm_k1_kernel<3>, grid, dim3(NT), G_LDS_BYTES, st, p);
+        hipLaunchKernelGGL(tdnn_gemm_k1_kernel, grid, dim3(NT), G_LDS_BYTES, st, p);
         return launch_status("tdnn_gemm_k1_kernel launch");
     }
     if (dma_ok) {
@@ -2086,10 +2082,9 @@ __global__ void fold_bn_kernel(const float *gamma, const float *beta, const floa
 extern "C" {
 
 void xv_internal_gemm8_tile_rows(int value);      // xv_gemm8.hip
-void xv_internal_gemm8_xcd_columns(int value);    // xv_gemm8.hip
 void xv_internal_first_tiles(int tiles);          // xv_first.hip
 
-int xv_version(void) { return 27; }
+int xv_version(void) { return 28; }
 
 int xv_set_tuning(int key, int value)
 {
@@ -2107,10 +2102,6 @@ int xv_set_tuning(int key, int value)
     case XV_TUNE_FP32_GEMM:
         if (value < 0 || value > 3) return fail(XV_ERR_BAD_ARG, "xv_set_tuning: fp32 GEMM form must be 0, 1, 2 or 3");
         g_fp32_form.store(value, std::memory_order_relaxed);
-        return 0;
-    case XV_TUNE_XCD_COLUMNS:
-        if (value < 0 || value > 1) return fail(XV_ERR_BAD_ARG, "xv_set_tuning: XCD column placement must be 0 or 1");
-        xv_internal_gemm8_xcd_columns(value);
         return 0;
     default:
         return fail(XV_ERR_BAD_ARG, "xv_set_tuning: unknown key");

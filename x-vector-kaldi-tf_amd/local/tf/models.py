@@ -225,7 +225,7 @@ class Model(object):
         jobclock.once("import torch")
         torch.cuda.init()
         jobclock.once("hip runtime up")
-        if getattr(self, "prepin_staging", False) and os.environ.get("XVECTOR_PREPIN", "1") != "0":
+        if getattr(self, "prepin_staging", False):
             # the CLI worker: its pinned staging sets come up beside the weights (engine.prewarm_staging), not in front of its first window
             try:
                 engine.prewarm_staging((int(w["frame_level_info_layer-0/w:0"].shape[1]) + 3) // 4 * 4, self.max_batch_rows)

@@ -222,15 +222,17 @@ class DeviceModel(object):
 
     POOL_SPLIT_ROWS = 512
 
-    def __init__(self, weights, topo, device="cuda:0", embedding_index=0, precision="bf16x3", fused_pool=None, pair_kernel=None):
+    def __init__(self, weights, topo, device="cuda:0", embedding_index=0, precision="bf16x3", fused_pool=None, pair_kernel=None,
+                 first_kernel=None):
         """precision: "fp32" = exact fp32 MFMA GEMMs; "bf16x3" = split-precision bf16 MFMA GEMMs (fp32-class
         accuracy, ~3e-6 rel-L2 on the x-vector; see include/xvector_hip.h).  fused_pool (default: on; fp32 needs a last layer whose
         width is a multiple of 4; never with attention pooling): the last frame-level layer reduces its output to 8-row block
         statistics in the GEMM epilogue instead of storing it (xv_tdnn_layer_pool_bf16x3 / _f32); batches must then be laid
-        out with ``align`` = 8.  pair_kernel (default: on with
-        fused_pool when the last two layers have kernel size 1 and a shape xv_tdnn_pair_pool_bf16x3 supports;
-        XVECTOR_PAIR_KERNEL=0 turns it off): those two layers and the block statistics run as one launch whose
-        intermediate activation stays in registers."""
+        out with ``align`` = 8.  pair_kernel (None, the default: on with
+        fused_pool when the last two layers have kernel size 1 and a shape xv_tdnn_pair_pool_bf16x3 supports; False: off;
+        True: required): those two layers and the block statistics run as one launch whose
+        intermediate activation stays in registers.  first_kernel (None, False or True, as pair_kernel): layer 0 of a bf16x3
+        model on xv_tdnn_first_bf16x3 when its shape allows."""
         import torch
         hiplib.require_gpu()
         assert precision in ("fp32", "fp32tc", "bf16x3", "f16bf8")
@@ -315,15 +317,15 @@ class DeviceModel(object):
             # layer 0 on the kernel built for it (output-stream bound; see csrc/xv_first.hip) when its shape allows
             self.first = None
             L0 = self.layers[0]
-            if precision == "bf16x3" and os.environ.get("XVECTOR_FIRST_KERNEL", "1") != "0" and len(self.layers) > 1 and \
+            if (first_kernel is None or first_kernel) and precision == "bf16x3" and len(self.layers) > 1 and \
                     self.in_dim % 8 == 0 and hiplib.first_supported(L0["K"], self.in_dim, L0["cout"]) and (L0["K"] - 1) * L0["dil"] <= 8:
                 w0 = weights["frame_level_info_layer-0/w:0"]
                 wpad = np.zeros((L0["K"], self.in_dim, w0.shape[2]), np.float32)
                 wpad[:, :self.feat_dim] = w0
                 self.first = hiplib.pack_first_bf16x3(self._dev(wpad))
+            assert not (first_kernel and self.first is None), "first_kernel=True but the topology / precision does not allow it"
             self.pair = None
-            want_pair = (os.environ.get("XVECTOR_PAIR_KERNEL", "1") != "0") if pair_kernel is None else bool(pair_kernel)
-            if want_pair and self.fused_pool and precision == "bf16x3" and len(self.layers) >= 3:
+            if (pair_kernel is None or pair_kernel) and self.fused_pool and precision == "bf16x3" and len(self.layers) >= 3:
                 La, Lb = self.layers[-2], self.layers[-1]
                 if La["K"] == 1 and Lb["K"] == 1 and hiplib.pair_supported(La["cin"], La["cout"], Lb["cout"]):
                     n = len(self.layers)
@@ -332,7 +334,7 @@ class DeviceModel(object):
                     self.pair = hiplib.pack_pair_bf16x3(wa, wb)
             assert not (pair_kernel and self.pair is None), "pair_kernel=True but the topology / precision does not allow it"
             self.pair8 = None
-            if self.f16bf8 and self.pair is not None and os.environ.get("XVECTOR_PAIR8_KERNEL", "1") != "0":
+            if self.f16bf8 and self.pair is not None:
                 La, Lb = self.layers[-2], self.layers[-1]
                 if hiplib.pair8_supported(La["cin"], La["cout"], Lb["cout"]):
                     n = len(self.layers)
@@ -401,7 +403,7 @@ class DeviceModel(object):
         if self.precision == "bf16x3":
             make = lambda: hiplib.pack_weights_bf16x3(self._dev(w3d))                 # tiled hi/lo bf16
         elif self.toom and scope == "frame_level_info_layer-0" and d == 1 and w3d.shape[1] == self.in_dim and \
-                w3d.shape[2] % 4 == 0 and os.environ.get("XVECTOR_ROWS_FIRST", "1") != "0":
+                w3d.shape[2] % 4 == 0:
             # layer 0 as a K = 1 GEMM over the overlapping windows of the packed feature rows (xv_tdnn_layer_rows_f32)
             make = lambda: hiplib.pack_weights_rows(self._dev(w3d), self.in_dim)
         elif self.toom and toom_ok and hiplib.toom_supported(k, d, w3d.shape[1], w3d.shape[2]):

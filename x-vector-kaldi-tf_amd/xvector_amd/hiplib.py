@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -136,7 +136,6 @@ SPLIT_PAD_BEFORE, SPLIT_PAD_AFTER = 8, 264
 TUNE_TILE_ROWS = 1
 TUNE_FIRST_TILES = 2
 TUNE_FP32_GEMM = 3
-TUNE_XCD_COLUMNS = 4
 
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_PRELU = 0, 1, 2, 3
 

@@ -35,7 +35,6 @@ class Trainer(object):
         assert precision in ("fp32", "bf16x3")
         self.attention = tp.is_attention(topo)              # self-attentive pooling (models.py:1036-1050)
         self.precision = precision
-        self.skinny_fc = os.environ.get("XVECTOR_TRAIN_SPLITK_FC", "1") != "0"
         # BN-backward column sums from their producers (the input-gradient GEMM's epilogue; the pooling gradient's per-chunk form)
         # instead of a pass over the gradient: XVECTOR_TRAIN_FUSED_SUMS=0 restores the separate col_sums launches (A/B, tests)
         self.fused_sums = os.environ.get("XVECTOR_TRAIN_FUSED_SUMS", "1") != "0"
@@ -106,9 +105,6 @@ class Trainer(object):
         self._one_start = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._one_len = {}
         self._side_busy = False
-        self.two_streams = os.environ.get("XVECTOR_TRAIN_STREAMS", "2") != "1"
-        self.wgrad_after = os.environ.get("XVECTOR_TRAIN_WGRAD_AFTER", "1") != "0"
-        self.fused_bias = os.environ.get("XVECTOR_TRAIN_FUSED_BIAS", "1") != "0"
         self._splits = {}                                          # split-format copies for the K = 1 layers' GEMMs (bf16x3)
         self.split_k1 = os.environ.get("XVECTOR_TRAIN_SPLIT_K1", "1") != "0"
         self._side = None                                          # second stream: weight gradients beside the input-gradient GEMMs
@@ -362,7 +358,7 @@ class Trainer(object):
             r = torch.empty((B, C), dtype=torch.float32, device=self.device)
             z = torch.empty_like(r) if (self.prelu and want_grad) else None
             e_in = S["e_in"][-1]
-            if self.skinny_fc and hiplib.fc_splitk_supported(B, e_in.shape[1], C):
+            if hiplib.fc_splitk_supported(B, e_in.shape[1], C):
                 # 64 rows x 3072 -> 512: four output tiles would each walk 96 slabs one after the other (168 us); split-K, exact fp32
                 key = sc + "/fc32"
                 if key not in pk:
@@ -411,8 +407,8 @@ class Trainer(object):
 
         def weight_side():
             # (bf16x3: the bias gradient comes out of the weight-gradient kernel, which streams dz anyway -- xv_wgrad_bias_bf16x3; the
-            # separate pass over dz was 4 % of a step.  XVECTOR_TRAIN_FUSED_BIAS=0: xv_col_sums_f32 as before)
-            fused = self.fused_bias and hiplib.wgrad_takes_bias(self.precision, x_in, dz)
+            # separate pass over dz was 4 % of a step; fp32 keeps xv_col_sums_f32)
+            fused = hiplib.wgrad_takes_bias(self.precision, x_in, dz)
             if scope == self.frame_scopes[0] and self.in_dim != self.feat_dim:
                 dw = torch.empty((K, cin, cout), dtype=torch.float32, device=self.device)
                 hiplib.wgrad(x_in, dz, K, dil, dw, self.precision, db=db if fused else None)
@@ -427,37 +423,26 @@ class Trainer(object):
         # dW / db and dx only share their inputs: the weight side goes to a second stream, so that its workgroups fill the
         # last, partly empty round of the input-gradient GEMM (a minibatch is 1.2 rounds of 128-row tiles) and vice versa;
         # whoever reads the gradients next (a bucket's all-reduce, Adam) waits for that stream (_join_side)
-        if need_dx and self.two_streams:
-            main = torch.cuda.current_stream(self.device)
-            side = self._side_stream()
-            ready = None
-            if self.wgrad_after:
-                ready = torch.cuda.Event()
-                ready.record(main)                                     # dz (and x_in) are final here
-            else:
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    weight_side()
-        else:
-            weight_side()
         if not need_dx:
+            weight_side()
             return None
+        side = self._side_stream()
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(self.device))          # dz (and x_in) are final here
         dx = dx_out if dx_out is not None else torch.empty((R, cin), dtype=torch.float32, device=self.device)
         if sums is not None:
             hiplib.tdnn_layer3_sums(dz_split if dz_split is not None else dz, R, pk[scope + "/T"], dil, valid, dx, sums[0], sums[1])
         else:
             hiplib.tdnn_layer(dz_split if dz_split is not None else dz, pk[scope + "/T"], None, None, None, tp.ACT_NONE, None, K, dil, valid,
                               dx, rows=R)
-        if need_dx and self.two_streams:
-            if self.wgrad_after:
-                # the weight side is queued BEHIND the input-gradient GEMM it runs beside (it waits for dz, not for that GEMM): when
-                # both are ready the hardware takes the critical path's workgroups first
-                side.wait_event(ready)
-                with torch.cuda.stream(side):
-                    weight_side()
-            dz.record_stream(side)
-            x_in.record_stream(side)
-            self._side_busy = True
+        # the weight side is queued BEHIND the input-gradient GEMM it runs beside (it waits for dz, not for that GEMM): when
+        # both are ready the hardware takes the critical path's workgroups first
+        side.wait_event(ready)
+        with torch.cuda.stream(side):
+            weight_side()
+        dz.record_stream(side)
+        x_in.record_stream(side)
+        self._side_busy = True
         return dx
 
     def _side_stream(self):
@@ -548,14 +533,10 @@ class Trainer(object):
         S = self._forward(x, labels, train=True, want_grad=True, keep_prob=1.0 - float(dropout_proportion), seed=seed)
         # moving <- 0.95*moving + 0.05*batch, all scopes at once -- beside the backward pass, not in front of it (every launch of the
         # segment level is a ~5 us link of one dependent chain); the stream is joined in front of the optimizer update
-        if self.two_streams:
-            main = torch.cuda.current_stream(self.device)
-            self._side_stream().wait_stream(main)
-            with torch.cuda.stream(self._side):
-                hiplib.ema(self.flat_moving, self.flat_batch, BN_DECAY)
-            self._side_busy = True
-        else:
+        self._side_stream().wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self._side):
             hiplib.ema(self.flat_moving, self.flat_batch, BN_DECAY)
+        self._side_busy = True
         L, B, T = S["L"], S["B"], S["T"]
         grads = {}
         if self.am:
