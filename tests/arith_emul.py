@@ -1,4 +1,4 @@
-"""Emulator of the split arithmetics of the forward GEMMs (bf16x3: csrc/xv_kernels.hip; f16bf8: csrc/xv_split8.h, xv_gemm8.hip).
+"""Emulator of the split arithmetics of the forward GEMMs (bf16x3: csrc/xv_gemm3.hip; f16bf8: csrc/xv_split8.h, xv_gemm8*.hip).
 
 Encoders are stated bit for bit; a contraction is formed from the EMULATED product terms, each exact in fp32 (fp16*fp16,
 bf16*bf16 and bf8*bf8 products all fit in 24 bits), summed in fp64.  What is left between a kernel and this emulator is the

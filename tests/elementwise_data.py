@@ -67,14 +67,14 @@ BOUND_CASES = [
     C("fp32tc toom<5> d2", "fp32tc", "toom", 64, 48, 5, 2, "lrelu", "relu"),
     C("fp32tc toom<7>", "fp32tc", "toom", 512, 512, 7, 1, "relu", "relu"),
     C("fp32tc rows form", "fp32tc", "rows", 23, 512, 5, 1, "relu", "mfcc"),
-    # ---- bf16x3: tdnn_gemm_bf16x3_kernel<SPLIT_A, K, POOL, WM, S16> (launch_gemm3), tdnn_first_kernel<MODE, false>
+    # ---- bf16x3: tdnn_gemm_bf16x3_kernel<SPLIT_A, K, POOL, WM, S16> (csrc/xv_gemm3.hip launch_gemm3), tdnn_first_kernel<MODE, false>
     C("bf16x3 f32 input", "bf16x3", "bf16x3", 512, 512, 5, 1, "relu", "relu"),
     C("bf16x3 split 128-row", "bf16x3", "bf16x3", 96, 512, 5, 1, "relu", "hostile", xfmt="split", fmt="split", tune={"rows": 128}),
     C("bf16x3 split 256-row", "bf16x3", "bf16x3", 96, 512, 7, 1, "prelu", "relu", xfmt="split", fmt="split", tune={"rows": 256}),
     C("bf16x3 split 16x16", "bf16x3", "bf16x3", 512, 512, 7, 1, "relu", "relu", xfmt="split", fmt="f32"),
     C("bf16x3 split ragged", "bf16x3", "bf16x3", 40, 200, 3, 2, "lrelu", "hostile", xfmt="split", fmt="split"),
     C("bf16x3 first layer", "bf16x3", "first", 23, 512, 5, 1, "relu", "mfcc", fmt="split"),
-    # ---- f16bf8: tdnn_gemm_f16bf8_kernel (128 / 256 rows), _wide_kernel (512), _wide16_kernel (1024); tdnn_first_kernel<MODE, true>
+    # ---- f16bf8 (csrc/xv_gemm8.hip launch_gemm8): tdnn_gemm_f16bf8_kernel (128 / 256 rows), _wide_kernel (512: xv_gemm8_wide.hip), _wide16_kernel (1024: xv_gemm8_wide16.hip); tdnn_first_kernel<MODE, true>
     #      (the first-layer kernel forms bf16x3 products whatever it writes)
     C("f16bf8 128-row f32 out", "f16bf8", "f16bf8", 512, 512, 5, 1, "relu", "relu", xfmt="split8", tune={"rows": 128}),
     C("f16bf8 256-row split out", "f16bf8", "f16bf8", 64, 200, 3, 1, "relu", "relu", xfmt="split8", fmt="split", tune={"rows": 256}),

@@ -1,4 +1,4 @@
-"""GPU parity tests of the f16bf8 arithmetic (xv_gemm8.hip, xv_split8.h) through the C ABI against the fp64 oracle.
+"""GPU parity tests of the f16bf8 arithmetic (xv_gemm8.hip, xv_gemm8_wide.hip, xv_gemm8_wide16.hip, xv_split8.h) through the C ABI against the fp64 oracle.
 
 A product is xh*wh + 2^-11 (xl8*wh8 + xh8*wl8): one fp16 MFMA + one block-scaled bf8 MFMA instead of three bf16 MFMAs.
 Per layer the result is good to ~1e-5 relative L2 (bf16x3: ~3e-6); the tolerance here is 4e-5, the north star's bar for

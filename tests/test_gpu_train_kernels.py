@@ -1,4 +1,4 @@
-"""GPU unit tests of the training-step kernels (csrc/xv_train.hip, xv_chunk_moments_f32 / xv_fold_bn_f32 of xv_kernels.hip), one hiplib
+"""GPU unit tests of the training-step kernels (csrc/xv_train.hip, xv_chunk_moments_f32 of xv_pool.hip, xv_fold_bn_f32 of xv_kernels.hip), one hiplib
 wrapper at a time, each against a float64 statement of the same operation written here from its TF definition (numpy, or torch-CPU
 float64 autograd for the backward ops).  No test compares one kernel with another and none uses oracle/train_ref.py.
 
@@ -16,7 +16,7 @@ RELU, LRELU = 1, 2
 BN_EPS = 1e-3              # batch_norm_wrapper(epsilon=1e-3), tf_block.py
 POOL_EPS = 1e-5            # VAR2STD_EPSILON, models.py:16 -- [mean, sqrt(var + 1e-5)], models.py:75-76
 NAN = float("nan")
-CM_BAR = 1e-4              # per-chunk variance: stats_pool_kernel (xv_kernels.hip) merges 8-row blocks in fp32 (measured: up to 4.1e-5)
+CM_BAR = 1e-4              # per-chunk variance: stats_pool_kernel (xv_pool.hip) merges 8-row blocks in fp32 (measured: up to 4.1e-5)
 
 
 def _note(what, err):

@@ -1,12 +1,16 @@
 """Development aid: build timing-only ablations of the bf16x3 GEMM main loop (their RESULTS ARE WRONG by construction)
 to see which resource bounds it.  Variants -> build/ablate/lib_<name>.so; time them with
-XVECTOR_HIP_LIB=build/ablate/lib_<name>.so python tools/layer_bench.py"""
+XVECTOR_HIP_LIB=build/ablate/lib_<name>.so python tools/layer_bench.py
+Patches csrc/xv_gemm3.hip by pattern and links the variant with the other objects of build/obj (run make first).  The patterns date from before
+the 16 x 16 form of the kernel: several now match twice or not at all, and the asserts below say which to bring up to date first."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "x-vector-kaldi-tf_amd", "csrc")
 OUT = os.path.join(ROOT, "build", "ablate")
 os.makedirs(OUT, exist_ok=True)
-base = open(os.path.join(SRC, "xv_kernels.hip")).read()
+base = open(os.path.join(SRC, "xv_gemm3.hip")).read()
+OBJ = os.path.join(ROOT, "build", "obj")
+others = [os.path.join(OBJ, f) for f in sorted(os.listdir(OBJ)) if f.endswith(".o") and f != "xv_gemm3.o"]
 A_LINES = ["XV_GLDS16(ag + ag_off[0][j], adst + al_off[0][j]);", "XV_GLDS16(anext + ag_off[t][j], adst_n + al_off[t][j]);"]
 B_LINES = ["XV_GLDS16_OFF(bnext, dst, %d);" % o for o in (0, 1024, 2048, 3072)]
 assert all(base.count(l) == 1 for l in A_LINES + B_LINES)
@@ -84,10 +88,10 @@ procs = []
 for name, text in variants.items():
     if len(sys.argv) > 1 and name not in sys.argv[1:]:
         continue
-    f = os.path.join(OUT, "xv_kernels_%s.hip" % name)
+    f = os.path.join(OUT, "xv_gemm3_%s.hip" % name)
     open(f, "w").write(text)
     procs.append(subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                                    "-I" + os.path.join(ROOT, "include"), "-I" + SRC, "-Wno-unused-function",
-                                   "-o", os.path.join(OUT, "lib_%s.so" % name), f, os.path.join(SRC, "xv_train.hip"), os.path.join(SRC, "xv_frontend.hip"), os.path.join(SRC, "xv_attention.hip")]))
+                                   "-o", os.path.join(OUT, "lib_%s.so" % name), f] + others))
 assert all(p.wait() == 0 for p in procs)
 print("built:", sorted(os.listdir(OUT)))

@@ -1,4 +1,4 @@
-// EXPERIMENT: what a CU's store path delivers for the epilogue pattern of the 256 x 256 f16bf8 kernel (xv_gemm8.hip) against a
+// EXPERIMENT: what a CU's store path delivers for the epilogue pattern of the 256 x 256 f16bf8 kernels (wide_epilogue, xv_gemm8.h) against a
 // row-contiguous pattern.  One workgroup (512 threads) writes a 256-row x 1 KB block of a [rows][2 KB] array, like one output
 // tile; 2048 workgroups.   hipcc --offload-arch=gfx950 -O3 -o store_probe store_probe.hip && ./store_probe
 #include <hip/hip_runtime.h>

@@ -7,7 +7,7 @@ through XVECTOR_HIP_LIB by tools/wide_bench.py -- which part of a pair the waves
 """
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-SRC = os.path.join(ROOT, "x-vector-kaldi-tf_amd", "csrc", "xv_gemm8.hip")
+SRC = os.path.join(ROOT, "x-vector-kaldi-tf_amd", "csrc", "xv_gemm8_wide16.hip")
 OUT = os.path.join(ROOT, "build", "variants")
 src = open(SRC).read()
 
@@ -36,11 +36,11 @@ def variant(name):
 
 
 for name in sys.argv[1:]:
-    path = os.path.join(OUT, "xv_gemm8_%s.hip" % name)
+    path = os.path.join(OUT, "xv_gemm8_wide16_%s.hip" % name)
     open(path, "w").write(variant(name))
-    obj = os.path.join(OUT, "xv_gemm8_%s.o" % name)
+    obj = os.path.join(OUT, "xv_gemm8_wide16_%s.o" % name)
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
                            "-I" + os.path.dirname(SRC), "-Wno-unused-function", "-c", "-o", obj, path])
-    objs = [os.path.join(ROOT, "build", "obj", f) for f in os.listdir(os.path.join(ROOT, "build", "obj")) if f.endswith(".o") and f != "xv_gemm8.o"]
+    objs = [os.path.join(ROOT, "build", "obj", f) for f in os.listdir(os.path.join(ROOT, "build", "obj")) if f.endswith(".o") and f != "xv_gemm8_wide16.o"]
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", os.path.join(OUT, "libxv_%s.so" % name), obj] + objs)
     print("built", name)

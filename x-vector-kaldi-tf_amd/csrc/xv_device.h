@@ -32,6 +32,9 @@ constexpr int XV_RSRC_FLAGS = 0x00020000;              // raw buffer, 32-bit dat
 
 namespace {
 
+// (K-1)*dilation limit of the GEMM families (xv_kernels.hip, xv_gemm3.hip, xv_gemm8*.hip): a tile's halo is at most 8 rows
+constexpr int MAX_SPAN = 8;
+
 int fail(int code, const char *msg)
 {
     xv_internal_set_error(msg);

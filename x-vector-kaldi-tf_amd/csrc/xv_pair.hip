@@ -2,7 +2,7 @@
 // kernel: frame_level_info_layer-3 -> frame_level_info_layer-4 -> per-8-row block statistics
 // (local/tf/models.py:54-76 / 470-486 for the last two layers of the default topology, kernel sizes [5,5,7,1,1]).
 //
-// Why a kernel of its own.  With K = 1 a GEMM tile has no tap re-use: the LDS-staged kernel of xv_kernels.hip moves one
+// Why a kernel of its own.  With K = 1 a GEMM tile has no tap re-use: the LDS-staged kernel of xv_gemm3.hip moves one
 // activation tile AND one weight tile per 24 MFMAs and spends a third of a tile's life in prologue/epilogue; layer 3
 // writes 0.54 GB per 262144-row batch that layer 4 reads back 12 times from L2.  Here the intermediate never leaves the
 // register file:
@@ -21,7 +21,7 @@
 //     s_waitcnt vmcnt, one s_barrier per stage); every fragment read is a conflict-free linear ds_read_b128.
 //   * the frames operand X is gathered by DMA straight into fragment order (per wave 16 rows x 32 channels x hi/lo per
 //     k-step) from the split-format activation buffer of the previous layer.
-// Arithmetic is the bf16x3 scheme of xv_kernels.hip (x = hi + lo, products lo*hi + hi*lo + hi*hi, fp32 accumulate).
+// Arithmetic is the bf16x3 scheme of xv_gemm3.hip (x = hi + lo, products lo*hi + hi*lo + hi*hi, fp32 accumulate).
 // Per 128-frame workgroup: 4.25 MB global->LDS (the unfused pair: 8 MB), no activation store, no activation reload.
 #include "xv_device.h"
 

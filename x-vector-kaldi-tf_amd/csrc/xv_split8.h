@@ -6,7 +6,7 @@
 // and a product x*w is formed as   xh*wh  +  2^-11 (xl8*wh8 + xh8*wl8)      (fp32 accumulate)
 // i.e. ONE fp16 MFMA and ONE block-scaled 8-bit MFMA (v_mfma_scale_f32_32x32x64_f8f6f4, twice the fp16 rate; its K = 64 holds
 // the two cross terms of 32 channels side by side, the 2^-11 is the instruction's E8M0 scale operand) where the bf16x3
-// arithmetic of xv_kernels.hip spends three bf16 MFMAs.  hi carries 11 significant bits, hi + l8/2^11 about 14; the cross
+// arithmetic of xv_gemm3.hip spends three bf16 MFMAs.  hi carries 11 significant bits, hi + l8/2^11 about 14; the cross
 // terms are 2^-12 of the product and are themselves good to 2-3 bits, so a product is good to ~2^-15 ... 2^-16 -- measured
 // on the full network: 1.1e-5 relative L2 against the fp64 oracle (bf16x3: 5e-6; the bar is 1e-4).
 //

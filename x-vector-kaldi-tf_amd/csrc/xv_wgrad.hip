@@ -7,7 +7,7 @@
 // cut into splits whose partial tiles are merged in a fixed order (deterministic).  What differs is the arithmetic: the
 // exact-fp32 kernel is bound by v_mfma_f32_32x32x2_f32 (157 TF peak; 26 % of a training step), here every fp32 operand is
 // split hi + lo (bf16 each) and a product is hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 with fp32 accumulation -- the
-// arithmetic of the forward / input-gradient GEMMs of --train-precision bf16x3 (xv_kernels.hip), ~5e-6 relative.
+// arithmetic of the forward / input-gradient GEMMs of --train-precision bf16x3 (xv_gemm3.hip), ~5e-6 relative.
 //
 // The reduction runs over ROWS, so both MFMA operands are needed "transposed": a lane of the A (cin) or B (cout) fragment holds
 // 8 consecutive rows of ONE channel, while memory holds a row's channels side by side.  The transposition happens on the way
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16x3_kernel(const WgradParams 
                 bh[i] = *reinterpret_cast<const bf16x8 *>(bfrag + i * 32 * CH_STRIDE + ks * 32);
                 bl[i] = *reinterpret_cast<const bf16x8 *>(bfrag + i * 32 * CH_STRIDE + ks * 32 + PLANE);
             }
-            // small terms first, as in the forward kernel (xv_kernels.hip): lo*hi + hi*lo + hi*hi
+            // small terms first, as in the forward kernel (xv_gemm3.hip): lo*hi + hi*lo + hi*hi
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
