@@ -344,7 +344,8 @@ int xv_rows_affine_f32(const float *x, int ldx, int64_t R, int c, const float *s
 int xv_rows_affine_split_f32(const float *x, int ldx, int64_t R, int c, const float *scale, const float *shift,
                              const uint8_t *row_valid, float *y, int ldy, void *y_split, void *stream);
 /* Weight gradient of a TDNN/FC layer: dw[k,ci,co] = sum_r x[r + (k-(K-1)/2)*dilation, ci] * dz[r, co]  (TF layout
- * [K,Cin,Cout]; rows outside [0,R) read as zero; gap rows of x and dz are zero by contract). */
+ * [K,Cin,Cout]; rows outside [0,R) read as zero; gap rows of x and dz are zero by contract).  x / dz may be column slices of wider
+ * buffers (ldx >= cin, lddz >= cout, else XV_ERR_BAD_ARG); K odd. */
 size_t xv_wgrad_workspace_bytes(int64_t R, int cin, int cout, int K);
 int xv_wgrad_f32(const float *x, int ldx, const float *dz, int lddz, int64_t R, int cin, int cout, int K, int dilation,
                  float *dw, void *workspace, void *stream);

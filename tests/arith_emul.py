@@ -146,6 +146,25 @@ def contract(arith, x, w, dilation=1):
     return z, M
 
 
+def wgrad(arith, x, dz, K, dilation=1):
+    """dw[k] = sum_r x[r + (k - (K-1)/2) d]^T dz[r] over the emulated terms (rows outside [0, R) are zero), and M = sum_r |terms|.
+    x [R, Cin], dz [R, Cout] -> (dw fp64 [K, Cin, Cout], M)."""
+    x = np.asarray(x, np.float32)
+    dz = np.asarray(dz, np.float32)
+    h = (K - 1) // 2
+    dw = np.zeros((K, x.shape[1], dz.shape[1]))
+    M = np.zeros_like(dw)
+    for xp, zp, coef in _parts(arith, x, dz):
+        xp = xp.astype(np.float64)
+        zp = zp.astype(np.float64) * coef
+        az = np.abs(zp)
+        for k in range(K):
+            xs = _shifted(xp, (k - h) * dilation)
+            dw[k] += xs.T @ zp
+            M[k] += np.abs(xs).T @ az
+    return dw, M
+
+
 def tdnn_layer(arith, x, w, b, scale, shift, act, alpha, dilation=1):
     """One layer on one chunk: (y fp64, z + b fp64, M = sum |terms| + |b|)."""
     z, M = contract(arith, x, w, dilation)

@@ -772,6 +772,31 @@ def test_bad_arguments_fail_loudly(env):
     y = torch.zeros((10, 8), dtype=torch.float32, device=dev)
     with pytest.raises(hiplib.XvectorHipError):
         hiplib.tdnn_layer(x, wp, None, None, None, 1, None, 9, 2, None, y)      # (K-1)*dil = 16 > 8
+    # both weight-gradient entry points (and the bias one) refuse the same arguments, through the raw binding
+    import ctypes
+    lib = hiplib.load()
+    R, cin, cout, K = 5000, 16, 8, 3
+    x = torch.zeros((R, cin), dtype=torch.float32, device=dev)
+    dz = torch.zeros((R, cout), dtype=torch.float32, device=dev)
+    dw = torch.full((K, cin, cout), float("nan"), dtype=torch.float32, device=dev)
+    db = torch.full((cout,), float("nan"), dtype=torch.float32, device=dev)
+    assert lib.xv_wgrad_workspace_bytes(R, cin, cout, K) > 0
+    ws = torch.empty(int(lib.xv_wgrad_bias_workspace_bytes(R, cin, cout, K)), dtype=torch.uint8, device=dev)
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+    BAD = -1                                                                # XV_ERR_BAD_ARG
+    for fn in (lib.xv_wgrad_f32, lib.xv_wgrad_bf16x3):
+        call = lambda ldx=cin, lddz=cout, rows=R, k=K, w=ws: fn(p(x), ldx, p(dz), lddz, rows, cin, cout, k, 1, p(dw), p(w), None)
+        assert call(ldx=cin - 1) == BAD and call(lddz=cout - 1) == BAD      # a row stride below the channel count
+        assert call(k=2) == BAD and call(k=0) == BAD                         # even K
+        assert call(rows=0) == BAD
+        assert call(w=None) == BAD                                           # splits > 1 without a workspace
+        assert call() == 0
+    callb = lambda d=db, w=ws, ldx=cin, k=K, rows=R: lib.xv_wgrad_bias_bf16x3(p(x), ldx, p(dz), cout, rows, cin, cout, k, 1, p(dw), p(d), p(w), None)
+    assert callb(d=None) == BAD and callb(w=None) == BAD                     # missing db / workspace
+    assert callb(ldx=cin - 1) == BAD and callb(k=4) == BAD and callb(rows=0) == BAD
+    assert callb() == 0
+    torch.cuda.synchronize()
+    assert (dw.cpu().numpy() == 0).all() and (db.cpu().numpy() == 0).all()
 
 
 # ---- self-attentive pooling kernels (models.py:1036-1050) ----------------------------------------------------------------

@@ -622,3 +622,158 @@ def test_pool_bn_act_backward_matches_float64_autograd(env, C, act):
     _note("pool_bn_act_backward dgamma / |terms|", np.abs(dg_h - dg_ref) / g_scale)
     assert (np.abs(db_h - db_ref) <= 2e-6 * b_scale).all(), float((np.abs(db_h - db_ref) / b_scale).max())
     assert (np.abs(dg_h - dg_ref) <= 2e-6 * g_scale).all(), float((np.abs(dg_h - dg_ref) / g_scale).max())
+
+
+# ------------------------------------------------------------------------------------------------
+# attention backward (csrc/xv_attention.hip), one kernel at a time, each from inputs made here -- a valid softmax computed on the
+# host, pooled statistics consistent with h and att (fp64, rounded to fp32), tanh values up to +-1 -- and compared element by
+# element with the fp64 evaluation of its formula on those same fp32 inputs.  The kernels are a handful of fp32 operations around
+# double accumulators, so each bound is a worst-case count of roundings (u = 2^-24 relative each, no statistical factor) times the
+# magnitudes the rounding sees; fused multiply-adds only remove roundings.  Second-order terms: the factor 1 + 2^-10; underflow:
+# 2^-149.
+# ------------------------------------------------------------------------------------------------
+U24 = 2.0 ** -24
+ATT_LENS = [1, 2, 31, 32, 33, 64, 1000, 5000]        # one row, the 32-row block of the pool backward +- 1, many blocks; 256-row loops of the softmax
+ATT_CHANNELS = [4, 48, 256, 260, 1500]               # the 256-channel loop of a wave: 1 trip (partly filled), 1, 2 (4 channels in the second), 6
+ATT_DIV = 5 * U24                                    # fp32 division: 2.5 ulp at worst (0.5 when correctly rounded)
+SLACK = 1 + 2.0 ** -10
+TINY = 2.0 ** -149
+
+
+def _att_case(env, A, seed):
+    """(layout, att [R] fp32 with NaN gap rows, per-chunk slices)."""
+    lay = env["engine"].BatchLayout(ATT_LENS, 3)
+    rng = np.random.default_rng(seed)
+    att = np.full(lay.rows, NAN, np.float32)
+    sl = [slice(int(s), int(s) + int(n)) for s, n in zip(lay.row_start, lay.row_len)]
+    for s in sl:
+        sc = 2.0 * rng.standard_normal(s.stop - s.start)
+        e = np.exp(sc - sc.max())
+        att[s] = (e / e.sum()).astype(np.float32)
+    return lay, rng, att, sl
+
+
+def _half(buf, C, side):
+    return buf[:, :C] if side == "left" else buf[:, C:]
+
+
+@pytest.mark.parametrize("side", ["left", "right"])
+@pytest.mark.parametrize("A", ATT_CHANNELS)
+def test_attention_pool_backward_elementwise(env, A, side):
+    """dh[t, c] = a_t (g1 + 2 x g2), datt_t = sum_c x (g1 + x g2) with g2 = dsd / (2 sd), g1 = dm - 2 m g2.  h and dh are column
+    slices (left / right half) of [R, 2C] buffers; gap rows and the other half of dh keep their NaN."""
+    hiplib = env["hiplib"]
+    C = A
+    lay, rng, att, sl = _att_case(env, A, 100 + A)
+    R, nb = lay.rows, lay.nchunks
+    x = (rng.standard_normal((R, C)) * 1.7 + 3.0 * rng.standard_normal(C)).astype(np.float32)
+    x[:, 1] = (100.0 + 1e-4 * rng.standard_normal(R)).astype(np.float32)      # large mean, tiny spread: sd ~ sqrt(eps)
+    valid = lay.row_valid().astype(bool)
+    hbuf = np.full((R, 2 * C), NAN, np.float32)
+    _half(hbuf, C, side)[valid] = x[valid]
+    pooled = np.zeros((nb, 2 * C), np.float32)
+    for b, s in enumerate(sl):
+        a64, x64 = att[s].astype(np.float64), x[s].astype(np.float64)
+        m = a64 @ x64
+        pooled[b] = np.concatenate([m, np.sqrt(np.maximum(a64 @ (x64 * x64) - m * m, 0.0) + POOL_EPS)]).astype(np.float32)
+    assert pooled[-1, C + 1] < 3 * np.sqrt(POOL_EPS)                           # (att sums to 1 only to fp32 rounding: 1e4 (sum a - 1) adds to the variance)
+    dp = rng.standard_normal((nb, 2 * C)).astype(np.float32)
+    dp[[1, 6], C:] = 0.0                                                       # no gradient into sd
+    dp[[2, 7], :C] = 0.0                                                       # no gradient into the mean
+    hd = _dev(env, hbuf)
+    dhbuf, datt = _nan(env, R, 2 * C), _nan(env, R)
+    hiplib.attention_pool_backward(_half(hd, C, side), _dev(env, att), _dev(env, lay.row_start), _dev(env, lay.row_len), nb, max(ATT_LENS),
+                                   _dev(env, pooled), _dev(env, dp), _half(dhbuf, C, side), datt)
+    dh_all, da = _host(dhbuf).astype(np.float64), _host(datt).astype(np.float64)
+    dh = _half(dh_all, C, side)
+    assert np.isnan(_half(dh_all, C, "right" if side == "left" else "left")).all()      # the other half is not touched
+    assert np.isnan(dh[~valid]).all() and np.isnan(da[~valid]).all()                     # gap rows are not written
+    worst_h = worst_a = 0.0
+    for b, s in enumerate(sl):
+        xx, a = x[s].astype(np.float64), att[s].astype(np.float64)[:, None]
+        pm, pd = pooled[b].astype(np.float64), dp[b].astype(np.float64)
+        g2 = pd[C:] / (2 * pm[C:])
+        g1 = pd[:C] - 2 * pm[:C] * g2
+        p = 2 * xx * g2
+        dh_ref = a * (g1 + p)
+        da_ref = (xx * (g1 + xx * g2)).sum(1)
+        # g2: one division.  g1: the error of g2 through 2 m, the rounding of 2 m g2, the subtraction.
+        e2 = ATT_DIV * np.abs(g2)
+        e1 = 2 * np.abs(pm[:C]) * e2 + U24 * np.abs(2 * pm[:C] * g2) + U24 * np.abs(g1)
+        # dh: the errors of g1, g2 (the latter through 2 x), the roundings of 2 x g2, of the sum (<= u (|g1| + |2 x g2|)) and of a * (..)
+        b_h = (a * (e1 + 2 * np.abs(xx) * e2 + U24 * np.abs(p) + U24 * (np.abs(g1) + np.abs(p))) + U24 * np.abs(dh_ref)) * SLACK + TINY
+        # datt: the errors of g1, g2 through sum |x| (e1 + |x| e2) (the sum itself runs in double: C 2^-52 of the magnitudes), the cast
+        mag = (np.abs(xx) * (np.abs(g1) + np.abs(xx * g2))).sum(1)
+        b_a = ((np.abs(xx) * (e1 + np.abs(xx) * e2)).sum(1) + C * 2.0 ** -52 * mag + U24 * np.abs(da_ref)) * SLACK + TINY
+        assert np.isfinite(dh[s]).all() and np.isfinite(da[s]).all()
+        rh, ra = np.abs(dh[s] - dh_ref) / b_h, np.abs(da[s] - da_ref) / b_a
+        worst_h, worst_a = max(worst_h, float(rh.max())), max(worst_a, float(ra.max()))
+        assert (rh <= 1).all(), ("dh", A, side, b, np.unravel_index(np.argmax(rh), rh.shape), float(rh.max()))
+        assert (ra <= 1).all(), ("datt", A, side, b, int(np.argmax(ra)), float(ra.max()))
+        if b in (1, 6):                                                                    # dsd = 0: dh = a dm exactly one rounding
+            assert (np.abs(dh[s] - dh_ref) <= U24 * np.abs(dh_ref) + TINY).all()
+    _note("attention_pool_backward dh / bound (A %d)" % A, worst_h)
+    _note("attention_pool_backward datt / bound (A %d)" % A, worst_a)
+
+
+def test_attention_softmax_backward_elementwise(env):
+    """ds_t = a_t (da_t - sum_tau a_tau da_tau), from att and datt made here; gap rows of dscores keep their NaN."""
+    hiplib = env["hiplib"]
+    lay, rng, att, sl = _att_case(env, 0, 7)
+    R = lay.rows
+    valid = lay.row_valid().astype(bool)
+    da = np.full(R, NAN, np.float32)
+    da[valid] = (rng.standard_normal(int(valid.sum())) * 10.0 ** rng.uniform(-2, 2, int(valid.sum())) + 3.0).astype(np.float32)
+    ds = _nan(env, R)
+    hiplib.attention_softmax_backward(_dev(env, att), _dev(env, da), _dev(env, lay.row_start), _dev(env, lay.row_len), lay.nchunks, ds)
+    got = _host(ds).astype(np.float64)
+    assert np.isnan(got[~valid]).all()
+    worst = 0.0
+    for s in sl:
+        a, d = att[s].astype(np.float64), da[s].astype(np.float64)
+        dot = a @ d
+        ref = a * (d - dot)
+        # the dot product and a (da - dot) are formed in double: (len + 8) 2^-53 of sum |a da| for the dot, 2^-52 for the difference and
+        # the product; then two casts (u |ds| each) are allowed for the result
+        n = s.stop - s.start
+        bnd = (np.abs(a) * ((n + 8) * 2.0 ** -53 * (np.abs(a) @ np.abs(d)) + 2.0 ** -52 * (np.abs(d) + np.abs(dot))) + 2 * U24 * np.abs(ref)) * SLACK + TINY
+        r = np.abs(got[s] - ref) / bnd
+        worst = max(worst, float(r.max()))
+        assert (r <= 1).all(), (n, int(np.argmax(r)), float(r.max()))
+    assert got[sl[0]][0] == 0.0                                                            # one row: a = 1, ds = da - da
+    _note("attention_softmax_backward ds / bound", worst)
+
+
+@pytest.mark.parametrize("A", ATT_CHANNELS)
+def test_attention_scores_backward_elementwise(env, A):
+    """du = ds v (1 - n^2), nonlin <- ds n, with n up to +-(1 - 2^-20) and exact +-1, where 1 - n^2 cancels.  nonlin is the left
+    half of its buffer, du the right half of its own; the other halves are not touched."""
+    hiplib = env["hiplib"]
+    rng = np.random.default_rng(300 + A)
+    R = 1031                                                   # not a multiple of the 4 rows of a workgroup
+    n = np.tanh(rng.standard_normal((R, A)) * 10.0 ** rng.uniform(-2, 1, (R, A))).astype(np.float32)
+    sat = np.array([1.0, -1.0, 1 - 2.0 ** -20, -(1 - 2.0 ** -20), 1 - 2.0 ** -24, 0.0, 2.0 ** -13, -0.70710678], np.float32)
+    pick = rng.random((R, A)) < 0.2
+    n[pick] = rng.choice(sat, int(pick.sum()))
+    n[0, :4] = sat[:4]
+    v = (rng.standard_normal(A) * 0.3).astype(np.float32)
+    ds = (rng.standard_normal(R) * 10.0 ** rng.uniform(-3, 1, R)).astype(np.float32)
+    nbuf = np.full((R, 2 * A), NAN, np.float32)
+    nbuf[:, :A] = n
+    nd = _dev(env, nbuf)
+    dubuf = _nan(env, R, 2 * A)
+    hiplib.attention_scores_backward(nd[:, :A], _dev(env, ds), _dev(env, v), dubuf[:, A:])
+    du_all, n_all = _host(dubuf).astype(np.float64), _host(nd).astype(np.float64)
+    assert np.isnan(du_all[:, :A]).all() and np.isnan(n_all[:, A:]).all()
+    n64, dsv = n.astype(np.float64), ds.astype(np.float64)[:, None] * v.astype(np.float64)
+    ref = dsv * (1 - n64 * n64)
+    # absolute, because 1 - n^2 cancels: n^2 is rounded (<= u, n^2 <= 1), 1 - fl(n^2) is exact from 0.5 up and rounded (<= u) below,
+    # ds v is rounded and so is the product (u |ds v| each, 1 - n^2 <= 1): 4 u |ds v|
+    bnd = 4 * U24 * np.abs(dsv) * SLACK + TINY
+    r = np.abs(du_all[:, A:] - ref) / bnd
+    assert (r <= 1).all(), (A, np.unravel_index(np.argmax(r), r.shape), float(r.max()))
+    assert (du_all[:, A:][n64 * n64 == 1] == 0).all()                                     # exact +-1: exactly zero
+    # nonlin after the call: ds n to one rounding
+    g_ref = ds.astype(np.float64)[:, None] * n64
+    assert (np.abs(n_all[:, :A] - g_ref) <= U24 * np.abs(g_ref) + TINY).all()
+    _note("attention_scores_backward du / bound (A %d)" % A, float(r.max()))

@@ -51,7 +51,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradParams p)
     const long r_end = min(p.R, r_begin + p.rows_per_split);
 
     f32x16 acc00 = {0}, acc01 = {0}, acc10 = {0}, acc11 = {0};
-    const bool vec = !(p.cin & 3) && !(p.ldx & 3) && !(p.cout & 3) && !(p.lddz & 3);
+    const bool vec = !(p.cin & 3) && !(p.ldx & 3) && !(p.cout & 3) && !(p.lddz & 3) &&
+                     !((reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.dz)) & 15);   // (a column slice may start anywhere)
     f32x4 va[4], vb[4];
     // 32 rows x 128 channels of x (shifted by the tap) and of dz -> registers (prefetched one step ahead)
     auto load = [&](long r0) {
@@ -932,7 +933,7 @@ size_t xv_wgrad_workspace_bytes(int64_t R, int cin, int cout, int K)
 int xv_wgrad_f32(const float *x, int ldx, const float *dz, int lddz, int64_t R, int cin, int cout, int K, int dilation, float *dw,
                  void *workspace, void *stream)
 {
-    if (!x || !dz || !dw || R <= 0 || cin <= 0 || cout <= 0 || K <= 0 || !(K & 1) || dilation <= 0)
+    if (!x || !dz || !dw || R <= 0 || cin <= 0 || cout <= 0 || K <= 0 || !(K & 1) || dilation <= 0 || ldx < cin || lddz < cout)
         return fail(XV_ERR_BAD_ARG, "wgrad: bad argument");
     WgradParams p{};
     p.x = x; p.dz = dz; p.R = (long)R; p.cin = cin; p.ldx = ldx; p.cout = cout; p.lddz = lddz; p.K = K; p.dil = dilation;

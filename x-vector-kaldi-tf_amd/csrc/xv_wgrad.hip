@@ -6,7 +6,8 @@
 // Same contract as xv_wgrad_f32 (xv_train.hip): TF layout [K, Cin, Cout], rows outside [0, R) read as zero, the row range is
 // cut into splits whose partial tiles are merged in a fixed order (deterministic).  What differs is the arithmetic: the
 // exact-fp32 kernel is bound by v_mfma_f32_32x32x2_f32 (157 TF peak; 26 % of a training step), here every fp32 operand is
-// split hi + lo (bf16 each) and a product is hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 with fp32 accumulation -- the
+// split hi + lo (bf16 each) and a product is hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (hi*hi and
+// the cross terms in accumulators of their own, added at the store) -- the
 // arithmetic of the forward / input-gradient GEMMs of --train-precision bf16x3 (xv_gemm3.hip), ~5e-6 relative.
 //
 // The reduction runs over ROWS, so both MFMA operands are needed "transposed": a lane of the A (cin) or B (cout) fragment holds
@@ -58,9 +59,10 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16x3_kernel(const WgradParams 
     const long r_end = r_begin + p.rows_per_split < p.R ? r_begin + p.rows_per_split : p.R;
 
     // operands through buffer descriptors of exactly R rows: a row index outside [0, R) -- before the first row the byte offset
-    // wraps to > 2^31 -- is out of range and loads as zero (the host checks R * ld * 4 < 2^31)
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.x), 0, (int)(p.R * p.ldx * 4), XV_RSRC_FLAGS);
-    const __amdgpu_buffer_rsrc_t zrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.dz), 0, (int)(p.R * p.lddz * 4), XV_RSRC_FLAGS);
+    // wraps to > 2^31 -- is out of range and loads as zero (the host checks R * ld * 4 < 2^31).  A descriptor ends with the last
+    // channel of the last row, not with that row's stride: of a column slice whose parent buffer ends there nothing past it is read
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.x), 0, (int)(((p.R - 1) * p.ldx + p.cin) * 4), XV_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t zrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.dz), 0, (int)(((p.R - 1) * p.lddz + p.cout) * 4), XV_RSRC_FLAGS);
     const int ch = tid & 127, half = tid >> 7;
     const bool xc_ok = c0 + ch < p.cin, zc_ok = o0 + ch < p.cout;      // a ragged last tile: the column would alias the next row
     const int xcol = (c0 + ch) * 4, zcol = (o0 + ch) * 4;
@@ -93,11 +95,14 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16x3_kernel(const WgradParams 
         *reinterpret_cast<bf16x8 *>(d + PLANE + 16) = lo[1];
     };
 
-    f32x16 acc[2][2];
+    // hi*hi and the two cross terms accumulate apart: every MFMA update rounds the whole accumulator (twice per 32x32x16: once
+    // per 8 products), so cross terms added into the hi*hi sum cost four more roundings of that sum per 16 rows for terms 2^-8
+    // of its size; in an accumulator of their own the roundings are 2^-8 as large, and the two meet in one addition at the end
+    f32x16 acc[2][2], acc_x[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = (f32x16){0};
+        for (int j = 0; j < 2; ++j) acc[i][j] = acc_x[i][j] = (f32x16){0};
     // fragment of tile i, k-step ks: channel wi*64 + 32 i + (lane & 31), rows 16 ks + 8 (lane >> 5) .. + 7
     const char *afrag = lds + (wi * 64 + (lane & 31)) * CH_STRIDE + 16 * (lane >> 5);
     const char *bfrag = lds + 2 * PLANE + (wj * 64 + (lane & 31)) * CH_STRIDE + 16 * (lane >> 5);
@@ -126,15 +131,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16x3_kernel(const WgradParams 
                 bh[i] = *reinterpret_cast<const bf16x8 *>(bfrag + i * 32 * CH_STRIDE + ks * 32);
                 bl[i] = *reinterpret_cast<const bf16x8 *>(bfrag + i * 32 * CH_STRIDE + ks * 32 + PLANE);
             }
-            // small terms first, as in the forward kernel (xv_gemm3.hip): lo*hi + hi*lo + hi*hi
+            // lo*hi + hi*lo into acc_x, hi*hi into acc
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < 2; ++j) acc_x[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc_x[i][j], 0, 0, 0);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < 2; ++j) acc_x[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc_x[i][j], 0, 0, 0);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -159,7 +164,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16x3_kernel(const WgradParams 
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
                 const int c = c0 + wi * 64 + bi * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-                if (c < p.cin) out[(size_t)c * p.cout + o] = acc[bi][bj][reg];
+                if (c < p.cin) out[(size_t)c * p.cout + o] = acc[bi][bj][reg] + acc_x[bi][bj][reg];
             }
         }
 }

@@ -911,7 +911,7 @@ def wgrad(x, dz, K, dilation, dw, precision="fp32", db=None):
     ``db`` (bf16x3 only, see wgrad_takes_bias): also db[Cout] = sum_r dz[r], out of the rows the kernel streams anyway."""
     lib = require_gpu()
     fn, name = (lib.xv_wgrad_bf16x3, "xv_wgrad_bf16x3") if precision == "bf16x3" else (lib.xv_wgrad_f32, "xv_wgrad_f32")
-    _rows2d(x, "x"); _f32(dz, "dz"); _f32(dw, "dw")
+    _rows2d(x, "x"); _rows2d(dz, "dz"); _f32(dw, "dw")
     R, cin = x.shape
     cout = dz.shape[1]
     assert dz.shape[0] == R and tuple(dw.shape) == (K, cin, cout)
