@@ -52,7 +52,7 @@ extern "C" {
 #define XV_ERR_BAD_ARG (-1)
 #define XV_ERR_UNSUPPORTED (-2)
 
-/* Library / ABI version (increments whenever an entry point is added or changed; currently 28). */
+/* Library / ABI version (increments whenever an entry point is added or changed; currently 29). */
 int xv_version(void);
 /* Thread-local description of the last non-zero return. */
 const char *xv_last_error(void);
@@ -548,6 +548,23 @@ int xv_score_pairs_f32(const float *e, const float *t, int64_t ldk, int kpad, co
                        int64_t n_trials, const float *r, float *scores, void *stream);
 int xv_topk_row_stats_f32(const float *scores, int64_t ld, int n_rows, int n_cols, int top_n, float *mean, float *std,
                           void *stream);
+
+/* ---- moments for PLDA adaptation (ivector-adapt-plda, stage 10; csrc/xv_moments.hip) --------------------
+ * xv_moment_stats_f64  sum[j] = sum_i x[i, j] and outer[j, k] = sum_i x[i, j] x[i, k] over the rows i < n_rows of x (row stride
+ *   ldx) for j, k < dim, in fp64: the fp32 inputs are widened (exact), the products go through v_mfma_f64_16x16x4_f64 (a product
+ *   of two fp32 values is exact in fp64) and every accumulation is fp64.
+ *   Fixed order: rows are cut into slabs of XV_MOMENT_SLAB rows; each slab is accumulated with its rows ascending (four rows
+ *   per MFMA) into a partial held in the workspace, and a second launch adds the partials in slab order.  No floating-point
+ *   atomics.  The output bits depend on the values, n_rows and dim only: not on ldx, ld_outer, the stream or what ran before.
+ *   Only the 16 x 16 tiles on or above the diagonal are computed and the rest is mirrored: outer is exactly symmetric.
+ *   Columns [dim, ldx) of x are never read; nothing outside sum[0, dim) and outer[j * ld_outer + k], j, k < dim, is written.
+ *   1 <= dim <= 256, else XV_ERR_UNSUPPORTED.  n_rows >= 1, ldx >= dim, ld_outer >= dim, x 16-byte aligned and ldx a multiple
+ *   of 4, a workspace of at least xv_moment_stats_workspace_bytes(n_rows, dim) bytes, else XV_ERR_BAD_ARG (nothing is launched).
+ * xv_moment_stats_workspace_bytes  the bytes of that workspace (0 for arguments xv_moment_stats_f64 refuses). */
+#define XV_MOMENT_SLAB 2048
+int xv_moment_stats_f64(const float *x, int64_t ldx, int64_t n_rows, int dim, double *sum, double *outer, int64_t ld_outer,
+                        void *workspace, size_t workspace_bytes, void *stream);
+size_t xv_moment_stats_workspace_bytes(int64_t n_rows, int dim);
 
 /* Stage 1 of the recipe: MFCC features and the energy VAD (compute-mfcc-feats / compute-vad; csrc/xv_mfcc.hip).
  * xv_mfcc_f32  MFCC rows of n_utts utterances in one launch.  samples: every utterance's samples back to back, int16

@@ -1,9 +1,11 @@
 """Timings of the scoring back-end: prepare at N = 100 k, D = 512; the dense scorer at Ne = Nt = 16384 against the
 157.3 TF fp32-MFMA peak; the trial scorer at 2 M trials; the `plda_backend.py score` CLI on an SRE16-sized synthetic job with a
-read / prepare / score / write breakdown.  Device events after warm-up.   python tools/backend_bench.py [--fit | --asnorm]
+read / prepare / score / write breakdown.  Device events after warm-up.   python tools/backend_bench.py [--fit | --asnorm | --adapt]
 (--fit: instead time the host fp64 LDA + PLDA fits at N = 100 k, D = 512; needs no GPU.  --asnorm: instead time AS-norm --
 cohort scoring and the top-N statistics kernel separately at the recipe shape and at 50 k rows x 50 k cohort in 1 GiB chunks,
-then the `score --cohort` CLI on the SRE16-sized job beside the same job without a cohort)."""
+then the `score --cohort` CLI on the SRE16-sized job beside the same job without a cohort.  --adapt: instead time the fp64
+moments kernel (xv_moment_stats_f64) at N = 10^6, d = 100 and 200 against the 78.6 TF fp64-MFMA peak and against NumPy's fp64
+x.T @ x on the host's threads, then the whole `plda_backend.py adapt-plda --lda` command at N = 10^5, D = 512, d = 200)."""
 import os, shutil, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TWIN = os.path.join(ROOT, "x-vector-kaldi-tf_amd", "local", "tf")
@@ -139,6 +141,77 @@ def asnorm_timing(top_n=300):
             del E, C
 
 
+PEAK_F64_TF = 78.6
+
+
+def adapt_timing():
+    """xv_moment_stats_f64 in one call at N = 10^6 (median of 5 timed launches after warm-up, device events; 2 N d^2 flop and
+    4 N d bytes of input), NumPy's fp64 x.T @ x of the same rows on the host (conversion to fp64 not counted), and the whole
+    adapt-plda command."""
+    import torch
+    import kaldi_io
+    import plda_backend
+    from xvector_amd import backend, hiplib
+    dev = "cuda:0"
+    N = 1000000
+    for d in (100, 200):
+        x = torch.randn((N, d), device=dev)
+        s = torch.empty(d, dtype=torch.float64, device=dev)
+        o = torch.empty((d, d), dtype=torch.float64, device=dev)
+        ws = torch.empty(hiplib.moment_stats_workspace_bytes(N, d), dtype=torch.uint8, device=dev)
+        for _ in range(2):
+            hiplib.moment_stats(x, s, o, workspace=ws)
+        ts = []
+        for _ in range(5):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); hiplib.moment_stats(x, s, o, workspace=ws); b.record(); torch.cuda.synchronize()
+            ts.append(a.elapsed_time(b))
+        ms = float(np.median(ts))
+        tf = 2.0 * N * d * d / ms / 1e9
+        x64 = x.cpu().numpy().astype(np.float64)
+        x64[:1000].T @ x64[:1000]                             # warm-up of the BLAS threads
+        th = []
+        for _ in range(3):
+            t0 = time.perf_counter(); ref = x64.T @ x64; th.append(time.perf_counter() - t0)
+        host = float(np.median(th)) * 1e3
+        err = np.abs(o.cpu().numpy() - ref).max() / np.abs(ref).max()
+        t0 = time.perf_counter(); backend.moment_stats(x, d); wall = (time.perf_counter() - t0) * 1e3
+        print("moment_stats N = %d, d = %d: kernel %.3f ms (min %.3f, max %.3f) = %.1f TF/s algorithmic = %.2f of the %.1f TF "
+              "fp64-MFMA peak, %.0f GB/s of x; workspace %.0f MB; backend.moment_stats (chunks of %d rows, results copied back "
+              "and added on the host) %.1f ms; NumPy fp64 x.T @ x on %s threads %.1f ms = %.1fx the kernel; max |diff| / max = %.1e"
+              % (N, d, ms, min(ts), max(ts), tf, tf / PEAK_F64_TF, PEAK_F64_TF, 4.0 * N * d / ms / 1e6, ws.numel() / 1e6,
+                 backend.MOMENT_CHUNK_ROWS, wall, os.environ.get("OMP_NUM_THREADS", "all"), host, host / ms, err))
+        del x, x64, ws
+    rng = np.random.default_rng(4)
+    n, D, d = 100000, 512, 200
+    tmp = tempfile.mkdtemp(prefix="backend_bench_")
+    with kaldi_io.TableWriter(tmp + "/major.ark", tmp + "/major.scp") as w:
+        kaldi_io.write_vec_flt_batch(w, ["utt%06d" % i for i in range(n)], list(rng.standard_normal((n, D)).astype(np.float32)))
+    backend.write_transform(tmp + "/transform.mat", rng.standard_normal((d, D + 1)) / D ** 0.5)
+    q, _ = np.linalg.qr(rng.standard_normal((d, d)))
+    backend.write_plda(tmp + "/plda", backend.Plda(np.zeros(d), q, np.sort(rng.uniform(0.1, 5, d))[::-1]))
+    args = ["adapt-plda", "--within-covar-scale", "0.75", "--between-covar-scale", "0.25", "--lda", tmp + "/transform.mat",
+            tmp + "/plda", "scp:%s/major.scp" % tmp, tmp + "/plda_adapt"]
+    plda_backend.main(args)                                   # warm-up
+    t = [time.perf_counter()]
+    plda = backend.read_plda(tmp + "/plda")
+    vec = plda_backend.read_vectors("scp:%s/major.scp" % tmp)
+    xs = np.stack(list(vec.values()))
+    lda = backend.read_transform(tmp + "/transform.mat")
+    t.append(time.perf_counter())
+    rows, _ = backend.prepare(xs, hiplib.SIDE_PLAIN, mean=xs.astype(np.float64).mean(axis=0).astype(np.float32), transform=lda)
+    torch.cuda.synchronize(); t.append(time.perf_counter())
+    nn, s1, s2 = backend.moment_stats(rows, d)
+    t.append(time.perf_counter())
+    backend.write_plda(tmp + "/plda_adapt", backend.adapt_plda(plda, nn, s1, s2, 0.75, 0.25))
+    t.append(time.perf_counter())
+    w0 = time.perf_counter(); plda_backend.main(args); w1 = time.perf_counter()
+    dt = np.diff(t)
+    print("adapt-plda CLI, %d vectors, D = %d, d = %d: whole command %.2f s; steps: read %.2f s, mean + upload + prepare %.3f s, "
+          "moments (incl. copy back) %.3f s, host fit + write %.3f s" % (n, D, d, w1 - w0, dt[0], dt[1], dt[2], dt[3]))
+    shutil.rmtree(tmp)
+
+
 def cli_job(cohort=False):
     """SRE16-sized: 800 enrolment speakers, 9.3 k test segments, 2 M trials, D = 512, LDA d = 100 (cohort: also the whole
     command with --cohort of 2,000 vectors, top-N 300, beside the same command without it)."""
@@ -210,6 +283,8 @@ def cli_job(cohort=False):
 if __name__ == "__main__":
     if "--fit" in sys.argv:
         fit_timing()
+    elif "--adapt" in sys.argv:
+        adapt_timing()
     elif "--asnorm" in sys.argv:
         asnorm_timing()
         cli_job(cohort=True)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""The recipe's back-end (stages 8-9 of run.sh) without Kaldi binaries.  Each subcommand is named after the binary it replaces:
+"""The recipe's back-end (stages 8-10 of run.sh) without Kaldi binaries.  Each subcommand is named after the binary it replaces:
 
   mean         ivector-mean scp:xvector.scp mean.vec
   compute-lda  ivector-subtract-global-mean scp:xvector.scp ark:- | ivector-compute-lda --total-covariance-factor=f --dim=d
@@ -11,6 +11,10 @@
                instead of Kaldi pipes; --scoring cosine scores the cosine of the same chain's vectors instead of the PLDA LLR;
                --cohort <vectors> [--cohort-top-n N] writes AS-norm scores (adaptive symmetric normalisation against the top N
                cohort scores of each side; the cohort goes through the same --mean / --lda chain as the tests)
+  adapt-plda   ivector-adapt-plda [--within-covar-scale f] [--between-covar-scale f] [--mean-diff-scale f] plda <vectors>
+               plda_adapt (stage 10's model); with --lda transform.mat the unlabelled in-domain vectors first go through stage
+               8's chain on the GPU, as in compute-plda, and their fp64 moments are taken there on the f64 MFMA without the
+               rows leaving the device
   compute-eer  compute-eer <file of "score target|nontarget" lines, or ->   (prints the EER in percent)
 
 Vector tables are ``scp:<file>`` or ``ark:<file>`` (options before the colon, e.g. ``ark,s,cs:``, are accepted and ignored).
@@ -117,6 +121,39 @@ def cmd_compute_plda(args):
         logger.warning("%d utterances of spk2utt absent from input" % missing)
     plda = backend.fit_plda(x, groups, num_em_iters=args.num_em_iters)
     backend.write_plda(args.plda, plda, binary=args.binary)
+
+
+def cmd_adapt_plda(args):
+    from xvector_amd import backend, hiplib
+    for name in ("within_covar_scale", "between_covar_scale", "mean_diff_scale"):
+        v = getattr(args, name)
+        if not (np.isfinite(v) and v >= 0.0):
+            raise SystemExit("--%s must be in [0, inf), got %r" % (name.replace("_", "-"), v))
+    hiplib.require_gpu()                                 # no CPU fallback: fail before reading anything
+    plda = backend.read_plda(args.plda_in)
+    vectors = read_vectors(args.vectors)
+    if not vectors:
+        raise SystemExit("no vectors in %s: nothing to adapt to, no model written" % args.vectors)
+    x = _stack(vectors, list(vectors))
+    t = backend.read_transform(args.lda) if args.lda else None
+    if t is not None and t.shape[1] not in (x.shape[1], x.shape[1] + 1):
+        raise SystemExit("%s has %d columns, the vectors have dimension %d" % (args.lda, t.shape[1], x.shape[1]))
+    dim = x.shape[1] if t is None else t.shape[0]
+    if dim != plda.dim:
+        raise SystemExit("the vectors have dimension %d%s, the PLDA %d: no model written" %
+                         (dim, " after the LDA" if t is not None else "", plda.dim))
+    if dim > hiplib.MOMENT_DIM_MAX:
+        raise SystemExit("vectors of dimension %d: the moments kernel takes at most %d" % (dim, hiplib.MOMENT_DIM_MAX))
+    if t is not None:
+        # stage 8's chain: subtract the set's own mean, transform-vec, ivector-normalize-length -- on the device, where the rows stay
+        mean = x.astype(np.float64).mean(axis=0).astype(np.float32)
+        rows, _ = backend.prepare(x, hiplib.SIDE_PLAIN, mean=mean, transform=t, length_norm=True)
+        n, s1, s2 = backend.moment_stats(rows, dim)
+    else:
+        n, s1, s2 = backend.moment_stats(x, dim)
+    logger.info("Read %d vectors of dimension %d" % (n, dim))
+    out = backend.adapt_plda(plda, n, s1, s2, args.within_covar_scale, args.between_covar_scale, args.mean_diff_scale)
+    backend.write_plda(args.plda_out, out, binary=args.binary)
 
 
 def cmd_score(args):
@@ -230,6 +267,14 @@ def main(argv=None):
     p.add_argument("--binary", type=lambda s: s.lower() in ("true", "1"), default=True)
     p.add_argument("spk2utt"); p.add_argument("vectors"); p.add_argument("plda")
     p.set_defaults(fn=cmd_compute_plda)
+    p = sub.add_parser("adapt-plda", help="ivector-adapt-plda")
+    p.add_argument("--within-covar-scale", type=float, default=0.3)
+    p.add_argument("--between-covar-scale", type=float, default=0.7)
+    p.add_argument("--mean-diff-scale", type=float, default=1.0)
+    p.add_argument("--lda", help="transform.mat: apply stage 8's chain to the vectors first (on the GPU)")
+    p.add_argument("--binary", type=lambda s: s.lower() in ("true", "1"), default=True)
+    p.add_argument("plda_in"); p.add_argument("vectors"); p.add_argument("plda_out")
+    p.set_defaults(fn=cmd_adapt_plda)
     p = sub.add_parser("score", help="ivector-plda-scoring")
     p.add_argument("--num-utts", help="ark:num_utts.ark (enrolment utterance counts)")
     p.add_argument("--mean", help="mean.vec: subtract it first (ivector-subtract-global-mean)")

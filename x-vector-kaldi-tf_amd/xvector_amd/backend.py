@@ -2,6 +2,8 @@
 
   fit_lda        ivector-compute-lda --total-covariance-factor f --dim d      (host, fp64)
   fit_plda       ivector-compute-plda --num-em-iters n  -> Plda (mean, transform, psi)   (host, fp64)
+  moment_stats   the first and second moment of vectors on the device, in fp64 on the f64 MFMA (xv_moment_stats_f64)
+  adapt_plda     ivector-adapt-plda: unsupervised adaptation of a Plda to those moments   (host, fp64)
   read_plda / write_plda, read_transform / write_transform   Kaldi's <Plda> object and transform.mat, binary and text
   prepare        ivector-subtract-global-mean | transform-vec | ivector-normalize-length | Plda::TransformIvector on the GPU
                  (xv_backend_prepare_f32)
@@ -172,6 +174,50 @@ def plda_from_covariances(mu, B, W):
     return Plda(mu, v.T @ t1, np.maximum(s, 0.0))
 
 
+def adapt_plda(plda, n, sum, outer, within_covar_scale=0.3, between_covar_scale=0.7, mean_diff_scale=1.0):
+    """ivector-adapt-plda (Kaldi's PldaUnsupervisedAdaptor::UpdatePlda): adapt `plda` to n unlabelled in-domain vectors given by
+    their moments sum[d] = sum_i y_i and outer[d, d] = sum_i y_i y_i^T (moment_stats).  -> Plda.
+
+    m = sum / n becomes the mean; V = outer / n - m m^T + mean_diff_scale (m - mu)(m - mu)^T is the in-domain total covariance.
+    In the space of P' = diag(1 / sqrt(1 + psi)) P the model's total covariance is I, its within-speaker covariance
+    diag(1 / (1 + psi)) and its between-speaker covariance diag(psi / (1 + psi)).  For every eigenvalue s_i > 1 of P' V P'^T
+    (eigenvector p_i) the excess (s_i - 1) p_i p_i^T is shared out: within_covar_scale of it to W, between_covar_scale of it
+    to B.  Directions in which the in-domain data varies less than the model are left alone.  The covariances are mapped back
+    with P'^-1 and diagonalised again (plda_from_covariances)."""
+    d = plda.dim
+    for name, v in (("within_covar_scale", within_covar_scale), ("between_covar_scale", between_covar_scale),
+                    ("mean_diff_scale", mean_diff_scale)):
+        if not (np.isfinite(v) and v >= 0.0):
+            raise ValueError("adapt_plda: %s must be in [0, inf), got %r" % (name, v))
+    if not n >= 1:
+        raise ValueError("adapt_plda: no vectors (n = %r)" % (n,))
+    s1 = np.asarray(sum, dtype=np.float64)
+    s2 = np.asarray(outer, dtype=np.float64)
+    if s1.shape != (d,) or s2.shape != (d, d):
+        raise ValueError("adapt_plda: moments of shape %r / %r do not fit a PLDA of dimension %d" % (s1.shape, s2.shape, d))
+    if not (np.all(np.isfinite(s1)) and np.all(np.isfinite(s2))):
+        raise ValueError("adapt_plda: the moments are not finite")
+    m = s1 / n
+    var = s2 / n - np.outer(m, m)
+    diff = m - plda.mean
+    var += mean_diff_scale * np.outer(diff, diff)
+    p1 = plda.transform / np.sqrt(1.0 + plda.psi)[:, None]
+    s, p = _eigh_desc(p1 @ var @ p1.T)
+    w1 = np.diag(1.0 / (1.0 + plda.psi))
+    b1 = np.diag(plda.psi / (1.0 + plda.psi))
+    above = 0
+    for i in range(d):
+        if s[i] > 1.0:
+            excess = (s[i] - 1.0) * np.outer(p[:, i], p[:, i])
+            w1 += within_covar_scale * excess
+            b1 += between_covar_scale * excess
+            above += 1
+    logger.info("Adapting to %d vectors: %d of %d eigenvalues of the in-domain covariance are above 1 in the model's space "
+                "(largest %g)" % (n, above, d, s[0]))
+    inv = np.linalg.inv(p1)
+    return plda_from_covariances(m, inv @ b1 @ inv.T, inv @ w1 @ inv.T)
+
+
 # ------------------------------------------------------------------------------------------------
 # Kaldi I/O: <Plda> and transform.mat
 # ------------------------------------------------------------------------------------------------
@@ -314,6 +360,56 @@ def prepare(x, side, num_utts=None, mean=None, transform=None, plda=None, length
                            plda_mean=None if plda is None else _dev(plda.mean, device),
                            plda_psi=None if plda is None else _dev(plda.psi, device), r=r)
     return out, r
+
+
+MOMENT_CHUNK_ROWS = 1 << 18        # rows per xv_moment_stats_f64 call of moment_stats: a constant, so the bits are too
+
+
+def moment_stats(x_rows, dim=None, device="cuda:0"):
+    """(n, sum[dim], outer[dim, dim]) of the first dim columns of x_rows[N, >= dim], float64 NumPy: sum = sum_i x_i,
+    outer = sum_i x_i x_i^T, on the f64 MFMA (xv_moment_stats_f64).
+
+    x_rows: a float32 torch tensor on the device whose row stride is a multiple of 4 (what prepare returns: the rows are used
+    where they are), or a host array (uploaded chunk by chunk, rows padded to a multiple of 4 columns).  The rows go through
+    the kernel in chunks of MOMENT_CHUNK_ROWS and the chunk results are added here in fp64 in chunk order, so the result's bits
+    depend on the values alone, not on the memory that happens to be free."""
+    import torch
+    hiplib.require_gpu()
+    on_device = isinstance(x_rows, torch.Tensor)
+    if not on_device:
+        x_rows = np.asarray(x_rows, dtype=np.float32)
+    if x_rows.ndim != 2:
+        raise ValueError("moment_stats: x_rows must be [N, D]")
+    n = int(x_rows.shape[0])
+    dim = int(x_rows.shape[1]) if dim is None else int(dim)
+    if n < 1:
+        raise ValueError("moment_stats: no vectors")
+    if not 1 <= dim <= x_rows.shape[1]:
+        raise ValueError("moment_stats: dim %d must be in 1..%d" % (dim, x_rows.shape[1]))
+    if dim > hiplib.MOMENT_DIM_MAX:
+        raise ValueError("moment_stats: dim %d exceeds %d, the limit of xv_moment_stats_f64" % (dim, hiplib.MOMENT_DIM_MAX))
+    if on_device:
+        x_rows = x_rows.to(device=device, dtype=torch.float32)
+        if x_rows.stride(1) != 1 or x_rows.stride(0) % 4 or x_rows.data_ptr() % 16:
+            x_rows = torch.nn.functional.pad(x_rows[:, :dim], (0, -dim % 4)).contiguous()
+    rows = min(n, MOMENT_CHUNK_ROWS)
+    s_d = torch.empty(dim, dtype=torch.float64, device=device)
+    o_d = torch.empty((dim, dim), dtype=torch.float64, device=device)
+    ws = torch.empty(hiplib.moment_stats_workspace_bytes(rows, dim), dtype=torch.uint8, device=device)
+    stage = None if on_device else torch.zeros((rows, (dim + 3) // 4 * 4), dtype=torch.float32, device=device)
+    total_s = np.zeros(dim)
+    total_o = np.zeros((dim, dim))
+    for i0 in range(0, n, MOMENT_CHUNK_ROWS):
+        m = min(MOMENT_CHUNK_ROWS, n - i0)
+        if on_device:
+            chunk = x_rows[i0:i0 + m]
+        else:
+            stage[:m, :dim] = torch.as_tensor(np.ascontiguousarray(x_rows[i0:i0 + m, :dim]), device=device)
+            chunk = stage[:m]
+        hiplib.moment_stats(chunk, s_d, o_d, dim=dim, workspace=ws)
+        total_s += s_d.cpu().numpy()
+        total_o += o_d.cpu().numpy()
+    return n, total_s, total_o
 
 
 DENSE_MAX_BYTES = 1 << 30          # the dense score matrix of one trial list is at most this large

@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -118,6 +118,9 @@ _SIGNATURES = {
     "xv_score_matrix_f32": (_ci, [_vp, _vp, _i64, _ci, _ci, _ci, _vp, _vp, _i64, _vp]),
     "xv_score_pairs_f32": (_ci, [_vp, _vp, _i64, _ci, _vp, _vp, _i64, _vp, _vp, _vp]),
     "xv_topk_row_stats_f32": (_ci, [_vp, _i64, _ci, _ci, _ci, _vp, _vp, _vp]),
+    # moments for PLDA adaptation
+    "xv_moment_stats_f64": (_ci, [_vp, _i64, _i64, _ci, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "xv_moment_stats_workspace_bytes": (_sz, [_i64, _ci]),
     "xv_mfcc_f32": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _ci, _i64, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _ci, _vp, _ci, _ci, _ci, _ci,
                           _cf, _cf, _ci, _ci, _ci, _cf, _vp, _i64, _vp, _i64, _vp]),
     "xv_vad_energy_f32": (_ci, [_vp, _i64, _vp, _vp, _ci, _cf, _cf, _ci, _cf, _vp, _vp]),
@@ -141,6 +144,8 @@ ACT_NONE, ACT_RELU, ACT_LRELU, ACT_PRELU = 0, 1, 2, 3
 
 BACKEND_KSTEP = 8
 SIDE_PLAIN, SIDE_ENROL, SIDE_TEST, SIDE_COSINE = 0, 1, 2, 3
+MOMENT_SLAB = 2048                # XV_MOMENT_SLAB: rows per partial of xv_moment_stats_f64
+MOMENT_DIM_MAX = 256
 
 _lib = None
 
@@ -1189,6 +1194,30 @@ def topk_row_stats(scores, top_n, mean, std):
         assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n_rows
     _check(lib.xv_topk_row_stats_f32(_ptr(scores), scores.stride(0), n_rows, n_cols, int(top_n), _ptr(mean), _ptr(std), _stream()),
            "xv_topk_row_stats_f32")
+
+
+def moment_stats_workspace_bytes(n_rows, dim):
+    return int(load().xv_moment_stats_workspace_bytes(int(n_rows), int(dim)))
+
+
+def moment_stats(x, sum, outer, dim=None, workspace=None):
+    """sum[j] = sum_i x[i, j], outer[j, k] = sum_i x[i, j] x[i, k] over the rows of x[N, >= dim] in fp64 on the f64 MFMA, in a
+    fixed order (see include/xvector_hip.h).  x may be a slice of a wider buffer (its row stride is passed as ldx; dim None: all
+    of its columns); sum: float64 [>= dim]; outer: float64 [>= dim, ld] (its row stride is passed as ld_outer).  workspace: a
+    device buffer of moment_stats_workspace_bytes(N, dim) bytes (None: allocated here)."""
+    import torch
+    lib = require_gpu()
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    n_rows = x.shape[0]
+    dim = x.shape[1] if dim is None else int(dim)
+    assert dim <= x.shape[1]
+    assert sum.is_cuda and sum.dtype == torch.float64 and sum.is_contiguous() and sum.numel() >= dim
+    assert outer.is_cuda and outer.dtype == torch.float64 and outer.dim() == 2 and outer.stride(1) == 1
+    assert outer.shape[0] >= dim and outer.shape[1] >= dim
+    if workspace is None:
+        workspace = _ws(lib.xv_moment_stats_workspace_bytes(n_rows, dim), x.device)
+    _check(lib.xv_moment_stats_f64(_ptr(x), x.stride(0), n_rows, dim, _ptr(sum), _ptr(outer), outer.stride(0), _ptr(workspace),
+                                   workspace.numel() * workspace.element_size(), _stream()), "xv_moment_stats_f64")
 
 
 def mfcc(samples, utt_offset, utt_samples, utt_row0, utt_key, total_rows, tables, opts, feats, logmel=None):
