@@ -660,6 +660,30 @@ int xv_augment_level_f32(const int64_t *utt, int n_utts, const double *utt_param
 int xv_augment_write(const double *y, const int64_t *utt, const double *utt_out, const int64_t *tiles, int64_t n_tiles, void *out,
                      int sample_format, unsigned long long *clipped, void *stream);
 
+/* ---- training examples: stages 3-5 of the recipe -----------------------------------------------------------
+ * What run.sh stage 3 (apply-cmvn-sliding | select-voiced-frames | copy-feats), local/tf/get_egs.sh and create_tar_files.py do to
+ * the features, without the intermediate no-silence copy: raw MFCC rows + VAD decisions in, packed float16 [B, T, F] members out.
+ * xv_vad_compact_i32  vad[n_frames]: the VAD values of n_utts utterances back to back (utt_start[u], utt_len[u] in frames;
+ *   non-zero = voiced).  voiced_count[u] = number of voiced frames of u (the utt2num_frames of the *_no_sil set);
+ *   voiced_row[utt_start[u] + j] = frame index inside u of its j-th voiced frame, j < voiced_count[u] (the other entries are left
+ *   alone; voiced_row has n_frames entries).  A segmented prefix sum without atomics: bit-identical on every run.  An utterance
+ *   whose span leaves [0, n_frames) gets voiced_count 0 and nothing else is touched for it.
+ * xv_egs_chunks_f16   x[x_rows, ldx]: the raw rows of the same utterances; chunk c is chunk_len[c] consecutive VOICED frames of
+ *   utterance chunk_utt[c] from voiced frame chunk_first[c] on (the numbering of a ranges file).  For j < chunk_len[c], with
+ *   t = voiced_row[utt_start[u] + chunk_first[c] + j]:
+ *       y[chunk_dst[c] + j feat_dim + f] = half_rne(float(double(x[t][f]) - sum_{ws <= s < we} double(x[s][f]) / (we - ws)))
+ *   [ws, we) is the window of xv_cmn_sliding_scatter_f32 around RAW frame t (CMN precedes the selection), the sum is taken in
+ *   double precision, the conversion to half rounds to nearest even from the float (overflow: inf, NaN stays NaN).  chunk_dst
+ *   counts halves from y (a packed [B, T, F] member is chunk_dst = member + slot T F); chunks may differ in length
+ *   (max_chunk_len = the longest), overlap in their sources and come in any order.  A row whose voiced index lies outside
+ *   [0, voiced_count[u]), whose utterance is out of range or whose halves would leave [0, y_elems) is skipped: no read, no write. */
+int xv_vad_compact_i32(const float *vad, const int32_t *utt_start, const int32_t *utt_len, int n_utts, int64_t n_frames,
+                       int32_t *voiced_count, int32_t *voiced_row, void *stream);
+int xv_egs_chunks_f16(const float *x, int ldx, int feat_dim, int64_t x_rows, const int32_t *utt_start, const int32_t *utt_len,
+                      int n_utts, const int32_t *voiced_count, const int32_t *voiced_row, const int32_t *chunk_utt,
+                      const int32_t *chunk_first, const int32_t *chunk_len, const int64_t *chunk_dst, int n_chunks, int max_chunk_len,
+                      int cmn_window, int center, int min_window, void *y, int64_t y_elems, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

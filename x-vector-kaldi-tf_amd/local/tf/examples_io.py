@@ -5,9 +5,9 @@ members ``minibatch_<i>.npy`` are float16 ``[B, T, F]`` arrays (one length T per
 ``examples_io.save_data_info_tar`` (examples_io.py:156-185), next to ``egs.<n>.npy`` holding the int labels ``[n_minibatches,
 B]`` (read at examples_io.py:226).  ``TarFileDataLoader`` (examples_io.py:223-255) serves them through a bounded queue
 filled by a background thread; the model pops ``(data, labels)`` with a timeout and gets ``(None, None)`` once the archive is
-exhausted.  This module keeps that protocol (class name, ``count``, ``pop(timeout)``) and adds the matching writer, so
-training runs end to end without the rest of the reference's example-generation tooling (ranges files, h5 export: control
-plane, out of scope).
+exhausted.  This module keeps that protocol (class name, ``count``, ``pop(timeout)``) and adds the matching writer; the
+example generation itself (stage 3's filters, the ranges files, the chunk cutting) is ``xvector_amd/egs.py`` /
+``make_egs.py``.  The reference's h5 export is out of scope.
 
 ``RangesDataLoader`` is the other input mode of the reference's trainer (train_dnn_one_iteration.py:177-200; always on the
 command line ``train_dnn.py:258-262`` builds, used when no tar exists): minibatches are cut on the fly from a feature

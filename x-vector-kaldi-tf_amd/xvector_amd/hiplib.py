@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -131,6 +131,9 @@ _SIGNATURES = {
     "xv_augment_mix_f64": (_ci, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "xv_augment_level_f32": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp]),
     "xv_augment_write": (_ci, [_vp, _vp, _vp, _vp, _i64, _vp, _ci, _vp, _vp]),
+    # stages 3-5: training examples
+    "xv_vad_compact_i32": (_ci, [_vp, _vp, _vp, _ci, _i64, _vp, _vp, _vp]),
+    "xv_egs_chunks_f16": (_ci, [_vp, _ci, _ci, _i64, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _i64, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)      # tests check the header declares exactly these and the .so exports all of them
 
@@ -1124,6 +1127,67 @@ def cmn_sliding_scatter(x, utt_start, utt_len, n_utts, max_len, cmn_window, cent
     _check(lib.xv_cmn_sliding_scatter_f32(_ptr(x), x.stride(0), x.shape[1], _ptr(utt_start), _ptr(utt_len), int(n_utts), int(max_len),
                                           int(cmn_window), 1 if center else 0, int(min_window), _ptr(dst_row), _ptr(y), y.stride(0),
                                           _stream()), "xv_cmn_sliding_scatter_f32")
+
+
+def vad_compact(vad, utt_start, utt_len):
+    """xv_vad_compact_i32: vad[n_frames] cuda float32 (non-zero = voiced), utt_start / utt_len cuda int32 -> (voiced_count[n_utts],
+    voiced_row[n_frames]) cuda int32; voiced_row[utt_start[u] + j] is the frame inside u of its j-th voiced frame."""
+    import torch
+    lib = require_gpu()
+    _f32(vad, "vad")
+    for t in (utt_start, utt_len):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
+    n_utts, n_frames = utt_start.numel(), vad.numel()
+    assert vad.dim() == 1 and utt_len.numel() == n_utts
+    count = torch.zeros(n_utts, dtype=torch.int32, device=vad.device)
+    rows = torch.full((max(n_frames, 1),), -1, dtype=torch.int32, device=vad.device)
+    _check(lib.xv_vad_compact_i32(_ptr(vad), _ptr(utt_start), _ptr(utt_len), n_utts, n_frames, _ptr(count), _ptr(rows), _stream()),
+           "xv_vad_compact_i32")
+    return count, rows
+
+
+def check_chunk_table(table, voiced_counts, feat_dim, y_elems):
+    """The chunk table (host arrays chunk_utt, chunk_first, chunk_len, chunk_dst) against host copies of the voiced counts and the
+    size of the destination: ValueError names the first chunk that would leave its utterance or the buffer.  Pure NumPy."""
+    import numpy as np
+    cu, cf, cl, cd = (np.asarray(a, np.int64).reshape(-1) for a in table)
+    counts = np.asarray(voiced_counts, np.int64).reshape(-1)
+    if not (len(cu) == len(cf) == len(cl) == len(cd)):
+        raise ValueError("chunk table: columns of different lengths")
+    bad = (cu < 0) | (cu >= len(counts))
+    if not bad.any():
+        bad = (cf < 0) | (cl <= 0) | (cf + cl > counts[cu]) | (cd < 0) | (cd + cl * int(feat_dim) > int(y_elems))
+    if bad.any():
+        c = int(np.flatnonzero(bad)[0])
+        n = int(counts[cu[c]]) if 0 <= cu[c] < len(counts) else -1
+        raise ValueError("chunk %d of the table (utterance %d, voiced frames [%d, %d), %d halves from %d) does not fit: the utterance "
+                         "has %d voiced frames, the destination %d halves" % (c, cu[c], cf[c], cf[c] + cl[c], cl[c] * int(feat_dim),
+                                                                             cd[c], n, int(y_elems)))
+    return cu.astype(np.int32), cf.astype(np.int32), cl.astype(np.int32), cd
+
+
+def egs_chunks(x, utt_start, utt_len, voiced_count, voiced_row, table, voiced_counts_host, cmn_window, center, min_window, y):
+    """xv_egs_chunks_f16: raw rows x[n_frames, F] (cuda float32, row stride >= F) -> float16 chunks in the flat cuda float16 tensor y.
+    ``table`` = host arrays (chunk_utt, chunk_first, chunk_len, chunk_dst); it is checked against ``voiced_counts_host`` (a host copy
+    of voiced_count) and y.numel() first: ValueError before anything is launched."""
+    import numpy as np
+    import torch
+    lib = require_gpu()
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1]
+    assert y.is_cuda and y.dtype == torch.float16 and y.is_contiguous()
+    for t in (utt_start, utt_len, voiced_count, voiced_row):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
+    n_utts = utt_start.numel()
+    assert utt_len.numel() == n_utts and voiced_count.numel() == n_utts and voiced_row.numel() >= x.shape[0]
+    assert len(voiced_counts_host) == n_utts
+    cu, cf, cl, cd = check_chunk_table(table, voiced_counts_host, x.shape[1], y.numel())
+    if len(cu) == 0:
+        return
+    dev = [torch.from_numpy(np.ascontiguousarray(a)).to(x.device) for a in (cu, cf, cl, cd)]
+    _check(lib.xv_egs_chunks_f16(_ptr(x), x.stride(0), x.shape[1], x.shape[0], _ptr(utt_start), _ptr(utt_len), n_utts, _ptr(voiced_count),
+                                 _ptr(voiced_row), _ptr(dev[0]), _ptr(dev[1]), _ptr(dev[2]), _ptr(dev[3]), len(cu), int(cl.max()),
+                                 int(cmn_window), 1 if center else 0, int(min_window), _ptr(y), y.numel(), _stream()),
+           "xv_egs_chunks_f16")
 
 
 def backend_prepare(x, out, side, num_utts=None, mean=None, lda=None, lda_offset=None, length_norm=True, plda_transform=None,
