@@ -194,7 +194,7 @@ int xv_tdnn_layer_bf16x3_moments(const void *x, int x_format, int64_t R, int cin
  * -- a quarter of the bytes of y, and y is never re-read.  Every chunk must START ON A ROW THAT IS A MULTIPLE OF 8 (gap
  * rows pad up to it), so that a block never mixes two chunks and the result does not depend on batch composition.
  * xv_stats_pool_blocks_f32 merges the blocks of each chunk in order (fp64) into out[B, 2*Cout] = [mean | sqrt(var+eps)],
- * the same quantity as xv_stats_pool_f32; a chunk whose row_start is not a multiple of 8 yields NaN. */
+ * the same quantity as xv_stats_pool_f32; a chunk whose row_start is not a multiple of 8, or whose row_len is <= 0, yields NaN. */
 size_t xv_block_stats_bytes(int64_t R, int cout);
 int xv_tdnn_layer_pool_bf16x3(const void *x, int x_format, int64_t R, int cin, int ldx, const void *wt, const float *bias,
                               const float *bn_scale, const float *bn_shift, int act_kind, const float *act_alpha, int K,
@@ -294,7 +294,10 @@ int xv_fc_bf16x3(const float *x, int nrows, int in_dim, const void *wt, const fl
  * (local/tf/models.py:16,75-76):  out[b] = [ mean_t h[t,:]  ||  sqrt(mean_t (h-mean)^2 + eps) ]
  * over the rows of chunk b.  h[R,C] row stride ldh, C % 4 == 0; out[B, 2C].
  * Chunks longer than `split_rows` rows are reduced by several workgroups; `workspace` must then hold
- * xv_stats_pool_workspace_bytes(C, B, max_len, split_rows) bytes (may be NULL when that is 0). */
+ * xv_stats_pool_workspace_bytes(C, B, max_len, split_rows) bytes (may be NULL when that is 0).
+ * ldh must be a multiple of 4 and >= C (XV_ERR_BAD_ARG otherwise; the same holds for xv_chunk_moments_f32 and
+ * xv_attention_pool_f32).  A chunk with row_len <= 0 has no statistics: its row of out is NaN, in the direct and in the split path
+ * (as xv_stats_pool_blocks_f32 writes it); its row_start is not read and the other chunks are not affected. */
 size_t xv_stats_pool_workspace_bytes(int c, int nchunks, int max_len, int split_rows);
 int xv_stats_pool_f32(const float *h, int64_t ldh, int c, const int32_t *row_start, const int32_t *row_len,
                       int nchunks, int max_len, int split_rows, float eps, float *out, void *workspace,
@@ -330,7 +333,7 @@ int xv_chunk_average_f32(const float *e, const int32_t *seg_start, const int32_t
  * accumulate in fp64.  Workspaces are caller-provided device buffers. */
 
 /* Per-chunk (mean, BIASED variance) over the rows of each chunk: out[B, 2C] = [mean || var].  Same kernel and arguments
- * as xv_stats_pool_f32 without the sqrt(var+eps).  With xv_merge_moments_f32 this is tf.nn.moments over all frames of
+ * as xv_stats_pool_f32 (ldh >= C, NaN for an empty chunk) without the sqrt(var+eps).  With xv_merge_moments_f32 this is tf.nn.moments over all frames of
  * the minibatch (local/tf/tf_block.py:19). */
 int xv_chunk_moments_f32(const float *h, int64_t ldh, int c, const int32_t *row_start, const int32_t *row_len, int nchunks,
                          int max_len, int split_rows, float *out, void *workspace, void *stream);
@@ -466,7 +469,8 @@ int xv_am_margin_f32(float *cosines, const int32_t *labels, int nrows, int nclas
  *                             (models.py:1048-1050; products and sums in fp64).  Chunks longer than split_rows rows are
  *                             reduced by several workgroups through `workspace`
  *                             (xv_attention_pool_workspace_bytes bytes, 8-byte aligned; may be NULL when that is 0).
- * Gap rows of scores / att are never read or written. */
+ * Gap rows of scores / att are never read or written.  A chunk with row_len <= 0: xv_attention_softmax_f32 writes nothing for it,
+ * xv_attention_pool_f32 sets its row of out to NaN (direct and split path); ldh >= C as for xv_stats_pool_f32. */
 int xv_attention_scores_f32(const float *u, int64_t ldu, int64_t R, int c, const float *v, float *scores, float *nonlin,
                             int64_t ldn, void *stream);
 int xv_attention_softmax_f32(const float *scores, const int32_t *row_start, const int32_t *row_len, int nchunks, float *att,

@@ -797,6 +797,22 @@ def test_bad_arguments_fail_loudly(env):
     assert callb() == 0
     torch.cuda.synchronize()
     assert (dw.cpu().numpy() == 0).all() and (db.cpu().numpy() == 0).all()
+    # the pooling entry points refuse a row stride below the channel count (as xv_attention_pool_f32 does)
+    C = 8
+    h = torch.zeros((16, C), dtype=torch.float32, device=dev)
+    att = torch.ones(16, dtype=torch.float32, device=dev)
+    rs = torch.zeros(1, dtype=torch.int32, device=dev)
+    rl = torch.full((1,), 4, dtype=torch.int32, device=dev)
+    out = torch.full((1, 2 * C), float("nan"), dtype=torch.float32, device=dev)
+    pool = lambda ldh: lib.xv_stats_pool_f32(p(h), ldh, C, p(rs), p(rl), 1, 4, 512, 1e-5, p(out), None, None)
+    mom = lambda ldh: lib.xv_chunk_moments_f32(p(h), ldh, C, p(rs), p(rl), 1, 4, 512, p(out), None, None)
+    apool = lambda ldh: lib.xv_attention_pool_f32(p(h), ldh, C, p(att), p(rs), p(rl), 1, 4, 512, 1e-5, p(out), None, None)
+    for fn in (pool, mom, apool):
+        assert fn(C - 4) == BAD and fn(0) == BAD
+        torch.cuda.synchronize()
+        assert np.isnan(out.cpu().numpy()).all()                             # nothing was launched
+    for fn in (pool, mom, apool):
+        assert fn(C) == 0
 
 
 # ---- self-attentive pooling kernels (models.py:1036-1050) ----------------------------------------------------------------

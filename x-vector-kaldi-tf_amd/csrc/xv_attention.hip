@@ -120,12 +120,21 @@ __global__ __launch_bounds__(256) void attention_pool_kernel(const float *__rest
     const int b = blockIdx.z, sp = blockIdx.y;
     const int len = row_len[b];
     const int begin = sp * split_rows;
-    if (begin >= len) return;
-    const int n_rows = min(split_rows, len - begin);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int phase = lane >> 4;
     const int c = (blockIdx.x * 4 + wave) * 64 + (lane & 15) * 4;
     if (c >= C) return;
+    if (len <= 0) {              // an empty chunk has no moments: NaN (the split path: attention_pool_merge_kernel)
+        if (max_splits == 1 && phase == 0) {
+            const float nan = __builtin_nanf("");
+            float *o = out + (size_t)b * 2 * C;
+            *reinterpret_cast<f32x4 *>(o + c) = (f32x4){nan, nan, nan, nan};
+            *reinterpret_cast<f32x4 *>(o + C + c) = (f32x4){nan, nan, nan, nan};
+        }
+        return;
+    }
+    if (begin >= len) return;
+    const int n_rows = min(split_rows, len - begin);
     const size_t r0 = (size_t)row_start[b] + begin;
     const float *base = h + r0 * ldh + c;
     const float *wts = att + r0;
@@ -198,6 +207,11 @@ __global__ void attention_pool_merge_kernel(const double *__restrict__ partial, 
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     const int len = row_len[b];
+    if (len <= 0) {              // empty chunk: NaN, as the direct path
+        out[(size_t)b * 2 * C + c] = __builtin_nanf("");
+        out[(size_t)b * 2 * C + C + c] = __builtin_nanf("");
+        return;
+    }
     double s1 = 0.0, s2 = 0.0;
     for (int sp = 0; sp * split_rows < len; ++sp) {
         const double *pm = partial + ((size_t)b * max_splits + sp) * 2 * C;

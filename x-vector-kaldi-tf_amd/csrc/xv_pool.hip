@@ -41,12 +41,21 @@ __global__ __launch_bounds__(256) void stats_pool_kernel(const float *__restrict
     const int b = blockIdx.z, sp = blockIdx.y;
     const int len = row_len[b];
     const int begin = sp * split_rows;
-    if (begin >= len) return;
-    const int n_rows = min(split_rows, len - begin);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int phase = lane >> 4;
     const int c = (blockIdx.x * 4 + wave) * 64 + (lane & 15) * 4;
     if (c >= C) return;          // C % 4 == 0: whole float4 in or out (lanes of other phases agree)
+    if (len <= 0) {              // an empty chunk has no statistics: NaN (the split path: stats_pool_merge_kernel)
+        if (max_splits == 1 && phase == 0) {
+            const float nan = __builtin_nanf("");
+            float *o = out + (size_t)b * 2 * C;
+            *reinterpret_cast<f32x4 *>(o + c) = (f32x4){nan, nan, nan, nan};
+            *reinterpret_cast<f32x4 *>(o + C + c) = (f32x4){nan, nan, nan, nan};
+        }
+        return;
+    }
+    if (begin >= len) return;
+    const int n_rows = min(split_rows, len - begin);
     const float *base = h + ((size_t)row_start[b] + begin) * ldh + c;
 
     Stat4 s;
@@ -141,6 +150,11 @@ __global__ void stats_pool_merge_kernel(const float *__restrict__ partial, int C
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     const int len = row_len[b];
+    if (len <= 0) {              // empty chunk: NaN, as the direct path
+        out[(size_t)b * 2 * C + c] = __builtin_nanf("");
+        out[(size_t)b * 2 * C + C + c] = __builtin_nanf("");
+        return;
+    }
     float n = 0.f, mean = 0.f, m2 = 0.f;
     for (int sp = 0; sp * split_rows < len; ++sp) {
         const float m = (float)min(split_rows, len - sp * split_rows);
@@ -251,8 +265,8 @@ static int stats_pool_impl(const float *h, int64_t ldh, int c, const int32_t *ro
 {
     if (nchunks <= 0) return 0;
     if (!h || !row_start || !row_len || !out) return fail(XV_ERR_BAD_ARG, "stats_pool: NULL pointer");
-    if (c <= 0 || (c & 3) || (ldh & 3) || (((uintptr_t)h) & 15) || (((uintptr_t)out) & 15))
-        return fail(XV_ERR_BAD_ARG, "stats_pool: C, ldh must be multiples of 4 and h/out 16-byte aligned");
+    if (c <= 0 || (c & 3) || (ldh & 3) || ldh < c || (((uintptr_t)h) & 15) || (((uintptr_t)out) & 15))
+        return fail(XV_ERR_BAD_ARG, "stats_pool: C, ldh >= C must be multiples of 4 and h/out 16-byte aligned");
     if (split_rows <= 0 || max_len <= 0) return fail(XV_ERR_BAD_ARG, "stats_pool: split_rows/max_len must be > 0");
     const int max_splits = (max_len + split_rows - 1) / split_rows;
     if (max_splits > 1 && !workspace) return fail(XV_ERR_BAD_ARG, "stats_pool: workspace required for split chunks");
