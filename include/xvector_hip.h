@@ -339,7 +339,8 @@ int xv_chunk_moments_f32(const float *h, int64_t ldh, int c, const int32_t *row_
                          int max_len, int split_rows, float *out, void *workspace, void *stream);
 int xv_merge_moments_f32(const float *chunk_mean_var, const int32_t *row_len, int nchunks, int c, float *mean, float *var,
                          void *stream);
-/* y[r,:] = row_valid[r] ? x[r,:]*scale + shift : 0   (batch-norm with batch statistics folded by xv_fold_bn_f32). */
+/* y[r,:] = row_valid[r] ? x[r,:]*scale + shift : 0   (batch-norm with batch statistics folded by xv_fold_bn_f32).  x / y may be
+ * column slices of wider buffers: ldx >= c and ldy >= c, else XV_ERR_BAD_ARG. */
 int xv_rows_affine_f32(const float *x, int ldx, int64_t R, int c, const float *scale, const float *shift,
                        const uint8_t *row_valid, float *y, int ldy, void *stream);
 /* The same with a second copy of y in the bf16 split activation format (XV_FMT_SPLIT; y_split = row 0 of a buffer with the format's
@@ -364,13 +365,16 @@ int xv_wgrad_bf16x3(const float *x, int ldx, const float *dz, int lddz, int64_t 
 size_t xv_wgrad_bias_workspace_bytes(int64_t R, int cin, int cout, int K);
 int xv_wgrad_bias_bf16x3(const float *x, int ldx, const float *dz, int lddz, int64_t R, int cin, int cout, int K, int dilation,
                          float *dw, float *db, void *workspace, void *stream);
-/* sum_a[c] = sum_r a[r,c];  sum_ab[c] = sum_r a[r,c]*b[r,c]  (b, sum_ab may be NULL). */
+/* sum_a[c] = sum_r a[r,c];  sum_ab[c] = sum_r a[r,c]*b[r,c]  (b, sum_ab may be NULL).  lda >= c, and ldb >= c when b is given, else
+ * XV_ERR_BAD_ARG.  Rows are read 16 bytes at a time only when lda, ldb are multiples of 4 and a, b are 16-byte aligned; any 4-byte
+ * aligned pointer and any ld >= c are accepted. */
 size_t xv_col_sums_workspace_bytes(int64_t R, int c);
 int xv_col_sums_f32(const float *a, int lda, const float *b, int ldb, int64_t R, int c, float *sum_a, float *sum_ab,
                     void *workspace, void *stream);
 /* Batch-norm backward through the activation (closed form): given dh = dL/d(BN output), r = activation output, the
  * batch statistics and sum_dh = sum_r dh, sum_dh_r = sum_r dh*r, writes dgamma, dbeta and dz = dL/d(pre-activation)
- * (gap rows zero).  coef_ws: 3*c floats.  act_kind: NONE / RELU / LRELU(act_alpha). */
+ * (gap rows zero).  coef_ws: 3*c floats.  act_kind: NONE / RELU / LRELU(act_alpha).  dh, r and dz share the row stride ld >= c (else
+ * XV_ERR_BAD_ARG; the same for the _split and _parts forms below). */
 int xv_bn_act_backward_f32(const float *dh, const float *r, int ld, int64_t R, int c, const float *sum_dh,
                            const float *sum_dh_r, const float *mean, const float *var, const float *gamma, float eps,
                            float n_frames, int act_kind, float act_alpha, const uint8_t *row_valid, float *dgamma,
@@ -398,7 +402,10 @@ int xv_col_sums_merge_f32(const void *sums_workspace, int64_t R, int c, float *s
 /* Backward of [statistics pooling -> BN -> activation] of the LAST frame-level layer in two launches: the gradient that reaches
  * h = BN(r) comes from the pooling alone (local/tf/models.py:75-76), so the BN backward's column sums follow from per-chunk numbers
  * (pooled = [mu | sig], dpooled, chunk_moments = xv_chunk_moments_f32 of r: [mean | biased var] per chunk) and dh is formed on the
- * fly, never stored.  Writes dgamma, dbeta, dz (gap rows and rows outside every chunk zero) and optionally dz in the split format. */
+ * fly, never stored.  Writes dgamma, dbeta, dz (gap rows and rows outside every chunk zero) and optionally dz in the split format.
+ * ld >= c, else XV_ERR_BAD_ARG; at most 65535 chunks.  Every chunk is required to have row_len >= 1.  A chunk with row_len <= 0 is
+ * tolerated as follows: it adds nothing to dgamma, dbeta and the coefficients (its pooled row, NaN from xv_stats_pool_f32, is not
+ * read for them), it owns no frame, and the rows from its row_start up to the next chunk's are zeroed like gap rows. */
 int xv_pool_bn_act_backward_f32(const float *h, const float *r, int ld, int c, const int32_t *row_start, const int32_t *row_len,
                                 int nchunks, int64_t R, const float *pooled, const float *dpooled, const float *chunk_moments,
                                 const float *mean, const float *var, const float *gamma, float eps, float n_frames,
@@ -414,7 +421,9 @@ int xv_bn_small_forward_f32(const float *x, int ldx, int nrows, int c, const flo
 int xv_bn_small_backward_f32(const float *dh, const float *r, int ld, int nrows, int c, const float *mean, const float *var,
                              const float *gamma, float eps, int act_kind, float act_alpha, float *dgamma, float *dbeta, float *dz,
                              void *stream);
-/* Gradient of statistics pooling: dh[t,c] = dmu[c]/T + dsig[c]*(h[t,c]-mu[c])/(T*sig[c]); dh gap rows are zeroed. */
+/* Gradient of statistics pooling: dh[t,c] = dmu[c]/T + dsig[c]*(h[t,c]-mu[c])/(T*sig[c]); dh gap rows are zeroed (all R * ldh floats of
+ * dh are written).  ldh >= c and R > 0, else XV_ERR_BAD_ARG.  Every chunk is required to have row_len >= 1; a chunk with
+ * row_len <= 0 writes nothing (its rows stay zero). */
 int xv_pool_backward_f32(const float *h, int ldh, int c, const int32_t *row_start, const int32_t *row_len, int nchunks,
                          int64_t R, const float *pooled, const float *dpooled, float *dh, void *stream);
 /* tf.nn.softmax_cross_entropy_with_logits + reduce_mean + accuracy (local/tf/models.py:106-117):

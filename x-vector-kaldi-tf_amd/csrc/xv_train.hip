@@ -135,14 +135,14 @@ constexpr long CS_ROWS = 128;      // rows per split: R = 19.6k frames -> ~150 s
 
 // block = 4 waves; a wave covers 256 channels (float4 per lane) of one row per load; waves take interleaved rows
 __global__ __launch_bounds__(256) void col_sums_kernel(const float *__restrict__ a, const float *__restrict__ b, long R, int C,
-                                                       int lda, int ldb, long rows_per_split, double *__restrict__ part)
+                                                       int lda, int ldb, long rows_per_split, int aligned, double *__restrict__ part)
 {
     __shared__ double sa[4][256], sb[4][256];
     const int lane = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const int c = blockIdx.x * 256 + lane * 4;
     const long r0 = (long)blockIdx.y * rows_per_split, r1 = min(R, r0 + rows_per_split);
     double s[4] = {0.0, 0.0, 0.0, 0.0}, sab[4] = {0.0, 0.0, 0.0, 0.0};
-    const bool vec = c + 4 <= C && !(lda & 3) && !(ldb & 3);
+    const bool vec = c + 4 <= C && aligned;              // aligned: the host's test of lda, ldb and both base pointers
     if (c < C)
         for (long r = r0 + ty; r < r1; r += 4) {
             float av[4], bv[4] = {0.f, 0.f, 0.f, 0.f};
@@ -512,6 +512,7 @@ __global__ void pool_backward_kernel(const float *__restrict__ h, int ldh, int C
 {
     const int b = blockIdx.y;
     const int T = row_len[b];
+    if (T <= 0) return;                                     // an empty chunk owns no row (and (size_t)T * C must not wrap)
     const size_t base = (size_t)row_start[b];
     const float invT = 1.0f / (float)T;
     const float *mu = pooled + (size_t)b * 2 * C, *sig = mu + C;
@@ -536,7 +537,8 @@ __global__ void pool_backward_kernel(const float *__restrict__ h, int ldh, int C
 // 64 channels x CSM_GROUPS groups of chunks per workgroup, the group sums added in group order (as col_sums_merge_kernel: a thread
 // per channel walking all chunks alone was 37 us of dependent loads for a few kilobytes)
 __global__ __launch_bounds__(64 * CSM_GROUPS) void pool_bn_coeffs_kernel(const float *__restrict__ pooled, const float *__restrict__ dpooled,
-                                                                         const float *__restrict__ cm, int nchunks, const float *mean,
+                                                                         const float *__restrict__ cm, const int *__restrict__ row_len,
+                                                                         int nchunks, const float *mean,
                                                                          const float *var, const float *gamma, float eps, float n_frames,
                                                                          int C, float *dgamma, float *dbeta, float *coefA, float *coefB,
                                                                          float *coefC)
@@ -553,6 +555,7 @@ __global__ __launch_bounds__(64 * CSM_GROUPS) void pool_bn_coeffs_kernel(const f
     double db = 0.0, sdr = 0.0;
     if (c < C)
         for (int b = grp; b < nchunks; b += CSM_GROUPS) {
+            if (row_len[b] <= 0) continue;                  // an empty chunk has no frames: nothing in either sum (its pooled row is NaN)
             const size_t o = (size_t)b * 2 * C + c;
             const double dmu = dpooled[o], dsig = dpooled[o + C];
             db += dmu;
@@ -960,10 +963,12 @@ size_t xv_col_sums_workspace_bytes(int64_t R, int c) { return (size_t)((R + CS_R
 int xv_col_sums_f32(const float *a, int lda, const float *b, int ldb, int64_t R, int c, float *sum_a, float *sum_ab, void *workspace,
                     void *stream)
 {
-    if (!a || !sum_a || !workspace || R <= 0 || c <= 0 || (b && !sum_ab)) return fail(XV_ERR_BAD_ARG, "col_sums: bad argument");
+    if (!a || !sum_a || !workspace || R <= 0 || c <= 0 || (b && !sum_ab) || lda < c || (b && ldb < c))
+        return fail(XV_ERR_BAD_ARG, "col_sums: bad argument");
     const int splits = (int)((R + CS_ROWS - 1) / CS_ROWS);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(col_sums_kernel, dim3((c + 255) / 256, splits), dim3(256), 0, st, a, b, (long)R, c, lda, ldb, CS_ROWS,
+    const int aligned = !(lda & 3) && !(b && (ldb & 3)) && !(((uintptr_t)a | (uintptr_t)b) & 15);      // float4 loads of whole rows
+    hipLaunchKernelGGL(col_sums_kernel, dim3((c + 255) / 256, splits), dim3(256), 0, st, a, b, (long)R, c, lda, ldb, CS_ROWS, aligned,
                        (double *)workspace);
     int rc = launch_status("col_sums_kernel");
     if (rc) return rc;
@@ -1009,7 +1014,7 @@ int xv_rows_affine_f32(const float *x, int ldx, int64_t R, int c, const float *s
 int xv_rows_affine_split_f32(const float *x, int ldx, int64_t R, int c, const float *scale, const float *shift, const uint8_t *row_valid,
                              float *y, int ldy, void *y_split, void *stream)
 {
-    if (!x || !y || !scale || !shift || R <= 0 || c <= 0) return fail(XV_ERR_BAD_ARG, "rows_affine: bad argument");
+    if (!x || !y || !scale || !shift || R <= 0 || c <= 0 || ldx < c || ldy < c) return fail(XV_ERR_BAD_ARG, "rows_affine: bad argument");
     const bool vec = !(c & 3) && !(ldx & 3) && !(ldy & 3) && !(((uintptr_t)x | (uintptr_t)y) & 15);
     const dim3 grid((unsigned)((c + 1023) / 1024), (unsigned)(R < 4096 ? R : 4096));
     if (y_split) {
@@ -1059,7 +1064,7 @@ int xv_bn_act_backward_split_f32(const float *dh, const float *r, int ld, int64_
                                  float act_alpha, const uint8_t *row_valid, float *dgamma, float *dbeta, float *coef_ws, float *dz,
                                  void *dz_split, void *stream)
 {
-    if (!dh || !r || !sum_dh || !sum_dh_r || !mean || !var || !gamma || !dgamma || !dbeta || !coef_ws || !dz || R <= 0 || c <= 0)
+    if (!dh || !r || !sum_dh || !sum_dh_r || !mean || !var || !gamma || !dgamma || !dbeta || !coef_ws || !dz || R <= 0 || c <= 0 || ld < c)
         return fail(XV_ERR_BAD_ARG, "bn_act_backward: bad argument");
     if (act_kind == XV_ACT_PRELU) return fail(XV_ERR_UNSUPPORTED, "bn_act_backward: PReLU training is not implemented");
     hipStream_t st = (hipStream_t)stream;
@@ -1075,7 +1080,7 @@ int xv_bn_act_backward_parts_f32(const float *dh, const float *r, int ld, int64_
                                  const uint8_t *row_valid, float *dgamma, float *dbeta, float *coef_ws, float *dz, void *dz_split,
                                  void *stream)
 {
-    if (!dh || !r || !sums_workspace || !mean || !var || !gamma || !dgamma || !dbeta || !coef_ws || !dz || R <= 0 || c <= 0)
+    if (!dh || !r || !sums_workspace || !mean || !var || !gamma || !dgamma || !dbeta || !coef_ws || !dz || R <= 0 || c <= 0 || ld < c)
         return fail(XV_ERR_BAD_ARG, "bn_act_backward_parts: bad argument");
     if (act_kind == XV_ACT_PRELU) return fail(XV_ERR_UNSUPPORTED, "bn_act_backward: PReLU training is not implemented");
     hipStream_t st = (hipStream_t)stream;
@@ -1115,7 +1120,7 @@ int xv_pool_bn_act_backward_f32(const float *h, const float *r, int ld, int c, c
                                 float act_alpha, float *dgamma, float *dbeta, float *coef_ws, float *dz, void *dz_split, void *stream)
 {
     if (!h || !r || !row_start || !row_len || !pooled || !dpooled || !chunk_moments || !mean || !var || !gamma || !dgamma || !dbeta ||
-        !coef_ws || !dz || nchunks <= 0 || nchunks > 65535 || R <= 0 || c <= 0)
+        !coef_ws || !dz || nchunks <= 0 || nchunks > 65535 || R <= 0 || c <= 0 || ld < c)
         return fail(XV_ERR_BAD_ARG, "pool_bn_act_backward: bad argument");
     if (act_kind == XV_ACT_PRELU) return fail(XV_ERR_UNSUPPORTED, "pool_bn_act_backward: PReLU training is not implemented");
     if ((c & 3) || (ld & 3) || (((uintptr_t)h | (uintptr_t)r | (uintptr_t)dz | (uintptr_t)coef_ws | (uintptr_t)pooled | (uintptr_t)dpooled) & 15))
@@ -1123,7 +1128,8 @@ int xv_pool_bn_act_backward_f32(const float *h, const float *r, int ld, int c, c
     if (dz_split && ((c & 31) || (((uintptr_t)dz_split) & 15)))
         return fail(XV_ERR_UNSUPPORTED, "pool_bn_act_backward: the split copy needs c % 32 == 0");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(pool_bn_coeffs_kernel, dim3((c + 63) / 64), dim3(64 * CSM_GROUPS), 0, st, pooled, dpooled, chunk_moments, nchunks, mean, var, gamma,
+    hipLaunchKernelGGL(pool_bn_coeffs_kernel, dim3((c + 63) / 64), dim3(64 * CSM_GROUPS), 0, st, pooled, dpooled, chunk_moments, row_len, nchunks,
+                       mean, var, gamma,
                        eps, n_frames, c, dgamma, dbeta, coef_ws, coef_ws + c, coef_ws + 2 * c);
     int rc = launch_status("pool_bn_coeffs_kernel");
     if (rc) return rc;
@@ -1141,7 +1147,8 @@ int xv_pool_bn_act_backward_f32(const float *h, const float *r, int ld, int c, c
 int xv_pool_backward_f32(const float *h, int ldh, int c, const int32_t *row_start, const int32_t *row_len, int nchunks, int64_t R,
                          const float *pooled, const float *dpooled, float *dh, void *stream)
 {
-    if (!h || !row_start || !row_len || !pooled || !dpooled || !dh || nchunks <= 0 || c <= 0) return fail(XV_ERR_BAD_ARG, "pool_backward: bad argument");
+    if (!h || !row_start || !row_len || !pooled || !dpooled || !dh || nchunks <= 0 || c <= 0 || ldh < c || R <= 0)
+        return fail(XV_ERR_BAD_ARG, "pool_backward: bad argument");
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(dh, 0, (size_t)R * ldh * sizeof(float), st);      // gap rows carry no gradient
     if (e != hipSuccess) return fail((int)e, "pool_backward: memset failed");
