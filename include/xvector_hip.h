@@ -52,7 +52,7 @@ extern "C" {
 #define XV_ERR_BAD_ARG (-1)
 #define XV_ERR_UNSUPPORTED (-2)
 
-/* Library / ABI version (increments whenever an entry point is added or changed; currently 29). */
+/* Library / ABI version (increments whenever an entry point is added or changed; currently 31). */
 int xv_version(void);
 /* Thread-local description of the last non-zero return. */
 const char *xv_last_error(void);
@@ -578,6 +578,38 @@ int xv_topk_row_stats_f32(const float *scores, int64_t ld, int n_rows, int n_col
 int xv_moment_stats_f64(const float *x, int64_t ldx, int64_t n_rows, int dim, double *sum, double *outer, int64_t ld_outer,
                         void *workspace, size_t workspace_bytes, void *stream);
 size_t xv_moment_stats_workspace_bytes(int64_t n_rows, int dim);
+
+/* ---- clustering for PLDA adaptation (csrc/xv_cluster.hip) ---------------------------------------------------
+ * xv_ahc_average_f64  average-linkage agglomerative clustering of n items from their n x n similarity matrix (the PLDA scores
+ *   of the unlabelled in-domain vectors against themselves, xv_score_matrix_f32).  The semantics are fixed completely, so that
+ *   any implementation gives the same bits:
+ *   Input: the similarity of items i < j is (double)scores[i * ld + j].  Only the strict upper triangle is read: the diagonal, the
+ *     lower triangle and columns [n, ld) never are.
+ *   State: every cluster lives in the slot of its smallest member; size[c] is an integer; T[c, e] is the fp64 sum of the
+ *     similarities between the members of c and of e, and T[i, j] starts as the widened score.
+ *   Step: avg(c, e) = T[c, e] / (double)(size[c] * size[e]), the integer product formed in int64, the division one IEEE fp64
+ *     division.  Among the live pairs c < e the largest avg is taken, ties to the lexicographically smallest (c, e).  Stop if the
+ *     cluster count equals min_clusters or if !(avg >= threshold) (a threshold of -inf: down to min_clusters).  Otherwise
+ *     (merge_a, merge_b, merge_score)[m] = (c, e, avg); for every other live k, T[k, c] = T[c, k] = T[c, k] + T[e, k] (one fp64
+ *     addition, the operands in that order); then size[c] += size[e], and e dies.
+ *   Output (device memory): *n_merges = the number of merges; labels[i] = the slot of i's cluster (its smallest member).  Entries
+ *     [*n_merges, n - 1) of the three merge arrays are not written, nor is anything past labels[n).
+ *   Determinism: no floating-point atomics; each row's best partner is cached and re-scanned only when it can have changed, which
+ *     cannot change the answer because avg is a pure function of T and the sizes.  The bits depend on the values, n, threshold and
+ *     min_clusters only: not on ld, the stream, the workspace contents or what ran before.
+ *   The merges run in one workgroup: launches of up to 256 merges chained in stream order behind a device-side "done"
+ *     word; the call enqueues ceil((n - min_clusters) / 256) + 3 launches and does NOT synchronise the stream or read anything back.
+ *   n = 1 is valid (0 merges, label 0).  XV_ERR_BAD_ARG, with nothing launched: n < 1, ld < n, ld not a multiple of 4 or scores
+ *     not 16-byte aligned, min_clusters outside [1, n], a NaN threshold, a NULL or misaligned output, a workspace that is missing,
+ *     not 8-byte aligned or smaller than xv_ahc_average_workspace_bytes(n).  n > XV_AHC_MAX_N: XV_ERR_UNSUPPORTED.  For non-finite
+ *     scores the result is unspecified, but the call terminates and writes only inside its outputs.
+ * xv_ahc_average_workspace_bytes  the bytes of that workspace: the fp64 n x n state plus O(n) bookkeeping, 8 n^2 + 24 n + 64
+ *   (0 for an n xv_ahc_average_f64 refuses). */
+#define XV_AHC_MAX_N 32768
+int xv_ahc_average_f64(const float *scores, int64_t ld, int n, double threshold, int min_clusters, int32_t *merge_a,
+                       int32_t *merge_b, double *merge_score, int32_t *n_merges, int32_t *labels, void *workspace,
+                       size_t workspace_bytes, void *stream);
+size_t xv_ahc_average_workspace_bytes(int n);
 
 /* Stage 1 of the recipe: MFCC features and the energy VAD (compute-mfcc-feats / compute-vad; csrc/xv_mfcc.hip).
  * xv_mfcc_f32  MFCC rows of n_utts utterances in one launch.  samples: every utterance's samples back to back, int16

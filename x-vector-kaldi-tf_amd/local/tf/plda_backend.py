@@ -15,6 +15,12 @@
                plda_adapt (stage 10's model); with --lda transform.mat the unlabelled in-domain vectors first go through stage
                8's chain on the GPU, as in compute-plda, and their fp64 moments are taken there on the f64 MFMA without the
                rows leaving the device
+  cluster      [--lda transform.mat] [--threshold t] [--num-clusters n] [--prefix c] plda <vectors> utt2cluster: clustering-based
+               adaptation, the step Kaldi has no binary for.  The PLDA scores of the unlabelled in-domain vectors
+               against themselves and their average-linkage agglomerative clustering both run on the GPU; with --lda the
+               vectors first go through stage 8's chain there, as in adapt-plda.  Writes one ``utt cluster`` line per vector.
+               Turn utt2cluster into a spk2utt, fit an in-domain model with compute-plda --lda, mix it with interpolate-plda
+  interpolate-plda   [--alpha a] plda_out plda_in plda: (1 - a) plda_out + a plda_in on the models' covariances and means (host)
   compute-eer  compute-eer <file of "score target|nontarget" lines, or ->   (prints the EER in percent)
 
 Vector tables are ``scp:<file>`` or ``ark:<file>`` (options before the colon, e.g. ``ark,s,cs:``, are accepted and ignored).
@@ -156,6 +162,56 @@ def cmd_adapt_plda(args):
     backend.write_plda(args.plda_out, out, binary=args.binary)
 
 
+def cmd_cluster(args):
+    from xvector_amd import backend, hiplib
+    if np.isnan(args.threshold):
+        raise SystemExit("--threshold must be a number, got %r" % args.threshold)
+    if args.num_clusters is not None and args.num_clusters < 1:
+        raise SystemExit("--num-clusters must be at least 1, got %d" % args.num_clusters)
+    hiplib.require_gpu()                                 # no CPU fallback: fail before reading anything
+    plda = backend.read_plda(args.plda)
+    vectors = read_vectors(args.vectors)
+    if not vectors:
+        raise SystemExit("no vectors in %s: nothing to cluster, no utt2cluster written" % args.vectors)
+    keys = list(vectors)
+    x = _stack(vectors, keys)
+    n = len(keys)
+    t = backend.read_transform(args.lda) if args.lda else None
+    if t is not None and t.shape[1] not in (x.shape[1], x.shape[1] + 1):
+        raise SystemExit("%s has %d columns, the vectors have dimension %d" % (args.lda, t.shape[1], x.shape[1]))
+    dim = x.shape[1] if t is None else t.shape[0]
+    if dim != plda.dim:
+        raise SystemExit("the vectors have dimension %d%s, the PLDA %d: no utt2cluster written" %
+                         (dim, " after the LDA" if t is not None else "", plda.dim))
+    if n > hiplib.AHC_MAX_N:
+        raise SystemExit("%d vectors: the clustering kernel takes at most %d" % (n, hiplib.AHC_MAX_N))
+    if args.num_clusters is not None and args.num_clusters > n:
+        raise SystemExit("--num-clusters %d exceeds the number of vectors %d" % (args.num_clusters, n))
+    # stage 8's chain: subtract the set's own mean, transform-vec, ivector-normalize-length -- on the device
+    mean = x.astype(np.float64).mean(axis=0).astype(np.float32) if t is not None else None
+    try:
+        labels, _ = backend.cluster_vectors(x, plda, mean=mean, transform=t, threshold=args.threshold, num_clusters=args.num_clusters)
+    except ValueError as e:
+        raise SystemExit("%s: no utt2cluster written" % e)
+    distinct, rank, counts = np.unique(labels, return_inverse=True, return_counts=True)
+    width = len(str(n))
+    with open(args.utt2cluster, "wt") as f:
+        f.write("".join("%s %s%0*d\n" % (k, args.prefix, width, r + 1) for k, r in zip(keys, rank.tolist())))
+    logger.info("Clustered %d vectors of dimension %d into %d clusters (%d with a single vector)" %
+                (n, dim, len(distinct), int((counts == 1).sum())))
+
+
+def cmd_interpolate_plda(args):
+    from xvector_amd import backend
+    if not (np.isfinite(args.alpha) and 0.0 <= args.alpha <= 1.0):
+        raise SystemExit("--alpha must be in [0, 1], got %r" % args.alpha)
+    a, b = backend.read_plda(args.plda_out), backend.read_plda(args.plda_in)
+    if a.dim != b.dim:
+        raise SystemExit("the models have dimensions %d and %d: no model written" % (a.dim, b.dim))
+    backend.write_plda(args.plda, backend.interpolate_plda(a, b, args.alpha), binary=args.binary)
+    logger.info("Wrote (1 - %g) %s + %g %s, dimension %d" % (args.alpha, args.plda_out, args.alpha, args.plda_in, a.dim))
+
+
 def cmd_score(args):
     from xvector_amd import backend, hiplib
     if args.cohort_top_n < 2:
@@ -275,6 +331,18 @@ def main(argv=None):
     p.add_argument("--binary", type=lambda s: s.lower() in ("true", "1"), default=True)
     p.add_argument("plda_in"); p.add_argument("vectors"); p.add_argument("plda_out")
     p.set_defaults(fn=cmd_adapt_plda)
+    p = sub.add_parser("cluster", help="cluster unlabelled vectors by PLDA score (average linkage)")
+    p.add_argument("--lda", help="transform.mat: apply stage 8's chain to the vectors first (on the GPU)")
+    p.add_argument("--threshold", type=float, default=0.0, help="stop when no pair of clusters has an average score this large")
+    p.add_argument("--num-clusters", type=int, help="stop at this many clusters at the latest")
+    p.add_argument("--prefix", default="c", help="cluster names are <prefix><rank>")
+    p.add_argument("plda"); p.add_argument("vectors"); p.add_argument("utt2cluster")
+    p.set_defaults(fn=cmd_cluster)
+    p = sub.add_parser("interpolate-plda", help="a PLDA between two")
+    p.add_argument("--alpha", type=float, default=0.5, help="weight of plda_in, in [0, 1]")
+    p.add_argument("--binary", type=lambda s: s.lower() in ("true", "1"), default=True)
+    p.add_argument("plda_out"); p.add_argument("plda_in"); p.add_argument("plda")
+    p.set_defaults(fn=cmd_interpolate_plda)
     p = sub.add_parser("score", help="ivector-plda-scoring")
     p.add_argument("--num-utts", help="ark:num_utts.ark (enrolment utterance counts)")
     p.add_argument("--mean", help="mean.vec: subtract it first (ivector-subtract-global-mean)")

@@ -4,6 +4,9 @@
   fit_plda       ivector-compute-plda --num-em-iters n  -> Plda (mean, transform, psi)   (host, fp64)
   moment_stats   the first and second moment of vectors on the device, in fp64 on the f64 MFMA (xv_moment_stats_f64)
   adapt_plda     ivector-adapt-plda: unsupervised adaptation of a Plda to those moments   (host, fp64)
+  cluster_vectors / ahc   clustering-based adaptation: the N x N PLDA score matrix of unlabelled vectors and its
+                 average-linkage agglomerative clustering, both on the device (xv_score_matrix_f32, xv_ahc_average_f64)
+  interpolate_plda   a Plda between two (the out-of-domain model and the one fitted on the clusters)   (host, fp64)
   read_plda / write_plda, read_transform / write_transform   Kaldi's <Plda> object and transform.mat, binary and text
   prepare        ivector-subtract-global-mean | transform-vec | ivector-normalize-length | Plda::TransformIvector on the GPU
                  (xv_backend_prepare_f32)
@@ -410,6 +413,123 @@ def moment_stats(x_rows, dim=None, device="cuda:0"):
         total_s += s_d.cpu().numpy()
         total_o += o_d.cpu().numpy()
     return n, total_s, total_o
+
+
+def interpolate_plda(plda_out, plda_in, alpha):
+    """(1 - alpha) * plda_out + alpha * plda_in, mixed where the models are linear: with P the transform, the between- and
+    within-speaker covariances B = P^-1 diag(psi) P^-T and W = P^-1 P^-T of both models and their means are mixed, and the mix
+    is diagonalised again (plda_from_covariances).  -> Plda."""
+    if not (np.isfinite(alpha) and 0.0 <= alpha <= 1.0):
+        raise ValueError("interpolate_plda: alpha must be in [0, 1], got %r" % (alpha,))
+    if plda_out.dim != plda_in.dim:
+        raise ValueError("interpolate_plda: the models have dimensions %d and %d" % (plda_out.dim, plda_in.dim))
+    parts = []
+    for p in (plda_out, plda_in):
+        inv = np.linalg.inv(p.transform)
+        parts.append((p.mean, (inv * p.psi) @ inv.T, inv @ inv.T))
+    mean, B, W = ((1.0 - alpha) * o + alpha * i for o, i in zip(*parts))
+    return plda_from_covariances(mean, B, W)
+
+
+# ------------------------------------------------------------------------------------------------
+# clustering of unlabelled vectors by PLDA score (DESIGN.md §8.9)
+# ------------------------------------------------------------------------------------------------
+AHC_MAX_BYTES = 12 << 30           # the fp64 state of ahc is at most this large by default (N = 32768 needs 8 GiB)
+_FINITE_CHECK_ELEMS = 1 << 26      # elements per slice of the device-side check of the upper triangle
+
+
+def labels_from_merges(n, a, b):
+    """labels[i] (int32) = the slot of i's cluster after the merges (a[m], b[m]) in order: b[m] joins a[m] < b[m], and a cluster
+    lives in the slot of its smallest member.  The host restatement of xv_ahc_average_f64's labels, for callers that cut the
+    dendrogram elsewhere."""
+    a = np.asarray(a, dtype=np.int64)
+    b = np.asarray(b, dtype=np.int64)
+    if a.shape != b.shape or a.ndim != 1:
+        raise ValueError("labels_from_merges: a and b must be 1-D and of the same length")
+    parent = np.arange(n, dtype=np.int64)
+    for c, e in zip(a.tolist(), b.tolist()):
+        if not (0 <= c < e < n) or parent[c] != c or parent[e] != e:
+            raise ValueError("labels_from_merges: merge (%d, %d) does not join two live slots c < e" % (c, e))
+        parent[e] = c
+    for i in range(n):                                       # parents only decrease: parent[parent[i]] is final when i is reached
+        parent[i] = parent[parent[i]]
+    return parent.astype(np.int32)
+
+
+def ahc(scores, threshold=0.0, num_clusters=None, max_bytes=AHC_MAX_BYTES):
+    """Average-linkage agglomerative clustering of scores[N, N] (a float32 device tensor; only the strict upper triangle is
+    used) on the device (xv_ahc_average_f64): merge the pair of clusters with the largest average score, ties to the
+    lexicographically smallest pair, until no average reaches ``threshold``.  num_clusters given: stop at that many clusters at
+    the latest (threshold None: at exactly that many).  -> (labels int32[N], (a int32[M], b int32[M], score float64[M])) as
+    NumPy: labels[i] is the smallest member of i's cluster, merge m joined b[m] into a[m] at average score[m]."""
+    import torch
+    hiplib.require_gpu()
+    if not (isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dim() == 2 and scores.shape[0] == scores.shape[1]):
+        raise ValueError("ahc: scores must be a device tensor [N, N]")
+    n = int(scores.shape[0])
+    if n < 1:
+        raise ValueError("ahc: no items")
+    if n > hiplib.AHC_MAX_N:
+        raise ValueError("ahc: %d items exceed %d, the limit of xv_ahc_average_f64" % (n, hiplib.AHC_MAX_N))
+    if threshold is None:
+        if num_clusters is None:
+            raise ValueError("ahc: threshold None needs num_clusters")
+        threshold = -np.inf
+    threshold = float(threshold)
+    if np.isnan(threshold):
+        raise ValueError("ahc: the threshold is NaN")
+    min_clusters = 1 if num_clusters is None else int(num_clusters)
+    if not 1 <= min_clusters <= n:
+        raise ValueError("ahc: num_clusters %d must be in 1..%d" % (min_clusters, n))
+    need = hiplib.ahc_average_workspace_bytes(n)
+    if need > max_bytes:
+        raise ValueError("ahc: %d items need a workspace of %d bytes, more than max_bytes = %d" % (n, need, max_bytes))
+    scores = scores.to(torch.float32)
+    if scores.stride(1) != 1 or scores.stride(0) % 4 or scores.data_ptr() % 16:
+        scores = torch.nn.functional.pad(scores, (0, -n % 4)).contiguous()[:, :n]
+    dev = scores.device
+    rows = max(1, _FINITE_CHECK_ELEMS // n)
+    col = torch.arange(n, device=dev)
+    for i0 in range(0, n - 1, rows):
+        blk = scores[i0:i0 + rows]
+        lower = col[None, :] <= torch.arange(i0, i0 + blk.shape[0], device=dev)[:, None]
+        if not bool((torch.isfinite(blk) | lower).all()):
+            raise ValueError("ahc: the upper triangle of the score matrix holds a value that is not finite")
+    with torch.cuda.device(dev):
+        m_a = torch.empty(max(n - 1, 1), dtype=torch.int32, device=dev)
+        m_b = torch.empty_like(m_a)
+        m_s = torch.empty(max(n - 1, 1), dtype=torch.float64, device=dev)
+        cnt = torch.empty(1, dtype=torch.int32, device=dev)
+        lab = torch.empty(n, dtype=torch.int32, device=dev)
+        hiplib.ahc_average(scores, threshold, min_clusters, m_a, m_b, m_s, cnt, lab)
+        m = int(cnt.cpu()[0])
+    return lab.cpu().numpy(), (m_a[:m].cpu().numpy(), m_b[:m].cpu().numpy(), m_s[:m].cpu().numpy())
+
+
+def score_matrix_self(x, plda, mean=None, transform=None, device="cuda:0"):
+    """S[N, ld] on the device, ld = N rounded up to a multiple of 4: S[i, j] = the PLDA LLR of vector i as a one-utterance
+    enrolment against vector j as a test (the pair of prepare calls of the test-side AS-norm statistics)."""
+    import torch
+    ln = transform is not None
+    n = len(x)
+    E, r = prepare(x, hiplib.SIDE_ENROL, np.ones(n, np.int32), mean, transform, plda, ln, device)
+    T, _ = prepare(x, hiplib.SIDE_TEST, None, mean, transform, plda, ln, device)
+    s = torch.empty((n, (n + 3) // 4 * 4), dtype=torch.float32, device=device)
+    hiplib.score_matrix(E, T, r, s)
+    return s
+
+
+def cluster_vectors(x, plda, mean=None, transform=None, threshold=0.0, num_clusters=None, device="cuda:0"):
+    """Cluster the raw vectors x[N, D] by PLDA score: mean / transform run the stage-9 chain on the device first (None: the vectors
+    are used as they are), the N x N score matrix stays there and goes through ``ahc``.  -> (labels, merges) as ``ahc``."""
+    hiplib.require_gpu()
+    n = len(x)
+    if n < 1:
+        raise ValueError("cluster_vectors: no vectors")
+    if n > hiplib.AHC_MAX_N:
+        raise ValueError("cluster_vectors: %d vectors exceed %d, the limit of xv_ahc_average_f64" % (n, hiplib.AHC_MAX_N))
+    s = score_matrix_self(x, plda, mean, transform, device)
+    return ahc(s[:, :n], threshold, num_clusters)
 
 
 DENSE_MAX_BYTES = 1 << 30          # the dense score matrix of one trial list is at most this large

@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -121,6 +121,9 @@ _SIGNATURES = {
     # moments for PLDA adaptation
     "xv_moment_stats_f64": (_ci, [_vp, _i64, _i64, _ci, _vp, _vp, _i64, _vp, _sz, _vp]),
     "xv_moment_stats_workspace_bytes": (_sz, [_i64, _ci]),
+    # clustering for PLDA adaptation
+    "xv_ahc_average_f64": (_ci, [_vp, _i64, _ci, ctypes.c_double, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "xv_ahc_average_workspace_bytes": (_sz, [_ci]),
     "xv_mfcc_f32": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _ci, _i64, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _ci, _vp, _ci, _ci, _ci, _ci,
                           _cf, _cf, _ci, _ci, _ci, _cf, _vp, _i64, _vp, _i64, _vp]),
     "xv_vad_energy_f32": (_ci, [_vp, _i64, _vp, _vp, _ci, _cf, _cf, _ci, _cf, _vp, _vp]),
@@ -149,6 +152,7 @@ BACKEND_KSTEP = 8
 SIDE_PLAIN, SIDE_ENROL, SIDE_TEST, SIDE_COSINE = 0, 1, 2, 3
 MOMENT_SLAB = 2048                # XV_MOMENT_SLAB: rows per partial of xv_moment_stats_f64
 MOMENT_DIM_MAX = 256
+AHC_MAX_N = 32768                  # XV_AHC_MAX_N: items of one xv_ahc_average_f64 call
 
 _lib = None
 
@@ -1282,6 +1286,36 @@ def moment_stats(x, sum, outer, dim=None, workspace=None):
         workspace = _ws(lib.xv_moment_stats_workspace_bytes(n_rows, dim), x.device)
     _check(lib.xv_moment_stats_f64(_ptr(x), x.stride(0), n_rows, dim, _ptr(sum), _ptr(outer), outer.stride(0), _ptr(workspace),
                                    workspace.numel() * workspace.element_size(), _stream()), "xv_moment_stats_f64")
+
+
+def ahc_average_workspace_bytes(n):
+    return int(load().xv_ahc_average_workspace_bytes(int(n)))
+
+
+def ahc_average(scores, threshold, min_clusters, merge_a, merge_b, merge_score, n_merges, labels, workspace=None):
+    """Average-linkage agglomerative clustering of the n items of scores[n, n] (xv_ahc_average_f64; see include/xvector_hip.h):
+    only the strict upper triangle is read.  scores may be a slice of a wider buffer (its row stride is passed as ld, a multiple
+    of 4).  merge_a, merge_b: int32 [>= n - 1]; merge_score: float64 [>= n - 1]; n_merges: int32 [1]; labels: int32 [>= n], all
+    on the device and written there: nothing is read back and the stream is not synchronised.  workspace: a device buffer of
+    ahc_average_workspace_bytes(n) bytes (None: allocated here)."""
+    import math
+    import torch
+    lib = require_gpu()
+    assert scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and scores.stride(1) == 1
+    n = scores.shape[0]
+    assert scores.shape[1] == n and 1 <= n <= AHC_MAX_N, "scores must be [n, n], 1 <= n <= %d" % AHC_MAX_N
+    assert scores.stride(0) >= n and scores.stride(0) % 4 == 0 and scores.data_ptr() % 16 == 0
+    assert 1 <= int(min_clusters) <= n and not math.isnan(float(threshold))
+    for t, m in ((merge_a, n - 1), (merge_b, n - 1), (n_merges, 1), (labels, n)):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= m
+    assert merge_score.is_cuda and merge_score.dtype == torch.float64 and merge_score.is_contiguous() and merge_score.numel() >= n - 1
+    need = lib.xv_ahc_average_workspace_bytes(n)
+    if workspace is None:
+        workspace = _ws(need, scores.device)
+    assert workspace.is_cuda and workspace.numel() * workspace.element_size() >= need, "ahc workspace too small"
+    _check(lib.xv_ahc_average_f64(_ptr(scores), scores.stride(0), n, float(threshold), int(min_clusters), _ptr(merge_a), _ptr(merge_b),
+                                  _ptr(merge_score), _ptr(n_merges), _ptr(labels), _ptr(workspace),
+                                  workspace.numel() * workspace.element_size(), _stream()), "xv_ahc_average_f64")
 
 
 def mfcc(samples, utt_offset, utt_samples, utt_row0, utt_key, total_rows, tables, opts, feats, logmel=None):
