@@ -15,6 +15,7 @@ import pytest
 
 import arith_emul as em
 import elementwise_data as ed
+from pair_data import _block_refs, _check_blocks  # noqa: F401  (shared with tests/test_gpu_pair_elementwise.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -234,45 +235,6 @@ def test_exact_on_integer_data(env, name, form, cin, cout, K, dil, act, xfmt, fm
         ref = _exact_ref(oracle, m, w, b, scale, shift, act, alpha, dil, 2048)
         bad = np.argwhere(y[s:s + n] != ref)
         assert bad.size == 0, (name, n, bad[:5].tolist())
-
-
-def _block_refs(layout, y_full, cout):
-    """Per 8-row block of the exact y: fp64 (mean, M2) of the valid rows, |mean - y0| and s2 = sum (y - y0)^2 (y0 = the block's
-    first row, valid whenever any row is), and the number of valid rows."""
-    valid = layout.row_valid().astype(bool)
-    R = len(valid)
-    nb = (R + 7) // 8
-    mean, m2, tmag, s2 = (np.zeros((nb, cout)) for _ in range(4))
-    cnt = np.zeros(nb, int)
-    for k in range(nb):
-        rows = np.arange(8 * k, min(8 * k + 8, R))
-        rows = rows[valid[rows]]
-        cnt[k] = len(rows)
-        if len(rows):
-            assert rows[0] == 8 * k
-            v = y_full[rows]
-            mean[k] = v.mean(0)
-            m2[k] = ((v - mean[k]) ** 2).sum(0)
-            tmag[k] = np.abs(mean[k] - v[0])
-            s2[k] = ((v - v[0]) ** 2).sum(0)
-    return mean, m2, tmag, s2, cnt
-
-
-def _check_blocks(blk, layout, y_full, cout, name):
-    """Blocks of 1, 2, 4 or 8 valid rows: (mean, M2) exact.  Others: within 4 ulp of the fp64 statistics, the ulp taken where the
-    kernels round.  They shift by the block's first row y0 (s1, s2 = sums of d = y - y0, d^2: exact on this data), then
-    t = s1 * fl(1/n), mean = y0 + t, M2 = fma(-t, s1, s2): the mean is off by <= 1.5 ulp(max(|t|, |mean|)), M2 by |s1| ulp(t) +
-    0.5 ulp(M2) <= 2.5 ulp(s2) (s1 t <= s2 by Cauchy-Schwarz) -- ulp(s2), not ulp(M2), since s2 - s1^2 / n cancels."""
-    mean, m2, tmag, s2, cnt = _block_refs(layout, y_full, cout)
-    live = cnt > 0
-    exact = np.isin(cnt, (1, 2, 4, 8))
-    got_m, got_2 = blk[:len(cnt), 0].astype(np.float64), blk[:len(cnt), 1].astype(np.float64)
-    assert np.isfinite(got_m[live]).all() and np.isfinite(got_2[live]).all()
-    assert np.array_equal(got_m[exact], mean[exact]) and np.array_equal(got_2[exact], m2[exact]), name
-    o = live & ~exact
-    ulp = lambda v: np.spacing(np.abs(v).astype(np.float32)).astype(np.float64)
-    assert (np.abs(got_m[o] - mean[o]) <= 4 * ulp(np.maximum(tmag[o], np.abs(mean[o])))).all(), name
-    assert (np.abs(got_2[o] - m2[o]) <= 4 * ulp(s2[o])).all(), name
 
 
 POOL_CASES = [

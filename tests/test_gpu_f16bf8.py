@@ -330,7 +330,8 @@ def test_f16bf8_bad_arguments_fail_loudly(env):
 def test_tdnn_pair_pool_f16bf8_matches_oracle(env, cin, cout, act, lens):
     """xv_tdnn_pair_pool_f16bf8 (two K = 1 layers, the intermediate split over a pair of waves and kept in registers, pooling
     block statistics) + xv_stats_pool_blocks_f32 == statistics pooling of layer(layer(x)) in the fp64 oracle; the block
-    statistics agree with the two-launch f16bf8 path; a chunk's result does not depend on its batch neighbours."""
+    statistics agree with the two-launch f16bf8 path; a chunk's result does not depend on its batch neighbours.  The element-level
+    guarantees (exact answers and per-block bounds on data with live low planes) live in tests/test_gpu_pair_elementwise.py."""
     torch, hiplib, engine, oracle, dev = env["torch"], env["hiplib"], env["engine"], env["oracle"], env["dev"]
     cmid = 512
     assert hiplib.pair8_supported(cin, cmid, cout) and not hiplib.pair8_supported(cin, 256, cout) and not hiplib.pair8_supported(40, cmid, cout)
