@@ -531,8 +531,14 @@ int xv_cmn_sliding_scatter_f32(const float *x, int ldx, int feat_dim, const int3
  *     side XV_SIDE_PLAIN   out = z (K = dim)            XV_SIDE_ENROL  out = enrolment row (K = 2 dim), r written
  *          XV_SIDE_TEST    out = test row (K = 2 dim)   XV_SIDE_COSINE out = z / |z| (K = dim)
  *   Columns [K, ldo) are written with zeros: ldo is the operand width Kpad of the scorers, a multiple of XV_BACKEND_KSTEP.
- *   r (may be NULL) receives the row's constant (0 except on the enrolment side).  ENROL / TEST need the PLDA.
- *   D <= 2048 and dim <= 256, else XV_ERR_UNSUPPORTED.
+ *   r (may be NULL) receives the row's constant: it is WRITTEN on every side, as exactly 0 on the sides that have none
+ *   (PLAIN, TEST, COSINE).  ENROL / TEST need the PLDA.
+ *   Arithmetic the tests rely on: both products (lda (x - mean) and P (y - m)) are fmaf chains per output element, k ascending
+ *   from 0 with a zero start, one fp32 rounding of x - mean (y - m) in front and lda_offset added after the chain; without an
+ *   lda, y = x - mean is that one subtraction.  A zero vector stays exactly zero through either length norm and the cosine
+ *   packing (its scale is taken as 1: no NaN).  The output bits do not depend on ldx, ld_lda, ldo or the other rows.
+ *   D <= 2048 and dim <= 256, else XV_ERR_UNSUPPORTED; ld_lda >= D, dim == D without an lda, ldo >= K and a multiple of
+ *   XV_BACKEND_KSTEP, all three PLDA arrays or none, else XV_ERR_BAD_ARG.  A refused call launches nothing.
  * xv_score_matrix_f32  scores[e, t] (ld_scores) = sum_{k < kpad} E[e, k] T[t, k] + r[e]   (r NULL: + 0) for every
  *   e < n_enrol, t < n_test, on the exact-fp32 MFMA.  Fixed summation order: one fp32 accumulator per score, k ascending from 0,
  *   no split-K, r added after the dot product.  E, T: row stride ldk (a multiple of 4 floats, 16-byte aligned), kpad a multiple

@@ -235,6 +235,15 @@ def _f32(t, name):
     return t
 
 
+def _f32_rows(t, name):
+    """A 2-D cuda float32 tensor whose rows are dense (stride(1) == 1): a row or column slice of a wider buffer passes, and its
+    stride(0) goes to the kernel as the leading dimension."""
+    import torch
+    assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1], \
+        "%s must be a 2-D cuda float32 tensor with dense rows" % name
+    return t
+
+
 # ------------------------------------------------------------------------------------------------
 # thin wrappers over the ABI, operating on torch-ROCm tensors (device memory + stream plumbing only)
 # ------------------------------------------------------------------------------------------------
@@ -1197,10 +1206,11 @@ def egs_chunks(x, utt_start, utt_len, voiced_count, voiced_row, table, voiced_co
 def backend_prepare(x, out, side, num_utts=None, mean=None, lda=None, lda_offset=None, length_norm=True, plda_transform=None,
                     plda_mean=None, plda_psi=None, r=None):
     """Operand rows of the scorers from raw vectors x[N, D] (see include/xvector_hip.h): mean subtraction, LDA, length norm,
-    PLDA transform and length norm, packed for ``side`` into out[N, Kpad] (zeros past K); r[N] the per-row constant."""
+    PLDA transform and length norm, packed for ``side`` into out[N, Kpad] (zeros past K); r[N] the per-row constant.  x and lda may
+    be slices of wider buffers (dense rows; the row stride is passed as ldx / ld_lda)."""
     import torch
     lib = require_gpu()
-    _f32(x, "x"); _f32(out, "out")
+    _f32_rows(x, "x"); _f32(out, "out")
     n_rows, dim_in = x.shape
     dim = lda.shape[0] if lda is not None else dim_in
     assert out.shape[0] >= n_rows and out.shape[1] == out.stride(0)
@@ -1209,7 +1219,7 @@ def backend_prepare(x, out, side, num_utts=None, mean=None, lda=None, lda_offset
         if t is not None:
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape, shape
     if lda is not None:
-        _f32(lda, "lda"); assert lda.shape[1] == dim_in
+        _f32_rows(lda, "lda"); assert lda.shape[1] == dim_in
     if num_utts is not None:
         assert num_utts.is_cuda and num_utts.dtype == torch.int32 and num_utts.is_contiguous() and num_utts.numel() >= n_rows
     _check(lib.xv_backend_prepare_f32(_ptr(x), x.stride(0), n_rows, dim_in, _ptr(num_utts), _ptr(mean), _ptr(lda),
@@ -1219,10 +1229,11 @@ def backend_prepare(x, out, side, num_utts=None, mean=None, lda=None, lda_offset
 
 
 def score_matrix(e, t, r, out):
-    """out[Ne, Nt] = e[Ne, Kpad] t[Nt, Kpad]^T + r[Ne] (r may be None), fixed summation order (k ascending)."""
+    """out[Ne, Nt] = e[Ne, Kpad] t[Nt, Kpad]^T + r[Ne] (r may be None), fixed summation order (k ascending).  e and t may be
+    slices of wider buffers with one common row stride, passed as ldk (a multiple of 4, bases 16-byte aligned)."""
     import torch
     lib = require_gpu()
-    _f32(e, "e"); _f32(t, "t"); _f32(out, "out")
+    _f32_rows(e, "e"); _f32_rows(t, "t"); _f32(out, "out")
     assert e.shape[1] == t.shape[1] and e.stride(0) == t.stride(0) and out.shape[0] >= e.shape[0] and out.shape[1] >= t.shape[0]
     if r is not None:
         assert r.is_cuda and r.dtype == torch.float32 and r.is_contiguous() and r.numel() >= e.shape[0]
@@ -1232,10 +1243,10 @@ def score_matrix(e, t, r, out):
 
 def score_pairs(e, t, r, e_idx, t_idx, out):
     """out[i] = e[e_idx[i]] . t[t_idx[i]] + r[e_idx[i]]: bit-identical to the cell of score_matrix.  The kernel reads the rows the
-    indices name, so their range is checked here first."""
+    indices name, so their range is checked here first.  e and t may be slices of wider buffers, as for score_matrix."""
     import torch
     lib = require_gpu()
-    _f32(e, "e"); _f32(t, "t")
+    _f32_rows(e, "e"); _f32_rows(t, "t")
     assert e.shape[1] == t.shape[1] and e.stride(0) == t.stride(0)
     for ix in (e_idx, t_idx):
         assert ix.is_cuda and ix.dtype == torch.int32 and ix.is_contiguous()
