@@ -215,6 +215,15 @@ class _Layer(dict):
             return self["wp"]
         raise KeyError(key)
 
+    def ep(self, act):
+        """(bias, scale, shift, act, alpha): the epilogue arguments every layer wrapper of hiplib takes in this order."""
+        return self["bias"], self["scale"], self["shift"], act, self["alpha"]
+
+    @property
+    def pp(self):
+        """(bias, scale, shift, alpha): this layer's half of the arguments of the pair kernels."""
+        return self["bias"], self["scale"], self["shift"], self["alpha"]
+
 
 class DeviceModel(object):
     """Weights of one model directory resident in HBM in kernel layout, plus reusable activation
@@ -324,7 +333,7 @@ class DeviceModel(object):
                 wpad[:, :self.feat_dim] = w0
                 self.first = hiplib.pack_first_bf16x3(self._dev(wpad))
             assert not (first_kernel and self.first is None), "first_kernel=True but the topology / precision does not allow it"
-            self.pair = None
+            self.pair = self.pair8 = None
             if (pair_kernel is None or pair_kernel) and self.fused_pool and precision == "bf16x3" and len(self.layers) >= 3:
                 La, Lb = self.layers[-2], self.layers[-1]
                 if La["K"] == 1 and Lb["K"] == 1 and hiplib.pair_supported(La["cin"], La["cout"], Lb["cout"]):
@@ -332,14 +341,9 @@ class DeviceModel(object):
                     wa = self._wdev(weights, "frame_level_info_layer-%d/w:0" % (n - 2))[0]
                     wb = self._wdev(weights, "frame_level_info_layer-%d/w:0" % (n - 1))[0]
                     self.pair = hiplib.pack_pair_bf16x3(wa, wb)
+                    if self.f16bf8 and hiplib.pair8_supported(La["cin"], La["cout"], Lb["cout"]):
+                        self.pair8 = hiplib.pack_pair_f16bf8(wa, wb)
             assert not (pair_kernel and self.pair is None), "pair_kernel=True but the topology / precision does not allow it"
-            self.pair8 = None
-            if self.f16bf8 and self.pair is not None:
-                La, Lb = self.layers[-2], self.layers[-1]
-                if hiplib.pair8_supported(La["cin"], La["cout"], Lb["cout"]):
-                    n = len(self.layers)
-                    self.pair8 = hiplib.pack_pair_f16bf8(self._wdev(weights, "frame_level_info_layer-%d/w:0" % (n - 2))[0],
-                                                         self._wdev(weights, "frame_level_info_layer-%d/w:0" % (n - 1))[0])
             if self.f16bf8:
                 if self.first is None:
                     self.layers[0]["wp"]                          # (deferred above: this model does use layer 0's bf16x3 packing)
@@ -488,36 +492,28 @@ class DeviceModel(object):
         bufs = (self._ping, self._pong)
         if events is not None:
             events[0].record()
-        if self.f16bf8:
+        layers = self.layers
+        if self.f16bf8:            # its own launch sequence; always with fused_pool, so the common tail below pools self._last
             self._frame_level_f16bf8(x, R, row_valid, self.status if status is None else status)
-            if events is not None:
-                events[1].record()
-            hiplib.stats_pool_blocks(self._last, self.layers[-1]["cout"], row_start, row_len, nchunks, tp.VAR2STD_EPSILON, pooled)
-            if events is not None:
-                events[2].record()
-            return pooled
-        for i, L in enumerate(self.layers):
+            layers = ()
+        for i, L in enumerate(layers):
             last = i == len(self.layers) - 1
             if i == 0 and self.first is not None and isinstance(bufs[0], hiplib.SplitBuf):
                 y = self._view(bufs[0], R, L["cout"])
-                hiplib.tdnn_first(h, R, self.first, L["bias"], L["scale"], L["shift"], self.act, L["alpha"], L["dil"], row_valid, y)
+                hiplib.tdnn_first(h, R, self.first, *L.ep(self.act), L["dil"], row_valid, y)
                 h = y
                 continue
             if self.pair is not None and i == len(self.layers) - 2:
-                Lb = self.layers[-1]
-                hiplib.tdnn_pair_pool(h, R, self.pair, (L["bias"], L["scale"], L["shift"], L["alpha"]),
-                                      (Lb["bias"], Lb["scale"], Lb["shift"], Lb["alpha"]), self.act, row_valid, self._last)
+                hiplib.tdnn_pair_pool(h, R, self.pair, L.pp, self.layers[-1].pp, self.act, row_valid, self._last)
                 break
             if last and self.fused_pool:
-                hiplib.tdnn_layer_pool(h, R, L["wp"], L["bias"], L["scale"], L["shift"], self.act, L["alpha"], L["dil"], row_valid,
-                                       self._last, K=L["K"])
+                hiplib.tdnn_layer_pool(h, R, L["wp"], *L.ep(self.act), L["dil"], row_valid, self._last, K=L["K"])
                 break
             if last and self.attention:
                 h = self._attention_scores(h, R, L, row_valid)
                 break
             y = self._view(self._last if last else bufs[i & 1], R, L["cout"])
-            hiplib.tdnn_layer(h, L["wp"], L["bias"], L["scale"], L["shift"], self.act, L["alpha"], L["K"], L["dil"],
-                              row_valid, y, rows=R)
+            hiplib.tdnn_layer(h, L["wp"], *L.ep(self.act), L["K"], L["dil"], row_valid, y, rows=R)
             h = y
         if events is not None:
             events[1].record()
@@ -552,32 +548,29 @@ class DeviceModel(object):
         h = bufs[0].view(L["cout"], pair_fmt if (self.pair is not None and stop == 1) else S8)
         mark("start")
         if self.first is not None:
-            hiplib.tdnn_first(x, R, self.first, L["bias"], L["scale"], L["shift"], self.act, L["alpha"], L["dil"], row_valid, h, status)
+            hiplib.tdnn_first(x, R, self.first, *L.ep(self.act), L["dil"], row_valid, h, status)
             mark("layer 0: tdnn_first_kernel (bf16x3)")
         else:
             # a first layer the dedicated kernel does not take: the general bf16x3 GEMM into fp32 rows, then one encoding pass
             y32 = self._l0_rows[:R]
-            hiplib.tdnn_layer(x, L["wp"], L["bias"], L["scale"], L["shift"], self.act, L["alpha"], L["K"], L["dil"], row_valid, y32, rows=R)
+            hiplib.tdnn_layer(x, L["wp"], *L.ep(self.act), L["K"], L["dil"], row_valid, y32, rows=R)
             hiplib.split_encode(y32, h, rows=R, status=status if h.fmt == S8 else None)
             mark("layer 0: tdnn_gemm_bf16x3_kernel + split encode")
         for i in range(1, stop):
             L = self.layers[i]
             y = bufs[i & 1].view(L["cout"], pair_fmt if (self.pair is not None and i == stop - 1) else S8)
-            hiplib.tdnn_layer8(h, R, L["wp8"], L["bias"], L["scale"], L["shift"], self.act, L["alpha"], L["dil"], row_valid, y, status)
+            hiplib.tdnn_layer8(h, R, L["wp8"], *L.ep(self.act), L["dil"], row_valid, y, status)
             mark("layer %d: tdnn_gemm_f16bf8 (K=%d, %d -> %d)" % (i, L["K"], L["cin"], L["cout"]))
             h = y
         if self.pair is not None:
             La, Lb = self.layers[-2], self.layers[-1]
             if self.pair8 is not None:
-                hiplib.tdnn_pair_pool8(h, R, self.pair8, (La["bias"], La["scale"], La["shift"], La["alpha"]),
-                                       (Lb["bias"], Lb["scale"], Lb["shift"], Lb["alpha"]), self.act, row_valid, self._last, status)
+                hiplib.tdnn_pair_pool8(h, R, self.pair8, La.pp, Lb.pp, self.act, row_valid, self._last, status)
             else:
-                hiplib.tdnn_pair_pool(h, R, self.pair, (La["bias"], La["scale"], La["shift"], La["alpha"]),
-                                      (Lb["bias"], Lb["scale"], Lb["shift"], Lb["alpha"]), self.act, row_valid, self._last)
+                hiplib.tdnn_pair_pool(h, R, self.pair, La.pp, Lb.pp, self.act, row_valid, self._last)
         else:
             L = self.layers[-1]
-            hiplib.tdnn_layer_pool8(h, R, L["wp8"], L["bias"], L["scale"], L["shift"], self.act, L["alpha"], L["dil"], row_valid,
-                                    self._last)
+            hiplib.tdnn_layer_pool8(h, R, L["wp8"], *L.ep(self.act), L["dil"], row_valid, self._last)
         mark("layers %d+%d + pooling statistics: %s" % (n - 2, n - 1, "tdnn_pair_pool_f16bf8_kernel" if self.pair8 is not None else
                                                         "tdnn_pair_pool_kernel (bf16x3)") if self.pair is not None else
              "layer %d + pooling statistics: tdnn_gemm_f16bf8 POOL" % (n - 1))
@@ -589,16 +582,13 @@ class DeviceModel(object):
         u = self._u[:R]
         if self.precision == "bf16x3":
             L1, L2 = self.last_halves
-            hiplib.tdnn_layer(h, L1["wp"], L1["bias"], L1["scale"], L1["shift"], self.act, L1["alpha"], L1["K"], L1["dil"],
-                              row_valid, self._h1, rows=R)
+            hiplib.tdnn_layer(h, L1["wp"], *L1.ep(self.act), L1["K"], L1["dil"], row_valid, self._h1, rows=R)
             h2 = self._last[:R]
-            hiplib.tdnn_layer(h, L2["wp"], L2["bias"], L2["scale"], L2["shift"], self.act, L2["alpha"], L2["K"], L2["dil"],
-                              row_valid, h2, rows=R)
+            hiplib.tdnn_layer(h, L2["wp"], *L2.ep(self.act), L2["K"], L2["dil"], row_valid, h2, rows=R)
             h1 = self._h1
         else:
             y = self._last[:R]
-            hiplib.tdnn_layer(h, L["wp"], L["bias"], L["scale"], L["shift"], self.act, L["alpha"], L["K"], L["dil"],
-                              row_valid, y, rows=R)
+            hiplib.tdnn_layer(h, L["wp"], *L.ep(self.act), L["K"], L["dil"], row_valid, y, rows=R)
             h1, h2 = y[:, :A], y[:, A:]
         hiplib.tdnn_layer(h1, T["wp"], T["bias"], None, None, tp.ACT_NONE, None, 1, 1, None, u, rows=R)
         hiplib.attention_scores(u, T["v"], self._scores, rows=R)
@@ -616,7 +606,7 @@ class DeviceModel(object):
             if self._a0 is None or self._a0.shape[0] < n:
                 self._a0 = self.torch.empty((n, E0["cout"]), dtype=self.torch.float32, device=self.device)
             a0 = self._a0[:n]
-            hiplib.fc(pooled, E0["wp"], E0["bias"], E0["scale"], E0["shift"], self.act, E0["alpha"], a0, None)
+            hiplib.fc(pooled, E0["wp"], *E0.ep(self.act), a0, None)
             E1 = self.embed[1]
             hiplib.fc(a0, E1["wp"], E1["bias"], None, None, tp.ACT_NONE, None, None, out)
         return out
@@ -639,8 +629,7 @@ class DeviceModel(object):
                 y = hiplib.SplitBuf(R, L["cout"], self.device)
             else:
                 y = torch.empty((R, L["cout"]), dtype=torch.float32, device=self.device)
-            hiplib.tdnn_layer(h, L["wp"], L["bias"], L["scale"], L["shift"], self.act, L["alpha"], L["K"], L["dil"],
-                              row_valid, y, rows=R)
+            hiplib.tdnn_layer(h, L["wp"], *L.ep(self.act), L["K"], L["dil"], row_valid, y, rows=R)
             outs.append(hiplib.split_decode(y, R) if isinstance(y, hiplib.SplitBuf) else y)
             h = y
         return outs

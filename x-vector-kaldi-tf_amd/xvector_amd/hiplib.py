@@ -6,6 +6,7 @@ HIP runtime torch already loaded (same SONAME) -- device pointers of torch tenso
 the kernels, and torch's current stream can be passed straight through.
 """
 import ctypes
+import functools
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -229,19 +230,91 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _f32(t, name):
+# ------------------------------------------------------------------------------------------------
+# argument checks: what keeps a wrong shape or a host tensor from a kernel that trusts its arguments
+# ------------------------------------------------------------------------------------------------
+# strictness of _f32: contiguous (any rank); 2-D with dense rows (a column slice of a wider buffer passes, its stride(0) goes to
+# the kernel as the leading dimension); the same with stride(0) >= shape[1] (no overlapping rows)
+_DENSE, _ROWS, _ROWS_LD = 0, 1, 2
+_F32_WHAT = ("%s must be a contiguous cuda float32 tensor", "%s must be cuda float32 rows",
+             "%s must be a 2-D cuda float32 tensor with dense rows")
+
+
+def _f32(t, name, level=_DENSE):
     import torch
-    assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), "%s must be a contiguous cuda float32 tensor" % name
+    assert t.is_cuda and t.dtype == torch.float32 and (
+        t.is_contiguous() if level == _DENSE else
+        t.dim() == 2 and t.stride(1) == 1 and (level == _ROWS or t.stride(0) >= t.shape[1])), _F32_WHAT[level] % name
     return t
 
 
-def _f32_rows(t, name):
-    """A 2-D cuda float32 tensor whose rows are dense (stride(1) == 1): a row or column slice of a wider buffer passes, and its
-    stride(0) goes to the kernel as the leading dimension."""
+_rows2d = functools.partial(_f32, level=_ROWS)          # _rows2d(t, name) / _f32_rows(t, name): the two stricter levels by name
+_f32_rows = functools.partial(_f32, level=_ROWS_LD)
+
+
+def _dev(t, dtype, name, n=None):
+    """Pointer of a contiguous cuda tensor of ``dtype`` (index tables, fp64 accumulators, ...) of at least ``n`` elements."""
+    assert t.is_cuda and t.dtype == dtype and t.is_contiguous(), "%s must be a contiguous cuda %s tensor" % (name, dtype)
+    assert n is None or t.numel() >= n, "%s must hold at least %d elements" % (name, n)
+    return _ptr(t)
+
+
+def _chunk_tables(row_start, row_len):
+    """The per-chunk tables of the pooling kernels.  (Dtype and device only, as every copy of this check had it: not _dev's
+    contiguity test.)"""
     import torch
-    assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1], \
-        "%s must be a 2-D cuda float32 tensor with dense rows" % name
-    return t
+    assert row_start.dtype == torch.int32 and row_len.dtype == torch.int32 and row_start.is_cuda and row_len.is_cuda
+
+
+def _valid(row_valid, R):
+    """Pointer of the optional row mask of ``R`` rows: one byte per row, on the device."""
+    assert row_valid is None or (row_valid.is_cuda and row_valid.numel() >= R and row_valid.element_size() == 1), \
+        "row_valid must be a cuda tensor of at least %d one-byte elements" % R
+    return _ptr(row_valid)
+
+
+def _operand(t, channels, R, name, fmts, level=_ROWS):
+    """(pointer, leading dimension, format) of an activation operand of ``channels`` channels and at least ``R`` rows.  ``fmts``
+    lists what the kernel takes: FMT_SPLIT / FMT_SPLIT8 for a SplitBuf in that format (leading dimension 0), FMT_F32 for fp32
+    rows (checked by _f32 at ``level``), None where the operand may be left out."""
+    if t is None:
+        assert None in fmts, "%s is required" % name
+        return None, 0, FMT_F32
+    if isinstance(t, SplitBuf):
+        assert t.fmt in fmts and t.channels == channels and t.rows >= R, \
+            "%s: a split buffer in one of the formats %s with %d channels and at least %d rows is expected" % (name, fmts, channels, R)
+        return ctypes.c_void_p(t.ptr), 0, t.fmt
+    assert FMT_F32 in fmts, "%s must be a SplitBuf" % name
+    _f32(t, name, level)
+    assert t.shape[1] == channels and t.shape[0] >= R, "%s must be [>= %d, %d]" % (name, R, channels)
+    return _ptr(t), t.stride(0), FMT_F32
+
+
+def _split_out(buf, c, R):
+    """Pointer of the optional bf16-split second output (``c`` channels, at least ``R`` rows) of an element-wise kernel."""
+    return _operand(buf, c, R, "split output", (FMT_SPLIT, None))[0]
+
+
+def _nbytes(t):
+    return t.numel() * t.element_size()
+
+
+def _ws(nbytes, device):
+    import torch
+    return torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=device)
+
+
+def _scale_shift(like):
+    """Uninitialised (scale, shift) of a BN fold, one float per element of ``like`` (gamma)."""
+    import torch
+    c = like.numel()
+    return torch.empty(c, dtype=torch.float32, device=like.device), torch.empty(c, dtype=torch.float32, device=like.device)
+
+
+def _bn_coef(c, device):
+    """The [3, c] coefficient scratch the BN-backward kernels fill and read back in one launch."""
+    import torch
+    return torch.empty(3 * c, dtype=torch.float32, device=device)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -258,11 +331,34 @@ def pack_weights(w2d):
     return wp
 
 
-class PackedRows(object):
-    """Weights of a first layer for the "rows" form (xv_pack_weights_rows_f32): wp[Cout, roundup32(K ldx)] for feature rows of ldx floats."""
+class _Packed(object):
+    """Packed weights of one kernel form + the shape they were packed for: the constructor takes the attributes a subclass
+    names in ``__slots__``, in that order."""
+    __slots__ = ()
 
-    def __init__(self, wp, K, cin, ldx, cout):
-        self.wp, self.K, self.cin, self.ldx, self.cout = wp, K, cin, ldx, cout
+    def __init__(self, *values):
+        assert len(values) == len(self.__slots__)
+        for k, v in zip(self.__slots__, values):
+            setattr(self, k, v)
+
+
+def _pack_bytes(size_fn, pack_fn, name, cls, tensors, dims, unsupported=None):
+    """A packing that lives in a byte buffer: ``size_fn(*dims)`` bytes are allocated, ``pack_fn`` (the entry point ``name``) fills
+    them from ``tensors``, and ``cls(buffer, *dims)`` comes back.  ``unsupported``: format of ``dims`` for the error raised when
+    the library reports 0 bytes (None: left to the entry point, which names what it does not take)."""
+    import torch
+    dims = tuple(int(v) for v in dims)
+    nbytes = int(size_fn(*dims))
+    if unsupported is not None and nbytes == 0:
+        raise XvectorHipError("%s: unsupported shape %s" % (name, unsupported % dims))
+    wt = torch.empty(nbytes, dtype=torch.uint8, device=tensors[0].device)
+    _check(pack_fn(*[_ptr(t) for t in tensors], *dims, _ptr(wt), _stream()), name)
+    return cls(wt, *dims)
+
+
+class PackedRows(_Packed):
+    """Weights of a first layer for the "rows" form (xv_pack_weights_rows_f32): wp[Cout, roundup32(K ldx)] for feature rows of ldx floats."""
+    __slots__ = ("wp", "K", "cin", "ldx", "cout")
 
 
 def pack_weights_rows(w3d, ldx):
@@ -284,17 +380,13 @@ def tdnn_layer_rows(x, w, bias, scale, shift, act, alpha, row_valid, y, rows=Non
     _rows2d(x, "x")
     R = x.shape[0] if rows is None else int(rows)
     assert x.shape[1] == w.ldx and x.stride(0) == w.ldx and y.shape[1] == w.cout and y.shape[0] >= R
-    if row_valid is not None:
-        assert row_valid.is_cuda and row_valid.numel() >= R and row_valid.element_size() == 1
     _check(lib.xv_tdnn_layer_rows_f32(_ptr(x), R, w.cin, w.ldx, _ptr(w.wp), _ptr(bias), _ptr(scale), _ptr(shift), int(act), _ptr(alpha),
-                                      w.K, w.cout, _ptr(row_valid), _ptr(y), y.stride(0), _stream()), "xv_tdnn_layer_rows_f32")
+                                      w.K, w.cout, _valid(row_valid, R), _ptr(y), y.stride(0), _stream()), "xv_tdnn_layer_rows_f32")
 
 
-class PackedToom(object):
+class PackedToom(_Packed):
     """Transformed taps of one K in {3, 5, 7} layer for the Toom-Cook F(2, K) kernel (xv_pack_weights_toom_f32): wp[Cout, (K+1) Cin]."""
-
-    def __init__(self, wp, K, cin, cout):
-        self.wp, self.K, self.cin, self.cout = wp, K, cin, cout
+    __slots__ = ("wp", "K", "cin", "cout")
 
 
 def toom_supported(K, dilation, cin, cout):
@@ -320,35 +412,26 @@ def tdnn_layer_toom(x, w, bias, scale, shift, act, alpha, row_valid, y, rows=Non
     _rows2d(x, "x")
     R = x.shape[0] if rows is None else int(rows)
     assert x.shape[1] == w.cin and y.shape[1] == w.cout and y.shape[0] >= R
-    if row_valid is not None:
-        assert row_valid.is_cuda and row_valid.numel() >= R and row_valid.element_size() == 1
     if int(dilation) == 1:
         _check(lib.xv_tdnn_layer_toom_f32(_ptr(x), R, w.cin, x.stride(0), _ptr(w.wp), _ptr(bias), _ptr(scale), _ptr(shift), int(act),
-                                          _ptr(alpha), w.K, w.cout, _ptr(row_valid), _ptr(y), y.stride(0), _stream()),
+                                          _ptr(alpha), w.K, w.cout, _valid(row_valid, R), _ptr(y), y.stride(0), _stream()),
                "xv_tdnn_layer_toom_f32")
         return
     _check(lib.xv_tdnn_layer_toom_dilated_f32(_ptr(x), R, w.cin, x.stride(0), _ptr(w.wp), _ptr(bias), _ptr(scale), _ptr(shift), int(act),
-                                              _ptr(alpha), w.K, int(dilation), w.cout, _ptr(row_valid), _ptr(y), y.stride(0), _stream()),
-           "xv_tdnn_layer_toom_dilated_f32")
+                                              _ptr(alpha), w.K, int(dilation), w.cout, _valid(row_valid, R), _ptr(y), y.stride(0),
+                                              _stream()), "xv_tdnn_layer_toom_dilated_f32")
 
 
-class Packed3(object):
+class Packed3(_Packed):
     """Tiled bf16x3 weights of one layer (xv_pack_weights_bf16x3) + the shape they were packed for."""
-
-    def __init__(self, wt, K, cin, cout):
-        self.wt, self.K, self.cin, self.cout = wt, K, cin, cout
+    __slots__ = ("wt", "K", "cin", "cout")
 
 
 def pack_weights_bf16x3(w3d):
     """w3d: [K, Cin, Cout] fp32 (TF layout; FC: [1, In, Out]) -> Packed3."""
-    import torch
     lib = require_gpu()
-    _f32(w3d, "w")
-    K, cin, cout = w3d.shape
-    nbytes = int(lib.xv_packed_weights_bf16x3_bytes(K, cin, cout))
-    wt = torch.empty(nbytes, dtype=torch.uint8, device=w3d.device)
-    _check(lib.xv_pack_weights_bf16x3(_ptr(w3d), K, cin, cout, _ptr(wt), _stream()), "xv_pack_weights_bf16x3")
-    return Packed3(wt, K, cin, cout)
+    return _pack_bytes(lib.xv_packed_weights_bf16x3_bytes, lib.xv_pack_weights_bf16x3, "xv_pack_weights_bf16x3", Packed3,
+                       (_f32(w3d, "w"),), w3d.shape)
 
 
 class PackPlan(object):
@@ -357,7 +440,6 @@ class PackPlan(object):
     ``layers``: [(w3d [K, Cin, Cout] fp32 device tensor -- a VIEW whose storage the optimizer updates in place --, cin_pad, want_bwd)]."""
 
     def __init__(self, layers):
-        import ctypes
         import torch
         lib = require_gpu()
         n = len(layers)
@@ -440,8 +522,8 @@ def split_decode(buf, rows, out=None):
     lib = require_gpu()
     if out is None:
         out = torch.empty((rows, buf.channels), dtype=torch.float32, device=buf.base.device)
-    fn = lib.xv_split8_decode_f32 if buf.fmt == FMT_SPLIT8 else lib.xv_split_decode_f32
-    _check(fn(ctypes.c_void_p(buf.ptr), int(rows), buf.channels, _ptr(out), out.stride(0), _stream()), "xv_split_decode_f32")
+    name = "xv_split8_decode_f32" if buf.fmt == FMT_SPLIT8 else "xv_split_decode_f32"
+    _check(getattr(lib, name)(ctypes.c_void_p(buf.ptr), int(rows), buf.channels, _ptr(out), out.stride(0), _stream()), name)
     return out
 
 
@@ -449,31 +531,12 @@ def tdnn_layer3(x, R, w, bias, scale, shift, act, alpha, dilation, row_valid, y,
     """bf16x3 layer.  x / y: contiguous fp32 tensors [>=R, C] (XV_FMT_F32) or SplitBuf (XV_FMT_SPLIT); w: Packed3."""
     lib = require_gpu()
     assert isinstance(w, Packed3)
-    xs, ys = isinstance(x, SplitBuf), isinstance(y, SplitBuf)
-    assert not (xs and x.fmt != FMT_SPLIT) and not (ys and y.fmt != FMT_SPLIT), "bf16x3 layers take the bf16 split format"
-    if xs:
-        assert x.channels == w.cin and x.rows >= R
-        xp, ldx = ctypes.c_void_p(x.ptr), 0
-    else:
-        _rows2d(x, "x"); assert x.shape[1] == w.cin and x.shape[0] >= R
-        xp, ldx = _ptr(x), x.stride(0)
-    if y is None:
-        yp, ldy = None, 0
-    elif ys:
-        assert y.channels == w.cout and y.rows >= R
-        yp, ldy = ctypes.c_void_p(y.ptr), 0
-    else:
-        _rows2d(y, "y"); assert y.shape[1] == w.cout and y.shape[0] >= R
-        yp, ldy = _ptr(y), y.stride(0)
-    ldpre = 0
-    if y_preact is not None:
-        _f32(y_preact, "y_preact"); assert y_preact.shape[1] == w.cout and y_preact.shape[0] >= R
-        ldpre = y_preact.stride(0)
-    if row_valid is not None:
-        assert row_valid.is_cuda and row_valid.numel() >= R and row_valid.element_size() == 1
-    _check(lib.xv_tdnn_layer_bf16x3(xp, FMT_SPLIT if xs else FMT_F32, int(R), w.cin, ldx, _ptr(w.wt), _ptr(bias), _ptr(scale),
-                                    _ptr(shift), int(act), _ptr(alpha), w.K, int(dilation), w.cout, _ptr(row_valid), yp,
-                                    FMT_SPLIT if ys else FMT_F32, ldy, _ptr(y_preact), ldpre, _stream()), "xv_tdnn_layer_bf16x3")
+    xp, ldx, xfmt = _operand(x, w.cin, R, "x", (FMT_F32, FMT_SPLIT))
+    yp, ldy, yfmt = _operand(y, w.cout, R, "y", (FMT_F32, FMT_SPLIT, None))
+    prep, ldpre, _ = _operand(y_preact, w.cout, R, "y_preact", (FMT_F32, None), _DENSE)      # contiguous: stricter than y, as before
+    _check(lib.xv_tdnn_layer_bf16x3(xp, xfmt, int(R), w.cin, ldx, _ptr(w.wt), _ptr(bias), _ptr(scale), _ptr(shift), int(act),
+                                    _ptr(alpha), w.K, int(dilation), w.cout, _valid(row_valid, R), yp, yfmt, ldy, prep, ldpre,
+                                    _stream()), "xv_tdnn_layer_bf16x3")
 
 
 def col_sums_workspace(rows, c, device):
@@ -486,20 +549,12 @@ def tdnn_layer3_sums(x, R, w, dilation, row_valid, y, sum_r, workspace):
     fp32 rows out, and per 128-row tile the partial column sums [sum y | sum y * sum_r] in ``workspace`` (col_sums_workspace)."""
     lib = require_gpu()
     assert isinstance(w, Packed3) and supports_sums(w.cout)
-    xs = isinstance(x, SplitBuf)
-    if xs:
-        assert x.fmt == FMT_SPLIT and x.channels == w.cin and x.rows >= R
-        xp, ldx = ctypes.c_void_p(x.ptr), 0
-    else:
-        _rows2d(x, "x"); assert x.shape[1] == w.cin and x.shape[0] >= R
-        xp, ldx = _ptr(x), x.stride(0)
-    _rows2d(y, "y"); assert y.shape[1] == w.cout and y.shape[0] >= R
-    _rows2d(sum_r, "sum_r"); assert sum_r.shape[1] == w.cout and sum_r.shape[0] >= R
-    if row_valid is not None:
-        assert row_valid.is_cuda and row_valid.numel() >= R and row_valid.element_size() == 1
-    _check(lib.xv_tdnn_layer_bf16x3_sums(xp, FMT_SPLIT if xs else FMT_F32, int(R), w.cin, ldx, _ptr(w.wt), None, None, None, ACT_NONE,
-                                         None, w.K, int(dilation), w.cout, _ptr(row_valid), _ptr(y), y.stride(0), _ptr(sum_r),
-                                         sum_r.stride(0), _ptr(workspace), _stream()), "xv_tdnn_layer_bf16x3_sums")
+    xp, ldx, xfmt = _operand(x, w.cin, R, "x", (FMT_F32, FMT_SPLIT))
+    yp, ldy, _ = _operand(y, w.cout, R, "y", (FMT_F32,))
+    sp, lds, _ = _operand(sum_r, w.cout, R, "sum_r", (FMT_F32,))
+    _check(lib.xv_tdnn_layer_bf16x3_sums(xp, xfmt, int(R), w.cin, ldx, _ptr(w.wt), None, None, None, ACT_NONE, None, w.K, int(dilation),
+                                         w.cout, _valid(row_valid, R), yp, ldy, sp, lds, _ptr(workspace), _stream()),
+           "xv_tdnn_layer_bf16x3_sums")
 
 
 def supports_sums(cout):
@@ -511,32 +566,19 @@ def tdnn_layer3_moments(x, R, w, bias, act, alpha, dilation, row_valid, y, y_pre
     128-row tile the partial sums [sum r | sum r^2] in ``workspace`` (col_sums_workspace) -- BN's batch moments (bn_moments_fold)."""
     lib = require_gpu()
     assert isinstance(w, Packed3) and supports_sums(w.cout)
-    xs = isinstance(x, SplitBuf)
-    if xs:
-        assert x.fmt == FMT_SPLIT and x.channels == w.cin and x.rows >= R
-        xp, ldx = ctypes.c_void_p(x.ptr), 0
-    else:
-        _rows2d(x, "x"); assert x.shape[1] == w.cin and x.shape[0] >= R
-        xp, ldx = _ptr(x), x.stride(0)
-    _rows2d(y, "y"); assert y.shape[1] == w.cout and y.shape[0] >= R
-    ldpre = 0
-    if y_preact is not None:
-        _f32(y_preact, "y_preact"); assert y_preact.shape[1] == w.cout and y_preact.shape[0] >= R
-        ldpre = y_preact.stride(0)
-    if row_valid is not None:
-        assert row_valid.is_cuda and row_valid.numel() >= R and row_valid.element_size() == 1
-    _check(lib.xv_tdnn_layer_bf16x3_moments(xp, FMT_SPLIT if xs else FMT_F32, int(R), w.cin, ldx, _ptr(w.wt), _ptr(bias), None, None, int(act),
-                                            _ptr(alpha), w.K, int(dilation), w.cout, _ptr(row_valid), _ptr(y), y.stride(0), _ptr(y_preact),
-                                            ldpre, _ptr(workspace), _stream()), "xv_tdnn_layer_bf16x3_moments")
+    xp, ldx, xfmt = _operand(x, w.cin, R, "x", (FMT_F32, FMT_SPLIT))
+    yp, ldy, _ = _operand(y, w.cout, R, "y", (FMT_F32,))
+    prep, ldpre, _ = _operand(y_preact, w.cout, R, "y_preact", (FMT_F32, None), _DENSE)      # contiguous: stricter than y, as before
+    _check(lib.xv_tdnn_layer_bf16x3_moments(xp, xfmt, int(R), w.cin, ldx, _ptr(w.wt), _ptr(bias), None, None, int(act), _ptr(alpha), w.K,
+                                            int(dilation), w.cout, _valid(row_valid, R), yp, ldy, prep, ldpre, _ptr(workspace),
+                                            _stream()), "xv_tdnn_layer_bf16x3_moments")
 
 
 def bn_moments_fold(workspace, rows, n_frames, gamma, beta, eps, mean, var):
     """(scale, shift) of the BN fold and the batch moments (into mean, var) from the partial sums of tdnn_layer3_moments."""
-    import torch
     lib = require_gpu()
     c = gamma.numel()
-    scale = torch.empty(c, dtype=torch.float32, device=gamma.device)
-    shift = torch.empty(c, dtype=torch.float32, device=gamma.device)
+    scale, shift = _scale_shift(gamma)
     _check(lib.xv_bn_moments_fold_f32(_ptr(workspace), int(rows), c, float(n_frames), _ptr(_f32(gamma, "gamma")), _ptr(_f32(beta, "beta")),
                                       float(eps), _ptr(_f32(mean, "mean")), _ptr(_f32(var, "var")), _ptr(scale), _ptr(shift), _stream()),
            "xv_bn_moments_fold_f32")
@@ -550,40 +592,34 @@ def block_stats_floats(rows, cout):
     return int(load().xv_block_stats_bytes(int(rows), int(cout))) // 4
 
 
+def _block_stats(block_stats, R, cout):
+    """Pointer of the block-statistics output of ``R`` rows of ``cout`` channels."""
+    assert _f32(block_stats, "block_stats").numel() >= block_stats_floats(R, cout), "block_stats too small"
+    return _ptr(block_stats)
+
+
 def tdnn_layer_pool(x, R, w, bias, scale, shift, act, alpha, dilation, row_valid, block_stats, K=None):
     """Last frame-level layer with the block-statistics epilogue: block_stats = flat fp32 tensor of
     >= block_stats_floats(R, cout) elements, laid out [ceil(R/8)][2][Cout].  w: Packed3 (bf16x3) or the packed fp32 weights
     of pack_weights() together with ``K`` (exact fp32, x: fp32 rows)."""
     lib = require_gpu()
-    _f32(block_stats, "block_stats")
-    if row_valid is not None:
-        assert row_valid.is_cuda and row_valid.numel() >= R and row_valid.element_size() == 1
     if not isinstance(w, Packed3):
         _rows2d(x, "x"); _f32(w, "wp")
         cin, cout = x.shape[1], w.shape[0]
         assert K is not None and w.shape[1] == int(K) * cin and x.shape[0] >= R
-        assert block_stats.numel() >= block_stats_floats(R, cout), "block_stats too small"
         _check(lib.xv_tdnn_layer_pool_f32(_ptr(x), int(R), cin, x.stride(0), _ptr(w), _ptr(bias), _ptr(scale), _ptr(shift), int(act),
-                                          _ptr(alpha), int(K), int(dilation), cout, _ptr(row_valid), _ptr(block_stats), _stream()),
-               "xv_tdnn_layer_pool_f32")
+                                          _ptr(alpha), int(K), int(dilation), cout, _valid(row_valid, R),
+                                          _block_stats(block_stats, R, cout), _stream()), "xv_tdnn_layer_pool_f32")
         return
-    if isinstance(x, SplitBuf):
-        assert x.channels == w.cin and x.rows >= R and x.fmt == FMT_SPLIT
-        xp, ldx, fmt = ctypes.c_void_p(x.ptr), 0, FMT_SPLIT
-    else:
-        _f32(x, "x"); assert x.shape[1] == w.cin and x.shape[0] >= R
-        xp, ldx, fmt = _ptr(x), x.stride(0), FMT_F32
-    assert block_stats.numel() >= block_stats_floats(R, w.cout), "block_stats too small"
+    xp, ldx, fmt = _operand(x, w.cin, R, "x", (FMT_F32, FMT_SPLIT), _DENSE)      # contiguous x: stricter than tdnn_layer3, as before
     _check(lib.xv_tdnn_layer_pool_bf16x3(xp, fmt, int(R), w.cin, ldx, _ptr(w.wt), _ptr(bias), _ptr(scale), _ptr(shift), int(act),
-                                         _ptr(alpha), w.K, int(dilation), w.cout, _ptr(row_valid), _ptr(block_stats), _stream()),
-           "xv_tdnn_layer_pool_bf16x3")
+                                         _ptr(alpha), w.K, int(dilation), w.cout, _valid(row_valid, R),
+                                         _block_stats(block_stats, R, w.cout), _stream()), "xv_tdnn_layer_pool_bf16x3")
 
 
-class PackedFirst(object):
+class PackedFirst(_Packed):
     """Weights of the first frame-level layer in the fragment order of xv_tdnn_first_bf16x3."""
-
-    def __init__(self, wt, K, cin, cout):
-        self.wt, self.K, self.cin, self.cout = wt, K, cin, cout
+    __slots__ = ("wt", "K", "cin", "cout")
 
 
 def first_supported(K, cin, cout):
@@ -592,16 +628,10 @@ def first_supported(K, cin, cout):
 
 def pack_first_bf16x3(w3d):
     """w[K, Cin, Cout] (device fp32, TF order) -> PackedFirst."""
-    import torch
     lib = require_gpu()
     _f32(w3d, "w"); assert w3d.dim() == 3
-    K, cin, cout = (int(v) for v in w3d.shape)
-    nbytes = int(lib.xv_packed_first_bf16x3_bytes(K, cin, cout))
-    if nbytes == 0:
-        raise XvectorHipError("xv_pack_first_bf16x3: unsupported shape K=%d, %d -> %d" % (K, cin, cout))
-    wt = torch.empty(nbytes, dtype=torch.uint8, device=w3d.device)
-    _check(lib.xv_pack_first_bf16x3(_ptr(w3d.contiguous()), K, cin, cout, _ptr(wt), _stream()), "xv_pack_first_bf16x3")
-    return PackedFirst(wt, K, cin, cout)
+    return _pack_bytes(lib.xv_packed_first_bf16x3_bytes, lib.xv_pack_first_bf16x3, "xv_pack_first_bf16x3", PackedFirst, (w3d,), w3d.shape,
+                       unsupported="K=%d, %d -> %d")
 
 
 def tdnn_first(x, R, w, bias, scale, shift, act, alpha, dilation, row_valid, y, status=None):
@@ -611,23 +641,19 @@ def tdnn_first(x, R, w, bias, scale, shift, act, alpha, dilation, row_valid, y, 
     assert isinstance(w, PackedFirst) and isinstance(y, SplitBuf)
     _rows2d(x, "x"); assert x.shape[0] >= R and x.shape[1] >= w.cin
     assert y.channels == w.cout and y.rows >= R
-    if row_valid is not None:
-        assert row_valid.is_cuda and row_valid.numel() >= R and row_valid.element_size() == 1
     if y.fmt == FMT_SPLIT8:
         _check(lib.xv_tdnn_first_f16bf8(_ptr(x), int(R), w.cin, x.stride(0), _ptr(w.wt), _ptr(bias), _ptr(scale), _ptr(shift), int(act),
-                                        _ptr(alpha), w.K, int(dilation), w.cout, _ptr(row_valid), ctypes.c_void_p(y.ptr), _ptr(status),
-                                        _stream()), "xv_tdnn_first_f16bf8")
+                                        _ptr(alpha), w.K, int(dilation), w.cout, _valid(row_valid, R), ctypes.c_void_p(y.ptr),
+                                        _ptr(status), _stream()), "xv_tdnn_first_f16bf8")
         return
     _check(lib.xv_tdnn_first_bf16x3(_ptr(x), int(R), w.cin, x.stride(0), _ptr(w.wt), _ptr(bias), _ptr(scale), _ptr(shift), int(act),
-                                    _ptr(alpha), w.K, int(dilation), w.cout, _ptr(row_valid), ctypes.c_void_p(y.ptr), _stream()),
+                                    _ptr(alpha), w.K, int(dilation), w.cout, _valid(row_valid, R), ctypes.c_void_p(y.ptr), _stream()),
            "xv_tdnn_first_bf16x3")
 
 
-class Packed8(object):
+class Packed8(_Packed):
     """Tiled f16bf8 weights of one layer (xv_pack_weights_f16bf8) + the shape they were packed for."""
-
-    def __init__(self, wt, K, cin, cout):
-        self.wt, self.K, self.cin, self.cout = wt, K, cin, cout
+    __slots__ = ("wt", "K", "cin", "cout")
 
 
 def f16bf8_supported(K, dilation):
@@ -638,81 +664,71 @@ def f16bf8_supported(K, dilation):
 
 def pack_weights_f16bf8(w3d):
     """w3d: [K, Cin, Cout] fp32 (TF layout) -> Packed8."""
-    import torch
     lib = require_gpu()
-    _f32(w3d, "w")
-    K, cin, cout = w3d.shape
-    nbytes = int(lib.xv_packed_weights_f16bf8_bytes(K, cin, cout))
-    wt = torch.empty(nbytes, dtype=torch.uint8, device=w3d.device)
-    _check(lib.xv_pack_weights_f16bf8(_ptr(w3d), K, cin, cout, _ptr(wt), _stream()), "xv_pack_weights_f16bf8")
-    return Packed8(wt, K, cin, cout)
+    return _pack_bytes(lib.xv_packed_weights_f16bf8_bytes, lib.xv_pack_weights_f16bf8, "xv_pack_weights_f16bf8", Packed8,
+                       (_f32(w3d, "w"),), w3d.shape)
 
 
 def tdnn_layer8(x, R, w, bias, scale, shift, act, alpha, dilation, row_valid, y, status=None):
     """f16bf8 layer.  x: SplitBuf in FMT_SPLIT8; y: contiguous fp32 tensor [>=R, C] or SplitBuf of either format; w: Packed8;
     status: int32 device tensor whose bit 0 is set when a FMT_SPLIT8 output had to be clamped (None: not reported)."""
     lib = require_gpu()
-    assert isinstance(w, Packed8) and isinstance(x, SplitBuf) and x.fmt == FMT_SPLIT8
-    assert x.channels == w.cin and x.rows >= R
-    if isinstance(y, SplitBuf):
-        assert y.channels == w.cout and y.rows >= R
-        yp, ldy, yfmt = ctypes.c_void_p(y.ptr), 0, y.fmt
-    else:
-        _rows2d(y, "y"); assert y.shape[1] == w.cout and y.shape[0] >= R
-        yp, ldy, yfmt = _ptr(y), y.stride(0), FMT_F32
-    if row_valid is not None:
-        assert row_valid.is_cuda and row_valid.numel() >= R and row_valid.element_size() == 1
-    _check(lib.xv_tdnn_layer_f16bf8(ctypes.c_void_p(x.ptr), int(R), w.cin, _ptr(w.wt), _ptr(bias), _ptr(scale), _ptr(shift), int(act),
-                                    _ptr(alpha), w.K, int(dilation), w.cout, _ptr(row_valid), yp, yfmt, ldy, _ptr(status), _stream()),
+    assert isinstance(w, Packed8)
+    xp = _operand(x, w.cin, R, "x", (FMT_SPLIT8,))[0]
+    yp, ldy, yfmt = _operand(y, w.cout, R, "y", (FMT_F32, FMT_SPLIT, FMT_SPLIT8))
+    _check(lib.xv_tdnn_layer_f16bf8(xp, int(R), w.cin, _ptr(w.wt), _ptr(bias), _ptr(scale), _ptr(shift), int(act), _ptr(alpha), w.K,
+                                    int(dilation), w.cout, _valid(row_valid, R), yp, yfmt, ldy, _ptr(status), _stream()),
            "xv_tdnn_layer_f16bf8")
 
 
 def tdnn_layer_pool8(x, R, w, bias, scale, shift, act, alpha, dilation, row_valid, block_stats):
     """tdnn_layer_pool in the f16bf8 arithmetic (x: SplitBuf in FMT_SPLIT8, w: Packed8)."""
     lib = require_gpu()
-    assert isinstance(w, Packed8) and isinstance(x, SplitBuf) and x.fmt == FMT_SPLIT8
-    assert x.channels == w.cin and x.rows >= R
-    _f32(block_stats, "block_stats")
-    assert block_stats.numel() >= block_stats_floats(R, w.cout), "block_stats too small"
-    if row_valid is not None:
-        assert row_valid.is_cuda and row_valid.numel() >= R and row_valid.element_size() == 1
-    _check(lib.xv_tdnn_layer_pool_f16bf8(ctypes.c_void_p(x.ptr), int(R), w.cin, _ptr(w.wt), _ptr(bias), _ptr(scale), _ptr(shift),
-                                         int(act), _ptr(alpha), w.K, int(dilation), w.cout, _ptr(row_valid), _ptr(block_stats),
-                                         _stream()), "xv_tdnn_layer_pool_f16bf8")
+    assert isinstance(w, Packed8)
+    xp = _operand(x, w.cin, R, "x", (FMT_SPLIT8,))[0]
+    _check(lib.xv_tdnn_layer_pool_f16bf8(xp, int(R), w.cin, _ptr(w.wt), _ptr(bias), _ptr(scale), _ptr(shift), int(act), _ptr(alpha), w.K,
+                                         int(dilation), w.cout, _valid(row_valid, R), _block_stats(block_stats, R, w.cout), _stream()),
+           "xv_tdnn_layer_pool_f16bf8")
 
 
-class PackedPair(object):
+class PackedPair(_Packed):
     """Weights of two consecutive K = 1 layers in the stage order of xv_tdnn_pair_pool_bf16x3."""
-
-    def __init__(self, wt, cin, cmid, cout):
-        self.wt, self.cin, self.cmid, self.cout = wt, cin, cmid, cout
+    __slots__ = ("wt", "cin", "cmid", "cout")
 
 
 def pair_supported(cin, cmid, cout):
     return int(load().xv_packed_pair_bf16x3_bytes(int(cin), int(cmid), int(cout))) > 0
 
 
-def pack_pair_bf16x3(w1, w2):
-    """w1[Cin, Cmid], w2[Cmid, Cout] (device fp32, TF's [in, out] order) -> PackedPair."""
-    import torch
+def _pack_pair(arith, cls, w1, w2):
+    """The pair packing of either arithmetic ("bf16x3" / "f16bf8": the suffix of its entry points)."""
     lib = require_gpu()
     _f32(w1, "w1"); _f32(w2, "w2")
     assert w1.dim() == 2 and w2.dim() == 2 and w1.shape[1] == w2.shape[0]
-    cin, cmid, cout = int(w1.shape[0]), int(w1.shape[1]), int(w2.shape[1])
-    nbytes = int(lib.xv_packed_pair_bf16x3_bytes(cin, cmid, cout))
-    if nbytes == 0:
-        raise XvectorHipError("xv_pack_pair_bf16x3: unsupported shape %d -> %d -> %d" % (cin, cmid, cout))
-    wt = torch.empty(nbytes, dtype=torch.uint8, device=w1.device)
-    _check(lib.xv_pack_pair_bf16x3(_ptr(w1.contiguous()), _ptr(w2.contiguous()), cin, cmid, cout, _ptr(wt), _stream()),
-           "xv_pack_pair_bf16x3")
-    return PackedPair(wt, cin, cmid, cout)
+    return _pack_bytes(getattr(lib, "xv_packed_pair_%s_bytes" % arith), getattr(lib, "xv_pack_pair_" + arith), "xv_pack_pair_" + arith,
+                       cls, (w1, w2), (w1.shape[0], w1.shape[1], w2.shape[1]), unsupported="%d -> %d -> %d")
 
 
-class PackedPair8(object):
+def _pair_pool(arith, cls, fmt, x, R, w, p1, p2, act, row_valid, block_stats, *status):
+    """The pair launch of either arithmetic: ``w`` a ``cls``, ``x`` a SplitBuf in ``fmt``; ``status``: the extra pointer argument
+    of the f16bf8 entry point."""
+    lib = require_gpu()
+    assert isinstance(w, cls)
+    xp = _operand(x, w.cin, R, "x", (fmt,))[0]
+    name = "xv_tdnn_pair_pool_" + arith
+    _check(getattr(lib, name)(xp, int(R), w.cin, w.cmid, w.cout, _ptr(w.wt), _ptr(p1[0]), _ptr(p1[1]), _ptr(p1[2]), _ptr(p1[3]),
+                              _ptr(p2[0]), _ptr(p2[1]), _ptr(p2[2]), _ptr(p2[3]), int(act), _valid(row_valid, R),
+                              _block_stats(block_stats, R, w.cout), *status, _stream()), name)
+
+
+def pack_pair_bf16x3(w1, w2):
+    """w1[Cin, Cmid], w2[Cmid, Cout] (device fp32, TF's [in, out] order) -> PackedPair."""
+    return _pack_pair("bf16x3", PackedPair, w1, w2)
+
+
+class PackedPair8(_Packed):
     """Weights of two consecutive K = 1 layers in the stage order of xv_tdnn_pair_pool_f16bf8."""
-
-    def __init__(self, wt, cin, cmid, cout):
-        self.wt, self.cin, self.cmid, self.cout = wt, cin, cmid, cout
+    __slots__ = ("wt", "cin", "cmid", "cout")
 
 
 def pair8_supported(cin, cmid, cout):
@@ -721,64 +737,34 @@ def pair8_supported(cin, cmid, cout):
 
 def pack_pair_f16bf8(w1, w2):
     """w1[Cin, Cmid], w2[Cmid, Cout] (device fp32, TF's [in, out] order) -> PackedPair8."""
-    import torch
-    lib = require_gpu()
-    _f32(w1, "w1"); _f32(w2, "w2")
-    assert w1.dim() == 2 and w2.dim() == 2 and w1.shape[1] == w2.shape[0]
-    cin, cmid, cout = int(w1.shape[0]), int(w1.shape[1]), int(w2.shape[1])
-    nbytes = int(lib.xv_packed_pair_f16bf8_bytes(cin, cmid, cout))
-    if nbytes == 0:
-        raise XvectorHipError("xv_pack_pair_f16bf8: unsupported shape %d -> %d -> %d" % (cin, cmid, cout))
-    wt = torch.empty(nbytes, dtype=torch.uint8, device=w1.device)
-    _check(lib.xv_pack_pair_f16bf8(_ptr(w1.contiguous()), _ptr(w2.contiguous()), cin, cmid, cout, _ptr(wt), _stream()),
-           "xv_pack_pair_f16bf8")
-    return PackedPair8(wt, cin, cmid, cout)
+    return _pack_pair("f16bf8", PackedPair8, w1, w2)
 
 
 def tdnn_pair_pool8(x, R, w, p1, p2, act, row_valid, block_stats, status=None):
     """tdnn_pair_pool in the f16bf8 arithmetic: x: SplitBuf in FMT_SPLIT8; w: PackedPair8; status: int32 device tensor (bit 0:
     the intermediate activation was clamped)."""
-    lib = require_gpu()
-    assert isinstance(x, SplitBuf) and isinstance(w, PackedPair8)
-    assert x.channels == w.cin and x.rows >= R and x.fmt == FMT_SPLIT8
-    _f32(block_stats, "block_stats"); assert block_stats.numel() >= block_stats_floats(R, w.cout)
-    if row_valid is not None:
-        assert row_valid.is_cuda and row_valid.numel() >= R and row_valid.element_size() == 1
-    _check(lib.xv_tdnn_pair_pool_f16bf8(ctypes.c_void_p(x.ptr), int(R), w.cin, w.cmid, w.cout, _ptr(w.wt), _ptr(p1[0]), _ptr(p1[1]),
-                                        _ptr(p1[2]), _ptr(p1[3]), _ptr(p2[0]), _ptr(p2[1]), _ptr(p2[2]), _ptr(p2[3]), int(act),
-                                        _ptr(row_valid), _ptr(block_stats), _ptr(status), _stream()), "xv_tdnn_pair_pool_f16bf8")
+    _pair_pool("f16bf8", PackedPair8, FMT_SPLIT8, x, R, w, p1, p2, act, row_valid, block_stats, _ptr(status))
 
 
 def tdnn_pair_pool(x, R, w, p1, p2, act, row_valid, block_stats):
     """Two K = 1 layers + pooling block statistics in one launch.  x: SplitBuf; w: PackedPair; p1 / p2: (bias, bn_scale,
     bn_shift, act_alpha) device tensors (None allowed) of the first / second layer."""
-    lib = require_gpu()
-    assert isinstance(x, SplitBuf) and isinstance(w, PackedPair)
-    assert x.channels == w.cin and x.rows >= R and x.fmt == FMT_SPLIT
-    _f32(block_stats, "block_stats"); assert block_stats.numel() >= block_stats_floats(R, w.cout)
-    if row_valid is not None:
-        assert row_valid.is_cuda and row_valid.numel() >= R and row_valid.element_size() == 1
-    _check(lib.xv_tdnn_pair_pool_bf16x3(ctypes.c_void_p(x.ptr), int(R), w.cin, w.cmid, w.cout, _ptr(w.wt), _ptr(p1[0]), _ptr(p1[1]),
-                                        _ptr(p1[2]), _ptr(p1[3]), _ptr(p2[0]), _ptr(p2[1]), _ptr(p2[2]), _ptr(p2[3]), int(act),
-                                        _ptr(row_valid), _ptr(block_stats), _stream()), "xv_tdnn_pair_pool_bf16x3")
+    _pair_pool("bf16x3", PackedPair, FMT_SPLIT, x, R, w, p1, p2, act, row_valid, block_stats)
 
 
 def stats_pool_blocks(block_stats, c, row_start, row_len, nchunks, eps, out):
-    import torch
     lib = require_gpu()
     _f32(block_stats, "block_stats"); _f32(out, "out")
-    assert row_start.dtype == torch.int32 and row_len.dtype == torch.int32 and row_start.is_cuda and row_len.is_cuda
+    _chunk_tables(row_start, row_len)
     assert out.shape[1] == 2 * c and out.shape[0] >= nchunks
     _check(lib.xv_stats_pool_blocks_f32(_ptr(block_stats), int(c), _ptr(row_start), _ptr(row_len), int(nchunks), float(eps),
                                         _ptr(out), _stream()), "xv_stats_pool_blocks_f32")
 
 
 def fold_bn(gamma, beta, mean, var, eps):
-    import torch
     lib = require_gpu()
     c = gamma.numel()
-    scale = torch.empty(c, dtype=torch.float32, device=gamma.device)
-    shift = torch.empty(c, dtype=torch.float32, device=gamma.device)
+    scale, shift = _scale_shift(gamma)
     _check(lib.xv_fold_bn_f32(_ptr(_f32(gamma, "gamma")), _ptr(_f32(beta, "beta")), _ptr(_f32(mean, "mean")),
                               _ptr(_f32(var, "var")), float(eps), c, _ptr(scale), _ptr(shift), _stream()),
            "xv_fold_bn_f32")
@@ -808,10 +794,8 @@ def tdnn_layer(x, wp, bias, scale, shift, act, alpha, K, dilation, row_valid, y,
     assert out.shape[1] == cout and out.shape[0] >= R
     if y is not None and y_preact is not None:
         assert y.shape[1] == y_preact.shape[1]
-    if row_valid is not None:
-        assert row_valid.is_cuda and row_valid.numel() >= R and row_valid.element_size() == 1
     _check(lib.xv_tdnn_layer_f32(_ptr(x), R, cin, x.stride(0), _ptr(wp), _ptr(bias), _ptr(scale), _ptr(shift), int(act),
-                                 _ptr(alpha), int(K), int(dilation), cout, _ptr(row_valid), _ptr(y), out.stride(0),
+                                 _ptr(alpha), int(K), int(dilation), cout, _valid(row_valid, R), _ptr(y), out.stride(0),
                                  _ptr(y_preact), _stream()), "xv_tdnn_layer_f32")
 
 
@@ -820,15 +804,14 @@ def stats_pool_workspace_bytes(c, nchunks, max_len, split_rows):
 
 
 def stats_pool(h, row_start, row_len, nchunks, max_len, split_rows, eps, out, workspace=None):
-    import torch
     lib = require_gpu()
     _f32(h, "h"); _f32(out, "out")
-    assert row_start.dtype == torch.int32 and row_len.dtype == torch.int32 and row_start.is_cuda and row_len.is_cuda
+    _chunk_tables(row_start, row_len)
     c = h.shape[1]
     assert out.shape[1] == 2 * c and out.shape[0] >= nchunks
     need = stats_pool_workspace_bytes(c, nchunks, max_len, split_rows)
     if need:
-        assert workspace is not None and workspace.numel() * workspace.element_size() >= need, "pool workspace too small"
+        assert workspace is not None and _nbytes(workspace) >= need, "pool workspace too small"
     _check(lib.xv_stats_pool_f32(_ptr(h), h.stride(0), c, _ptr(row_start), _ptr(row_len), int(nchunks), int(max_len),
                                  int(split_rows), float(eps), _ptr(out), _ptr(workspace), _stream()), "xv_stats_pool_f32")
 
@@ -889,11 +872,6 @@ def chunk_average(e, seg_start, chunk_len, nutts, out):
 # ------------------------------------------------------------------------------------------------
 # training-step wrappers
 # ------------------------------------------------------------------------------------------------
-def _ws(nbytes, device):
-    import torch
-    return torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=device)
-
-
 def chunk_moments(h, row_start, row_len, nchunks, max_len, out, split_rows=512):
     """out[B, 2C] = per-chunk [mean || biased variance]."""
     lib = require_gpu()
@@ -915,11 +893,9 @@ def rows_affine(x, scale, shift, row_valid, y, rows=None, y_split=None):
     """y_split: optional SplitBuf (bf16 split format) that receives a second copy of y."""
     lib = require_gpu()
     R = x.shape[0] if rows is None else int(rows)
-    if y_split is not None:
-        assert y_split.fmt == FMT_SPLIT and y_split.channels == x.shape[1] and y_split.rows >= R
-    _check(lib.xv_rows_affine_split_f32(_ptr(_f32(x, "x")), x.stride(0), R, x.shape[1], _ptr(scale), _ptr(shift), _ptr(row_valid),
-                                        _ptr(_f32(y, "y")), y.stride(0), ctypes.c_void_p(y_split.ptr) if y_split is not None else None,
-                                        _stream()), "xv_rows_affine_split_f32")
+    _check(lib.xv_rows_affine_split_f32(_ptr(_f32(x, "x")), x.stride(0), R, x.shape[1], _ptr(scale), _ptr(shift), _valid(row_valid, R),
+                                        _ptr(_f32(y, "y")), y.stride(0), _split_out(y_split, x.shape[1], R), _stream()),
+           "xv_rows_affine_split_f32")
 
 
 def wgrad_takes_bias(precision, x, dz):
@@ -957,32 +933,24 @@ def col_sums(a, b, sum_a, sum_ab=None):
 
 def bn_act_backward(dh, r, sum_dh, sum_dh_r, mean, var, gamma, eps, n_frames, act, alpha, row_valid, dgamma, dbeta, dz, dz_split=None):
     """dz_split: optional SplitBuf (bf16 split format) that receives a second copy of dz."""
-    import torch
     lib = require_gpu()
     R, c = dh.shape
-    coef = torch.empty(3 * c, dtype=torch.float32, device=dh.device)
-    if dz_split is not None:
-        assert dz_split.fmt == FMT_SPLIT and dz_split.channels == c and dz_split.rows >= R
+    coef = _bn_coef(c, dh.device)
     _check(lib.xv_bn_act_backward_split_f32(_ptr(_f32(dh, "dh")), _ptr(_f32(r, "r")), dh.stride(0), R, c, _ptr(sum_dh), _ptr(sum_dh_r),
                                             _ptr(mean), _ptr(var), _ptr(gamma), float(eps), float(n_frames), int(act), float(alpha),
-                                            _ptr(row_valid), _ptr(dgamma), _ptr(dbeta), _ptr(coef), _ptr(_f32(dz, "dz")),
-                                            ctypes.c_void_p(dz_split.ptr) if dz_split is not None else None, _stream()),
-           "xv_bn_act_backward_split_f32")
+                                            _valid(row_valid, R), _ptr(dgamma), _ptr(dbeta), _ptr(coef), _ptr(_f32(dz, "dz")),
+                                            _split_out(dz_split, c, R), _stream()), "xv_bn_act_backward_split_f32")
 
 
 def bn_act_backward_parts(dh, r, workspace, mean, var, gamma, eps, n_frames, act, alpha, row_valid, dgamma, dbeta, dz, dz_split=None):
     """bn_act_backward from the partial sums a producer left in ``workspace`` (tdnn_layer3_sums): no col_sums pass."""
-    import torch
     lib = require_gpu()
     R, c = dh.shape
-    coef = torch.empty(3 * c, dtype=torch.float32, device=dh.device)
-    if dz_split is not None:
-        assert dz_split.fmt == FMT_SPLIT and dz_split.channels == c and dz_split.rows >= R
+    coef = _bn_coef(c, dh.device)
     _check(lib.xv_bn_act_backward_parts_f32(_ptr(_f32(dh, "dh")), _ptr(_f32(r, "r")), dh.stride(0), R, c, _ptr(workspace), _ptr(mean),
-                                            _ptr(var), _ptr(gamma), float(eps), float(n_frames), int(act), float(alpha), _ptr(row_valid),
-                                            _ptr(dgamma), _ptr(dbeta), _ptr(coef), _ptr(_f32(dz, "dz")),
-                                            ctypes.c_void_p(dz_split.ptr) if dz_split is not None else None, _stream()),
-           "xv_bn_act_backward_parts_f32")
+                                            _ptr(var), _ptr(gamma), float(eps), float(n_frames), int(act), float(alpha),
+                                            _valid(row_valid, R), _ptr(dgamma), _ptr(dbeta), _ptr(coef), _ptr(_f32(dz, "dz")),
+                                            _split_out(dz_split, c, R), _stream()), "xv_bn_act_backward_parts_f32")
 
 
 BN_SMALL_MAX_ROWS = 1024
@@ -1017,19 +985,15 @@ def col_sums_merge(workspace, rows, c, sum_a, sum_ab=None):
 def pool_bn_act_backward(h, r, row_start, row_len, nchunks, pooled, dpooled, chunk_moments_r, mean, var, gamma, eps, n_frames, act, alpha,
                          dgamma, dbeta, dz, dz_split=None):
     """Backward of [statistics pooling -> BN -> activation] of the last frame-level layer (xv_pool_bn_act_backward_f32)."""
-    import torch
     lib = require_gpu()
     R, c = r.shape
-    coef = torch.empty(3 * c, dtype=torch.float32, device=r.device)
+    coef = _bn_coef(c, r.device)
     assert h.shape == r.shape and h.stride(0) == r.stride(0) == dz.stride(0)
-    if dz_split is not None:
-        assert dz_split.fmt == FMT_SPLIT and dz_split.channels == c and dz_split.rows >= R
     _check(lib.xv_pool_bn_act_backward_f32(_ptr(_f32(h, "h")), _ptr(_f32(r, "r")), r.stride(0), c, _ptr(row_start), _ptr(row_len),
                                            int(nchunks), R, _ptr(_f32(pooled, "pooled")), _ptr(_f32(dpooled, "dpooled")),
                                            _ptr(_f32(chunk_moments_r, "chunk_moments")), _ptr(mean), _ptr(var), _ptr(gamma), float(eps),
                                            float(n_frames), int(act), float(alpha), _ptr(dgamma), _ptr(dbeta), _ptr(coef),
-                                           _ptr(_f32(dz, "dz")), ctypes.c_void_p(dz_split.ptr) if dz_split is not None else None,
-                                           _stream()), "xv_pool_bn_act_backward_f32")
+                                           _ptr(_f32(dz, "dz")), _split_out(dz_split, c, R), _stream()), "xv_pool_bn_act_backward_f32")
 
 
 def pool_backward(h, row_start, row_len, nchunks, pooled, dpooled, dh):
@@ -1099,9 +1063,8 @@ def pack_minibatch(src, B, T, F, gap, dst):
 
 def dropout(x, seed, keep_prob, rows=None):
     """In-place tf.nn.dropout on x[R, C] with the stateless mask of include/xvector_hip.h (same call = backward)."""
-    import torch
     lib = require_gpu()
-    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1, "x must be a row-major cuda float32 matrix"
+    _rows2d(x, "x")
     R = x.shape[0] if rows is None else int(rows)
     _check(lib.xv_dropout_f32(_ptr(x), x.stride(0), R, x.shape[1], int(seed) & 0xFFFFFFFFFFFFFFFF, float(keep_prob), _stream()),
            "xv_dropout_f32")
@@ -1133,13 +1096,12 @@ def cmn_sliding_scatter(x, utt_start, utt_len, n_utts, max_len, cmn_window, cent
     import torch
     lib = require_gpu()
     _f32(x, "x")
-    assert y.is_cuda and y.dtype == torch.float32 and y.dim() == 2 and y.stride(1) == 1 and y.shape[1] >= x.shape[1]
-    for t in (utt_start, utt_len, dst_row):
-        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
-    assert dst_row.numel() >= x.shape[0] and utt_start.numel() >= n_utts and utt_len.numel() >= n_utts
-    _check(lib.xv_cmn_sliding_scatter_f32(_ptr(x), x.stride(0), x.shape[1], _ptr(utt_start), _ptr(utt_len), int(n_utts), int(max_len),
-                                          int(cmn_window), 1 if center else 0, int(min_window), _ptr(dst_row), _ptr(y), y.stride(0),
-                                          _stream()), "xv_cmn_sliding_scatter_f32")
+    _rows2d(y, "y"); assert y.shape[1] >= x.shape[1]
+    i32 = torch.int32
+    _check(lib.xv_cmn_sliding_scatter_f32(_ptr(x), x.stride(0), x.shape[1], _dev(utt_start, i32, "utt_start", n_utts),
+                                          _dev(utt_len, i32, "utt_len", n_utts), int(n_utts), int(max_len), int(cmn_window),
+                                          1 if center else 0, int(min_window), _dev(dst_row, i32, "dst_row", x.shape[0]), _ptr(y),
+                                          y.stride(0), _stream()), "xv_cmn_sliding_scatter_f32")
 
 
 def vad_compact(vad, utt_start, utt_len):
@@ -1148,14 +1110,12 @@ def vad_compact(vad, utt_start, utt_len):
     import torch
     lib = require_gpu()
     _f32(vad, "vad")
-    for t in (utt_start, utt_len):
-        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
+    starts, lens = _dev(utt_start, torch.int32, "utt_start"), _dev(utt_len, torch.int32, "utt_len")
     n_utts, n_frames = utt_start.numel(), vad.numel()
     assert vad.dim() == 1 and utt_len.numel() == n_utts
     count = torch.zeros(n_utts, dtype=torch.int32, device=vad.device)
     rows = torch.full((max(n_frames, 1),), -1, dtype=torch.int32, device=vad.device)
-    _check(lib.xv_vad_compact_i32(_ptr(vad), _ptr(utt_start), _ptr(utt_len), n_utts, n_frames, _ptr(count), _ptr(rows), _stream()),
-           "xv_vad_compact_i32")
+    _check(lib.xv_vad_compact_i32(_ptr(vad), starts, lens, n_utts, n_frames, _ptr(count), _ptr(rows), _stream()), "xv_vad_compact_i32")
     return count, rows
 
 
@@ -1186,10 +1146,9 @@ def egs_chunks(x, utt_start, utt_len, voiced_count, voiced_row, table, voiced_co
     import numpy as np
     import torch
     lib = require_gpu()
-    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1]
-    assert y.is_cuda and y.dtype == torch.float16 and y.is_contiguous()
-    for t in (utt_start, utt_len, voiced_count, voiced_row):
-        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
+    _f32_rows(x, "x"); _dev(y, torch.float16, "y")
+    for t, name in ((utt_start, "utt_start"), (utt_len, "utt_len"), (voiced_count, "voiced_count"), (voiced_row, "voiced_row")):
+        _dev(t, torch.int32, name)
     n_utts = utt_start.numel()
     assert utt_len.numel() == n_utts and voiced_count.numel() == n_utts and voiced_row.numel() >= x.shape[0]
     assert len(voiced_counts_host) == n_utts
@@ -1217,11 +1176,11 @@ def backend_prepare(x, out, side, num_utts=None, mean=None, lda=None, lda_offset
     for t, shape in ((mean, (dim_in,)), (lda_offset, (dim,)), (plda_transform, (dim, dim)), (plda_mean, (dim,)), (plda_psi, (dim,)),
                      (r, (n_rows,))):
         if t is not None:
-            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape, shape
+            assert tuple(_f32(t, "a parameter vector").shape) == shape, shape
     if lda is not None:
         _f32_rows(lda, "lda"); assert lda.shape[1] == dim_in
     if num_utts is not None:
-        assert num_utts.is_cuda and num_utts.dtype == torch.int32 and num_utts.is_contiguous() and num_utts.numel() >= n_rows
+        _dev(num_utts, torch.int32, "num_utts", n_rows)
     _check(lib.xv_backend_prepare_f32(_ptr(x), x.stride(0), n_rows, dim_in, _ptr(num_utts), _ptr(mean), _ptr(lda),
                                       lda.stride(0) if lda is not None else 0, _ptr(lda_offset), dim, 1 if length_norm else 0,
                                       _ptr(plda_transform), _ptr(plda_mean), _ptr(plda_psi), int(side), _ptr(out), out.stride(0),
@@ -1231,12 +1190,10 @@ def backend_prepare(x, out, side, num_utts=None, mean=None, lda=None, lda_offset
 def score_matrix(e, t, r, out):
     """out[Ne, Nt] = e[Ne, Kpad] t[Nt, Kpad]^T + r[Ne] (r may be None), fixed summation order (k ascending).  e and t may be
     slices of wider buffers with one common row stride, passed as ldk (a multiple of 4, bases 16-byte aligned)."""
-    import torch
     lib = require_gpu()
     _f32_rows(e, "e"); _f32_rows(t, "t"); _f32(out, "out")
     assert e.shape[1] == t.shape[1] and e.stride(0) == t.stride(0) and out.shape[0] >= e.shape[0] and out.shape[1] >= t.shape[0]
-    if r is not None:
-        assert r.is_cuda and r.dtype == torch.float32 and r.is_contiguous() and r.numel() >= e.shape[0]
+    assert r is None or _f32(r, "r").numel() >= e.shape[0]
     _check(lib.xv_score_matrix_f32(_ptr(e), _ptr(t), e.stride(0), e.shape[1], e.shape[0], t.shape[0], _ptr(r), _ptr(out), out.stride(0),
                                    _stream()), "xv_score_matrix_f32")
 
@@ -1248,12 +1205,10 @@ def score_pairs(e, t, r, e_idx, t_idx, out):
     lib = require_gpu()
     _f32_rows(e, "e"); _f32_rows(t, "t")
     assert e.shape[1] == t.shape[1] and e.stride(0) == t.stride(0)
-    for ix in (e_idx, t_idx):
-        assert ix.is_cuda and ix.dtype == torch.int32 and ix.is_contiguous()
+    _dev(e_idx, torch.int32, "e_idx"); _dev(t_idx, torch.int32, "t_idx")
     m = e_idx.numel()
-    assert t_idx.numel() == m and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= m
-    if r is not None:
-        assert r.is_cuda and r.dtype == torch.float32 and r.is_contiguous() and r.numel() >= e.shape[0]
+    assert t_idx.numel() == m and _f32(out, "out").numel() >= m
+    assert r is None or _f32(r, "r").numel() >= e.shape[0]
     if m:
         lo = torch.stack([e_idx.min(), t_idx.min(), e_idx.max() - e.shape[0], t_idx.max() - t.shape[0]]).cpu().tolist()
         if lo[0] < 0 or lo[1] < 0 or lo[2] >= 0 or lo[3] >= 0:
@@ -1265,12 +1220,9 @@ def score_pairs(e, t, r, e_idx, t_idx, out):
 def topk_row_stats(scores, top_n, mean, std):
     """mean[i], std[i] = mean and population std of the top_n largest values of row i of scores[R, C] (exact selection, fp64 sums;
     see include/xvector_hip.h).  scores may be a row slice of a wider buffer: its row stride is passed as ld."""
-    import torch
     lib = require_gpu()
-    assert scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and scores.stride(1) == 1
-    n_rows, n_cols = scores.shape
-    for t in (mean, std):
-        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n_rows
+    n_rows, n_cols = _rows2d(scores, "scores").shape
+    assert _f32(mean, "mean").numel() >= n_rows and _f32(std, "std").numel() >= n_rows
     _check(lib.xv_topk_row_stats_f32(_ptr(scores), scores.stride(0), n_rows, n_cols, int(top_n), _ptr(mean), _ptr(std), _stream()),
            "xv_topk_row_stats_f32")
 
@@ -1286,17 +1238,16 @@ def moment_stats(x, sum, outer, dim=None, workspace=None):
     device buffer of moment_stats_workspace_bytes(N, dim) bytes (None: allocated here)."""
     import torch
     lib = require_gpu()
-    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    _rows2d(x, "x")
     n_rows = x.shape[0]
     dim = x.shape[1] if dim is None else int(dim)
     assert dim <= x.shape[1]
-    assert sum.is_cuda and sum.dtype == torch.float64 and sum.is_contiguous() and sum.numel() >= dim
     assert outer.is_cuda and outer.dtype == torch.float64 and outer.dim() == 2 and outer.stride(1) == 1
     assert outer.shape[0] >= dim and outer.shape[1] >= dim
     if workspace is None:
         workspace = _ws(lib.xv_moment_stats_workspace_bytes(n_rows, dim), x.device)
-    _check(lib.xv_moment_stats_f64(_ptr(x), x.stride(0), n_rows, dim, _ptr(sum), _ptr(outer), outer.stride(0), _ptr(workspace),
-                                   workspace.numel() * workspace.element_size(), _stream()), "xv_moment_stats_f64")
+    _check(lib.xv_moment_stats_f64(_ptr(x), x.stride(0), n_rows, dim, _dev(sum, torch.float64, "sum", dim), _ptr(outer), outer.stride(0),
+                                   _ptr(workspace), _nbytes(workspace), _stream()), "xv_moment_stats_f64")
 
 
 def ahc_average_workspace_bytes(n):
@@ -1312,21 +1263,20 @@ def ahc_average(scores, threshold, min_clusters, merge_a, merge_b, merge_score, 
     import math
     import torch
     lib = require_gpu()
-    assert scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and scores.stride(1) == 1
+    _rows2d(scores, "scores")
     n = scores.shape[0]
     assert scores.shape[1] == n and 1 <= n <= AHC_MAX_N, "scores must be [n, n], 1 <= n <= %d" % AHC_MAX_N
     assert scores.stride(0) >= n and scores.stride(0) % 4 == 0 and scores.data_ptr() % 16 == 0
     assert 1 <= int(min_clusters) <= n and not math.isnan(float(threshold))
-    for t, m in ((merge_a, n - 1), (merge_b, n - 1), (n_merges, 1), (labels, n)):
-        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= m
-    assert merge_score.is_cuda and merge_score.dtype == torch.float64 and merge_score.is_contiguous() and merge_score.numel() >= n - 1
     need = lib.xv_ahc_average_workspace_bytes(n)
     if workspace is None:
         workspace = _ws(need, scores.device)
-    assert workspace.is_cuda and workspace.numel() * workspace.element_size() >= need, "ahc workspace too small"
-    _check(lib.xv_ahc_average_f64(_ptr(scores), scores.stride(0), n, float(threshold), int(min_clusters), _ptr(merge_a), _ptr(merge_b),
-                                  _ptr(merge_score), _ptr(n_merges), _ptr(labels), _ptr(workspace),
-                                  workspace.numel() * workspace.element_size(), _stream()), "xv_ahc_average_f64")
+    assert workspace.is_cuda and _nbytes(workspace) >= need, "ahc workspace too small"
+    i32 = torch.int32
+    _check(lib.xv_ahc_average_f64(_ptr(scores), scores.stride(0), n, float(threshold), int(min_clusters),
+                                  _dev(merge_a, i32, "merge_a", n - 1), _dev(merge_b, i32, "merge_b", n - 1),
+                                  _dev(merge_score, torch.float64, "merge_score", n - 1), _dev(n_merges, i32, "n_merges", 1),
+                                  _dev(labels, i32, "labels", n), _ptr(workspace), _nbytes(workspace), _stream()), "xv_ahc_average_f64")
 
 
 def mfcc(samples, utt_offset, utt_samples, utt_row0, utt_key, total_rows, tables, opts, feats, logmel=None):
@@ -1337,11 +1287,10 @@ def mfcc(samples, utt_offset, utt_samples, utt_row0, utt_key, total_rows, tables
     import torch
     lib = require_gpu()
     assert samples.is_cuda and samples.dim() == 1 and samples.dtype in (torch.int16, torch.float32)
-    for t in (utt_offset, utt_samples, utt_row0, utt_key):
-        assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == utt_offset.numel()
+    for t, name in ((utt_offset, "utt_offset"), (utt_samples, "utt_samples"), (utt_row0, "utt_row0"), (utt_key, "utt_key")):
+        _dev(t, torch.int64, name); assert t.numel() == utt_offset.numel()
     for t in (feats, logmel):
-        if t is not None:
-            assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] >= total_rows
+        assert t is None or _rows2d(t, "feats / logmel").shape[0] >= total_rows
     tb = tables
     _check(lib.xv_mfcc_f32(_ptr(samples), 0 if samples.dtype == torch.int16 else 1, _ptr(utt_offset), _ptr(utt_samples),
                            _ptr(utt_row0), _ptr(utt_key), int(utt_offset.numel()), int(total_rows), _ptr(tb["window"]),
@@ -1358,18 +1307,12 @@ def vad_energy(feats, utt_row0, n_frames, vopts, out):
     utt_row0[u] .. + n_frames[u] (int64 / int32 device tensors); out[rows] float32 receives 0.0 / 1.0."""
     import torch
     lib = require_gpu()
-    assert feats.is_cuda and feats.dtype == torch.float32 and feats.dim() == 2 and feats.stride(1) == 1
+    _rows2d(feats, "feats"); _f32(out, "out")
     assert utt_row0.is_cuda and utt_row0.dtype == torch.int64 and n_frames.is_cuda and n_frames.dtype == torch.int32
-    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
     _check(lib.xv_vad_energy_f32(_ptr(feats), feats.stride(0), _ptr(utt_row0), _ptr(n_frames), int(utt_row0.numel()),
                                  float(vopts.vad_energy_threshold), float(vopts.vad_energy_mean_scale),
                                  int(vopts.vad_frames_context), float(vopts.vad_proportion_threshold), _ptr(out), _stream()),
            "xv_vad_energy_f32")
-
-
-def _dev(t, dtype, name):
-    assert t.is_cuda and t.dtype == dtype and t.is_contiguous(), "%s must be a contiguous cuda %s tensor" % (name, dtype)
-    return _ptr(t)
 
 
 def augment_power(sig, segments, tiles, tile_sumsq):
@@ -1473,13 +1416,6 @@ def am_margin(cosines, labels, scale, margin):
 # ------------------------------------------------------------------------------------------------
 # self-attentive statistics pooling (local/tf/models.py:1036-1052)
 # ------------------------------------------------------------------------------------------------
-def _rows2d(t, name):
-    """2-D cuda float32 tensor whose rows are contiguous (a column slice of a wider buffer is fine)."""
-    import torch
-    assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1, "%s must be cuda float32 rows" % name
-    return t
-
-
 def attention_scores(u, v, scores, nonlin=None, rows=None):
     """scores[r] = sum_c v[c]*tanh(u[r,c]); nonlin (optional, same shape as u) receives tanh(u)."""
     lib = require_gpu()
@@ -1495,10 +1431,9 @@ def attention_scores(u, v, scores, nonlin=None, rows=None):
 
 
 def attention_softmax(scores, row_start, row_len, nchunks, att):
-    import torch
     lib = require_gpu()
     _f32(scores, "scores"); _f32(att, "att")
-    assert row_start.dtype == torch.int32 and row_len.dtype == torch.int32 and row_start.is_cuda and row_len.is_cuda
+    _chunk_tables(row_start, row_len)
     assert att.numel() >= scores.numel()
     _check(lib.xv_attention_softmax_f32(_ptr(scores), _ptr(row_start), _ptr(row_len), int(nchunks), _ptr(att), _stream()),
            "xv_attention_softmax_f32")
@@ -1511,15 +1446,14 @@ def attention_pool_workspace_bytes(c, nchunks, max_len, split_rows):
 def attention_pool(h, att, row_start, row_len, nchunks, max_len, split_rows, eps, out, workspace=None):
     """out[b] = [sum_t att h | sqrt(sum_t att h^2 - (sum_t att h)^2 + eps)] over the rows of chunk b; h: [R, C] rows (may be a
     column slice of a wider buffer)."""
-    import torch
     lib = require_gpu()
     _rows2d(h, "h"); _f32(att, "att"); _f32(out, "out")
-    assert row_start.dtype == torch.int32 and row_len.dtype == torch.int32 and row_start.is_cuda and row_len.is_cuda
+    _chunk_tables(row_start, row_len)
     c = h.shape[1]
     assert out.shape[1] == 2 * c and out.shape[0] >= nchunks and att.numel() >= h.shape[0]
     need = attention_pool_workspace_bytes(c, nchunks, max_len, split_rows)
     if need:
-        assert workspace is not None and workspace.numel() * workspace.element_size() >= need, "attention pool workspace too small"
+        assert workspace is not None and _nbytes(workspace) >= need, "attention pool workspace too small"
     _check(lib.xv_attention_pool_f32(_ptr(h), h.stride(0), c, _ptr(att), _ptr(row_start), _ptr(row_len), int(nchunks), int(max_len),
                                      int(split_rows), float(eps), _ptr(out), _ptr(workspace), _stream()), "xv_attention_pool_f32")
 
