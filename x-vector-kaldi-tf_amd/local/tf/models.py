@@ -35,7 +35,7 @@ if _PKG_ROOT not in sys.path:
     sys.path.insert(0, _PKG_ROOT)
 
 import kaldi_io  # noqa: E402  (the sibling module, as in the reference)
-from xvector_amd import engine, frontend, synthetic, topology, weights as wio  # noqa: E402
+from xvector_amd import engine, extract_stream, frontend, synthetic, topology, weights as wio  # noqa: E402
 
 VAR2STD_EPSILON = topology.VAR2STD_EPSILON        # models.py:16
 
@@ -45,13 +45,6 @@ def _device():
     if dev:
         return dev
     return "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0"))
-
-
-_Subset = engine._Rows          # utterances idx of a window, not materialised (multi-GPU shares of a stream window)
-
-
-class _Cancelled(Exception):
-    pass
 
 
 class VectorCollector(object):
@@ -140,13 +133,6 @@ def _checkpoint_identity(model_dir):
         except OSError:
             pass
     return (tuple(ident) or None,)
-
-
-class _Held(object):
-    """Keeps a gathered block alive as the holder of an ``ArkMats`` piece and hands out its utterances as views."""
-
-    def __init__(self, feats, offsets):
-        self.buf, self.addr, self._feats, self._off = feats, feats.ctypes.data, feats, offsets
 
 
 class _StepDone(object):
@@ -544,415 +530,76 @@ class Model(object):
         ``blocks()`` method (kaldi_io.MatScp).  Under torchrun every
         rank reads the same stream and extracts its share of each window (one gather per window to rank 0) unless
         ``distributed=False`` says that the caller sharded the input itself."""
-        import queue
-        import threading
         start_time = time.time()
         if distributed and vad_stream is None and cmn_window <= 0 and self._extract_byte_ranges(
                 input_stream, output_stream, model_dir, min_chunk_size, chunk_size, use_gpu, logger):
             return
-        # A reader thread parses the next window of the ark stream while the GPU works on the current one
-        # (bounded queue: at most 2 parsed windows in memory).  Order is preserved; a parse error is re-raised here.
-        windows = queue.Queue(maxsize=2)
-        # The utterances are used IN PLACE: the stream is read (readinto) into a few long-lived arenas, the native scanner
-        # locates the matrices there, and the native packer copies them from the arena straight into the pinned staging sets
-        # -- one host copy between the ark bytes and the H2D DMA, no fresh pages per window (at GB/s the page faults of
-        # ever-new arrays and the extra gather copy cost more than the parsing).  An arena goes back to the pool once the
-        # window's batches are packed.  Without libxvector_host.so the generic (gathering) block reader is used.
-        in_place = kaldi_io._host_lib() is not None and (hasattr(input_stream, "read") or hasattr(input_stream, "windows"))
-        arena_bytes = int(self.arena_bytes)
-        cancel = threading.Event()                    # set when the consumer gives up (e.g. the model failed to load)
-        pool = queue.Queue()
-        mine = []                                     # arenas this call took from the process-wide free list
-
-        def take_arena():
-            if len(mine) < self.arena_count and pool.empty():
-                mine.append(kaldi_io.arena_acquire(arena_bytes))
-                return mine[-1]
-            while True:
-                try:
-                    return pool.get(timeout=0.2)
-                except queue.Empty:
-                    if cancel.is_set():           # the consumer gave up: nobody will ever return an arena
-                        raise _Cancelled()
-
-        def prefetched(blocks, depth=2):
-            """``blocks`` read by a thread of its own, ``depth`` ahead (the VAD table beside the features: its reads release the
-            interpreter lock, so the two files are read side by side)."""
-            q, end = queue.Queue(maxsize=depth), object()
-
-            def run():
-                def put(x):
-                    while not cancel.is_set():
-                        try:
-                            q.put(x, timeout=0.2)
-                            return True
-                        except queue.Full:
-                            pass
-                    return False
-                try:
-                    for b in blocks:
-                        if not put(b):
-                            return
-                    put(end)
-                except BaseException as e:      # noqa: B902 -- forwarded to the consumer
-                    put(e)
-            threading.Thread(target=run, daemon=True).start()
-            while True:
-                b = q.get()
-                if b is end:
-                    return
-                if isinstance(b, BaseException):
-                    raise b
-                yield b
-
-        def reader():
+        # three threads (xvector_amd.extract_stream): a reader parses the windows, this one runs them, a writer serialises the
+        # vectors.  The reader starts BEFORE the model is loaded: the first arena is read and scanned while the weights are packed
+        reader = extract_stream.WindowReader(self, input_stream, vad_stream)
+        try:
             try:
-                keys, vads = [], None
-                vad_it, pending = None, {}
-                vad_blocks, vad_cur = None, None               # block source of the VAD table and [keys, values, offsets, position] in it
-                if vad_stream is not None:
-                    vads = frontend.VadRuns()
-                    # an ark stream or a table with blocks() (kaldi_io.VecScp) is read in scanner passes; while its keys arrive in the
-                    # order of the features -- the recipe's tables do -- whole runs of a block go into the window (frontend.VadRuns),
-                    # no Python step per utterance
-                    if hasattr(vad_stream, "read") or hasattr(vad_stream, "blocks"):
-                        vad_blocks = prefetched(kaldi_io.read_vec_flt_ark_blocks(vad_stream) if hasattr(vad_stream, "read") else vad_stream.blocks())
+                self._may_borrow = os.environ.get("XVECTOR_MODEL_CACHE", "1") != "0"
+                self.load_model(None, model_dir, logger)
+            finally:
+                self._may_borrow = False
+            F_dim = self.device_model.feat_dim
+            ex = engine.Extractor(self.device_model, min_chunk_size, chunk_size, max_batch_rows=self.max_batch_rows)
+            front = None
+            if cmn_window > 0 or vad_stream is not None:
+                front = frontend.FrontEnd(self.device_model.device, cmn_window, cmn_center)     # cmn_window <= 0: selection only
+
+            # Multi-GPU (one process per GPU, torchrun) on a stream nobody can split (ark file, pipe): every rank reads the same
+            # stream and extracts only its frame-balanced share of each window -- the partition follows from the lengths, so it
+            # needs no communication -- keeps its x-vectors, and ONE gather at the very end brings them to rank 0, which restores
+            # the input order and alone writes (the role of split_data.sh + nj jobs + `cat xvector.*.scp`,
+            # extract_xvectors.sh:63-95).  An scp table is better served by extract_embedding.py's line-range sharding, where
+            # the ranks do not even parse each other's utterances.
+            from xvector_amd import dist as xdist, jobclock
+            jobclock.once("weights packed on the device + accuracy probe")
+            if distributed:
+                # the group is only needed for the exchange at the end: it comes up on a side thread (RCCL's first communicator takes
+                # about a second) while this one extracts; nothing is written to the output before the exchange
+                rank, world = xdist.group_shape()
+                if xdist.group_wanted():
+                    if world > 1:
+                        xdist.init_process_group_async()
                     else:
-                        vad_it = iter(vad_stream)
+                        # a forced one-rank group (XV_FORCE_DIST=1): this process emits vectors as windows finish, and fd 1 points at
+                        # stderr while a communicator comes up (dist.init_process_group) -- an 'ark:-' output would lose records to
+                        # stderr.  Nothing to overlap with in this mode: the group comes up first.
+                        xdist.wait_process_group()
+            else:
+                # the caller already gave every rank its own part of the input (extract_embedding.py shards scp tables by line
+                # range): behave as a single process and leave the exchange to the caller
+                rank, world = 0, 1
 
-                def vad_records(blocks, cur):
-                    """The rest of the block source one vector at a time (after the first key out of order)."""
-                    while True:
-                        if cur is not None:
-                            vkeys, vals, vo, pos = cur
-                            o = vo.tolist()
-                            for n_ in range(pos, len(vkeys)):
-                                yield vkeys[n_], vals[o[n_]:o[n_ + 1]]
-                        nxt = next(blocks, None)
-                        if nxt is None:
-                            return
-                        cur = [list(nxt[0]), nxt[1], np.asarray(nxt[2], np.int64), 0]
-
-                def vad_for(key):
-                    # same key order as the features (extract_xvectors.sh reads it as scp,s,cs); out-of-order tables still
-                    # work, at the price of holding the skipped vectors
-                    if key in pending:
-                        return pending.pop(key)
-                    for k, v in vad_it:
-                        if k == key:
-                            return v
-                        pending[k] = v
-                    return np.zeros(0, np.float32)        # no VAD for this key -> length mismatch -> dropped with a warning
-
-                def take_vads(bkeys, runs):
-                    """The VAD vectors of the utterances ``bkeys`` (a piece of a window) -> runs."""
-                    nonlocal vad_it, vad_blocks, vad_cur
-                    i, n = 0, len(bkeys)
-                    while vad_blocks is not None and i < n:
-                        if vad_cur is None or vad_cur[3] == len(vad_cur[0]):
-                            nxt = next(vad_blocks, None)
-                            if nxt is None:                    # table exhausted: the remaining keys have no VAD
-                                vad_blocks, vad_cur, vad_it = None, None, iter(())
-                                break
-                            vad_cur = [list(nxt[0]), nxt[1], np.asarray(nxt[2], np.int64), 0]
-                            continue
-                        vkeys, vals, vo, pos = vad_cur
-                        m = min(n - i, len(vkeys) - pos)
-                        if vkeys[pos:pos + m] == bkeys[i:i + m]:
-                            runs.add_run(vals[int(vo[pos]):int(vo[pos + m])], vo[pos:pos + m + 1] - vo[pos])
-                            vad_cur[3] = pos + m
-                            i += m
-                        else:
-                            # the first key that differs: the longest common prefix goes as a run; then either the table has entries
-                            # the features do not (a feats.scp that lists a subset: skip them, kept in case they are asked for
-                            # later) or the key is one that was skipped before
-                            c = 0
-                            while vkeys[pos + c] == bkeys[i + c]:
-                                c += 1
-                            if c:
-                                runs.add_run(vals[int(vo[pos]):int(vo[pos + c])], vo[pos:pos + c + 1] - vo[pos])
-                                pos += c
-                                i += c
-                            key = bkeys[i]
-                            if key in pending:
-                                runs.add_one(pending.pop(key))
-                                vad_cur[3] = pos
-                                i += 1
-                                continue
-                            try:
-                                j = vkeys.index(key, pos)
-                            except ValueError:                 # not in this block: one vector at a time from here on
-                                vad_cur[3] = pos
-                                vad_it = vad_records(vad_blocks, list(vad_cur))
-                                vad_blocks = None
-                                break
-                            o = vo.tolist()
-                            for q in range(pos, j):
-                                pending[vkeys[q]] = vals[o[q]:o[q + 1]]
-                            vad_cur[3] = j
-                    for key in bkeys[i:]:
-                        runs.add_one(vad_for(key))
-
-                def pieces():
-                    """(keys, addr[n], rows[n], cols, holder) -- utterances where they lie: whole arenas for ark streams and scp
-                    tables (first arena short, then doubling: the GPU starts after a fraction of a window), gathered blocks
-                    without the host library, one matrix at a time for (key, matrix) iterators."""
-                    first = int(self.first_arena_bytes)
-                    if in_place:
-                        # an ark that already sits in memory (a BytesIO, a regular file through the page cache) is not read at
-                        # all: the scanner walks the mapping and the packer takes the rows from there
-                        mapped = kaldi_io.map_stream(input_stream) if (hasattr(input_stream, "read") and self.map_input) else None
-                        if mapped is not None:
-                            source = kaldi_io.scan_mat_ark_mapped(
-                                mapped, arena_bytes, first,
-                                fallback=lambda rest: kaldi_io.scan_mat_ark_windows(kaldi_io.MemStream(rest), take_arena, None, pool.put))
-                        elif hasattr(input_stream, "read"):
-                            source = kaldi_io.scan_mat_ark_windows(input_stream, take_arena, first, pool.put)
-                        else:
-                            source = input_stream.windows(take_arena, first, pool.put)
-                        for item in source:
-                            yield item
-                    elif hasattr(input_stream, "read") or hasattr(input_stream, "blocks"):
-                        source = kaldi_io.read_mat_ark_blocks(input_stream) if hasattr(input_stream, "read") else input_stream.blocks()
-                        for bkeys, bfeats, off in source:
-                            row_bytes = bfeats.shape[1] * bfeats.itemsize if bfeats.ndim == 2 else 0
-                            yield bkeys, (bfeats.ctypes.data + off[:-1] * row_bytes).astype(np.uint64), np.diff(off).astype(np.int32), \
-                                (bfeats.shape[1] if bfeats.ndim == 2 else 0), _Held(bfeats, off)
-                    else:
-                        for key, mat in input_stream:
-                            mat = np.ascontiguousarray(mat, dtype=np.float32)
-                            yield [key], np.array([mat.__array_interface__["data"][0]], np.uint64), \
-                                np.array([mat.shape[0]], np.int32), (mat.shape[1] if mat.ndim == 2 else 0), mat
-
-                mats, frames = kaldi_io.ArkMats(), 0
-
-                def put():
-                    item = (keys, mats, vads)
-                    while not cancel.is_set():
-                        try:
-                            windows.put(item, timeout=0.2)
-                            return
-                        except queue.Full:
-                            pass
-                    raise _Cancelled()
-
-                # a window closes at the first piece boundary past its frame limit (in place: one arena = one window)
-                limit = min(self.window_frames, self.first_window_frames)
-                for bkeys, addr, rows, cols, holder in pieces():
-                    keys.extend(bkeys)
-                    mats.add(addr, rows, cols, holder)
-                    if vads is not None:
-                        take_vads(list(bkeys), vads)
-                    frames += int(np.sum(rows))
-                    if frames >= limit or in_place:
-                        put()
-                        keys, vads, mats, frames = [], (None if vads is None else frontend.VadRuns()), kaldi_io.ArkMats(), 0
-                        limit = min(self.window_frames, 2 * limit)
-                if keys:
-                    put()
-                windows.put(None)
-            except _Cancelled:
-                pass
-            except BaseException as e:          # noqa: B902 -- forwarded to the consumer
-                windows.put(e)
-
-        # the reader starts BEFORE the model is loaded: the first arena is read and scanned while the weights are packed
-        reader_thread = threading.Thread(target=reader, daemon=True)
-        reader_thread.start()
-
-        try:
-            self._may_borrow = os.environ.get("XVECTOR_MODEL_CACHE", "1") != "0"
-            self.load_model(None, model_dir, logger)
-        except BaseException:
-            cancel.set()
-            raise
+            writer = extract_stream.VectorWriter(output_stream)
+            run = extract_stream.Extraction(self, ex, front, writer, logger, min_chunk_size, chunk_size, rank, world)
+            # software pipeline of depth 2 over the windows: the host work of window i+1 (packing, H2D, launches) is issued
+            # before the vectors of window i are awaited and written, so the GPU never waits for the writer
+            in_flight = None
+            try:
+                for keys, mats, vads in reader:
+                    writer.check()
+                    # a column count other than the model's goes down the checked NumPy packing path and raises there
+                    addrs = mats.addrs if mats.uniform_cols() == F_dim else None
+                    run.total_segments += len(keys)
+                    nxt = run.submit(keys, mats, vads, addrs)
+                    jobclock.once("first window launched")
+                    arenas = [held for held in mats.holders if isinstance(held, kaldi_io.ArkArena)]
+                    del mats
+                    run.retire(in_flight, reader)
+                    in_flight = (nxt, arenas)
+                run.retire(in_flight, reader)
+                if world > 1 and (run.stash or not self.exchange_windows):
+                    run.exchange()
+            finally:
+                reader.cancel()                         # (no-op after a complete pass: the reader has already returned)
+                writer.close()
         finally:
-            self._may_borrow = False
-        F_dim = self.device_model.feat_dim
-        ex = engine.Extractor(self.device_model, min_chunk_size, chunk_size, max_batch_rows=self.max_batch_rows)
-        front = None
-        if cmn_window > 0 or vad_stream is not None:
-            front = frontend.FrontEnd(self.device_model.device, cmn_window, cmn_center)     # cmn_window <= 0: selection only
-
-        total_segments = 0
-        num_fail = 0
-        num_success = 0
-        compute_time = 0.0
-
-        # Multi-GPU (one process per GPU, torchrun) on a stream nobody can split (ark file, pipe): every rank reads the same
-        # stream and extracts only its frame-balanced share of each window -- the partition follows from the lengths, so it
-        # needs no communication -- keeps its x-vectors, and ONE gather at the very end brings them to rank 0, which restores
-        # the input order and alone writes (the role of split_data.sh + nj jobs + `cat xvector.*.scp`,
-        # extract_xvectors.sh:63-95).  An scp table is better served by extract_embedding.py's line-range sharding, where
-        # the ranks do not even parse each other's utterances.
-        from xvector_amd import dist as xdist, jobclock
-        jobclock.once("weights packed on the device + accuracy probe")
-        if distributed:
-            # the group is only needed for the exchange at the end: it comes up on a side thread (RCCL's first communicator takes
-            # about a second) while this one extracts; nothing is written to the output before the exchange
-            rank, world = xdist.group_shape()
-            if xdist.group_wanted():
-                if world > 1:
-                    xdist.init_process_group_async()
-                else:
-                    # a forced one-rank group (XV_FORCE_DIST=1): this process emits vectors as windows finish, and fd 1 points at
-                    # stderr while a communicator comes up (dist.init_process_group) -- an 'ark:-' output would lose records to
-                    # stderr.  Nothing to overlap with in this mode: the group comes up first.
-                    xdist.wait_process_group()
-        else:
-            # the caller already gave every rank its own part of the input (extract_embedding.py shards scp tables by line
-            # range): behave as a single process and leave the exchange to the caller
-            rank, world = 0, 1
-
-        def submit_window(mats, addrs):
-            """-> a zero-argument function returning the vectors of the window (None on non-root ranks)."""
-            if world == 1:
-                handle = ex.submit(mats, addrs)                   # packed, copied and launched; results are collected later
-                return lambda: ex.finish(handle, as_array=True)
-            lens = mats.lengths if hasattr(mats, "lengths") else np.array([m.shape[0] for m in mats], np.int64)
-            shards = xdist.partition_lpt(lens, world)
-            idx = shards[rank].tolist()
-            mine = _Subset(mats, shards[rank], lens, addrs)
-            handle = ex.submit(mine, mine.addrs)
-            return lambda: ("shard", shards, ex.finish(handle, as_array=True)[0])
-
-        def submit(keys, mats, vads=None, addrs=None):
-            """Front-end (optional) + everything up to the kernel launches of one window; returns what ``collect`` needs:
-            the keys that go on, their (selected) lengths and a function that yields the vectors."""
-            nonlocal num_fail, compute_time
-            t0 = time.time()
-            lens = None
-            if front is not None and front.cmn_window > 0 and world == 1 and hasattr(ex, "submit_raw") and \
-                    engine._host_lib() is not None and (addrs is not None or engine.can_submit_raw(mats, self.device_model.feat_dim)):
-                # CMN + voiced-frame selection on the device, scattered straight into the packed batches
-                handle, lens, dropped = ex.submit_raw(mats, vads, front.cmn_window, front.center, front.min_window, addrs)
-                for i in np.flatnonzero(dropped).tolist():
-                    logger.warning("No voiced frames (or VAD / feature length mismatch) for utterance: '%s'" % keys[i])
-                num_fail += int(dropped.sum())
-                if dropped.any():
-                    keep_idx = np.flatnonzero(~dropped)
-                    keys, lens = [keys[i] for i in keep_idx.tolist()], lens[keep_idx]
-
-                    def result(h=handle, sel=keep_idx):
-                        full, valid = ex.finish(h, as_array=True)
-                        return full[sel], valid[sel]
-                else:
-                    def result(h=handle):
-                        return ex.finish(h, as_array=True)
-                compute_time += time.time() - t0
-                return keys, lens, result
-            if front is not None:
-                done = front.apply(mats, vads)
-                kept = []
-                for key, m in zip(keys, done):
-                    if m is None:      # select-voiced-frames: VAD length mismatch or no voiced frame -> nothing written
-                        logger.warning("No voiced frames (or VAD / feature length mismatch) for utterance: '%s'" % key)
-                        num_fail += 1
-                    else:
-                        kept.append((key, m))
-                keys, mats, addrs = [k for k, _ in kept], [m for _, m in kept], None
-            result = submit_window(mats, addrs)
-            lens = mats.lengths if hasattr(mats, "lengths") else np.fromiter((m.shape[0] for m in mats), dtype=np.int64, count=len(mats))
-            compute_time += time.time() - t0
-            return keys, lens, result
-
-        def collect(keys, lens, result):
-            """Wait for a submitted window and write its vectors (input order)."""
-            nonlocal num_fail, num_success, compute_time
-            t0 = time.time()
-            out = result()
-            compute_time += time.time() - t0
-            if len(out) == 3:                     # multi-GPU: this rank's share of the window; exchanged once, at the end
-                stash.append((keys, lens, out[1], out[2]))
-                # XVECTOR_EXCHANGE_WINDOWS=N (default 0 = the single gather at the very end): exchange -- and let rank 0 write --
-                # every N windows instead: bounds what a rank holds and what a late failure loses on an endless pipe, at the
-                # price of N-th as many collectives.  Every rank sees the same windows, so the counts agree without talking.
-                if self.exchange_windows > 0 and len(stash) >= self.exchange_windows:
-                    xdist.wait_process_group()
-                    self._exchange_shards(stash, rank, world, min_chunk_size, chunk_size, emit)
-                    del stash[:]
-                return
-            emit(keys, lens, *out)
-
-        def emit(keys, lens, vecs, valid):
-            """Warn about rejected utterances, hand the rest to the writer thread."""
-            nonlocal num_fail, num_success
-            if not valid.all():
-                for i in np.flatnonzero(~valid).tolist():
-                    if lens[i] == 0:
-                        logger.warning("Zero-length utterance: '%s'" % keys[i])
-                    else:
-                        logger.warning("Minimum chunk size of %d is greater than the number of rows in utterance: %s" %
-                                       (min_chunk_size, keys[i]))
-                num_fail += int((~valid).sum())
-                keys = [k for k, ok in zip(keys, valid.tolist()) if ok]
-                vecs = vecs[valid]
-            out_q.put((keys, vecs))                 # written by the writer thread, in order
-            num_success += len(keys)
-
-        # ... and a writer thread serialises the records of finished windows (same bytes as write_vec_flt per key), so that
-        # formatting ~50 k records per window does not sit between two kernel launches.  Its error, if any, is re-raised below.
-        out_q = queue.Queue(maxsize=4)
-        writer_error = []
-
-        def writer():
-            while True:
-                item = out_q.get()
-                if item is None:
-                    return
-                if writer_error:
-                    continue                        # keep draining so that the producer never blocks
-                try:
-                    kaldi_io.write_vec_flt_batch(output_stream, item[0], item[1])
-                except BaseException as e:          # noqa: B902 -- forwarded to the caller
-                    writer_error.append(e)
-
-        writer_thread = threading.Thread(target=writer, daemon=True)
-        writer_thread.start()
-        # software pipeline of depth 2 over the windows: the host work of window i+1 (packing, H2D, launches) is issued
-        # before the vectors of window i are awaited and written, so the GPU never waits for the writer
-        in_flight = None
-        stash = []                                  # multi-GPU: (keys, lens, shards, local vectors) per window
-        try:
-            while True:
-                item = windows.get()
-                if item is None:
-                    break
-                if isinstance(item, BaseException):
-                    raise item
-                if writer_error:
-                    raise writer_error[0]
-                keys, mats, vads = item
-                # a column count other than the model's goes down the checked NumPy packing path and raises there
-                addrs = mats.addrs if mats.uniform_cols() == F_dim else None
-                total_segments += len(keys)
-                nxt = submit(keys, mats, vads, addrs)
-                jobclock.once("first window launched")
-                # the window's arenas stay out of the pool until its vectors are down: finish() may have to pack the window
-                # again (out-of-range f16bf8 window -> bf16x3 twin), and it does so from the raw addresses
-                arenas = [held for held in mats.holders if isinstance(held, kaldi_io.ArkArena)]
-                del mats, item
-                if in_flight is not None:
-                    collect(*in_flight[0])
-                    for held in in_flight[1]:
-                        pool.put(held)
-                in_flight = (nxt, arenas)
-            if in_flight is not None:
-                collect(*in_flight[0])
-                for held in in_flight[1]:
-                    pool.put(held)
-            if world > 1 and (stash or not self.exchange_windows):
-                xdist.wait_process_group()
-                self._exchange_shards(stash, rank, world, min_chunk_size, chunk_size, emit)
-        finally:
-            cancel.set()                            # (no-op after a complete pass: the reader has already returned)
-            out_q.put(None)
-            writer_thread.join()                    # the caller closes output_stream right after we return
-            if not reader_thread.is_alive():        # (a reader still inside an arena keeps it; the others are recycled)
-                for a in mine:
-                    kaldi_io.arena_release(a)
-        if writer_error:
-            raise writer_error[0]
+            reader.close()
+        writer.check()
 
         if getattr(self, "_model_key", None) is not None and hasattr(self.device_model, "frame_level"):
             parked = _IDLE_MODELS.setdefault(self._model_key, [])         # (only after a complete pass: the model is in a known state)
@@ -966,8 +613,8 @@ class Model(object):
         self.last_stats = dict(st, demoted=bool(getattr(ex, "demoted", False)),
                                selection=dict(getattr(self.device_model, "selection", None) or {}))
         logger.info("Processed %d features of average size %d frames. Done %d and failed %d" %
-                    (total_segments, st["frames"] / max(total_segments, 1), num_success, num_fail))
-        logger.info("Total time for neural network computations is %.2f minutes." % (compute_time / 60.0))
+                    (run.total_segments, st["frames"] / max(run.total_segments, 1), run.num_success, run.num_fail))
+        logger.info("Total time for neural network computations is %.2f minutes." % (run.compute_time / 60.0))
         logger.info("Elapsed time for extracting whole embeddings is %.2f minutes." %
                     ((time.time() - start_time) / 60.0))
 

@@ -972,11 +972,8 @@ class Extractor(object):
         torch = self.model.torch
         model = self.model
         dev = model.device
-        lens = mats.lengths if hasattr(mats, "lengths") else [m.shape[0] for m in mats]
-        # chunk table, utterances ordered by length so that batches are length-homogeneous
-        order, c_utt, c_start, c_len, seg_start = plan_chunk_table(lens, self.min_chunk_size, self.chunk_size)
-        nch = len(c_utt)
-        handle = dict(n=len(lens), order=order, nch=nch)
+        handle, (c_utt, c_start, c_len, seg_start), bounds = self._plan(mats.lengths if hasattr(mats, "lengths") else [m.shape[0] for m in mats])
+        nch = handle["nch"]
         if nch == 0:
             return handle
         F = model.feat_dim
@@ -990,12 +987,6 @@ class Extractor(object):
         else:
             assert mats[int(c_utt[0])].shape[1] == F, "feature dimension does not match the model"
             l_utt, l_start, l_len = c_utt.tolist(), c_start.tolist(), c_len.tolist()
-        gap, align = model.gap, model.align
-        lead = (gap + align - 1) // align * align
-        # batch boundaries: greedy fill up to max_batch_rows / max_batch_chunks (a single chunk may exceed the row budget)
-        cum = np.zeros(nch + 1, dtype=np.int64)
-        np.cumsum(slot_rows(c_len, gap, align), out=cum[1:])
-        bounds = self._batch_bounds(cum, lead)
         stage = self._staging(max(r for _, _, r in bounds), max(b1 - b0 for b0, b1, _ in bounds))
         with torch.cuda.device(dev):
             compute = torch.cuda.current_stream()
@@ -1005,7 +996,7 @@ class Extractor(object):
             keep = []                                   # device inputs stay referenced until the window is done
             status = torch.zeros(1, dtype=torch.int32, device=dev) if model.f16bf8 else None
             for bi, (b0, b1, _) in enumerate(bounds):
-                layout = BatchLayout(c_len[b0:b1], gap, align)
+                layout = BatchLayout(c_len[b0:b1], model.gap, model.align)
                 st = stage[self._turn % self.NBUF]
                 self._turn += 1
                 if st["event"] is not None:
@@ -1034,32 +1025,59 @@ class Extractor(object):
                 keep.append((x, rv, md))
                 if bi == 0:
                     self._start_probe(handle, x, md, rv, layout)
-                self.stats["batches"] += 1
-                self.stats["chunks"] += layout.nchunks
-                self.stats["frames"] += int(layout.row_len.sum())
-                self.stats["rows"] += layout.rows
-            model.segment_level(P_all, E_all)
-            # (pinned + copy stream: a pageable H2D copy here would block the host until every kernel of the window is done)
-            tail_np = np.concatenate([np.asarray(seg_start, dtype=np.int32), c_len.astype(np.int32)])
-            tail_flat, tail = self._pinned("tail", tail_np.shape, torch.int32)
-            tail.numpy()[:] = tail_np
-            with torch.cuda.stream(self._copy_stream):
-                tail_d = tail.to(dev, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(self._copy_stream)
-            compute.wait_event(ev)
-            seg, cl = tail_d[:len(order) + 1], tail_d[len(order) + 1:]
-            out = torch.empty((len(order), model.embed_dim), dtype=torch.float32, device=dev)
-            hiplib.chunk_average(E_all, seg, cl, len(order), out)
-            host_flat, host = self._pinned("xvec", (len(order), model.embed_dim), torch.float32)
-            host.copy_(out, non_blocking=True)
-            self._end_probe(handle, E_all)
-            self._watch(handle, status, lambda ex: ex.submit(mats, addrs))
-            done = torch.cuda.Event()
-            done.record(compute)
+                self._count(layout)
+            self._window_tail(handle, compute, P_all, E_all, seg_start, c_len, status, keep, mats, lambda ex: ex.submit(mats, addrs))
+        return handle
+
+    def _plan(self, lens):
+        """The plan of a window of utterances of ``lens`` frames: the chunk table (utterances ordered by length, so that batches
+        are length-homogeneous) and its batch boundaries (greedy fill up to max_batch_rows / max_batch_chunks; a single chunk
+        may exceed the row budget).  Returns ``(handle, (c_utt, c_start, c_len, seg_start), bounds)``; bounds is None for a
+        window without a chunk."""
+        order, c_utt, c_start, c_len, seg_start = plan_chunk_table(lens, self.min_chunk_size, self.chunk_size)
+        nch = len(c_utt)
+        handle = dict(n=len(lens), order=order, nch=nch)
+        bounds = None
+        if nch:
+            gap, align = self.model.gap, self.model.align
+            lead = (gap + align - 1) // align * align
+            cum = np.zeros(nch + 1, dtype=np.int64)
+            np.cumsum(slot_rows(c_len, gap, align), out=cum[1:])
+            bounds = self._batch_bounds(cum, lead)
+        return handle, (c_utt, c_start, c_len, seg_start), bounds
+
+    def _count(self, layout):
+        self.stats["batches"] += 1
+        self.stats["chunks"] += layout.nchunks
+        self.stats["frames"] += int(layout.row_len.sum())
+        self.stats["rows"] += layout.rows
+
+    def _window_tail(self, handle, compute, P_all, E_all, seg_start, c_len, status, keep, mats, redo):
+        """Behind the last batch of a window (on its device, ``compute`` its stream): ONE segment-level pass and ONE chunk
+        average over all its chunks, the asynchronous D2H copy of the x-vectors, and what ``finish`` waits for and releases."""
+        torch, model = self.model.torch, self.model
+        dev, order = model.device, handle["order"]
+        model.segment_level(P_all, E_all)
+        # (pinned + copy stream: a pageable H2D copy here would block the host until every kernel of the window is done)
+        tail_np = np.concatenate([np.asarray(seg_start, dtype=np.int32), c_len.astype(np.int32)])
+        tail_flat, tail = self._pinned("tail", tail_np.shape, torch.int32)
+        tail.numpy()[:] = tail_np
+        with torch.cuda.stream(self._copy_stream):
+            tail_d = tail.to(dev, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self._copy_stream)
+        compute.wait_event(ev)
+        seg, cl = tail_d[:len(order) + 1], tail_d[len(order) + 1:]
+        out = torch.empty((len(order), model.embed_dim), dtype=torch.float32, device=dev)
+        hiplib.chunk_average(E_all, seg, cl, len(order), out)
+        host_flat, host = self._pinned("xvec", (len(order), model.embed_dim), torch.float32)
+        host.copy_(out, non_blocking=True)
+        self._end_probe(handle, E_all)
+        self._watch(handle, status, redo)
+        done = torch.cuda.Event()
+        done.record(compute)
         # mats (the native packer read them in place) and the device buffers stay referenced until finish()
         handle.update(host=host, done=done, keep=(keep, E_all, P_all, tail, tail_d, out, mats), pinned=(tail_flat, host_flat))
-        return handle
 
     def _watch(self, handle, status, redo):
         """f16bf8 models: bring the window's out-of-range flag down with its x-vectors; ``finish`` repeats the window on the
@@ -1193,17 +1211,11 @@ class Extractor(object):
         else:
             if not isinstance(vads, VadRuns):             # (runs: every utterance has a vector)
                 vad_dropped &= np.fromiter((v is not None for v in vads), dtype=bool, count=n)
-        order, c_utt, c_start, c_len, seg_start = plan_chunk_table(V, self.min_chunk_size, self.chunk_size)
-        nch = len(c_utt)
-        handle = dict(n=n, order=order, nch=nch)
+        handle, (_, _, c_len, seg_start), bounds = self._plan(V)
+        order, nch = handle["order"], handle["nch"]
         if nch == 0:
             return handle, V, vad_dropped
-        gap, align = model.gap, model.align
-        lead = (gap + align - 1) // align * align
-        cum = np.zeros(nch + 1, dtype=np.int64)
-        np.cumsum(slot_rows(c_len, gap, align), out=cum[1:])
-        bounds = self._batch_bounds(cum, lead)
-        kept = np.ascontiguousarray(np.diff(seg_start), dtype=np.int64)                  # chunks per utterance of `order`
+        kept =np.ascontiguousarray(np.diff(seg_start), dtype=np.int64)                  # chunks per utterance of `order`
         first_len = np.ascontiguousarray(c_len[seg_start[:-1]], dtype=np.int64)          # = the chunk size the plan used for the utterance
         seg_o = np.ascontiguousarray(seg_start[:-1], dtype=np.int64)
         vstart_o = np.ascontiguousarray(vstart[order], dtype=np.int64)                   # (per utterance of `order`, like the three above)
@@ -1223,7 +1235,7 @@ class Extractor(object):
             keep = []
             status = torch.zeros(1, dtype=torch.int32, device=dev) if model.f16bf8 else None
             for bi, ((b0, b1, _), (lo, hi)) in enumerate(zip(bounds, spans)):
-                layout = BatchLayout(c_len[b0:b1], gap, align)
+                layout = BatchLayout(c_len[b0:b1], model.gap, model.align)
                 U = order[lo:hi]
                 Tb = T[U]
                 nU, rows_in = len(U), int(Tb.sum())
@@ -1268,29 +1280,9 @@ class Extractor(object):
                 keep.append((x, rv, md, raw_d, dst_d, utt_d))
                 if bi == 0:
                     self._start_probe(handle, x, md, rv, layout)
-                self.stats["batches"] += 1
-                self.stats["chunks"] += layout.nchunks
-                self.stats["frames"] += int(layout.row_len.sum())
-                self.stats["rows"] += layout.rows
-            model.segment_level(P_all, E_all)
-            tail_np = np.concatenate([np.asarray(seg_start, dtype=np.int32), c_len.astype(np.int32)])
-            tail_flat, tail = self._pinned("tail", tail_np.shape, torch.int32)
-            tail.numpy()[:] = tail_np
-            with torch.cuda.stream(self._copy_stream):
-                tail_d = tail.to(dev, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(self._copy_stream)
-            compute.wait_event(ev)
-            seg, cl = tail_d[:len(order) + 1], tail_d[len(order) + 1:]
-            out = torch.empty((len(order), model.embed_dim), dtype=torch.float32, device=dev)
-            hiplib.chunk_average(E_all, seg, cl, len(order), out)
-            host_flat, host = self._pinned("xvec", (len(order), model.embed_dim), torch.float32)
-            host.copy_(out, non_blocking=True)
-            self._end_probe(handle, E_all)
-            self._watch(handle, status, lambda ex: ex.submit_raw(mats, vads, cmn_window, center, min_window, addrs)[0])
-            done = torch.cuda.Event()
-            done.record(compute)
-        handle.update(host=host, done=done, keep=(keep, E_all, P_all, tail, tail_d, out, mats), pinned=(tail_flat, host_flat))
+                self._count(layout)
+            self._window_tail(handle, compute, P_all, E_all, seg_start, c_len, status, keep, mats,
+                              lambda ex: ex.submit_raw(mats, vads, cmn_window, center, min_window, addrs)[0])
         return handle, V, vad_dropped
 
     def _raw_staging(self, rows, nutts, feat_dim):

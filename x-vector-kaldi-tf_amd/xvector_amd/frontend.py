@@ -65,6 +65,100 @@ class VadRuns(object):
         return vals[int(offs[i]):int(offs[i + 1])]
 
 
+class VadAligner(object):
+    """Hands out the VAD vectors of a VAD table for the feature keys, window piece by window piece.  ``vad_stream`` is what
+    Model.make_embedding accepts: an ark stream or a table with ``blocks()`` (kaldi_io.VecScp) -- read in scanner passes of
+    (keys, values, offsets) blocks, through ``prefetch`` (the caller's read-ahead; this class starts no thread) -- or a
+    (key, vector) iterator.  While the table's keys arrive in the order of the features -- the recipe's tables do
+    (extract_xvectors.sh reads them as scp,s,cs) -- whole runs of a block go into the window (VadRuns), no Python step per
+    utterance; entries the features lack are parked; the first key that is not in the current block switches for good to one
+    vector at a time (out-of-order tables still work, at the price of holding the skipped vectors)."""
+
+    def __init__(self, vad_stream, prefetch=iter):
+        self._pending = {}                      # vectors stepped over, by key
+        self._blocks, self._cur = None, None    # block source and [keys, values, offsets, position] in its current block
+        self._it = None                         # (key, vector) iterator: given, or the rest of the block source
+        if hasattr(vad_stream, "read"):
+            import kaldi_io
+            self._blocks = prefetch(kaldi_io.read_vec_flt_ark_blocks(vad_stream))
+        elif hasattr(vad_stream, "blocks"):
+            self._blocks = prefetch(vad_stream.blocks())
+        else:
+            self._it = iter(vad_stream)
+
+    @staticmethod
+    def _records(blocks, cur):
+        """The rest of the block source one vector at a time (after the first key out of order)."""
+        while True:
+            if cur is not None:
+                vkeys, vals, vo, pos = cur
+                o = vo.tolist()
+                for n_ in range(pos, len(vkeys)):
+                    yield vkeys[n_], vals[o[n_]:o[n_ + 1]]
+            nxt = next(blocks, None)
+            if nxt is None:
+                return
+            cur = [list(nxt[0]), nxt[1], np.asarray(nxt[2], np.int64), 0]
+
+    def _one(self, key):
+        if key in self._pending:
+            return self._pending.pop(key)
+        for k, v in self._it:
+            if k == key:
+                return v
+            self._pending[k] = v
+        return np.zeros(0, np.float32)        # no VAD for this key -> length mismatch -> dropped with a warning
+
+    def append(self, bkeys, runs):
+        """The VAD vectors of the utterances ``bkeys`` (a piece of a window) -> ``runs`` (a VadRuns)."""
+        pending = self._pending
+        i, n = 0, len(bkeys)
+        while self._blocks is not None and i < n:
+            if self._cur is None or self._cur[3] == len(self._cur[0]):
+                nxt = next(self._blocks, None)
+                if nxt is None:                    # table exhausted: the remaining keys have no VAD
+                    self._blocks, self._cur, self._it = None, None, iter(())
+                    break
+                self._cur = [list(nxt[0]), nxt[1], np.asarray(nxt[2], np.int64), 0]
+                continue
+            vkeys, vals, vo, pos = self._cur
+            m = min(n - i, len(vkeys) - pos)
+            if vkeys[pos:pos + m] == bkeys[i:i + m]:
+                runs.add_run(vals[int(vo[pos]):int(vo[pos + m])], vo[pos:pos + m + 1] - vo[pos])
+                self._cur[3] = pos + m
+                i += m
+            else:
+                # the first key that differs: the longest common prefix goes as a run; then either the table has entries
+                # the features do not (a feats.scp that lists a subset: skip them, kept in case they are asked for
+                # later) or the key is one that was skipped before
+                c = 0
+                while vkeys[pos + c] == bkeys[i + c]:
+                    c += 1
+                if c:
+                    runs.add_run(vals[int(vo[pos]):int(vo[pos + c])], vo[pos:pos + c + 1] - vo[pos])
+                    pos += c
+                    i += c
+                key = bkeys[i]
+                if key in pending:
+                    runs.add_one(pending.pop(key))
+                    self._cur[3] = pos
+                    i += 1
+                    continue
+                try:
+                    j = vkeys.index(key, pos)
+                except ValueError:                 # not in this block: one vector at a time from here on
+                    self._cur[3] = pos
+                    self._it = self._records(self._blocks, list(self._cur))
+                    self._blocks = None
+                    break
+                o = vo.tolist()
+                for q in range(pos, j):
+                    pending[vkeys[q]] = vals[o[q]:o[q + 1]]
+                self._cur[3] = j
+        for key in bkeys[i:]:
+            runs.add_one(self._one(key))
+
+
 def select_voiced(mats, vads):
     """The utterance-level rules of select-voiced-frames for a window, vectorised.  Returns
     ``(T, cand, voiced, empty, dropped)``: frame counts of all utterances; indices of the utterances that go on (T > 0, VAD of
