@@ -52,7 +52,7 @@ extern "C" {
 #define XV_ERR_BAD_ARG (-1)
 #define XV_ERR_UNSUPPORTED (-2)
 
-/* Library / ABI version (increments whenever an entry point is added or changed; currently 31). */
+/* Library / ABI version (increments whenever an entry point is added or changed; currently 32). */
 int xv_version(void);
 /* Thread-local description of the last non-zero return. */
 const char *xv_last_error(void);
@@ -734,6 +734,39 @@ int xv_egs_chunks_f16(const float *x, int ldx, int feat_dim, int64_t x_rows, con
                       int n_utts, const int32_t *voiced_count, const int32_t *voiced_row, const int32_t *chunk_utt,
                       const int32_t *chunk_first, const int32_t *chunk_len, const int64_t *chunk_dst, int n_chunks, int max_chunk_len,
                       int cmn_window, int center, int min_window, void *y, int64_t y_elems, void *stream);
+
+/* ---- compressed feature output: Kaldi CompressedMatrix payloads (csrc/xv_compress.hip) ------------------------
+ * What compute-mfcc-feats --compress=true / copy-feats --compress=true do with CompressedMatrix::CopyFromMat (kAutomaticMethod),
+ * restated; the format contract and the error bounds of DESIGN.md §8.10 are claimed, byte equality with Kaldi's own writer is not.
+ * All arithmetic is fp32 unless (double) is shown; no fused multiply-add is formed, division is IEEE, subnormals are kept.
+ * For a matrix m[T, C], T >= 1:
+ *     gmin = min(m); gmax = max(m)        (exact; of a zero extreme, -0.0 is the minimum and +0.0 the maximum when both occur)
+ *     if gmax == gmin: gmax = (float)((double)gmin + (1.0 + fabs((double)gmin)))
+ *     grange = gmax - gmin
+ *     U16(v): f = (v - gmin) / grange; f = min(max(f, 0), 1); (int)trunc((double)(f * 65535.0f) + 0.499)
+ *     F16(q): gmin + (grange * 1.52590218966964e-05f) * (float)q
+ *     (int) of a double that is not finite or lies outside int: INT_MIN, as the x86 conversion gives (a zero-width segment).
+ *     payload = {float gmin, float grange, int32 T, int32 C}, little endian, then
+ *     T <= 8 (token "CM2 "): U16(m[t, c]) as uint16, row-major;
+ *     T  > 8 (token "CM "), q = T / 4, s = column c sorted ascending:
+ *         p0 = min(U16(s[0]), 65532)              p25  = min(max(U16(s[q]), p0 + 1), 65533)
+ *         p75 = min(max(U16(s[3 q]), p25 + 1), 65534)   p100 = max(U16(s[T - 1]), p75 + 1)
+ *         C x {uint16 p0, p25, p75, p100}, then C x T bytes column-major, with P* = F16(p*):
+ *         v < P25: b = clamp(      (int)trunc((double)(((v - P0 ) / (P25  - P0 )) *  64.0f) + 0.5),   0,  64)
+ *         v < P75: b = clamp( 64 + (int)trunc((double)(((v - P25) / (P75  - P25)) * 128.0f) + 0.5),  64, 192)
+ *         else   : b = clamp(192 + (int)trunc((double)(((v - P75) / (P100 - P75)) *  63.0f) + 0.5), 192, 255)
+ * xv_cm_payload_bytes  16 + (rows > 8 ? 8 cols + rows cols : 2 rows cols); 0 for rows == 0 (such a matrix stays a plain record).
+ * xv_cm_encode_f32  utterances addressed as in xv_vad_energy_f32: utterance u is rows utt_row0[u] .. + n_frames[u] - 1 of feats,
+ *   row stride ld >= n_cols.  Its payload goes to out + out_offset[u] (each offset a multiple of 16, out 16-byte aligned, the
+ *   ranges disjoint: the caller's); no byte outside [out_offset[u], out_offset[u] + xv_cm_payload_bytes(T_u, n_cols)) is written,
+ *   nothing for T_u = 0.  status[u] = 0, 1 when the utterance holds a NaN or an infinity (or gmax - gmin overflows), or 2 when T_u n_cols >= 2^31 (the frame
+ *   counts live on the device); with a non-zero status the payload bytes are unspecified, every other utterance is unaffected.
+ *   The bytes of an utterance depend on its values, T and n_cols only: not on the batch, ld or the offsets.
+ *   1 <= n_cols <= 128 and n_utts n_cols < 2^31, else XV_ERR_UNSUPPORTED.  Three launches (range, column statistics by an exact
+ *   radix select, elements) that leave their results in the payload itself: no workspace.  Enqueues and returns. */
+int64_t xv_cm_payload_bytes(int rows, int cols);
+int xv_cm_encode_f32(const float *feats, int64_t ld, const int64_t *utt_row0, const int32_t *n_frames, int n_utts, int n_cols,
+                     const int64_t *out_offset, uint8_t *out, int32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

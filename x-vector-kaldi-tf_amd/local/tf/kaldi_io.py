@@ -1721,3 +1721,18 @@ def write_mat(file_or_fd, m, key=""):
     finally:
         if fd is not file_or_fd:
             fd.close()
+
+
+def write_cm_payload(file_or_fd, payload, rows, key=""):
+    """Write a Kaldi CompressedMatrix record whose payload (global header, per-column headers, data) is already encoded
+    (xvector_amd/compress.py): ``key + " \\0B"``, the token -- "CM2 " for up to 8 rows, "CM " above, Kaldi's automatic choice --
+    and the payload bytes.  Through a TableWriter the scp offset comes out as for write_mat."""
+    fd = open_or_fd(file_or_fd, mode="wb")
+    try:
+        if rows < 1:
+            raise BadInputFormat("a matrix without rows has no compressed form: write it with write_mat")
+        _write_header(fd, key, b"CM " if rows > 8 else b"CM2 ")
+        fd.write(payload.tobytes() if hasattr(payload, "tobytes") else bytes(payload))
+    finally:
+        if fd is not file_or_fd:
+            fd.close()

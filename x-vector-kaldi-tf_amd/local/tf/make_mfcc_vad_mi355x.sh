@@ -3,9 +3,16 @@
 # sid/compute_vad_decision.sh do with nj CPU jobs and Kaldi binaries, as ONE pass (mfcc_vad.py compute-mfcc-vad):
 # writes <out-dir>/raw_mfcc_<name>.{ark,scp}, <out-dir>/vad_<name>.{ark,scp} and puts feats.scp, vad.scp and utt2num_frames
 # into the data dir, as the Kaldi scripts do.  Data dirs with a segments file are refused (not supported).
-# Usage: make_mfcc_vad_mi355x.sh <data-dir> <mfcc.conf> <vad.conf> <out-dir>
+# --compress true writes the features as Kaldi CompressedMatrix records, encoded on the GPU (a quarter of the bytes).  The default
+# here is false; Kaldi's steps/make_mfcc.sh defaults to true.
+# Usage: make_mfcc_vad_mi355x.sh [--compress true|false] <data-dir> <mfcc.conf> <vad.conf> <out-dir>
 set -euo pipefail
-[[ $# -eq 4 ]] || { sed -n 2,6p "$0"; exit 1; }
+compress=false
+if [[ ${1:-} == --compress ]]; then
+  [[ ${2:-} == true || ${2:-} == false ]] || { echo "$0: --compress takes true or false" >&2; exit 1; }
+  compress=$2; shift 2
+fi
+[[ $# -eq 4 ]] || { sed -n 2,8p "$0"; exit 1; }
 data=$1; mfcc_conf=$2; vad_conf=$3; dir=$4
 here=$(cd "$(dirname "$0")" && pwd)
 for f in "$data/wav.scp" "$mfcc_conf" "$vad_conf"; do [[ -f $f ]] || { echo "$0: no such file $f" >&2; exit 1; }; done
@@ -16,7 +23,7 @@ fi
 name=$(basename "$data")
 mkdir -p "$dir/log"
 dir=$(cd "$dir" && pwd)
-python "$here/mfcc_vad.py" compute-mfcc-vad --config="$mfcc_conf" --vad-config="$vad_conf" \
+python "$here/mfcc_vad.py" compute-mfcc-vad --compress=$compress --config="$mfcc_conf" --vad-config="$vad_conf" \
     --write-num-frames="ark,t:$data/utt2num_frames" "scp:$data/wav.scp" \
     "ark,scp:$dir/raw_mfcc_$name.ark,$dir/raw_mfcc_$name.scp" "ark,scp:$dir/vad_$name.ark,$dir/vad_$name.scp" \
     2>&1 | tee "$dir/log/make_mfcc_vad_$name.log"

@@ -6,10 +6,14 @@
   compute-mfcc-vad   [--config F] [--vad-config F] [--name=value ...] [--write-num-frames ark,t:F] scp:wav.scp <feats-wspec>
                      <vad-wspec>       (both in one pass: the VAD reads the features on the device, nothing is re-read)
   wav-to-duration    [--read-entire-file] scp:wav.scp ark,t:utt2dur
+  copy-feats         [--compress[=true|false]] <feats-rspec> <wspec>     (FM, DM and CM* tables in; plain or compressed out)
 
 Options carry Kaldi's names and defaults (xvector_amd/mfcc.py); a ``--config`` file is read first, the command line
 overrides it.  ``--seed`` keys the dither noise with the utterance id.  Outputs are ``ark,scp:A,S`` or
 ``ark:A``; features are written as ``FM`` records, VAD decisions as ``FV`` records, ``--write-num-frames`` as ``key N`` lines.
+``--compress[=true|false]`` (compute-mfcc-feats, compute-mfcc-vad, copy-feats; default false, as in the binaries -- Kaldi's
+steps/make_mfcc.sh passes true) writes features as Kaldi CompressedMatrix records instead (``CM``, or ``CM2`` for matrices of up
+to 8 rows), encoded on the GPU (xvector_amd/compress.py); a matrix without rows stays an ``FM`` record.
 wav.scp entries are paths or ``cmd |`` pipes; 16-bit PCM WAV only.  A pipe whose last stage is ``wav-reverberate`` (what
 Kaldi's reverberate_data_dir.py / augment_data_dir.py write) is evaluated in-process on the GPU (xvector_amd/augment.py,
 DESIGN.md §8.7); no wav-reverberate process is started.  The arithmetic runs on the MI355X: no CPU fallback.
@@ -29,7 +33,7 @@ if _HERE not in sys.path:
 sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))
 
 import kaldi_io  # noqa: E402
-from xvector_amd import augment, mfcc  # noqa: E402
+from xvector_amd import augment, compress, mfcc  # noqa: E402
 
 logger = logging.getLogger('mfcc_vad')
 logger.addHandler(logging.StreamHandler())
@@ -83,6 +87,23 @@ class _NumFrames(object):
 
     def close(self):
         self.f.close()
+
+
+def _compress_flag(p):
+    p.add_argument("--compress", default="false",
+                   help="write features as Kaldi CompressedMatrix records (default false, as in the Kaldi binary)")
+
+
+def _want_compress(args):
+    return mfcc._convert("compress", bool, args.compress)
+
+
+def _write_feats(fd, f, key):
+    """One feature matrix: a compress.Packed as a CM / CM2 record, an array (also the empty one of a compressed run) as FM / DM."""
+    if isinstance(f, compress.Packed):
+        kaldi_io.write_cm_payload(fd, f.payload, f.rows, key=key)
+    else:
+        kaldi_io.write_mat(fd, f, key=key)
 
 
 def _wav_scp_path(rspec):
@@ -173,14 +194,15 @@ def cmd_mfcc(args, with_vad):
     nf_out = _NumFrames(args.write_num_frames) if args.write_num_frames else None
     engine = mfcc.Mfcc(opts, vopts, window_samples=WINDOW_SAMPLES)
     augmenter = augment.Augmenter()
+    want_cm = _want_compress(args)
     n_done = n_vad_skipped = 0
     for keys, waves in _planned_batches(path, opts, augmenter, WINDOW_SAMPLES):
         if any(isinstance(w, augment.Pending) for w in waves):
-            feats, vads, _ = augment.mfcc_compute(engine, augmenter, keys, waves)
+            feats, vads, _ = augment.mfcc_compute(engine, augmenter, keys, waves, compress=want_cm)
         else:
-            feats, vads, _ = engine.compute(keys, waves)
+            feats, vads, _ = engine.compute(keys, waves, compress=want_cm)
         for i, (k, f) in enumerate(zip(keys, feats)):
-            kaldi_io.write_mat(feats_out.fd, f, key=k)
+            _write_feats(feats_out.fd, f, k)
             if nf_out:
                 nf_out.write(k, f.shape[0])
             if with_vad:
@@ -226,6 +248,36 @@ def cmd_vad(args):
     logger.info("Applied energy based voice activity detection; processed %d utterances", len(keys))
 
 
+COPY_WINDOW_ROWS = 1 << 20        # rows held (and, compressed, uploaded) per window of copy-feats
+
+
+def cmd_copy_feats(args):
+    """copy-feats: every matrix of the input table to the output, plain (FM / DM as read; CM* decoded to FM) or compressed."""
+    want_cm = _want_compress(args)
+    out = _Out(args.feats_wspecifier)
+    n = 0
+
+    def flush(keys, mats):
+        packed = compress.encode_host(mats, keys=keys, window_rows=COPY_WINDOW_ROWS) if want_cm else mats
+        for k, m, f in zip(keys, mats, packed):
+            _write_feats(out.fd, m if f is None else f, k)
+
+    keys, mats, rows = [], [], 0
+    for k, m in _read_feats(args.feats_rspecifier):
+        m = np.asarray(m)
+        if keys and rows + m.shape[0] > COPY_WINDOW_ROWS:
+            flush(keys, mats)
+            keys, mats, rows = [], [], 0
+        keys.append(k)
+        mats.append(m)
+        rows += m.shape[0]
+        n += 1
+    if keys:
+        flush(keys, mats)
+    out.close()
+    logger.info("Copied %d feature matrices.", n)
+
+
 def cmd_wav_to_duration(args):
     """key + samples / rate per entry (Kaldi's wav-to-duration); an augmented entry's length comes from its options and the
     header of its input, without evaluating it."""
@@ -252,6 +304,7 @@ def build_parser():
     m = sub.add_parser("compute-mfcc-feats")
     m.add_argument("--config", default=None)
     m.add_argument("--write-num-frames", default=None)
+    _compress_flag(m)
     _flags(m, mfcc.MfccOptions)
     m.add_argument("wav_rspecifier")
     m.add_argument("feats_wspecifier")
@@ -264,11 +317,16 @@ def build_parser():
     b.add_argument("--config", default=None)
     b.add_argument("--vad-config", default=None)
     b.add_argument("--write-num-frames", default=None)
+    _compress_flag(b)
     _flags(b, mfcc.MfccOptions)
     _flags(b, mfcc.VadOptions)
     b.add_argument("wav_rspecifier")
     b.add_argument("feats_wspecifier")
     b.add_argument("vad_wspecifier")
+    c = sub.add_parser("copy-feats")
+    _compress_flag(c)
+    c.add_argument("feats_rspecifier")
+    c.add_argument("feats_wspecifier")
     d = sub.add_parser("wav-to-duration")
     d.add_argument("--read-entire-file", action="store_true", help="accepted for Kaldi compatibility: every file is read whole")
     d.add_argument("wav_rspecifier")
@@ -276,11 +334,17 @@ def build_parser():
     return p
 
 
-def main(argv=None):
-    argv = sys.argv[1:] if argv is None else list(argv)
+def parse_args(argv):
+    argv = list(argv)
     if argv[:1] == ["wav-to-duration"]:               # Kaldi's --read-entire-file=true|false form
         argv = [a.split("=")[0] if a.startswith("--read-entire-file=") else a for a in argv]
-    args = build_parser().parse_args(argv)
+    # Kaldi's bare boolean: "--compress scp:wav.scp ..." must not take the rspecifier for its value
+    argv = ["--compress=true" if a == "--compress" else a for a in argv]
+    return build_parser().parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(sys.argv[1:] if argv is None else argv)
     try:
         if args.cmd == "compute-mfcc-feats":
             args.vad_config = None
@@ -289,6 +353,8 @@ def main(argv=None):
             cmd_mfcc(args, True)
         elif args.cmd == "compute-vad":
             cmd_vad(args)
+        elif args.cmd == "copy-feats":
+            cmd_copy_feats(args)
         elif args.cmd == "wav-to-duration":
             cmd_wav_to_duration(args)
         else:

@@ -533,10 +533,11 @@ class Pending(object):
         self.shape = (node.M,)
 
 
-def mfcc_compute(engine, augmenter, keys, items, vad=None):
+def mfcc_compute(engine, augmenter, keys, items, vad=None, compress=False):
     """``mfcc.Mfcc.compute`` over a batch mixing clean waves (int16 arrays) and ``Pending`` entries: the augmented samples are
     written by the GPU straight into the buffer the MFCC kernel reads.  The entries of a batch may come from more than one
-    plan (a reader plans an entry before it knows which batch takes it); each plan is evaluated on its own."""
+    plan (a reader plans an entry before it knows which batch takes it); each plan is evaluated on its own.
+    ``compress``: as ``mfcc.Mfcc.compute``."""
     waves = [np.broadcast_to(np.int16(0), (it.M,)) if isinstance(it, Pending) else it for it in items]
 
     def fill(x, i, j, off):
@@ -549,4 +550,4 @@ def mfcc_compute(engine, augmenter, keys, items, vad=None):
         for p in plans:
             ks = [k for k in sel if items[k].plan is p]
             augmenter.run(p, x, [int(off[k - i]) for k in ks], 0 if x.dtype == torch.int16 else 1, tops=[items[k].node for k in ks])
-    return engine.compute(keys, waves, vad=vad, fill=fill)
+    return engine.compute(keys, waves, vad=vad, fill=fill, compress=compress)

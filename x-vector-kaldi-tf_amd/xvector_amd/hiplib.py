@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -138,6 +138,9 @@ _SIGNATURES = {
     # stages 3-5: training examples
     "xv_vad_compact_i32": (_ci, [_vp, _vp, _vp, _ci, _i64, _vp, _vp, _vp]),
     "xv_egs_chunks_f16": (_ci, [_vp, _ci, _ci, _i64, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _i64, _vp]),
+    # compressed feature output
+    "xv_cm_payload_bytes": (_i64, [_ci, _ci]),
+    "xv_cm_encode_f32": (_ci, [_vp, _i64, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)      # tests check the header declares exactly these and the .so exports all of them
 
@@ -1313,6 +1316,25 @@ def vad_energy(feats, utt_row0, n_frames, vopts, out):
                                  float(vopts.vad_energy_threshold), float(vopts.vad_energy_mean_scale),
                                  int(vopts.vad_frames_context), float(vopts.vad_proportion_threshold), _ptr(out), _stream()),
            "xv_vad_energy_f32")
+
+
+def cm_payload_bytes(rows, cols):
+    """Bytes of the CompressedMatrix payload of a rows x cols matrix (xv_cm_payload_bytes; 0 for rows == 0)."""
+    return int(load().xv_cm_payload_bytes(int(rows), int(cols)))
+
+
+def cm_encode(feats, utt_row0, n_frames, n_cols, out_offset, out, status):
+    """CompressedMatrix payloads of ragged utterances (xv_cm_encode_f32): utterance u = rows utt_row0[u] .. + n_frames[u] of feats
+    [rows, ld] (int64 / int32 device tensors, as vad_energy), columns 0 .. n_cols - 1; its payload goes to the uint8 device buffer
+    ``out`` at out_offset[u] (int64, multiples of 16: compress.plan), status[u] (int32) receives 0 or the reason it was refused."""
+    import torch
+    lib = require_gpu()
+    _rows2d(feats, "feats")
+    n = int(utt_row0.numel())
+    assert 1 <= int(n_cols) <= feats.shape[1] and out.dim() == 1 and out.data_ptr() % 16 == 0
+    _check(lib.xv_cm_encode_f32(_ptr(feats), feats.stride(0), _dev(utt_row0, torch.int64, "utt_row0"),
+                                _dev(n_frames, torch.int32, "n_frames", n), n, int(n_cols), _dev(out_offset, torch.int64, "out_offset", n),
+                                _dev(out, torch.uint8, "out"), _dev(status, torch.int32, "status", n), _stream()), "xv_cm_encode_f32")
 
 
 def augment_power(sig, segments, tiles, tile_sumsq):

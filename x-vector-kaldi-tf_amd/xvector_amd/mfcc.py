@@ -20,7 +20,7 @@ import subprocess
 
 import numpy as np
 
-from . import frontend, hiplib
+from . import compress as cm, frontend, hiplib
 
 logger = logging.getLogger("mfcc")
 
@@ -413,12 +413,16 @@ class Mfcc(object):
             yield i, j
             i = j
 
-    def compute(self, keys, waves, vad=None, fill=None):
+    def compute(self, keys, waves, vad=None, fill=None, compress=False):
         """keys: utterance ids (they key the dither); waves: 1-D int16 (or float32) sample arrays.  Returns
         ``(feats, vads, logmel)``: float32 [T, num_ceps] per utterance, a ``frontend.VadRuns`` (None unless VAD options were
         given or ``vad`` is True), and the float32 [T, num_mel_bins] log-mel energies (None unless ``with_logmel``).
         ``fill(x, i, j, offsets)``: called with each window's device sample buffer after the upload, before the MFCC launch, for
-        utterances i .. j - 1 at ``offsets`` (the augmented entries of xvector_amd/augment.py write their samples there)."""
+        utterances i .. j - 1 at ``offsets`` (the augmented entries of xvector_amd/augment.py write their samples there).
+        ``compress``: the features come back as ``compress.Packed`` records (``rows``, ``cols``, ``payload``: a Kaldi
+        CompressedMatrix payload for ``kaldi_io.write_cm_payload``) encoded on this engine's stream behind the MFCC launch; the
+        fp32 table is not downloaded, the VAD still reads it on the device.  An utterance without frames gives a float32
+        [0, num_ceps] array, as without ``compress``."""
         opts = self.opts
         waves = [np.asarray(w).reshape(-1) for w in waves]
         assert len(keys) == len(waves)
@@ -427,14 +431,14 @@ class Mfcc(object):
         lens = [w.shape[0] for w in waves]
         for i, j in self._windows(lens):
             f, lm, v = self._launch(keys[i:j], waves[i:j], do_vad,
-                                    None if fill is None else (lambda x, off, i=i, j=j: fill(x, i, j, off)))
+                                    None if fill is None else (lambda x, off, i=i, j=j: fill(x, i, j, off)), compress)
             feats += f
             logmels += lm
             if do_vad:
                 runs.add_run(*v)
         return feats, runs, (logmels if self.with_logmel else None)
 
-    def _launch(self, keys, waves, do_vad, fill=None):
+    def _launch(self, keys, waves, do_vad, fill=None, compress=False):
         torch, opts = self.torch, self.opts
         n = len(waves)
         ns = np.array([w.shape[0] for w in waves], np.int64)
@@ -457,18 +461,25 @@ class Mfcc(object):
             y = torch.empty((max(rows, 1), C), dtype=torch.float32, device=self.device)
             lm = torch.empty((max(rows, 1), B), dtype=torch.float32, device=self.device) if self.with_logmel else None
             hiplib.mfcc(x, d_off, d_ns, d_row0, d_key, rows, self._dev, opts, y, lm)
+            d_T = dev(T.astype(np.int32)) if do_vad or compress else None
             if do_vad:
                 vad = torch.empty(max(rows, 1), dtype=torch.float32, device=self.device)
-                hiplib.vad_energy(y, d_row0, dev(T.astype(np.int32)), self.vad_opts, vad)
+                hiplib.vad_energy(y, d_row0, d_T, self.vad_opts, vad)
                 vad_h = vad[:rows].cpu().numpy()
-            y_h = y[:rows].cpu().numpy()
+            if compress:
+                block, records = cm.encode(y, row0, T, C, stream=self._stream, keys=keys, d_row0=d_row0, d_T=d_T)
+            else:
+                y_h = y[:rows].cpu().numpy()
             lm_h = lm[:rows].cpu().numpy() if lm is not None else None
         self.stats["utterances"] += n
         self.stats["samples"] += int(ns.sum())
         self.stats["frames"] += rows
         self.stats["launches"] += 1
         bounds = list(zip(row0.tolist(), (row0 + T).tolist()))
-        feats = [y_h[a:b] for a, b in bounds]
+        if compress:
+            feats = [p if p.rows else np.zeros((0, C), np.float32) for p in cm.packed(block, records, C)]
+        else:
+            feats = [y_h[a:b] for a, b in bounds]
         logmel = [lm_h[a:b] for a, b in bounds] if lm_h is not None else []
         v = None
         if do_vad:
