@@ -52,7 +52,7 @@ extern "C" {
 #define XV_ERR_BAD_ARG (-1)
 #define XV_ERR_UNSUPPORTED (-2)
 
-/* Library / ABI version (increments whenever an entry point is added or changed; currently 32). */
+/* Library / ABI version (increments whenever an entry point is added or changed; currently 33). */
 int xv_version(void);
 /* Thread-local description of the last non-zero return. */
 const char *xv_last_error(void);
@@ -767,6 +767,52 @@ int xv_egs_chunks_f16(const float *x, int ldx, int feat_dim, int64_t x_rows, con
 int64_t xv_cm_payload_bytes(int rows, int cols);
 int xv_cm_encode_f32(const float *feats, int64_t ld, const int64_t *utt_row0, const int32_t *n_frames, int n_utts, int n_cols,
                      const int64_t *out_offset, uint8_t *out, int32_t *status, void *stream);
+
+/* ---- sample-rate conversion in front of the MFCC kernel (csrc/xv_resample.hip) -------------------------------
+ * What compute-mfcc-feats does with --allow-downsample / --allow-upsample: Kaldi's ResampleWaveform (LinearResample, a
+ * Hann-windowed sinc with 6 zeros and a cutoff of 0.99 of the lower Nyquist frequency, applied once to the whole wave),
+ * restated.  The algorithm below is what is claimed; bit equality with Kaldi's binary (a BLAS dot product) is not.
+ * For a rate pair fi -> fo (positive integers, fi != fo): g = gcd(fi, fo), Ui = fi / g, Uo = fo / g.  Output o = u Uo + p
+ * (0 <= p < Uo) of a wave x[0 .. n) is
+ *     k0 = first[p] + u Ui;   y[o] = sum_j w[p][j] x[k0 + j]   over j < ntaps[p] with 0 <= k0 + j < n
+ * as ONE fp32 accumulator from 0.0f, acc = fmaf(w, x, acc), j ascending; a tap outside the wave is skipped.  x is the int16
+ * sample converted to fp32 or the fp32 sample; y stays fp32.  The tables of a pair (first, ntaps: Uo int32 each; w: Uo rows of
+ * `row` floats, row = the longest tap count, the rest of a row unused) are the caller's (xvector_amd/resample.py forms them in
+ * fp64 as Kaldi's LinearResample::SetIndexesAndWeights does and rounds to fp32).
+ * xv_resample_num_output  the number of outputs for n input samples: with tick = lcm(fi, fo), L = n (tick / fi), 0 when L <= 0,
+ *   else last = L / (tick / fo), less one when that division is exact, and the count is last + 1 (int64 throughout).
+ *   -1 for a non-positive rate or fi == fo.  A host function.
+ * xv_resample_f32  n_utts ragged utterances of any mix of rate pairs in one launch.  in: every utterance's samples back to back,
+ *   int16 (in_format 0) or fp32 (1); utterance u has in_samples[u] samples from element in_offset[u], uses table utt_table[u]
+ *   and its outputs o < out_samples[u] go to out[out_offset[u] + o]; nothing else of out is written.  out_samples[u] may not
+ *   exceed what xv_resample_num_output gives (the caller's: the kernel does not re-derive it; a smaller count is a prefix).
+ *   tables: n_tables descriptors of XV_RS_TAB_FIELDS int64 each IN HOST MEMORY (they travel as a kernel argument, at most
+ *   XV_RS_MAX_TABLES per launch): UI, UO, ROW, PHASE_OFF (table t's first and ntaps are first[PHASE_OFF ..] and
+ *   ntaps[PHASE_OFF ..], Uo entries each), W_OFF (its weights are w[W_OFF + p ROW + j]) and SPAN (the most input samples the
+ *   XV_RS_OUT_TILE consecutive outputs of a tile reach over, from the first tap of the first to the last tap of the last; it
+ *   sizes the LDS staging buffer, and first[p] + u Ui and the row ends must be non-decreasing in o).  first, ntaps, w, the
+ *   per-utterance arrays and tiles are device memory.  tiles: [n_tiles, 2] int64 = (utterance, first output), the first output
+ *   a multiple of XV_RS_OUT_TILE; every output is covered by exactly one tile (the host's list).  A sample's bits depend on
+ *   its own wave and table only.  XV_ERR_BAD_ARG: a null pointer, a negative count, an in_format other than 0 / 1, a
+ *   descriptor with a non-positive UI / UO / ROW / SPAN or a negative offset.  XV_ERR_UNSUPPORTED: ROW > XV_RS_MAX_ROW, UO >
+ *   XV_RS_MAX_UO, n_tables > XV_RS_MAX_TABLES, more than 2^31 - 1 tiles, or a SPAN beyond the LDS of a CU (32760 samples: a
+ *   rate ratio above ~31).  A refused call launches nothing; n_tiles == 0 returns 0 and launches nothing. */
+#define XV_RS_OUT_TILE 1024
+#define XV_RS_MAX_TABLES 8
+#define XV_RS_MAX_ROW 1024
+#define XV_RS_MAX_UO 4096
+#define XV_RS_TAB_FIELDS 6
+#define XV_RS_UI 0
+#define XV_RS_UO 1
+#define XV_RS_ROW 2
+#define XV_RS_PHASE_OFF 3
+#define XV_RS_W_OFF 4
+#define XV_RS_SPAN 5
+int64_t xv_resample_num_output(int64_t n, int rate_in, int rate_out);
+int xv_resample_f32(const void *in, int in_format, const int64_t *in_offset, const int64_t *in_samples, const int64_t *out_offset,
+                    const int64_t *out_samples, const int64_t *utt_table, int n_utts, const int64_t *tables, int n_tables,
+                    const int32_t *first, const int32_t *ntaps, const float *w, const int64_t *tiles, int64_t n_tiles, float *out,
+                    void *stream);
 
 #ifdef __cplusplus
 }

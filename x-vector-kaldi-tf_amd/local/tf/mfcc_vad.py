@@ -16,7 +16,11 @@ steps/make_mfcc.sh passes true) writes features as Kaldi CompressedMatrix record
 to 8 rows), encoded on the GPU (xvector_amd/compress.py); a matrix without rows stays an ``FM`` record.
 wav.scp entries are paths or ``cmd |`` pipes; 16-bit PCM WAV only.  A pipe whose last stage is ``wav-reverberate`` (what
 Kaldi's reverberate_data_dir.py / augment_data_dir.py write) is evaluated in-process on the GPU (xvector_amd/augment.py,
-DESIGN.md §8.7); no wav-reverberate process is started.  The arithmetic runs on the MI355X: no CPU fallback.
+DESIGN.md §8.7); no wav-reverberate process is started.  ``--allow-downsample`` / ``--allow-upsample`` (compute-mfcc-feats,
+compute-mfcc-vad; also through ``--config``) take a wave whose rate differs from ``--sample-frequency`` as it is and resample it
+on the GPU (xvector_amd/resample.py); frame counts are those of the resampled wave.  Without them such a wave
+is skipped with a warning, and an augmented entry at another rate is skipped either way (the augmenter's output is not
+resampled).  The arithmetic runs on the MI355X: no CPU fallback.
 """
 from __future__ import print_function
 
@@ -114,7 +118,8 @@ def _wav_scp_path(rspec):
 
 
 def _read_waves(path, opts, state=None):
-    """(key, int16 samples) of every usable entry, in order (Kaldi's skip rules applied).  An entry whose last pipeline stage
+    """(key, int16 samples) of every usable entry, in order (Kaldi's skip rules applied; a wave to be resampled is a
+    ``mfcc.Wave`` carrying its rate).  An entry whose last pipeline stage
     is wav-reverberate comes as (key, augment.Pending) added to ``state['plan']``: only its length is known here, the GPU makes
     its samples (xvector_amd/augment.py)."""
     for key, rx in mfcc.read_wav_scp(path):
@@ -144,7 +149,8 @@ def _read_waves(path, opts, state=None):
 
 
 def _select_pending(key, p, opts):
-    """mfcc.select_channel's rules for an augmented entry (one channel, p.M samples at p.rate)."""
+    """mfcc.select_channel's rules for an augmented entry (one channel, p.M samples at p.rate).  Its samples are made on the
+    device at p.rate and are not resampled: another rate is skipped whatever --allow-downsample / --allow-upsample say."""
     if opts.channel not in (-1, 0):
         logger.warning("Invalid channel %d/1 for key %s; skipping", opts.channel, key)
         return False
@@ -185,7 +191,7 @@ def cmd_mfcc(args, with_vad):
     opts = _options(mfcc.MfccOptions, args.config, args)
     vopts = _options(mfcc.VadOptions, args.vad_config, args) if with_vad else None
     try:
-        opts.check()
+        opts.check(resample=True)
     except (NotImplementedError, ValueError) as e:
         raise SystemExit(str(e))
     path = _wav_scp_path(args.wav_rspecifier)

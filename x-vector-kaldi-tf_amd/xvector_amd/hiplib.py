@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -141,6 +141,9 @@ _SIGNATURES = {
     # compressed feature output
     "xv_cm_payload_bytes": (_i64, [_ci, _ci]),
     "xv_cm_encode_f32": (_ci, [_vp, _i64, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp]),
+    # sample-rate conversion in front of the MFCC kernel
+    "xv_resample_num_output": (_i64, [_i64, _ci, _ci]),
+    "xv_resample_f32": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)      # tests check the header declares exactly these and the .so exports all of them
 
@@ -1335,6 +1338,46 @@ def cm_encode(feats, utt_row0, n_frames, n_cols, out_offset, out, status):
     _check(lib.xv_cm_encode_f32(_ptr(feats), feats.stride(0), _dev(utt_row0, torch.int64, "utt_row0"),
                                 _dev(n_frames, torch.int32, "n_frames", n), n, int(n_cols), _dev(out_offset, torch.int64, "out_offset", n),
                                 _dev(out, torch.uint8, "out"), _dev(status, torch.int32, "status", n), _stream()), "xv_cm_encode_f32")
+
+
+def resample_num_output(n, rate_in, rate_out):
+    """Outputs of n input samples at rate_in resampled to rate_out (xv_resample_num_output; -1 for rates it refuses)."""
+    return int(load().xv_resample_num_output(int(n), int(rate_in), int(rate_out)))
+
+
+def resample(inp, utt, tab, first, ntaps, w, tiles, out):
+    """Rate conversion of ragged utterances (xv_resample_f32; see include/xvector_hip.h).  inp: int16 or float32 (1-D, device);
+    utt: HOST int64 [5, U] = (in_offset, in_samples, out_offset, out_samples, table) rows, uploaded here; tab: HOST int64
+    [n_tables, 6] descriptors; first / ntaps (int32), w (float32), tiles ([n_tiles, 2] int64): device; out: float32 (1-D, device).
+    The host side of the ABI's argument checks lives here: every span must lie inside its buffer, and an out_samples beyond
+    what the rates give is refused as XV_ERR_BAD_ARG before anything is launched."""
+    import numpy as np
+    import torch
+    lib = require_gpu()
+    assert inp.is_cuda and inp.dim() == 1 and inp.dtype in (torch.int16, torch.float32) and inp.is_contiguous()
+    assert utt.dtype == np.int64 and utt.ndim == 2 and utt.shape[0] == 5 and tab.dtype == np.int64 and tab.ndim == 2 and tab.shape[1] == 6
+    assert tiles.dim() == 2 and tiles.shape[1] == 2 and out.dim() == 1
+    utt, tab = np.ascontiguousarray(utt), np.ascontiguousarray(tab)
+    in_off, n_in, out_off, n_out, table = utt
+    assert np.all((table >= 0) & (table < len(tab))), "utt: table index out of range"
+    assert np.all((in_off >= 0) & (n_in >= 0) & (in_off + n_in <= inp.numel())), "utt: an input span leaves inp"
+    assert np.all((out_off >= 0) & (n_out >= 0) & (out_off + n_out <= out.numel())), "utt: an output span leaves out"
+    if len(tab) and np.all(tab[:, :3] >= 1):
+        assert np.all(tab[:, 3] + tab[:, 1] <= min(first.numel(), ntaps.numel())), "tab: phase tables too short"
+        assert np.all(tab[:, 4] + tab[:, 1] * tab[:, 2] <= w.numel()), "tab: weight table too short"
+        Ui, Uo = tab[table, 0], tab[table, 1]
+        L = n_in * Uo                                              # xv_resample_num_output in units of lcm ticks
+        most = np.where(L <= 0, 0, (L - 1) // Ui + 1)
+        if np.any(n_out > most):
+            u = int(np.flatnonzero(n_out > most)[0])
+            raise XvectorHipError("xv_resample_f32 failed (-1): resample: out_samples[%d] = %d exceeds the %d outputs of %d input "
+                                  "samples" % (u, n_out[u], most[u], n_in[u]))
+    d_utt = torch.from_numpy(utt).to(inp.device)
+    _check(lib.xv_resample_f32(_ptr(inp), 0 if inp.dtype == torch.int16 else 1, _ptr(d_utt[0]), _ptr(d_utt[1]), _ptr(d_utt[2]),
+                               _ptr(d_utt[3]), _ptr(d_utt[4]), int(utt.shape[1]), tab.ctypes.data_as(ctypes.c_void_p), int(len(tab)),
+                               _dev(first, torch.int32, "first"), _dev(ntaps, torch.int32, "ntaps"), _dev(w, torch.float32, "w"),
+                               _dev(tiles, torch.int64, "tiles"), int(tiles.shape[0]), _dev(out, torch.float32, "out"), _stream()),
+           "xv_resample_f32")
 
 
 def augment_power(sig, segments, tiles, tile_sumsq):

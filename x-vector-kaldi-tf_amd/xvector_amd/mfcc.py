@@ -8,7 +8,9 @@ What ``steps/make_mfcc.sh`` (compute-mfcc-feats) and ``sid/compute_vad_decision.
   once, the twiddles exp(-2 pi i k / N) likewise, the sparse mel bank in fp32 the way Kaldi's MelBanks forms it.
 * ``read_wav`` / ``read_wav_scp`` -- RIFF/WAVE 16-bit PCM (plain or WAVE_FORMAT_EXTENSIBLE), paths and ``cmd |`` pipes.
 * ``Mfcc.compute`` -- MFCC rows and VAD decisions of many utterances per launch (csrc/xv_mfcc.hip); the decisions come back as
-  a ``frontend.VadRuns``, so they plug straight into ``FrontEnd.apply``.
+  a ``frontend.VadRuns``, so they plug straight into ``FrontEnd.apply``.  A wave at another rate than ``--sample-frequency`` is
+  resampled on the device in front of the kernel when ``--allow-downsample`` / ``--allow-upsample`` permits (xvector_amd/resample.py,
+  DESIGN.md §8.11).
 
 There is no CPU path: the arithmetic runs on the GPU, and a missing device is an error.
 """
@@ -20,7 +22,7 @@ import subprocess
 
 import numpy as np
 
-from . import compress as cm, frontend, hiplib
+from . import compress as cm, frontend, hiplib, resample
 
 logger = logging.getLogger("mfcc")
 
@@ -117,15 +119,17 @@ class MfccOptions(_Options):
         t = np.asarray(t, np.int64)
         return t * S if self.snip_edges else t * S + S // 2 - L // 2
 
-    def check(self):
-        """What the kernel does not implement raises (the analogue of XV_ERR_UNSUPPORTED on the host side)."""
+    def check(self, resample=False):
+        """What the kernel does not implement raises (the analogue of XV_ERR_UNSUPPORTED on the host side).  ``resample``: the
+        caller puts the resampler (xvector_amd/resample.py) in front of the kernel, as ``Mfcc`` does, so --allow-downsample /
+        --allow-upsample pass; the kernel itself takes one rate."""
         if not self.round_to_power_of_two:
             raise NotImplementedError("--round-to-power-of-two=false (non-power-of-two FFT) is not supported")
         if self.htk_compat:
             raise NotImplementedError("--htk-compat=true is not supported")
         if self.vtln_warp != 1.0:
             raise NotImplementedError("VTLN (--vtln-warp != 1) is not supported")
-        if self.allow_downsample or self.allow_upsample:
+        if (self.allow_downsample or self.allow_upsample) and not resample:
             raise NotImplementedError("resampling (--allow-downsample / --allow-upsample) is not supported")
         if self.subtract_mean or self.max_feature_vectors != -1 or self.output_format != "kaldi":
             raise NotImplementedError("--subtract-mean, --max-feature-vectors and --output-format are not supported")
@@ -273,8 +277,8 @@ def twiddles(opts):
 
 
 class MfccTables(object):
-    def __init__(self, opts):
-        opts.check()
+    def __init__(self, opts, resample=False):
+        opts.check(resample)
         self.window = window_function(opts)
         self.mel_first, self.mel_w, self.mel_len = mel_banks(opts)
         self.lifter_dct = lifter_dct(opts)
@@ -361,8 +365,18 @@ def load_wav(key, rx):
     return read_wav(data, key)
 
 
+class Wave(np.ndarray):
+    """The samples of a wave that is to be resampled: an array that carries its own ``rate`` (Hz).  ``Mfcc.compute`` reads it."""
+    rate = None
+
+    def __array_finalize__(self, obj):
+        self.rate = getattr(obj, "rate", None)
+
+
 def select_channel(key, rate, x, opts):
-    """compute-mfcc-feats' utterance rules: -> int16 [samples], or None (skipped, with Kaldi's warning)."""
+    """compute-mfcc-feats' utterance rules: -> int16 [samples], or None (skipped, with Kaldi's warning).  A wave whose rate
+    differs from --sample-frequency comes back as a ``Wave`` carrying that rate when --allow-downsample / --allow-upsample
+    permits resampling it."""
     nch = x.shape[0]
     ch = opts.channel
     if ch == -1:
@@ -372,14 +386,25 @@ def select_channel(key, rate, x, opts):
     elif ch < 0 or ch >= nch:
         logger.warning("Invalid channel %d/%d for key %s; skipping", ch, nch, key)
         return None
-    if rate != opts.sample_frequency:
+    resample = rate != opts.sample_frequency
+    if resample and not (opts.allow_downsample or opts.allow_upsample):
         logger.warning("Sample frequency %g of key %s differs from --sample-frequency=%g; skipping (no resampling)",
                        rate, key, opts.sample_frequency)
         return None
-    if x.shape[1] < opts.min_duration * rate:
+    if resample and not (opts.allow_downsample if rate > opts.sample_frequency else opts.allow_upsample):
+        # Kaldi's KALDI_ERR text; the binary's catch block turns it into a warning and goes on to the next utterance
+        logger.warning("Waveform and config sample Frequency mismatch: %g .vs %g (use --allow-%s=true to allow %s) (key %s); "
+                       "skipping", rate, opts.sample_frequency, *(("downsample", "downsampling") if rate > opts.sample_frequency
+                                                                  else ("upsample", "upsampling")), key)
+        return None
+    if x.shape[1] < opts.min_duration * rate:                  # the original length at the original rate, as in Kaldi
         logger.warning("File: %s is too short (%g sec): producing no output.", key, x.shape[1] / float(rate))
         return None
-    return np.ascontiguousarray(x[ch])
+    w = np.ascontiguousarray(x[ch])
+    if resample:
+        w = w.view(Wave)
+        w.rate = int(rate)
+    return w
 
 
 # ------------------------------------------------------------------------------------------------
@@ -392,18 +417,20 @@ class Mfcc(object):
         import torch
         hiplib.require_gpu()
         self.torch = torch
-        self.opts = opts.check()
+        self.opts = opts.check(resample=True)
         self.vad_opts = vad_opts
         self.device = torch.device(device)
         self.window_samples = int(window_samples)
         self.with_logmel = with_logmel
-        self.tables = MfccTables(opts)
+        self.tables = MfccTables(opts, resample=True)
+        self._resampler = None                   # resample.Resampler, made when the first wave at another rate arrives
         self._dev = self.tables.to_device(self.device)
         # own stream, as FrontEnd: the results go back to the host, nothing on the compute stream waits for them
         self._stream = torch.cuda.Stream(device=self.device)
-        self.stats = dict(utterances=0, samples=0, frames=0, launches=0)
+        self.stats = dict(utterances=0, samples=0, frames=0, launches=0, resampled=0)
 
     def _windows(self, lens):
+        """``lens``: the samples each utterance takes on the device (a resampled one: its output and its input)."""
         i, n = 0, len(lens)
         while i < n:
             j, tot = i, 0
@@ -413,8 +440,27 @@ class Mfcc(object):
             yield i, j
             i = j
 
-    def compute(self, keys, waves, vad=None, fill=None, compress=False):
-        """keys: utterance ids (they key the dither); waves: 1-D int16 (or float32) sample arrays.  Returns
+    def _rates(self, waves, rates):
+        """Per utterance: None (the wave has --sample-frequency) or the integer rate it is resampled from."""
+        fs = self.opts.sample_frequency
+        rates = [getattr(w, "rate", None) for w in waves] if rates is None else list(rates)
+        assert len(rates) == len(waves)
+        rates = [None if r is None or r == fs else r for r in rates]
+        for r in rates:
+            if r is None:
+                continue
+            if int(fs) != fs or int(r) != r or r <= 0:
+                raise NotImplementedError("resampling %r -> %r: only integer sample rates are supported" % (r, fs))
+            if not (self.opts.allow_downsample if r > fs else self.opts.allow_upsample):
+                raise ValueError("Waveform and config sample Frequency mismatch: %g .vs %g (use --allow-%s=true to allow %s)"
+                                 % ((r, fs) + (("downsample", "downsampling") if r > fs else ("upsample", "upsampling"))))
+        return [None if r is None else int(r) for r in rates]
+
+    def compute(self, keys, waves, vad=None, fill=None, compress=False, rates=None):
+        """keys: utterance ids (they key the dither); waves: 1-D int16 (or float32) sample arrays.  ``rates``: the sample rate of
+        each wave (None: ``--sample-frequency``, or the ``rate`` a ``Wave`` carries); a wave at another rate is uploaded as it is
+        and resampled on the device (xvector_amd/resample.py) into the fp32 sample buffer the MFCC kernel reads, when
+        --allow-downsample / --allow-upsample permits, and its frames are those of the resampled length.  Returns
         ``(feats, vads, logmel)``: float32 [T, num_ceps] per utterance, a ``frontend.VadRuns`` (None unless VAD options were
         given or ``vad`` is True), and the float32 [T, num_mel_bins] log-mel energies (None unless ``with_logmel``).
         ``fill(x, i, j, offsets)``: called with each window's device sample buffer after the upload, before the MFCC launch, for
@@ -423,38 +469,74 @@ class Mfcc(object):
         CompressedMatrix payload for ``kaldi_io.write_cm_payload``) encoded on this engine's stream behind the MFCC launch; the
         fp32 table is not downloaded, the VAD still reads it on the device.  An utterance without frames gives a float32
         [0, num_ceps] array, as without ``compress``."""
-        opts = self.opts
+        rates = self._rates(waves, rates)
         waves = [np.asarray(w).reshape(-1) for w in waves]
         assert len(keys) == len(waves)
         do_vad = self.vad_opts is not None if vad is None else bool(vad)
         feats, logmels, runs = [], [], frontend.VadRuns() if do_vad else None
         lens = [w.shape[0] for w in waves]
+        if any(r is not None for r in rates):
+            fs = int(self.opts.sample_frequency)
+            lens = [n if r is None else n + int(resample.num_output_samples(n, r, fs)) for n, r in zip(lens, rates)]
         for i, j in self._windows(lens):
             f, lm, v = self._launch(keys[i:j], waves[i:j], do_vad,
-                                    None if fill is None else (lambda x, off, i=i, j=j: fill(x, i, j, off)), compress)
+                                    None if fill is None else (lambda x, off, i=i, j=j: fill(x, i, j, off)), compress, rates[i:j])
             feats += f
             logmels += lm
             if do_vad:
                 runs.add_run(*v)
         return feats, runs, (logmels if self.with_logmel else None)
 
-    def _launch(self, keys, waves, do_vad, fill=None, compress=False):
+    def _upload_resampled(self, waves, rates, res, ns, off):
+        """The sample buffer of a window that holds resampled utterances (``res``: their indices): fp32, the utterances at
+        --sample-frequency uploaded in place (one copy per run of neighbours), the others uploaded at their own rate into a
+        side buffer and resampled into their spans on this engine's stream."""
+        torch = self.torch
+        if self._resampler is None:
+            self._resampler = resample.Resampler(self.device)
+        x = torch.empty(max(int(ns.sum()), 1), dtype=torch.float32, device=self.device)
+        i, n = 0, len(waves)
+        while i < n:
+            if rates[i] is not None:
+                i += 1
+                continue
+            j = i
+            while j < n and rates[j] is None:
+                j += 1
+            run = np.concatenate([w.astype(np.float32, copy=False) for w in waves[i:j]])
+            if len(run):
+                x[int(off[i]):int(off[i]) + len(run)].copy_(torch.from_numpy(run))
+            i = j
+        side = [waves[k] for k in res]
+        dtype = np.float32 if any(w.dtype != np.int16 for w in side) else np.int16
+        pl = resample.plan([w.shape[0] for w in side], [rates[k] for k in res], int(self.opts.sample_frequency), out_offsets=off[res])
+        assert np.array_equal(pl.out_samples, ns[res])
+        flat = np.concatenate([w.astype(dtype, copy=False) for w in side])
+        self._resampler.run(torch.from_numpy(flat if len(flat) else np.zeros(1, dtype)).to(self.device), pl, x)
+        self.stats["resampled"] += len(res)
+        return x
+
+    def _launch(self, keys, waves, do_vad, fill=None, compress=False, rates=None):
         torch, opts = self.torch, self.opts
         n = len(waves)
         ns = np.array([w.shape[0] for w in waves], np.int64)
+        res = np.array([k for k in range(n) if rates is not None and rates[k] is not None], np.int64)
+        if len(res):                                # frames, rows and offsets: of the lengths after resampling
+            ns[res] = resample.num_output_samples(ns[res], np.array([rates[k] for k in res], np.int64), int(opts.sample_frequency))
         T = opts.num_frames(ns).astype(np.int64)
         row0 = np.zeros(n, np.int64)
         np.cumsum(T[:-1], out=row0[1:])
         rows = int(T.sum())
         off = np.zeros(n, np.int64)
         np.cumsum(ns[:-1], out=off[1:])
-        dtype = np.float32 if any(w.dtype != np.int16 for w in waves) else np.int16
-        flat = np.concatenate([w.astype(dtype, copy=False) for w in waves]) if n else np.zeros(0, dtype)
+        if not len(res):
+            dtype = np.float32 if any(w.dtype != np.int16 for w in waves) else np.int16
+            flat = np.concatenate([w.astype(dtype, copy=False) for w in waves]) if n else np.zeros(0, dtype)
         keyv = np.array([dither_key(k, opts.seed) for k in keys], np.uint64).view(np.int64)
         C, B = opts.num_ceps, opts.num_mel_bins
         with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
             dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device, non_blocking=False)  # noqa: E731
-            x = dev(flat if len(flat) else np.zeros(1, dtype))
+            x = self._upload_resampled(waves, rates, res, ns, off) if len(res) else dev(flat if len(flat) else np.zeros(1, dtype))
             if fill is not None:
                 fill(x, off)
             d_off, d_ns, d_row0, d_key = dev(off), dev(ns), dev(row0), dev(keyv)
