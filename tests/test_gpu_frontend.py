@@ -169,6 +169,66 @@ def test_device_front_end_path_equals_host_round_trip(tmp_path):
                 assert got[i] is None
 
 
+def test_device_front_end_redo_and_demotion_equal_bf16x3(monkeypatch):
+    """Extractor.submit_raw on an f16bf8 model: a window inside the fp16 range stays in f16bf8; a window with one utterance
+    scaled by 1e6 raises the status word and is repeated on the bf16x3 twin; a failed run-time probe demotes the extractor and
+    later windows are routed to the twin.  Whatever was repeated or routed equals submit_raw on a bf16x3 model bit for bit."""
+    from xvector_amd import engine, synthetic, topology
+    if engine._host_lib() is None:
+        pytest.skip("libxvector_host.so disabled: make_embedding then takes the host round trip")
+    topo = topology.get("ModelWithoutDropout")
+    w = synthetic.trained_like(topo, 23, seed=3)
+    rng = np.random.default_rng(12)
+    Ts = [300, 40, 1, 0, 777, 25, 1300, 90, 260, 33]
+    mats = [(rng.standard_normal((t, 23)) * 3 + 1.5).astype(np.float32) for t in Ts]
+    vads = [(rng.random(t) < 0.7).astype(np.float32) for t in Ts]
+    vads[1] = np.zeros(40, np.float32)              # nothing voiced -> dropped
+    vads[4] = vads[4][:-1]                          # length mismatch -> dropped
+    vads[7] = None                                  # no VAD for this key: every frame voiced
+    loud = list(mats)
+    loud[6] = mats[6] * np.float32(1e6)
+    fast = engine.DeviceModel(w, topo, "cuda:0", precision="f16bf8")
+    exact = engine.DeviceModel(w, topo, "cuda:0", precision="bf16x3")
+
+    def run(ex, ms):
+        handle, lens, dropped = ex.submit_raw(ms, vads, 300, True)
+        return handle, ex.finish(handle), lens, dropped
+
+    def same(got, want):
+        assert np.array_equal(got[2], want[2]) and np.array_equal(got[3], want[3])
+        assert len(got[1]) == len(want[1]) == len(Ts)
+        for a, b in zip(got[1], want[1]):
+            assert (a is None) == (b is None) and (a is None or np.array_equal(a, b))
+
+    for rows in (262144, 700):
+        ref_ex = engine.Extractor(exact, 25, 200, max_batch_rows=rows)
+        ref, ref_loud = run(ref_ex, mats), run(ref_ex, loud)
+        frames = ref_ex.stats["frames"] // 2        # chunk frames of one window (scaling changes no length)
+        assert frames > 0 and ref_ex.stats["frames"] == 2 * frames
+        # (a) inside the range: nothing is repeated
+        ex = engine.Extractor(fast, 25, 200, max_batch_rows=rows)
+        got = run(ex, mats)
+        assert ex.stats.get("fallback_windows", 0) == 0 and not ex.demoted and ex.stats["probe_windows"] == 1
+        assert np.array_equal(got[2], ref[2]) and np.array_equal(got[3], ref[3])
+        # (b) out of range: the status word alone (no probe) has the window repeated on the twin
+        ex = engine.Extractor(fast, 25, 200, max_batch_rows=rows, accuracy_probe=False)
+        got = run(ex, loud)
+        assert ex.stats["fallback_windows"] == 1 and not ex.demoted
+        same(got, ref_loud)
+        # (c) demotion: the probed window is repeated, the next one is routed
+        with monkeypatch.context() as mp:
+            mp.setattr(engine, "DATA_PROBE_LIMIT", 0.0)
+            ex = engine.Extractor(fast, 25, 200, max_batch_rows=rows)
+            before = run(ex, mats)
+            assert ex.demoted and ex.stats["fallback_windows"] == 1 and ex.stats["frames"] == frames
+            same(before, ref)
+            after = run(ex, mats)
+            assert after[0].get("owner") is ex._fallback_ex and after[0].get("owner") is not None
+            assert np.array_equal(after[2], before[2]) and np.array_equal(after[3], before[3])
+            same(after, ref)
+            assert ex.stats["fallback_windows"] == 1 and ex.stats["frames"] == 2 * frames
+
+
 def test_cli_on_a_kaldi_shaped_data_directory(env, tmp_path):
     """What a Kaldi data directory really holds: COMPRESSED feature matrices (make_mfcc.sh's default) spread over several arks, a
     feats.scp that lists a subset of them (utterances removed by a filter), a vad.scp over ALL utterances.  The CLI with the device

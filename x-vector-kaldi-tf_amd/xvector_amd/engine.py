@@ -17,6 +17,7 @@ is one of the HIP kernels behind the C ABI.
 import ctypes
 import math
 import os
+import threading
 
 import numpy as np
 
@@ -146,7 +147,7 @@ class BatchLayout(object):
         self.gap = int(gap)
         self.align = int(align)
         self.row_len = lengths.astype(np.int32)
-        self.lead = (self.gap + self.align - 1) // self.align * self.align
+        self.lead = int(slot_rows(0, self.gap, self.align))            # (the slot of a chunk without frames)
         self.slots = slot_rows(lengths, self.gap, self.align)
         starts = np.empty(len(lengths), dtype=np.int64)
         if len(lengths):
@@ -304,7 +305,6 @@ class DeviceModel(object):
                 if isinstance(self.layers[-1].get("wp"), hiplib.PackedToom) and d > 1:
                     # a dilated Toom-Cook layer pairs the rows (r, r + d) with floor(r / d) even: chunks on multiples of 2 d rows, so
                     # that a chunk's pairing -- its bits -- does not depend on where in a batch it lies (d = 3: 24-row alignment)
-                    import math
                     self.align = math.lcm(self.align, 2 * int(d))
             if self.attention:
                 # models.py:1036-1046: h = [h1 | h2]; u = h1 . attention/w + attention/b is one more K=1 layer.  On the
@@ -746,7 +746,7 @@ class _Rows(object):
 # extractor: utterances in, x-vectors out
 # ------------------------------------------------------------------------------------------------
 _STAGE_CACHE = {}          # (in_dim, NBUF) -> parked pinned staging sets of finished extractors (at most 2 per key)
-_STAGE_LOCK = __import__("threading").Lock()
+_STAGE_LOCK = threading.Lock()
 
 
 _STAGE_PENDING = {}        # (in_dim, NBUF) -> side thread that is pinning a set for the cache (prewarm_staging)
@@ -763,7 +763,6 @@ def prewarm_staging(in_dim, rows=262144, nchunks=8192):
     together (tools/experiments/startup_contention_probe.py) -- the ranks of a node's job do start together.  Called by the CLI
     worker as soon as the HIP runtime is up, the ~100 MB of a worker are pinned while its weights are read, packed and probed
     instead of in front of its first window."""
-    import threading
     import torch
     key = (int(in_dim), Extractor.NBUF)
     with _STAGE_LOCK:
@@ -825,6 +824,7 @@ class Extractor(object):
         self.max_batch_chunks = int(max_batch_chunks)
         self.stats = dict(batches=0, chunks=0, frames=0, rows=0)
         self._stage = None
+        self._raw_stage = None                         # (submit_raw's own pinned sets, rotated with ``_stage``)
         self._copy_stream = None
         self._turn = 0
         self._finalizer = None
@@ -838,10 +838,7 @@ class Extractor(object):
         (``_STAGE_CACHE``) and the next one -- every ``make_embedding`` call builds its own -- picks them up."""
         torch = self.model.torch
         if self._stage is None or self._stage[0]["x"].shape[0] < rows or self._stage[0]["meta"].shape[1] < nchunks:
-            # sized for the largest regular batch up front: re-pinning 3 x 25 MB whenever a window brings a slightly larger
-            # batch costs more than the kernels of that batch
-            rows = max(rows, 1024) if rows <= 4096 else max(rows, self.max_batch_rows)
-            nchunks = max(nchunks, 64) if nchunks <= 64 else max(nchunks, min(self.max_batch_chunks, 8192))
+            rows, nchunks = self._regular_caps(rows, nchunks, self.PIN_FLOOR, self.max_batch_rows)
             if self._stage is not None:
                 _park_stage(self._holder)
             with _STAGE_LOCK:
@@ -860,17 +857,18 @@ class Extractor(object):
             self._holder[:] = [(self.model.in_dim, self.NBUF), self._stage]
         if self._copy_stream is None:
             self._copy_stream = torch.cuda.Stream(device=self.model.device)
-        return self._stage
 
-    def _reserve_caps(self, bounds):
-        """Rows / chunks to size the device buffers for: the largest REGULAR batch from the first window on (as the pinned
-        staging sets above) -- growing them when a later window brings a larger batch is a hipMalloc of gigabytes in the
-        middle of the stream (50 ms per call when the first read window was a short one)."""
-        rows = max(r for _, _, r in bounds)
-        nch = max(b1 - b0 for b0, b1, _ in bounds)
-        rows = rows if rows <= 4096 else max(rows, self.max_batch_rows)
-        nch = nch if nch <= 64 else max(nch, min(self.max_batch_chunks, 8192))
-        return rows, nch
+    PIN_FLOOR = (1024, 64)       # smallest pinned staging set: rows, chunks (or utterances)
+
+    def _regular_caps(self, rows, count, floor, regular_rows):
+        """Rows / chunks (or utterances) to size a buffer for when a window's largest batch needs ``rows`` / ``count``: a small
+        window gets what it needs, at least ``floor``; any other the largest REGULAR batch (``regular_rows``, the chunk budget) from
+        the first window on.  Growing when a later window brings a slightly larger batch costs more than that batch's kernels:
+        re-pinning 3 x 25 MB for a pinned set; for the device buffers a hipMalloc of gigabytes in the middle of the stream (50 ms
+        per call when the first read window was a short one)."""
+        rows = max(rows, floor[0]) if rows <= 4096 else max(rows, regular_rows)
+        count = max(count, floor[1]) if count <= 64 else max(count, min(self.max_batch_chunks, 8192))
+        return rows, count
 
     def _pinned(self, kind, shape, dtype):
         """A pinned host tensor of ``shape`` from this extractor's free list (per-window buffers: the chunk table that goes up,
@@ -967,15 +965,18 @@ class Extractor(object):
         i+1 then overlaps the kernels of window i).  ``addrs``: optional ``matrix_addresses(mats, F)`` computed elsewhere
         (e.g. by the reader thread).  ``mats`` may be a lazy sequence with a ``lengths`` array (kaldi_io.ArkMats): with ``addrs``
         the native packer reads the rows in place and no matrix object is ever built."""
+
+        def again(ex):                                   # this window on another extractor: routed there, or repeated
+            return ex.submit(mats, addrs)
         if self.demoted:
-            return self._on_twin(lambda ex: ex.submit(mats, addrs))
-        torch = self.model.torch
-        model = self.model
-        dev = model.device
-        handle, (c_utt, c_start, c_len, seg_start), bounds = self._plan(mats.lengths if hasattr(mats, "lengths") else [m.shape[0] for m in mats])
-        nch = handle["nch"]
-        if nch == 0:
+            owner, handle = self._on_twin(again)
+            handle["owner"] = owner
             return handle
+        handle, win = self._open_window(mats.lengths if hasattr(mats, "lengths") else [m.shape[0] for m in mats])
+        if win is None:
+            return handle
+        model = self.model
+        c_utt, c_start, c_len, seg_start = win["table"]
         F = model.feat_dim
         lib = _host_lib()
         if lib is not None and addrs is None:
@@ -987,20 +988,10 @@ class Extractor(object):
         else:
             assert mats[int(c_utt[0])].shape[1] == F, "feature dimension does not match the model"
             l_utt, l_start, l_len = c_utt.tolist(), c_start.tolist(), c_len.tolist()
-        stage = self._staging(max(r for _, _, r in bounds), max(b1 - b0 for b0, b1, _ in bounds))
-        with torch.cuda.device(dev):
-            compute = torch.cuda.current_stream()
-            E_all = torch.empty((nch, model.embed_dim), dtype=torch.float32, device=dev)
-            P_all = torch.empty((nch, model.pooled_dim), dtype=torch.float32, device=dev)
-            model.reserve(*self._reserve_caps(bounds), int(c_len.max()))
-            keep = []                                   # device inputs stay referenced until the window is done
-            status = torch.zeros(1, dtype=torch.int32, device=dev) if model.f16bf8 else None
-            for bi, (b0, b1, _) in enumerate(bounds):
+        with model.torch.cuda.device(model.device):
+            for bi, (b0, b1, _) in enumerate(win["bounds"]):
                 layout = BatchLayout(c_len[b0:b1], model.gap, model.align)
-                st = stage[self._turn % self.NBUF]
-                self._turn += 1
-                if st["event"] is not None:
-                    st["event"].synchronize()            # the copy that last read this pinned set has finished
+                st, = self._take(self._stage)
                 if native:
                     xs = st["x"].numpy()
                     rc = lib.xv_pack_rows_f32(c_src[b0:b1].ctypes.data, c_len32[b0:b1].ctypes.data, layout.row_start.ctypes.data,
@@ -1010,40 +1001,80 @@ class Extractor(object):
                 else:
                     layout.pack([mats[l_utt[i]][l_start[i]:l_start[i] + l_len[i]] for i in range(b0, b1)], st["x"].numpy())
                     layout.row_valid(st["rv"].numpy())
-                meta = st["meta"].numpy()
-                meta[0, :layout.nchunks] = layout.row_start
-                meta[1, :layout.nchunks] = layout.row_len
-                with torch.cuda.stream(self._copy_stream):
-                    x = st["x"][:layout.rows].to(dev, non_blocking=True)
-                    rv = st["rv"][:layout.rows].to(dev, non_blocking=True)
-                    md = st["meta"][:, :layout.nchunks].to(dev, non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(self._copy_stream)
-                st["event"] = ev
-                compute.wait_event(ev)
-                model.frame_level(x, md[0], md[1], rv, layout.nchunks, layout.max_len, P_all[b0:b1], status=status)
-                keep.append((x, rv, md))
-                if bi == 0:
-                    self._start_probe(handle, x, md, rv, layout)
-                self._count(layout)
-            self._window_tail(handle, compute, P_all, E_all, seg_start, c_len, status, keep, mats, lambda ex: ex.submit(mats, addrs))
+                st["event"] = self._launch(handle, win, bi, layout, st, [st["x"][:layout.rows]], lambda x: x)
+            self._window_tail(handle, win["compute"], win["P_all"], win["E_all"], seg_start, c_len, win["status"], win["keep"], mats, again)
         return handle
+
+    def _open_window(self, lens):
+        """What a window of utterances of ``lens`` frames needs before its first batch: the plan, and pinned staging sets, model
+        buffers and per-chunk outputs for its batches.  Returns ``(handle, win)``; ``win`` is None for a window without a chunk.
+        ``win["keep"]``: the device inputs stay referenced until the window is done."""
+        handle, table, bounds = self._plan(lens)
+        if not handle["nch"]:
+            return handle, None
+        model, torch = self.model, self.model.torch
+        dev, nch = model.device, handle["nch"]
+        rows, chunks = max(r for _, _, r in bounds), max(b1 - b0 for b0, b1, _ in bounds)
+        self._staging(rows, chunks)
+        with torch.cuda.device(dev):
+            win = dict(table=table, bounds=bounds, compute=torch.cuda.current_stream(), keep=[],
+                       E_all=torch.empty((nch, model.embed_dim), dtype=torch.float32, device=dev),
+                       P_all=torch.empty((nch, model.pooled_dim), dtype=torch.float32, device=dev))
+            model.reserve(*self._regular_caps(rows, chunks, (0, 0), self.max_batch_rows), int(table[2].max()))
+            win["status"] = torch.zeros(1, dtype=torch.int32, device=dev) if model.f16bf8 else None
+        return handle, win
+
+    def _take(self, *stages):
+        """This batch's pinned set of each of ``stages`` (they rotate together), once the copy that last read it has finished."""
+        sets = [stage[self._turn % self.NBUF] for stage in stages]
+        self._turn += 1
+        for st in sets:
+            if st["event"] is not None:
+                st["event"].synchronize()
+        return sets
+
+    def _upload(self, compute, *pinned):
+        """Pinned host tensors to the device on the copy stream; ``compute`` waits for them.  Returns the device tensors and the
+        copies' event (what has to pass before their pinned source is written again)."""
+        torch = self.model.torch
+        with torch.cuda.stream(self._copy_stream):
+            out = [t.to(self.model.device, non_blocking=True) for t in pinned]
+            ev = torch.cuda.Event()
+            ev.record(self._copy_stream)
+        compute.wait_event(ev)
+        return out, ev
+
+    def _launch(self, handle, win, bi, layout, st, pinned, make_x):
+        """Batch ``bi`` of a window, behind the route's own filling: ``st`` is its regular pinned set with ``rv`` filled, ``pinned``
+        the route's slices to upload, ``make_x(*their device copies)`` the packed device batch.  Returns the upload's event."""
+        b0, b1, _ = win["bounds"][bi]
+        n = layout.nchunks
+        meta = st["meta"].numpy()
+        meta[0, :n] = layout.row_start
+        meta[1, :n] = layout.row_len
+        (*mine, rv, md), ev = self._upload(win["compute"], *pinned, st["rv"][:layout.rows], st["meta"][:, :n])
+        x = make_x(*mine)
+        self.model.frame_level(x, md[0], md[1], rv, n, layout.max_len, win["P_all"][b0:b1], status=win["status"])
+        win["keep"].append((x, rv, md, mine))
+        if bi == 0:
+            self._start_probe(handle, x, md, rv, layout)
+        self._count(layout)
+        return ev
 
     def _plan(self, lens):
         """The plan of a window of utterances of ``lens`` frames: the chunk table (utterances ordered by length, so that batches
-        are length-homogeneous) and its batch boundaries (greedy fill up to max_batch_rows / max_batch_chunks; a single chunk
-        may exceed the row budget).  Returns ``(handle, (c_utt, c_start, c_len, seg_start), bounds)``; bounds is None for a
-        window without a chunk."""
+        are length-homogeneous) and its batch boundaries (the rows dealt evenly to the fewest batches within max_batch_rows /
+        max_batch_chunks; a single chunk may exceed the row budget).  Returns
+        ``(handle, (c_utt, c_start, c_len, seg_start), bounds)``; bounds is None for a window without a chunk."""
         order, c_utt, c_start, c_len, seg_start = plan_chunk_table(lens, self.min_chunk_size, self.chunk_size)
         nch = len(c_utt)
         handle = dict(n=len(lens), order=order, nch=nch)
         bounds = None
         if nch:
             gap, align = self.model.gap, self.model.align
-            lead = (gap + align - 1) // align * align
             cum = np.zeros(nch + 1, dtype=np.int64)
             np.cumsum(slot_rows(c_len, gap, align), out=cum[1:])
-            bounds = self._batch_bounds(cum, lead)
+            bounds = self._batch_bounds(cum, int(slot_rows(0, gap, align)))               # (the batch's lead: BatchLayout)
         return handle, (c_utt, c_start, c_len, seg_start), bounds
 
     def _count(self, layout):
@@ -1062,11 +1093,7 @@ class Extractor(object):
         tail_np = np.concatenate([np.asarray(seg_start, dtype=np.int32), c_len.astype(np.int32)])
         tail_flat, tail = self._pinned("tail", tail_np.shape, torch.int32)
         tail.numpy()[:] = tail_np
-        with torch.cuda.stream(self._copy_stream):
-            tail_d = tail.to(dev, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(self._copy_stream)
-        compute.wait_event(ev)
+        (tail_d,), _ = self._upload(compute, tail)
         seg, cl = tail_d[:len(order) + 1], tail_d[len(order) + 1:]
         out = torch.empty((len(order), model.embed_dim), dtype=torch.float32, device=dev)
         hiplib.chunk_average(E_all, seg, cl, len(order), out)
@@ -1096,15 +1123,14 @@ class Extractor(object):
         return self._fallback_ex
 
     def _on_twin(self, submit):
-        """A window of a demoted extractor: submitted on the twin (``finish`` follows the handle's ``owner``); its batches
-        count in this extractor's statistics."""
+        """A window of a demoted extractor: ``submit(twin's extractor)`` submits it there; its batches count in this extractor's
+        statistics.  Returns that extractor (the ``owner`` that ``finish`` follows, for the window's handle) and ``submit``'s result."""
         ex = self._twin()
         before = dict(ex.stats)
-        handle = submit(ex)
+        out = submit(ex)
         for k in ("batches", "chunks", "frames", "rows"):
             self.stats[k] += ex.stats[k] - before[k]
-        handle["owner"] = ex
-        return handle
+        return ex, out
 
     PROBE_MIN_LEN = 128          # chunks the probe prefers (a vector pooled over a handful of frames is noisier in EVERY arithmetic)
 
@@ -1136,11 +1162,7 @@ class Extractor(object):
         mh = meta.numpy()
         mh[0] = layout.row_start[i0:i0 + m] - base
         mh[1] = layout.row_len[i0:i0 + m]
-        with torch.cuda.stream(self._copy_stream):
-            md2 = meta.to(dev, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(self._copy_stream)
-        torch.cuda.current_stream().wait_event(ev)
+        (md2,), _ = self._upload(torch.cuda.current_stream(), meta)
         P = torch.empty((m, twin.pooled_dim), dtype=torch.float32, device=dev)
         E = torch.empty((m, twin.embed_dim), dtype=torch.float32, device=dev)
         twin.frame_level(x[base:base + rows], md2[0], md2[1], rv[base:base + rows], m, int(layout.row_len[i0:i0 + m].max()), P)
@@ -1178,13 +1200,13 @@ class Extractor(object):
         utterance; addrs: optional ``matrix_addresses(mats, F)``.  Returns ``(handle, lengths, vad_dropped)``: the handle for ``finish``; the number of selected frames per
         utterance; a bool mask of the utterances select-voiced-frames drops (VAD length mismatch / no voiced frame)."""
         from .frontend import VadRuns, select_voiced
-        if self.demoted:
-            box = []
 
-            def go(ex):
-                box[:] = ex.submit_raw(mats, vads, cmn_window, center, min_window, addrs)
-                return box[0]
-            return (self._on_twin(go),) + tuple(box[1:])
+        def again(ex):                                   # this window on another extractor: routed there, or repeated
+            return ex.submit_raw(mats, vads, cmn_window, center, min_window, addrs)
+        if self.demoted:
+            owner, out = self._on_twin(again)
+            out[0]["owner"] = owner
+            return out
         torch = self.model.torch
         model = self.model
         dev = model.device
@@ -1211,11 +1233,11 @@ class Extractor(object):
         else:
             if not isinstance(vads, VadRuns):             # (runs: every utterance has a vector)
                 vad_dropped &= np.fromiter((v is not None for v in vads), dtype=bool, count=n)
-        handle, (_, _, c_len, seg_start), bounds = self._plan(V)
-        order, nch = handle["order"], handle["nch"]
-        if nch == 0:
+        handle, win = self._open_window(V)
+        if win is None:
             return handle, V, vad_dropped
-        kept =np.ascontiguousarray(np.diff(seg_start), dtype=np.int64)                  # chunks per utterance of `order`
+        order, bounds, (_, _, c_len, seg_start) = handle["order"], win["bounds"], win["table"]
+        kept = np.ascontiguousarray(np.diff(seg_start), dtype=np.int64)                  # chunks per utterance of `order`
         first_len = np.ascontiguousarray(c_len[seg_start[:-1]], dtype=np.int64)          # = the chunk size the plan used for the utterance
         seg_o = np.ascontiguousarray(seg_start[:-1], dtype=np.int64)
         vstart_o = np.ascontiguousarray(vstart[order], dtype=np.int64)                   # (per utterance of `order`, like the three above)
@@ -1226,14 +1248,7 @@ class Extractor(object):
                  for b0, b1, _ in bounds]
         raw_rows = max(int(T[order[lo:hi]].sum()) for lo, hi in spans)
         self._raw_staging(raw_rows, max(hi - lo for lo, hi in spans), F)
-        self._staging(max(r for _, _, r in bounds), max(b1 - b0 for b0, b1, _ in bounds))
         with torch.cuda.device(dev):
-            compute = torch.cuda.current_stream()
-            E_all = torch.empty((nch, model.embed_dim), dtype=torch.float32, device=dev)
-            P_all = torch.empty((nch, model.pooled_dim), dtype=torch.float32, device=dev)
-            model.reserve(*self._reserve_caps(bounds), int(c_len.max()))
-            keep = []
-            status = torch.zeros(1, dtype=torch.int32, device=dev) if model.f16bf8 else None
             for bi, ((b0, b1, _), (lo, hi)) in enumerate(zip(bounds, spans)):
                 layout = BatchLayout(c_len[b0:b1], model.gap, model.align)
                 U = order[lo:hi]
@@ -1241,12 +1256,7 @@ class Extractor(object):
                 nU, rows_in = len(U), int(Tb.sum())
                 ustart = np.zeros(nU, dtype=np.int64)
                 np.cumsum(Tb[:-1], out=ustart[1:])
-                st = self._raw_stage[self._turn % self.NBUF]
-                sx = self._stage[self._turn % self.NBUF]
-                self._turn += 1
-                for s_ in (st, sx):
-                    if s_["event"] is not None:
-                        s_["event"].synchronize()
+                st, sx = self._take(self._raw_stage, self._stage)
                 src_b, len_b, start_b = addrs[U], Tb.astype(np.int32), ustart.astype(np.int32)      # (kept alive across the call)
                 rc = lib.xv_pack_rows_f32(src_b.ctypes.data, len_b.ctypes.data, start_b.ctypes.data, nU, F,
                                           st["raw"].numpy().ctypes.data, F, rows_in, None, self.PACK_THREADS)
@@ -1261,43 +1271,33 @@ class Extractor(object):
                 um[0, :nU] = ustart
                 um[1, :nU] = Tb
                 layout.row_valid(sx["rv"].numpy())
-                meta = sx["meta"].numpy()
-                meta[0, :layout.nchunks] = layout.row_start
-                meta[1, :layout.nchunks] = layout.row_len
-                with torch.cuda.stream(self._copy_stream):
-                    raw_d = st["raw"][:rows_in].to(dev, non_blocking=True)
-                    dst_d = st["dst"][:rows_in].to(dev, non_blocking=True)
-                    utt_d = st["utt"][:, :nU].to(dev, non_blocking=True)
-                    rv = sx["rv"][:layout.rows].to(dev, non_blocking=True)
-                    md = sx["meta"][:, :layout.nchunks].to(dev, non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(self._copy_stream)
-                st["event"] = sx["event"] = ev
-                compute.wait_event(ev)
-                x = torch.zeros((layout.rows, model.in_dim), dtype=torch.float32, device=dev)      # gap rows and padding columns
-                hiplib.cmn_sliding_scatter(raw_d, utt_d[0], utt_d[1], nU, int(Tb.max()), cmn_window, center, min_window, dst_d, x)
-                model.frame_level(x, md[0], md[1], rv, layout.nchunks, layout.max_len, P_all[b0:b1], status=status)
-                keep.append((x, rv, md, raw_d, dst_d, utt_d))
-                if bi == 0:
-                    self._start_probe(handle, x, md, rv, layout)
-                self._count(layout)
-            self._window_tail(handle, compute, P_all, E_all, seg_start, c_len, status, keep, mats,
-                              lambda ex: ex.submit_raw(mats, vads, cmn_window, center, min_window, addrs)[0])
+
+                def scatter(raw_d, dst_d, utt_d):
+                    x = torch.zeros((layout.rows, model.in_dim), dtype=torch.float32, device=dev)      # gap rows and padding columns
+                    hiplib.cmn_sliding_scatter(raw_d, utt_d[0], utt_d[1], nU, int(Tb.max()), cmn_window, center, min_window, dst_d, x)
+                    return x
+                st["event"] = sx["event"] = self._launch(handle, win, bi, layout, sx,
+                                                         [st["raw"][:rows_in], st["dst"][:rows_in], st["utt"][:, :nU]], scatter)
+            self._window_tail(handle, win["compute"], win["P_all"], win["E_all"], seg_start, c_len, win["status"], win["keep"], mats,
+                              lambda ex: again(ex)[0])
         return handle, V, vad_dropped
 
     def _raw_staging(self, rows, nutts, feat_dim):
         """NBUF pinned sets for submit_raw: raw features [rows, F], destination rows int32[rows], (start, length) int32[2, utts]."""
         torch = self.model.torch
-        cur = getattr(self, "_raw_stage", None)
+        cur = self._raw_stage
         if cur is None or cur[0]["raw"].shape[0] < rows or cur[0]["utt"].shape[1] < nutts or cur[0]["raw"].shape[1] != feat_dim:
-            rows = max(rows, 2 * self.max_batch_rows) if rows > 4096 else max(rows, 1024)
-            nutts = max(nutts, min(self.max_batch_chunks, 8192)) if nutts > 64 else max(nutts, 64)
+            rows, nutts = self._regular_caps(rows, nutts, self.PIN_FLOOR, 2 * self.max_batch_rows)
             self._raw_stage = [dict(raw=torch.zeros((rows, feat_dim), dtype=torch.float32).pin_memory(),
                                     dst=torch.zeros(rows, dtype=torch.int32).pin_memory(),
                                     utt=torch.zeros((2, nutts), dtype=torch.int32).pin_memory(), event=None) for _ in range(self.NBUF)]
-        if self._copy_stream is None:
-            self._copy_stream = torch.cuda.Stream(device=self.model.device)
-        return self._raw_stage
+
+    def _release(self, handle):
+        """The pinned chunk table and x-vector buffer of a window go round again (nobody may still hold rows of ``host``)."""
+        pinned = handle.pop("pinned", None)
+        if pinned is not None:
+            self._unpin("tail", pinned[0])
+            self._unpin("xvec", pinned[1])
 
     def finish(self, handle, as_array=False):
         """Wait for a submitted window and return its x-vectors in input order: a list with None for rejected utterances,
@@ -1320,10 +1320,7 @@ class Extractor(object):
                     # (this window's, or an earlier one's while this window was already in flight): the whole window again on
                     # the bf16x3 twin -- its results replace these
                     redo = handle.pop("redo")
-                    pinned = handle.pop("pinned", None)
-                    if pinned is not None:
-                        self._unpin("tail", pinned[0])
-                        self._unpin("xvec", pinned[1])
+                    self._release(handle)
                     handle["keep"] = None
                     self.stats["fallback_windows"] = self.stats.get("fallback_windows", 0) + 1
                     return self._twin().finish(redo(self._twin()), as_array)
@@ -1336,13 +1333,11 @@ class Extractor(object):
             if handle["nch"]:
                 full[handle["order"]] = host_out
                 valid[handle["order"]] = True
-                pinned = handle.pop("pinned", None)          # the vectors were copied out: the pinned buffers go round again
-                if pinned is not None:
-                    self._unpin("tail", pinned[0])
-                    self._unpin("xvec", pinned[1])
+                self._release(handle)                        # the vectors were copied out
             return full, valid
         results = [None] * n
         if handle["nch"]:
+            # (no ``_release``: the rows handed out alias the pinned buffer)
             for j, u in enumerate(handle["order"].tolist()):
                 results[u] = host_out[j]
         return results
