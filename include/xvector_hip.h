@@ -52,7 +52,7 @@ extern "C" {
 #define XV_ERR_BAD_ARG (-1)
 #define XV_ERR_UNSUPPORTED (-2)
 
-/* Library / ABI version (increments whenever an entry point is added or changed; currently 33). */
+/* Library / ABI version (increments whenever an entry point is added or changed; currently 34). */
 int xv_version(void);
 /* Thread-local description of the last non-zero return. */
 const char *xv_last_error(void);
@@ -813,6 +813,45 @@ int xv_resample_f32(const void *in, int in_format, const int64_t *in_offset, con
                     const int64_t *out_samples, const int64_t *utt_table, int n_utts, const int64_t *tables, int n_tables,
                     const int32_t *first, const int32_t *ntaps, const float *w, const int64_t *tiles, int64_t n_tiles, float *out,
                     void *stream);
+
+/* ---- NIST SPHERE audio decoded in front of the MFCC kernel (csrc/xv_sphere.hip) --------------------------------
+ * What `sph2pipe -f wav -p [-c N] x.sph |` does for an uncompressed file: the expansion of 8-bit G.711 codes to 16-bit linear
+ * PCM (or a byte swap of 16-bit PCM) and the choice of one channel.  The formulas below, exact integer arithmetic, are what is
+ * claimed (they give ITU-T G.711's tables); equality with the sph2pipe binary is not.  For a code byte b (0 .. 255):
+ *     mu-law:  u = ~b;  t = (((u & 15) << 3) + 132) << ((u >> 4) & 7);  y = (u & 128) ? 132 - t : t - 132
+ *     A-law:   a = b ^ 0x55;  t = (a & 15) << 4;  s = (a >> 4) & 7;  t += s ? 0x108 : 8;  if (s > 1) t <<= s - 1;
+ *              y = (a & 128) ? t : -t
+ *     PCM16:   y = b0 | b1 << 8 (little-endian) or b0 << 8 | b1 (big-endian), as a signed 16-bit value
+ * xv_wave_decode  n_utts ragged utterances of any mix of codings in one launch.  raw: raw_bytes bytes of device memory holding
+ *   the data regions of the files as they lie on disk.  Utterance u is described by utt[XV_DEC_FIELDS * u + XV_DEC_*] (int64,
+ *   device): sample s < N is the code at byte RAW_OFF + s STRIDE + CH_OFF of raw (STRIDE: the bytes of a frame, 1, 2 or 4;
+ *   CH_OFF: the chosen channel's place in it, CH_OFF + width <= STRIDE with width 2 for PCM16 and 1 for G.711) and goes to
+ *   out[OUT_OFF + s] as int16 (sample_format 0) or as that value in fp32 (1; exact), the formats of xv_mfcc_f32 and
+ *   xv_augment_write.  Two utterances may read the same bytes (the two channels of one file).  Nothing of out outside
+ *   [OUT_OFF, OUT_OFF + N) is written, whatever the offsets' alignment.  The two reserved fields are zero.
+ *   tiles: [n_tiles, 2] int64 (device) = (utterance, o0), o0 a multiple of XV_DEC_TILE: with h = OUT_OFF mod 8 the tile makes the
+ *   samples s with o0 <= s + h < o0 + XV_DEC_TILE (tiles are cut at 16-byte boundaries of out, not of the utterance), so an
+ *   utterance takes ceil((N + h) / XV_DEC_TILE) tiles; every sample is covered by exactly one tile (the host's list).
+ *   raw and out must be 16-byte aligned.  The kernel cannot see how long out is, and the descriptors are device memory: the
+ *   caller checks that every span lies inside raw and out and that CODING, STRIDE and CH_OFF are in range before the call
+ *   (xvector_amd/hiplib.py wave_decode does, refusing with XV_ERR_BAD_ARG); a workgroup that meets a descriptor outside these
+ *   rules, or a span leaving raw, writes nothing.  XV_ERR_BAD_ARG: a null pointer, a negative count, a sample_format other than
+ *   0 / 1, a misaligned raw or out.  XV_ERR_UNSUPPORTED: more than 2^31 - 1 tiles.  A refused call launches nothing; n_tiles == 0
+ *   returns 0 and launches nothing.  Enqueues and returns. */
+#define XV_DEC_TILE 4096
+#define XV_DEC_FIELDS 8
+#define XV_DEC_RAW_OFF 0
+#define XV_DEC_N 1
+#define XV_DEC_STRIDE 2
+#define XV_DEC_CH_OFF 3
+#define XV_DEC_CODING 4
+#define XV_DEC_OUT_OFF 5
+#define XV_DEC_PCM16_LE 0
+#define XV_DEC_PCM16_BE 1
+#define XV_DEC_ULAW 2
+#define XV_DEC_ALAW 3
+int xv_wave_decode(const uint8_t *raw, int64_t raw_bytes, const int64_t *utt, int n_utts, const int64_t *tiles, int64_t n_tiles,
+                   void *out, int sample_format, void *stream);
 
 #ifdef __cplusplus
 }

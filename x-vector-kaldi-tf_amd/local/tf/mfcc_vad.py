@@ -14,7 +14,11 @@ overrides it.  ``--seed`` keys the dither noise with the utterance id (DESIGN.md
 ``--compress[=true|false]`` (compute-mfcc-feats, compute-mfcc-vad, copy-feats; default false, as in the binaries -- Kaldi's
 steps/make_mfcc.sh passes true) writes features as Kaldi CompressedMatrix records instead (``CM``, or ``CM2`` for matrices of up
 to 8 rows), encoded on the GPU (xvector_amd/compress.py); a matrix without rows stays an ``FM`` record.
-wav.scp entries are paths or ``cmd |`` pipes; 16-bit PCM WAV only.  A pipe whose last stage is ``wav-reverberate`` (what
+wav.scp entries are paths or ``cmd |`` pipes; 16-bit PCM WAV only.  A pipe that is exactly ``sph2pipe -f wav [-p] [-c 1|2]
+x.sph |`` (what the recipe's data-preparation scripts write) is read in-process and, for the feature commands, decoded on the
+GPU: no sph2pipe process is started (xvector_amd/sphere.py; mu-law, A-law and 16-bit PCM files of one or two
+channels; anything else, and everything under ``XVECTOR_NATIVE_SPH=0``, runs in the shell as before).  A pipe whose last stage is
+``wav-reverberate`` (what
 Kaldi's reverberate_data_dir.py / augment_data_dir.py write) is evaluated in-process on the GPU (xvector_amd/augment.py,
 DESIGN.md §8.7); no wav-reverberate process is started.  ``--allow-downsample`` / ``--allow-upsample`` (compute-mfcc-feats,
 compute-mfcc-vad; also through ``--config``) take a wave whose rate differs from ``--sample-frequency`` as it is and resample it
@@ -37,7 +41,7 @@ if _HERE not in sys.path:
 sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))
 
 import kaldi_io  # noqa: E402
-from xvector_amd import augment, compress, mfcc  # noqa: E402
+from xvector_amd import augment, compress, mfcc, sphere  # noqa: E402
 
 logger = logging.getLogger('mfcc_vad')
 logger.addHandler(logging.StreamHandler())
@@ -45,7 +49,8 @@ logger.setLevel(logging.INFO)
 logging.getLogger('mfcc').addHandler(logging.StreamHandler())
 logging.getLogger('augment').addHandler(logging.StreamHandler())
 
-WINDOW_SAMPLES = 1 << 26          # samples per launch (128 MiB of int16)
+WINDOW_SAMPLES = 1 << 26          # samples per launch (128 MiB of int16; coded SPHERE entries add a side buffer of their
+                                  # files' bytes, at most 4 per sample: both channels of 16-bit PCM)
 
 
 def _flags(p, cls):
@@ -119,7 +124,8 @@ def _wav_scp_path(rspec):
 
 def _read_waves(path, opts, state=None):
     """(key, int16 samples) of every usable entry, in order (Kaldi's skip rules applied; a wave to be resampled is a
-    ``mfcc.Wave`` carrying its rate).  An entry whose last pipeline stage
+    ``mfcc.Wave`` carrying its rate).  An entry that is one recognised ``sph2pipe`` command comes as a ``mfcc.CodedWave``: only its
+    header is read here, its bytes go to the GPU as they lie in the file (xvector_amd/sphere.py).  An entry whose last pipeline stage
     is wav-reverberate comes as (key, augment.Pending) added to ``state['plan']``: only its length is known here, the GPU makes
     its samples (xvector_amd/augment.py)."""
     for key, rx in mfcc.read_wav_scp(path):
@@ -140,10 +146,12 @@ def _read_waves(path, opts, state=None):
             except augment.AugmentError as e:
                 raise SystemExit("Failed to read the wave of %s: %s" % (key, e))
         try:
-            rate, x = mfcc.load_wav(key, rx)
+            coded = sphere.recognise(key, rx)
+            if coded is None:
+                rate, x = mfcc.load_wav(key, rx)
         except mfcc.WavError as e:
             raise SystemExit("Failed to read the wave of %s: %s" % (key, e))
-        w = mfcc.select_channel(key, rate, x, opts)
+        w = mfcc.select_coded(key, coded, opts) if coded is not None else mfcc.select_channel(key, rate, x, opts)
         if w is not None:
             yield key, w
 

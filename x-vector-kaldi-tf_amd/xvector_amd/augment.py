@@ -5,7 +5,8 @@ last pipeline stage is ``wav-reverberate ... - |``.  This module
 
 * parses such an entry into a tree (``parse_rx``): the input, the impulse response and every additive signal are rxfilenames
   themselves, so a nested ``wav-reverberate`` (the ``--duration`` repeat of background noises) becomes a child node, never a
-  process; stages before the last one (sox, sph2pipe) still run in the shell;
+  process; stages before the last one (sox) still run in the shell, except a single recognised ``sph2pipe`` command, which
+  ``mfcc.load_wav`` reads in-process (xvector_amd/sphere.py);
 * works out each node's output length and rate on the host (``Augmenter.plan``), decoding every distinct rxfilename once and
   forming every distinct impulse response once;
 * evaluates the nodes on the GPU level by level (csrc/xv_augment.hip; children first), writing the top-level outputs straight
@@ -516,6 +517,10 @@ def duration_samples(key, rx, augmenter=None):
     """(samples, rate) of a wav.scp entry without evaluating it: an augmented entry's M from its options and inputs."""
     node = parse_rx(rx)
     if isinstance(node, Source):
+        from . import sphere
+        coded = sphere.recognise(key, rx)
+        if coded is not None:                     # a recognised sph2pipe entry: its header says it
+            return coded.n, coded.rate
         rate, x = mfcc.load_wav(key, rx)
         return x.shape[1], rate
     plan = (augmenter or Augmenter()).plan([(key, node)])

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -144,6 +144,8 @@ _SIGNATURES = {
     # sample-rate conversion in front of the MFCC kernel
     "xv_resample_num_output": (_i64, [_i64, _ci, _ci]),
     "xv_resample_f32": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    # SPHERE audio (G.711, big-endian PCM) decoded in front of the MFCC kernel
+    "xv_wave_decode": (_ci, [_vp, _i64, _vp, _ci, _vp, _i64, _vp, _ci, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)      # tests check the header declares exactly these and the .so exports all of them
 
@@ -1378,6 +1380,40 @@ def resample(inp, utt, tab, first, ntaps, w, tiles, out):
                                _dev(first, torch.int32, "first"), _dev(ntaps, torch.int32, "ntaps"), _dev(w, torch.float32, "w"),
                                _dev(tiles, torch.int64, "tiles"), int(tiles.shape[0]), _dev(out, torch.float32, "out"), _stream()),
            "xv_resample_f32")
+
+
+def wave_decode(raw, utt, tiles, out, sample_format):
+    """Coded audio to samples (xv_wave_decode; see include/xvector_hip.h).  raw: uint8 (1-D, device), the data regions of the
+    files; utt: HOST int64 [U, 8] descriptors (RAW_OFF, N, STRIDE, CH_OFF, CODING, OUT_OFF, 0, 0), uploaded here; tiles: [n_tiles,
+    2] int64 (device); out: int16 (sample_format 0) or float32 (1), 1-D, device.  The host side of the ABI's argument checks
+    lives here, as in ``resample``: every span must lie inside raw and out, CODING and STRIDE must be in range and the channel
+    inside its frame, else the call is refused as XV_ERR_BAD_ARG before anything is launched."""
+    import numpy as np
+    import torch
+    lib = require_gpu()
+    assert raw.is_cuda and raw.dim() == 1 and raw.dtype == torch.uint8 and raw.is_contiguous()
+    assert out.is_cuda and out.dim() == 1 and out.is_contiguous() and sample_format in (0, 1)
+    assert out.dtype == (torch.int16 if sample_format == 0 else torch.float32)
+    assert isinstance(utt, np.ndarray) and utt.dtype == np.int64 and utt.ndim == 2 and utt.shape[1] == 8
+    assert tiles.dim() == 2 and tiles.shape[1] == 2
+    utt = np.ascontiguousarray(utt)
+    raw_off, n, stride, ch_off, coding, out_off = (utt[:, f] for f in range(6))
+
+    def refuse(bad, what):
+        if np.any(bad):
+            u = int(np.flatnonzero(bad)[0])
+            raise XvectorHipError("xv_wave_decode failed (-1): wave_decode: utterance %d: %s (descriptor %s)" % (u, what, utt[u].tolist()))
+
+    refuse((coding < 0) | (coding > 3), "CODING outside 0 .. 3")
+    refuse((stride != 1) & (stride != 2) & (stride != 4), "STRIDE is not 1, 2 or 4")
+    refuse((ch_off < 0) | (ch_off + np.where(coding < 2, 2, 1) > stride), "CH_OFF + width exceeds STRIDE")
+    refuse(n < 0, "a negative sample count")
+    refuse((raw_off < 0) | (n > (raw.numel() - raw_off) // np.maximum(stride, 1)), "the span leaves raw")
+    refuse((out_off < 0) | (n > out.numel() - out_off), "the span leaves out")
+    refuse((utt[:, 6] != 0) | (utt[:, 7] != 0), "a reserved field is not zero")
+    d_utt = torch.from_numpy(utt).to(raw.device)
+    _check(lib.xv_wave_decode(_ptr(raw), int(raw.numel()), _ptr(d_utt), int(utt.shape[0]), _dev(tiles, torch.int64, "tiles"),
+                              int(tiles.shape[0]), _ptr(out), int(sample_format), _stream()), "xv_wave_decode")
 
 
 def augment_power(sig, segments, tiles, tile_sumsq):

@@ -6,7 +6,9 @@ What ``steps/make_mfcc.sh`` (compute-mfcc-feats) and ``sid/compute_vad_decision.
   ``--config`` file (``read_config``), not through changed defaults.
 * ``MfccTables`` -- every table the kernel reads, built here: the window and the lifter x DCT-II in fp64 rounded to fp32
   once, the twiddles exp(-2 pi i k / N) likewise, the sparse mel bank in fp32 the way Kaldi's MelBanks forms it.
-* ``read_wav`` / ``read_wav_scp`` -- RIFF/WAVE 16-bit PCM (plain or WAVE_FORMAT_EXTENSIBLE), paths and ``cmd |`` pipes.
+* ``read_wav`` / ``read_wav_scp`` -- RIFF/WAVE 16-bit PCM (plain or WAVE_FORMAT_EXTENSIBLE), paths and ``cmd |`` pipes; a pipe
+  that is one recognised ``sph2pipe`` command is read in-process (xvector_amd/sphere.py), and comes to
+  ``Mfcc.compute`` as a ``CodedWave``: the file's bytes are uploaded as they are and decoded on the device (csrc/xv_sphere.hip).
 * ``Mfcc.compute`` -- MFCC rows and VAD decisions of many utterances per launch (csrc/xv_mfcc.hip); the decisions come back as
   a ``frontend.VadRuns``, so they plug straight into ``FrontEnd.apply``.  A wave at another rate than ``--sample-frequency`` is
   resampled on the device in front of the kernel when ``--allow-downsample`` / ``--allow-upsample`` permits (xvector_amd/resample.py,
@@ -353,8 +355,14 @@ def read_wav_scp(path):
 
 
 def load_wav(key, rx):
-    """The bytes of a wav.scp entry: a path, or a ``cmd |`` pipe whose non-zero exit is an error naming the key."""
+    """The wave of a wav.scp entry, (rate, int16 [channels, samples]): a path, or a ``cmd |`` pipe whose non-zero exit is an error
+    naming the key.  A pipe that is one recognised ``sph2pipe`` command is read in-process (xvector_amd/sphere.py, DESIGN.md
+    §8.12); every other one runs in the shell."""
     if rx.endswith("|"):
+        from . import sphere
+        coded = sphere.recognise(key, rx)
+        if coded is not None:
+            return coded.rate, sphere.decode_host(coded)
         p = subprocess.run(rx[:-1], shell=True, stdout=subprocess.PIPE)
         if p.returncode != 0:
             raise WavError("%s: command %r exited with status %d" % (key, rx[:-1], p.returncode))
@@ -373,11 +381,31 @@ class Wave(np.ndarray):
         self.rate = getattr(obj, "rate", None)
 
 
-def select_channel(key, rate, x, opts):
-    """compute-mfcc-feats' utterance rules: -> int16 [samples], or None (skipped, with Kaldi's warning).  A wave whose rate
-    differs from --sample-frequency comes back as a ``Wave`` carrying that rate when --allow-downsample / --allow-upsample
-    permits resampling it."""
-    nch = x.shape[0]
+class CodedWave(object):
+    """One channel of a recognised SPHERE entry whose samples are still coded (xvector_amd/sphere.py): ``Mfcc.compute`` uploads
+    the file's data region as it lies on disk and decodes it on the device.  ``shape`` mirrors a 1-D sample array's; ``coded``
+    (a ``sphere.Coded``) says where the bytes are (``read_into`` / ``region``: one read, no pass over the samples); ``coding``,
+    ``channels`` (of the file), ``channel`` (the one taken), ``rate`` and ``ident`` (the file's identity: entries of one file
+    share one upload) are what the engine reads."""
+    __slots__ = ("coded", "channel", "shape")
+
+    def __init__(self, coded, channel):
+        assert 0 <= channel < coded.channels
+        self.coded, self.channel = coded, int(channel)
+        self.shape = (coded.n,)
+
+    coding = property(lambda self: self.coded.coding)
+    channels = property(lambda self: self.coded.channels)
+    rate = property(lambda self: self.coded.rate)
+    ident = property(lambda self: self.coded.ident)
+
+    def region(self):
+        return self.coded.region()
+
+
+def _select_rules(key, rate, nch, n, opts):
+    """compute-mfcc-feats' utterance rules on what a header says (``nch`` channels of ``n`` samples at ``rate``): -> (channel,
+    whether it is to be resampled), or None (skipped, with Kaldi's warning)."""
     ch = opts.channel
     if ch == -1:
         if nch > 1:
@@ -397,14 +425,40 @@ def select_channel(key, rate, x, opts):
                        "skipping", rate, opts.sample_frequency, *(("downsample", "downsampling") if rate > opts.sample_frequency
                                                                   else ("upsample", "upsampling")), key)
         return None
-    if x.shape[1] < opts.min_duration * rate:                  # the original length at the original rate, as in Kaldi
-        logger.warning("File: %s is too short (%g sec): producing no output.", key, x.shape[1] / float(rate))
+    if n < opts.min_duration * rate:                           # the original length at the original rate, as in Kaldi
+        logger.warning("File: %s is too short (%g sec): producing no output.", key, n / float(rate))
         return None
+    return ch, resample
+
+
+def select_channel(key, rate, x, opts):
+    """compute-mfcc-feats' utterance rules: -> int16 [samples], or None (skipped, with Kaldi's warning).  A wave whose rate
+    differs from --sample-frequency comes back as a ``Wave`` carrying that rate when --allow-downsample / --allow-upsample
+    permits resampling it."""
+    sel = _select_rules(key, rate, x.shape[0], x.shape[1], opts)
+    if sel is None:
+        return None
+    ch, resample = sel
     w = np.ascontiguousarray(x[ch])
     if resample:
         w = w.view(Wave)
         w.rate = int(rate)
     return w
+
+
+def select_coded(key, coded, opts):
+    """``select_channel`` for a recognised SPHERE entry (a ``sphere.Coded``), from its header alone: -> a ``CodedWave`` (decoded
+    on the device), a ``Wave`` (an entry that is to be resampled is decoded on the host), or None (skipped)."""
+    from . import sphere
+    sel = _select_rules(key, coded.rate, coded.out_channels, coded.n, opts)
+    if sel is None:
+        return None
+    ch, resample = sel
+    if resample:
+        w = np.ascontiguousarray(sphere.decode_host(coded)[ch]).view(Wave)
+        w.rate = int(coded.rate)
+        return w
+    return CodedWave(coded, ch if coded.channel is None else coded.channel)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -427,7 +481,7 @@ class Mfcc(object):
         self._dev = self.tables.to_device(self.device)
         # own stream, as FrontEnd: the results go back to the host, nothing on the compute stream waits for them
         self._stream = torch.cuda.Stream(device=self.device)
-        self.stats = dict(utterances=0, samples=0, frames=0, launches=0, resampled=0)
+        self.stats = dict(utterances=0, samples=0, frames=0, launches=0, resampled=0, decoded=0, raw_bytes=0)
 
     def _windows(self, lens):
         """``lens``: the samples each utterance takes on the device (a resampled one: its output and its input)."""
@@ -446,6 +500,8 @@ class Mfcc(object):
         rates = [getattr(w, "rate", None) for w in waves] if rates is None else list(rates)
         assert len(rates) == len(waves)
         rates = [None if r is None or r == fs else r for r in rates]
+        if any(r is not None and isinstance(w, CodedWave) for w, r in zip(waves, rates)):
+            raise NotImplementedError("a CodedWave at another rate than --sample-frequency: decode it on the host (select_coded)")
         for r in rates:
             if r is None:
                 continue
@@ -460,7 +516,10 @@ class Mfcc(object):
         """keys: utterance ids (they key the dither); waves: 1-D int16 (or float32) sample arrays.  ``rates``: the sample rate of
         each wave (None: ``--sample-frequency``, or the ``rate`` a ``Wave`` carries); a wave at another rate is uploaded as it is
         and resampled on the device (xvector_amd/resample.py) into the fp32 sample buffer the MFCC kernel reads, when
-        --allow-downsample / --allow-upsample permits, and its frames are those of the resampled length.  Returns
+        --allow-downsample / --allow-upsample permits, and its frames are those of the resampled length.  A ``CodedWave`` among
+        ``waves`` (a SPHERE entry at --sample-frequency) is uploaded as the bytes of its file and decoded on the device
+        (csrc/xv_sphere.hip): per window the data regions of the distinct files go up in one uint8 side buffer
+        (at most 4 bytes per sample of the window budget) and one launch writes their samples into the sample buffer.  Returns
         ``(feats, vads, logmel)``: float32 [T, num_ceps] per utterance, a ``frontend.VadRuns`` (None unless VAD options were
         given or ``vad`` is True), and the float32 [T, num_mel_bins] log-mel energies (None unless ``with_logmel``).
         ``fill(x, i, j, offsets)``: called with each window's device sample buffer after the upload, before the MFCC launch, for
@@ -470,7 +529,7 @@ class Mfcc(object):
         fp32 table is not downloaded, the VAD still reads it on the device.  An utterance without frames gives a float32
         [0, num_ceps] array, as without ``compress``."""
         rates = self._rates(waves, rates)
-        waves = [np.asarray(w).reshape(-1) for w in waves]
+        waves = [w if isinstance(w, CodedWave) else np.asarray(w).reshape(-1) for w in waves]
         assert len(keys) == len(waves)
         do_vad = self.vad_opts is not None if vad is None else bool(vad)
         feats, logmels, runs = [], [], frontend.VadRuns() if do_vad else None
@@ -487,33 +546,47 @@ class Mfcc(object):
                 runs.add_run(*v)
         return feats, runs, (logmels if self.with_logmel else None)
 
-    def _upload_resampled(self, waves, rates, res, ns, off):
-        """The sample buffer of a window that holds resampled utterances (``res``: their indices): fp32, the utterances at
-        --sample-frequency uploaded in place (one copy per run of neighbours), the others uploaded at their own rate into a
-        side buffer and resampled into their spans on this engine's stream."""
+    def _upload_parts(self, waves, rates, res, cod, ns, off):
+        """The sample buffer of a window that holds resampled utterances (``res``: their indices) or coded ones (``cod``): fp32
+        when anything is resampled or a plain wave is, else int16.  The plain utterances at --sample-frequency are uploaded in
+        place (one copy per run of neighbours); the resampled ones are uploaded at their own rate into a side buffer and
+        resampled into their spans; the coded ones are uploaded as the bytes of their files, each distinct file once, and
+        decoded into their spans -- all on this engine's stream."""
         torch = self.torch
-        if self._resampler is None:
-            self._resampler = resample.Resampler(self.device)
-        x = torch.empty(max(int(ns.sum()), 1), dtype=torch.float32, device=self.device)
+        plain = [k for k in range(len(waves)) if rates[k] is None and not isinstance(waves[k], CodedWave)]
+        f32 = bool(len(res)) or any(waves[k].dtype != np.int16 for k in plain)
+        dtype = np.float32 if f32 else np.int16
+        x = torch.empty(max(int(ns.sum()), 1), dtype=torch.float32 if f32 else torch.int16, device=self.device)
+        is_plain = np.zeros(len(waves) + 1, bool)
+        is_plain[plain] = True
         i, n = 0, len(waves)
         while i < n:
-            if rates[i] is not None:
+            if not is_plain[i]:
                 i += 1
                 continue
             j = i
-            while j < n and rates[j] is None:
+            while is_plain[j]:
                 j += 1
-            run = np.concatenate([w.astype(np.float32, copy=False) for w in waves[i:j]])
+            run = np.concatenate([w.astype(dtype, copy=False) for w in waves[i:j]])
             if len(run):
                 x[int(off[i]):int(off[i]) + len(run)].copy_(torch.from_numpy(run))
             i = j
-        side = [waves[k] for k in res]
-        dtype = np.float32 if any(w.dtype != np.int16 for w in side) else np.int16
-        pl = resample.plan([w.shape[0] for w in side], [rates[k] for k in res], int(self.opts.sample_frequency), out_offsets=off[res])
-        assert np.array_equal(pl.out_samples, ns[res])
-        flat = np.concatenate([w.astype(dtype, copy=False) for w in side])
-        self._resampler.run(torch.from_numpy(flat if len(flat) else np.zeros(1, dtype)).to(self.device), pl, x)
-        self.stats["resampled"] += len(res)
+        if len(res):
+            if self._resampler is None:
+                self._resampler = resample.Resampler(self.device)
+            side = [waves[k] for k in res]
+            sdtype = np.float32 if any(w.dtype != np.int16 for w in side) else np.int16
+            pl = resample.plan([w.shape[0] for w in side], [rates[k] for k in res], int(self.opts.sample_frequency), out_offsets=off[res])
+            assert np.array_equal(pl.out_samples, ns[res])
+            flat = np.concatenate([w.astype(sdtype, copy=False) for w in side])
+            self._resampler.run(torch.from_numpy(flat if len(flat) else np.zeros(1, sdtype)).to(self.device), pl, x)
+            self.stats["resampled"] += len(res)
+        if len(cod):
+            from . import sphere
+            raw, utt, tiles = sphere.pack([(waves[k].coded, waves[k].channel) for k in cod], off[cod])
+            hiplib.wave_decode(torch.from_numpy(raw).to(self.device), utt, torch.from_numpy(tiles).to(self.device), x, 1 if f32 else 0)
+            self.stats["decoded"] += len(cod)
+            self.stats["raw_bytes"] += len(raw)
         return x
 
     def _launch(self, keys, waves, do_vad, fill=None, compress=False, rates=None):
@@ -529,14 +602,16 @@ class Mfcc(object):
         rows = int(T.sum())
         off = np.zeros(n, np.int64)
         np.cumsum(ns[:-1], out=off[1:])
-        if not len(res):
+        cod = np.array([k for k in range(n) if isinstance(waves[k], CodedWave)], np.int64)
+        parts = len(res) or len(cod)
+        if not parts:
             dtype = np.float32 if any(w.dtype != np.int16 for w in waves) else np.int16
             flat = np.concatenate([w.astype(dtype, copy=False) for w in waves]) if n else np.zeros(0, dtype)
         keyv = np.array([dither_key(k, opts.seed) for k in keys], np.uint64).view(np.int64)
         C, B = opts.num_ceps, opts.num_mel_bins
         with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
             dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device, non_blocking=False)  # noqa: E731
-            x = self._upload_resampled(waves, rates, res, ns, off) if len(res) else dev(flat if len(flat) else np.zeros(1, dtype))
+            x = self._upload_parts(waves, rates, res, cod, ns, off) if parts else dev(flat if len(flat) else np.zeros(1, dtype))
             if fill is not None:
                 fill(x, off)
             d_off, d_ns, d_row0, d_key = dev(off), dev(ns), dev(row0), dev(keyv)
