@@ -286,6 +286,17 @@ int xv_tdnn_pair_pool_f16bf8(const void *x, int64_t R, int cin, int cmid, int co
                              const float *bn_scale2, const float *bn_shift2, const float *act_alpha2, int act_kind,
                              const uint8_t *row_valid, float *block_stats, int32_t *status, void *stream);
 
+/* xv_tdnn_pair_pool_f16bf8 with the cross terms of the SECOND layer in block-scaled e2m3 (6-bit elements, one power-of-two scale
+ * per 16 channels of a frame / of a weight column: csrc/xv_split6.h) at half the matrix cycles of the bf8 form.  Same x, same
+ * arguments, same status semantics, same supported shapes; wt = xv_pack_pair_f16mx6(w1, w2) (xv_packed_pair_f16mx6_bytes bytes;
+ * the first layer's stages are byte for byte those of xv_pack_pair_f16bf8). */
+size_t xv_packed_pair_f16mx6_bytes(int cin, int cmid, int cout);
+int xv_pack_pair_f16mx6(const float *w1, const float *w2, int cin, int cmid, int cout, void *wt, void *stream);
+int xv_tdnn_pair_pool_f16mx6(const void *x, int64_t R, int cin, int cmid, int cout, const void *wt, const float *bias1,
+                             const float *bn_scale1, const float *bn_shift1, const float *act_alpha1, const float *bias2,
+                             const float *bn_scale2, const float *bn_shift2, const float *act_alpha2, int act_kind,
+                             const uint8_t *row_valid, float *block_stats, int32_t *status, void *stream);
+
 /* xv_fc_f32 twin: fp32 rows in, fp32 rows out; wt = xv_pack_weights_bf16x3(w, 1, In, Out). */
 int xv_fc_bf16x3(const float *x, int nrows, int in_dim, const void *wt, const float *bias, const float *bn_scale,
                  const float *bn_shift, int act_kind, const float *act_alpha, int out_dim, float *y, float *y_preact, void *stream);

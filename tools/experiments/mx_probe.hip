@@ -1,12 +1,14 @@
 // EXPERIMENT: (1) operand layout of v_mfma_scale_f32_32x32x64_f8f6f4 with bf8 (e5m2) operands, (2) MFMA-only throughput of the
 // shipped bf16x3 pattern (24 x bf16 32x32x16 per 32-channel stage and wave) against the candidate "f16 + bf8 cross terms"
-// pattern (8 x f16 32x32x16 + 4 x MX 32x32x64) with register-resident operands.
-//   hipcc --offload-arch=gfx950 -O3 -o mx_probe mx_probe.hip && ./mx_probe
+// pattern (8 x f16 32x32x16 + 4 x MX 32x32x64) with register-resident operands, (3) the e2m3 conversion instruction and the
+// per-lane scale bytes of the same MFMA with 6-bit operands (cbsz:2 blgp:2).
+//   hipcc --offload-arch=gfx950 -O3 -o mx_probe mx_probe.hip && ./mx_probe [fp6]
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <math.h>
+#include <string.h>
 #include <vector>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -180,8 +182,208 @@ static double run_rate(const uint8_t *src, float *out, int iters, const char *na
     return best;
 }
 
-int main()
+// ---- (3) e2m3 (fp6) operands: v_cvt_scalef32_2xpk16_fp6_f32 and v_mfma_scale_f32_32x32x64_f8f6f4 with cbsz:2 blgp:2 -----------------
+// Hypothesis H6: lane l supplies row/col (l & 31) and the 32 values of K block (l >> 5); element e of an A lane meets element e of
+// the B lane of the same block; the scale byte of that block of that row/col is taken from the SAME lane (byte op_sel of its scale
+// register).  The operands are made by the conversion instruction itself, so the bit order inside the six dwords cancels.
+typedef unsigned u32x6 __attribute__((ext_vector_type(6)));
+
+// The conversion through asm with an early-clobber result: the first run of this part used the builtin, for which this compiler
+// chose "v[0:5], v[2:17], v[18:33], v1" -- result registers on top of a source and of the scale -- and everything behind the
+// twelfth element came out converted with a clobbered scale (7.5 or 0).  The instruction writes while it still reads.
+__device__ __forceinline__ u32x6 cvt_fp6(f32x16 a, f32x16 b, float scale)
 {
+    u32x6 r;
+    asm volatile("v_cvt_scalef32_2xpk16_fp6_f32 %0, %1, %2, %3\n\ts_nop 1" : "=&v"(r) : "v"(a), "v"(b), "v"(scale));
+    return r;
+}
+
+__global__ void fp6_cvt_kernel(const float *x, const float *scale, unsigned *out)      // lane: 32 floats -> six dwords
+{
+    const int lane = threadIdx.x;
+    f32x16 a, b;
+    for (int i = 0; i < 16; ++i) { a[i] = x[lane * 32 + i]; b[i] = x[lane * 32 + 16 + i]; }
+    const u32x6 r = cvt_fp6(a, b, scale[lane]);
+    for (int i = 0; i < 6; ++i) out[lane * 6 + i] = r[i];
+}
+
+template <int OPA, int OPB>
+__global__ void fp6_mfma_kernel(const float *xa, const float *xb, const int *sa, const int *sb, float *D)
+{
+    const int lane = threadIdx.x;
+    f32x16 a0, a1, b0, b1;
+    for (int i = 0; i < 16; ++i) {
+        a0[i] = xa[lane * 32 + i]; a1[i] = xa[lane * 32 + 16 + i];
+        b0[i] = xb[lane * 32 + i]; b1[i] = xb[lane * 32 + 16 + i];
+    }
+    const u32x6 ra = cvt_fp6(a0, a1, 1.f);
+    const u32x6 rb = cvt_fp6(b0, b1, 1.f);
+    const i32x8 A = {(int)ra[0], (int)ra[1], (int)ra[2], (int)ra[3], (int)ra[4], (int)ra[5], 0, 0};
+    const i32x8 B = {(int)rb[0], (int)rb[1], (int)rb[2], (int)rb[3], (int)rb[4], (int)rb[5], 0, 0};
+    // the scale byte in byte OPA / OPB of the register, the other bytes hold a decoy (2^9) that must not show
+    const int va = (sa[lane] << (8 * OPA)) | (0x88888888 & ~(0xff << (8 * OPA)));
+    const int vb = (sb[lane] << (8 * OPB)) | (0x88888888 & ~(0xff << (8 * OPB)));
+    f32x16 c = {0};
+    c = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B, c, 2, 2, OPA, va, OPB, vb);
+    for (int r = 0; r < 16; ++r) D[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 32 + (lane & 31)] = c[r];
+}
+
+static float e2m3_rne(float x)          // host model: round to nearest even on the e2m3 grid, saturate at 7.5
+{
+    const float a = fabsf(x);
+    float q;
+    if (!(a < 7.75f)) q = 7.5f;         // (7.75 is the midpoint to the non-existent 8: ties to "even" = 8 -> saturates)
+    else {
+        const float step = a < 2.f ? 0.125f : a < 4.f ? 0.25f : 0.5f;
+        q = nearbyintf(a / step) * step;     // default rounding mode: nearest even
+        if (q > 7.5f) q = 7.5f;
+    }
+    return x < 0 ? -q : q;
+}
+
+static float e2m3_decode(unsigned c)
+{
+    const int s = (c >> 5) & 1, e = (c >> 3) & 3, m = c & 7;
+    const float v = e == 0 ? m * 0.125f : ldexpf(1.f + m / 8.f, e - 1);
+    return s ? -v : v;
+}
+
+static int fp6_probe()
+{
+    int bad = 0;
+    // (a) conversion: grid points, midpoints, saturation; scale 1 and scale 4
+    float *dx, *dsc; unsigned *dout;
+    CK(hipMalloc(&dx, 64 * 32 * 4)); CK(hipMalloc(&dsc, 64 * 4)); CK(hipMalloc(&dout, 64 * 6 * 4));
+    std::vector<float> x(64 * 32), sc(64);
+    const float pts[] = {0.f, 0.0625f, 0.125f, 0.1875f, 0.3125f, 0.9375f, 1.f, 1.0625f, 1.1875f, 1.9375f, 2.125f, 2.375f, 3.875f,
+                         4.25f, 4.75f, 7.f, 7.25f, 7.5f, 7.74f, 7.75f, 8.f, 100.f, 60000.f, 0.06f, 0.07f, 3.3f, 5.1f, 6.26f, 1e-20f, 0.5f, 2.f, 4.f};
+    for (int l = 0; l < 64; ++l) {
+        sc[l] = l < 32 ? 1.f : 4.f;
+        for (int i = 0; i < 32; ++i) {
+            float v = pts[(i + l) % 32];
+            if (l & 1) v = -v;
+            x[l * 32 + i] = v * sc[l];
+        }
+    }
+    CK(hipMemcpy(dx, x.data(), x.size() * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dsc, sc.data(), sc.size() * 4, hipMemcpyHostToDevice));
+    fp6_cvt_kernel<<<1, 64>>>(dx, dsc, dout);
+    std::vector<unsigned> out(64 * 6);
+    CK(hipMemcpy(out.data(), dout, out.size() * 4, hipMemcpyDeviceToHost));
+    // bit order hypothesis: code of element k at bits [6k, 6k+6) of the lane's 192-bit string; element 2i = src0[i], 2i+1 = src1[i];
+    // alternative: element i = src0[i], element 16 + i = src1[i]
+    int ok_inter = 0, ok_cat = 0;
+    for (int l = 0; l < 64; ++l)
+        for (int k = 0; k < 32; ++k) {
+            const int bit = 6 * k;
+            unsigned long long w = out[l * 6 + bit / 32];
+            if (bit / 32 + 1 < 6) w |= (unsigned long long)out[l * 6 + bit / 32 + 1] << 32;
+            const float got = e2m3_decode((unsigned)(w >> (bit % 32)) & 63u);
+            const float want_i = e2m3_rne(x[l * 32 + (k & 1) * 16 + (k >> 1)] / sc[l]);
+            const float want_c = e2m3_rne(x[l * 32 + k] / sc[l]);
+            ok_inter += got == want_i;
+            ok_cat += got == want_c;
+        }
+    printf("fp6 cvt: %d / 2048 elements match RNE + saturation under 'interleaved' order, %d under 'concatenated' order\n", ok_inter, ok_cat);
+    printf("fp6 cvt lane 0 dwords:"); for (int i = 0; i < 6; ++i) printf(" %08x", out[i]); printf("\n");
+    printf("fp6 cvt lane 0 inputs:"); for (int i = 0; i < 32; ++i) printf(" %g", x[i]); printf("\n");
+    if (ok_inter != 2048 && ok_cat != 2048) {
+        bad |= 1;
+        const bool inter = ok_inter >= ok_cat;
+        int shown = 0;
+        for (int l = 0; l < 64 && shown < 24; ++l)
+            for (int k = 0; k < 32 && shown < 24; ++k) {
+                const int bit = 6 * k;
+                unsigned long long w = out[l * 6 + bit / 32];
+                if (bit / 32 + 1 < 6) w |= (unsigned long long)out[l * 6 + bit / 32 + 1] << 32;
+                const float got = e2m3_decode((unsigned)(w >> (bit % 32)) & 63u);
+                const float in = x[l * 32 + (inter ? (k & 1) * 16 + (k >> 1) : k)] / sc[l];
+                if (got != e2m3_rne(in)) { printf("  lane %d element %d: in %g -> %g, model %g\n", l, k, in, got, e2m3_rne(in)); ++shown; }
+            }
+    }
+
+    // (b) MFMA: values on the grid (products and sums exact), per-lane scales
+    float *dxa, *dxb, *dD; int *dsa, *dsb;
+    CK(hipMalloc(&dxa, 64 * 32 * 4)); CK(hipMalloc(&dxb, 64 * 32 * 4)); CK(hipMalloc(&dD, 32 * 32 * 4));
+    CK(hipMalloc(&dsa, 64 * 4)); CK(hipMalloc(&dsb, 64 * 4));
+    std::vector<float> xa(64 * 32), xb(64 * 32), D(32 * 32);
+    std::vector<int> sa(64), sb(64);
+    const float grid[] = {0.f, 0.125f, 0.5f, 1.f, 1.5f, 2.f, 3.f, 4.f, 6.f, 7.5f, 0.875f, 1.125f};
+    srand(6);
+    for (auto &v : xa) v = grid[rand() % 12] * (rand() & 1 ? 1.f : -1.f);
+    for (auto &v : xb) v = grid[rand() % 12] * (rand() & 1 ? 1.f : -1.f);
+    CK(hipMemcpy(dxa, xa.data(), xa.size() * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dxb, xb.data(), xb.size() * 4, hipMemcpyHostToDevice));
+    auto run = [&](int opa, int opb, const char *what) {
+        CK(hipMemcpy(dsa, sa.data(), 256, hipMemcpyHostToDevice));
+        CK(hipMemcpy(dsb, sb.data(), 256, hipMemcpyHostToDevice));
+        if (opa == 0 && opb == 0) fp6_mfma_kernel<0, 0><<<1, 64>>>(dxa, dxb, dsa, dsb, dD);
+        else if (opa == 1 && opb == 2) fp6_mfma_kernel<1, 2><<<1, 64>>>(dxa, dxb, dsa, dsb, dD);
+        else fp6_mfma_kernel<3, 1><<<1, 64>>>(dxa, dxb, dsa, dsb, dD);
+        CK(hipMemcpy(D.data(), dD, D.size() * 4, hipMemcpyDeviceToHost));
+        double worst = 0, ref_max = 0;
+        for (int i = 0; i < 32; ++i)
+            for (int j = 0; j < 32; ++j) {
+                double ref = 0;
+                for (int hh = 0; hh < 2; ++hh) {
+                    double s = 0;
+                    for (int e = 0; e < 32; ++e) s += (double)xa[(i + 32 * hh) * 32 + e] * xb[(j + 32 * hh) * 32 + e];
+                    ref += s * ldexp(1.0, sa[i + 32 * hh] - 127 + sb[j + 32 * hh] - 127);
+                }
+                worst = fmax(worst, fabs((double)(float)ref - D[i * 32 + j]));      // (two blocks at different scales: one fp32 rounding)
+                ref_max = fmax(ref_max, fabs(ref));
+            }
+        printf("fp6 mfma H6, %-44s op_sel %d/%d: max |D - ref| = %g (max |ref| %g)  %s\n", what, opa, opb, worst, ref_max, worst == 0 ? "EXACT" : "MISMATCH");
+        return worst == 0;
+    };
+    for (int l = 0; l < 64; ++l) sa[l] = sb[l] = 127;
+    bad |= run(0, 0, "uniform scales") ? 0 : 2;
+    for (int l = 0; l < 64; ++l) sa[l] = 120 + rand() % 12;
+    bad |= run(0, 0, "per-lane scale A") ? 0 : 4;
+    for (int l = 0; l < 64; ++l) { sa[l] = 127; sb[l] = 122 + rand() % 9; }
+    bad |= run(0, 0, "per-lane scale B") ? 0 : 8;
+    // (both sides at once: scales close together, so that the sum of the two blocks still fits fp32 exactly -- with A at 2^-11 ..
+    // 2^0 and B at 2^-5 .. 2^3 the first run was off by 2^-17 at |D| ~ 1200: the two blocks' sums are not added in one rounding)
+    for (int l = 0; l < 64; ++l) { sa[l] = 126 + rand() % 3; sb[l] = 127 + rand() % 2; }
+    bad |= run(0, 0, "per-lane scales A and B") ? 0 : 16;
+    bad |= run(1, 2, "per-lane scales A and B, decoy bytes") ? 0 : 32;
+    bad |= run(3, 1, "per-lane scales A and B, decoy bytes") ? 0 : 64;
+    if (bad & ~1) {
+        // diagnosis: which (K block, element) of row 0 / column j does the scale byte of lane L act on?  A = 1 everywhere,
+        // B one-hot in K (block hb, element e) for every column, scale 2^3 in lane L of A only: D[i][*] = 8 where it acts, else 1
+        for (auto &v : xa) v = 1.f;
+        CK(hipMemcpy(dxa, xa.data(), xa.size() * 4, hipMemcpyHostToDevice));
+        const int Ls[] = {0, 1, 32, 33};
+        const int es[] = {0, 1, 7, 8, 15, 16, 17, 24, 31};
+        for (int L : Ls)
+            for (int hb = 0; hb < 2; ++hb) {
+                printf("  scale byte of A lane %2d, B one-hot in block %d:", L, hb);
+                for (int e : es) {
+                    for (auto &v : xb) v = 0.f;
+                    for (int j = 0; j < 32; ++j) xb[(j + 32 * hb) * 32 + e] = 1.f;
+                    CK(hipMemcpy(dxb, xb.data(), xb.size() * 4, hipMemcpyHostToDevice));
+                    for (int l = 0; l < 64; ++l) { sa[l] = l == L ? 130 : 127; sb[l] = 127; }
+                    CK(hipMemcpy(dsa, sa.data(), 256, hipMemcpyHostToDevice));
+                    CK(hipMemcpy(dsb, sb.data(), 256, hipMemcpyHostToDevice));
+                    fp6_mfma_kernel<0, 0><<<1, 64>>>(dxa, dxb, dsa, dsb, dD);
+                    CK(hipMemcpy(D.data(), dD, D.size() * 4, hipMemcpyDeviceToHost));
+                    printf("  e%-2d:", e);
+                    int n = 0;
+                    for (int i = 0; i < 32; ++i) if (D[i * 32] != 1.f && n++ < 3) printf(" row %d = %g", i, D[i * 32]);
+                    if (!n) printf(" -");
+                }
+                printf("\n");
+            }
+    }
+    printf("fp6 probe: %s (mask %d)\n", bad ? "SURPRISE" : "all as hypothesised", bad);
+    return bad;
+}
+
+int main(int argc, char **argv)
+{
+    // ---- e2m3 conversion and scale semantics ("fp6" as the only argument: this part alone) ----
+    const int fp6_bad = fp6_probe();
+    if (argc > 1 && !strcmp(argv[1], "fp6")) return fp6_bad ? 1 : 0;
     // ---- layout check ----
     std::vector<uint8_t> A(32 * 64), B(64 * 32);
     srand(1);

@@ -27,8 +27,16 @@
 // fragment, two 1 KB planes], lane-linear 16-byte fragments; ring of three.  ONE barrier per stage, between its third and
 // fourth unit (the fourth unit's fragments are in registers by then): behind it the slot is refilled with stage s+3, so a
 // DMA has two full stages to land and the barrier's wait is a counted vmcnt(4), never a drain.
+//
+// MX6 form (xv_tdnn_pair_pool_f16mx6): the cross terms of the SECOND GEMM in block-scaled e2m3 (xv_split6.h) -- the one place where
+// the A operand is made in registers inside the consuming kernel, so nothing in HBM changes but that layer's packed weights.  The
+// conversion between the GEMMs makes, per 32-channel slab, one e2m3 block of the lane's 16 channels (six dwords) and its scale
+// byte (eight of them in two registers, picked by op_sel) in place of the eight-dword bf8 fragment; a layer-4 unit of the weight
+// stream keeps its 4 KB and its two 16-byte 8-bit-fragment reads per lane: [fp16 k-step 0 | fp16 k-step 1 | e2m3 dwords 0-3 |
+// e2m3 dwords 4-5, scale byte, pad], the scaled MFMA runs with cbsz:2 blgp:2 at half the cycles.  Phase 1, the RED / KEEP
+// exchange, the swaps and the pooling are the same source.
 #include "xv_device.h"
-#include "xv_split8.h"
+#include "xv_split6.h"
 
 namespace {
 
@@ -65,7 +73,7 @@ struct Pair8Params {
 // LDS read then degrades to lgkmcnt(0): a step could not start its first MFMA before ALL fragment reads of the previous step
 // had returned.
 
-template <int MODE>
+template <int MODE, bool MX6>
 __global__ __launch_bounds__(P8_WAVES * 64, 2) void tdnn_pair_pool_f16bf8_kernel(const Pair8Params p)
 {
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -314,7 +322,9 @@ __global__ __launch_bounds__(P8_WAVES * 64, 2) void tdnn_pair_pool_f16bf8_kernel
 
     // ---- accumulators -> A operands of the second GEMM: bias, activation, BN, split8 encoding ----------------------------------------
     xv_f16x8 Hf0[8], Hf1[8];
-    xv_i32x8 Hx[8];
+    xv_i32x8 Hx[8];                                            // bf8 form: the 8-bit fragment of slab u
+    xv_u32x6 H6[8];                                            // MX6 form: its e2m3 block ...
+    int sa6[2] = {0, 0};                                       // ... and the block's scale byte (less the 11 of the cross terms), byte u & 3 of sa6[u >> 2]
     float amax = 0.f;
     {
         auto conv = [&](auto U) {
@@ -322,12 +332,30 @@ __global__ __launch_bounds__(P8_WAVES * 64, 2) void tdnn_pair_pool_f16bf8_kernel
             // tile u's parameter reads must not start before tile u-1 is converted (the optimiser would hoist all of them and
             // spill): an opaque zero that depends on the previous result
             int dep = 0;
-            if constexpr (u > 0) {
+            if constexpr (u > 0 && MX6) {
+                const xv_u32x6 a = H6[u - 1];
+                asm volatile("" : "+v"(dep) : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]));
+            } else if constexpr (u > 0) {
                 const xv_i32x8 a = Hx[u - 1];
                 asm volatile("" : "+v"(dep) : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]));
             }
             const f32x4 *P1 = reinterpret_cast<const f32x4 *>(lds + P8_P1_OFF + dep);
             const f32x16 t = acc[u];
+            if constexpr (MX6) {
+                float v[16];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {                                  // r = 4j .. 4j+3: channels (r&3) + 8(r>>2) + 4hh
+                    const int c4 = (256 * hf + 32 * u + 8 * j + 4 * hh) >> 2;
+                    const f32x4 b = P1[c4], s = P1[CMID / 4 + c4], o = P1[2 * CMID / 4 + c4], a = P1[3 * CMID / 4 + c4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[4 * j + e] = act_fn<MODE>(t[4 * j + e] + b[e], a[e]) * s[e] + o[e];
+                }
+                int e8m0;
+                xv_split6_encode16<true>(v, Hf0[u], Hf1[u], H6[u], e8m0, amax);
+                sa6[u >> 2] |= (e8m0 - 11) << (8 * (u & 3));
+                __builtin_amdgcn_sched_barrier(0);
+                return;
+            }
             xv_i32x4 x8[2];
 #pragma unroll
             for (int g = 0; g < 2; ++g) {                                  // r = 8g .. 8g+7: channels (r&3) + 8(r>>2) + 4hh
@@ -519,7 +547,13 @@ __global__ __launch_bounds__(P8_WAVES * 64, 2) void tdnn_pair_pool_f16bf8_kernel
         };
         auto mxb = [&](auto SET, auto U, auto ROLE) {
             constexpr int set = decltype(SET)::value, u = decltype(U)::value, role = decltype(ROLE)::value;
-            if constexpr (role == 0) yR = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(Hx[u], Mx[set], yR, 1, 1, 0, scale_a, 0, scale_b);
+            if constexpr (MX6) {
+                // (the instruction reads six registers of either operand; the weight block's byte came in with its fragment)
+                const xv_u32x6 h = H6[u];
+                const xv_i32x8 a = {(int)h[0], (int)h[1], (int)h[2], (int)h[3], (int)h[4], (int)h[5], 0, 0};
+                if constexpr (role == 0) yR = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, Mx[set], yR, 2, 2, u & 3, sa6[u >> 2], 0, Mx[set][6]);
+                else yK = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, Mx[set], yK, 2, 2, u & 3, sa6[u >> 2], 0, Mx[set][6]);
+            } else if constexpr (role == 0) yR = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(Hx[u], Mx[set], yR, 1, 1, 0, scale_a, 0, scale_b);
             else yK = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(Hx[u], Mx[set], yK, 1, 1, 0, scale_a, 0, scale_b);
         };
         auto quarter = [&](auto Q) {                        // stage (ct, q): slabs 4(q&1) .. 4(q&1)+3 of half-tile q >> 1 (0: RED, 1: KEEP)
@@ -621,6 +655,9 @@ __global__ __launch_bounds__(P8_WAVES * 64, 2) void tdnn_pair_pool_f16bf8_kernel
 //       fp16 k-step s: w1[32 ks + 16 s + 8 kh + e][o];  8-bit: channels 32 ks + 16 kh + {0..7 | 8..15}
 //   layer 2, stage 4 ct + q, half h, unit j (slab u = 4 (q & 1) + j, column tile c = 1 - h for q < 2, h for q >= 2): column n = 64 ct + 32 c + (lane & 31)
 //       channel of (r, kh) = 256 h + 32 u + (r&3) + 8 (r>>2) + 4 kh;  fp16 k-step s: r = 8 s + e;  8-bit: r = {0..7 | 8..15}
+// MX6: the 8-bit fragment of a layer-2 unit is the e2m3 block of the lane's 16 channels and its byte (xv_split6.h): plane 0 =
+// dwords 0-3, plane 1 = [dwords 4-5 | E8M0 byte, zero-extended | 0]; the layer-1 stages are the same bytes in either form.
+template <bool MX6>
 __global__ void pack_pair8_kernel(const float *__restrict__ w1, const float *__restrict__ w2, int n_ks, int cout, int n_ct,
                                   uint8_t *__restrict__ wt, size_t total)
 {
@@ -668,11 +705,19 @@ __global__ void pack_pair8_kernel(const float *__restrict__ w1, const float *__r
         xv_f16x8 h0, h1;
         xv_i32x4 x0, x1;
         float amax = 0.f;
-        float a[8], b[8];
+        if constexpr (MX6) {
+            xv_u32x6 x6;
+            int e8m0;
+            xv_split6_encode16<false>(v, h0, h1, x6, e8m0, amax);
+            x0 = (xv_i32x4){(int)x6[0], (int)x6[1], (int)x6[2], (int)x6[3]};
+            x1 = (xv_i32x4){(int)x6[4], (int)x6[5], e8m0, 0};
+        } else {
+            float a[8], b[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { a[e] = v[e]; b[e] = v[8 + e]; }
-        xv_split8_encode8<false>(a, h0, x0, amax);
-        xv_split8_encode8<false>(b, h1, x1, amax);
+            for (int e = 0; e < 8; ++e) { a[e] = v[e]; b[e] = v[8 + e]; }
+            xv_split8_encode8<false>(a, h0, x0, amax);
+            xv_split8_encode8<false>(b, h1, x1, amax);
+        }
         uint8_t *t = wt + (size_t)stage * P8_STAGE + h * 16384 + unit * 4096 + lane * 16;
         *reinterpret_cast<xv_f16x8 *>(t) = h0;
         *reinterpret_cast<xv_f16x8 *>(t + 1024) = h1;
@@ -683,26 +728,72 @@ __global__ void pack_pair8_kernel(const float *__restrict__ w1, const float *__r
 
 bool pair8_shape_ok(int cin, int cmid, int cout) { return cmid == CMID && cin > 0 && (cin & 31) == 0 && cout > 0 && (cout & 63) == 0 && cout <= 4096; }
 
-}  // namespace
-
-extern "C" {
-
-size_t xv_packed_pair_f16bf8_bytes(int cin, int cmid, int cout)
+size_t pair8_packed_bytes(int cin, int cmid, int cout)
 {
     if (!pair8_shape_ok(cin, cmid, cout)) return 0;
     return (size_t)(2 * (cin / 32) + 4 * (cout / 64)) * P8_STAGE;
 }
 
-int xv_pack_pair_f16bf8(const float *w1, const float *w2, int cin, int cmid, int cout, void *wt, void *stream)
+int pair8_fail(int code, const char *entry, const char *name, const char *msg)
 {
-    if (!w1 || !w2 || !wt) return fail(XV_ERR_BAD_ARG, "pack_pair_f16bf8: NULL pointer");
+    char buf[192];
+    snprintf(buf, sizeof(buf), "%s%s%s", entry, name, msg);
+    return fail(code, buf);
+}
+
+// The two forms' entry points: `name` is the arithmetic's suffix in the messages ("f16bf8" / "f16mx6").
+template <bool MX6>
+int pair8_pack(const char *name, const float *w1, const float *w2, int cin, int cmid, int cout, void *wt, void *stream)
+{
+    if (!w1 || !w2 || !wt) return pair8_fail(XV_ERR_BAD_ARG, "pack_pair_", name, ": NULL pointer");
     if (!pair8_shape_ok(cin, cmid, cout))
-        return fail(XV_ERR_UNSUPPORTED, "pack_pair_f16bf8: needs cmid == 512, cin % 32 == 0, cout % 64 == 0, cout <= 4096");
-    if (((uintptr_t)wt) & 15) return fail(XV_ERR_BAD_ARG, "pack_pair_f16bf8: wt must be 16-byte aligned");
-    const size_t total = xv_packed_pair_f16bf8_bytes(cin, cmid, cout) / 64;      // one thread per 64 packed bytes
-    hipLaunchKernelGGL(pack_pair8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w1, w2, cin / 32,
+        return pair8_fail(XV_ERR_UNSUPPORTED, "pack_pair_", name, ": needs cmid == 512, cin % 32 == 0, cout % 64 == 0, cout <= 4096");
+    if (((uintptr_t)wt) & 15) return pair8_fail(XV_ERR_BAD_ARG, "pack_pair_", name, ": wt must be 16-byte aligned");
+    const size_t total = pair8_packed_bytes(cin, cmid, cout) / 64;      // one thread per 64 packed bytes
+    hipLaunchKernelGGL(pack_pair8_kernel<MX6>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w1, w2, cin / 32,
                        cout, cout / 64, (uint8_t *)wt, total);
     return launch_status();
+}
+
+template <bool MX6>
+int pair8_launch(const char *name, const void *x, int64_t R, int cin, int cmid, int cout, const void *wt, const float *bias1,
+                 const float *bn_scale1, const float *bn_shift1, const float *act_alpha1, const float *bias2,
+                 const float *bn_scale2, const float *bn_shift2, const float *act_alpha2, int act_kind,
+                 const uint8_t *row_valid, float *block_stats, int32_t *status, void *stream)
+{
+    if (R <= 0) return 0;
+    if (!x || !wt || !block_stats) return pair8_fail(XV_ERR_BAD_ARG, "tdnn_pair_pool_", name, ": NULL pointer");
+    if (act_kind < XV_ACT_NONE || act_kind > XV_ACT_PRELU) return pair8_fail(XV_ERR_BAD_ARG, "tdnn_pair_pool_", name, ": unknown act_kind");
+    if ((act_kind == XV_ACT_LRELU || act_kind == XV_ACT_PRELU) && (!act_alpha1 || !act_alpha2))
+        return pair8_fail(XV_ERR_BAD_ARG, "tdnn_pair_pool_", name, ": act_alpha is NULL");
+    if (!pair8_shape_ok(cin, cmid, cout))
+        return pair8_fail(XV_ERR_UNSUPPORTED, "tdnn_pair_pool_", name, ": needs cmid == 512, cin % 32 == 0, cout % 64 == 0, cout <= 4096");
+    if ((((uintptr_t)x) | ((uintptr_t)wt) | ((uintptr_t)block_stats)) & 15)
+        return pair8_fail(XV_ERR_BAD_ARG, "tdnn_pair_pool_", name, ": x, wt and block_stats must be 16-byte aligned");
+    Pair8Params p{};
+    p.x = (const uint8_t *)x; p.R = (long)R; p.n_ks = cin / 32; p.cout = cout; p.n_ct = cout / 64; p.wt = (const uint8_t *)wt;
+    p.b1 = bias1; p.sc1 = bn_scale1; p.sh1 = bn_shift1; p.al1 = act_alpha1;
+    p.b2 = bias2; p.sc2 = bn_scale2; p.sh2 = bn_shift2; p.al2 = act_alpha2;
+    p.act = act_kind; p.valid = row_valid; p.blk = block_stats; p.n_blocks = (long)((R + 7) / 8); p.status = (int *)status;
+    typedef void (*kern_t)(const Pair8Params);
+    const kern_t kerns[3] = {tdnn_pair_pool_f16bf8_kernel<0, MX6>, tdnn_pair_pool_f16bf8_kernel<1, MX6>, tdnn_pair_pool_f16bf8_kernel<2, MX6>};
+    static std::atomic<unsigned long long> lds_done{0};                 // (one per form: a static of the template instance)
+    if (const int rc = opt_in_dynamic_lds(lds_done, kerns, P8_LDS_BYTES)) return rc;
+    const int mode = act_kind == XV_ACT_LRELU ? 1 : act_kind == XV_ACT_RELU ? 2 : 0;
+    hipLaunchKernelGGL(kerns[mode], dim3((unsigned)((R + P8_ROWS - 1) / P8_ROWS)), dim3(P8_WAVES * 64), P8_LDS_BYTES,
+                       (hipStream_t)stream, p);
+    return launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t xv_packed_pair_f16bf8_bytes(int cin, int cmid, int cout) { return pair8_packed_bytes(cin, cmid, cout); }
+
+int xv_pack_pair_f16bf8(const float *w1, const float *w2, int cin, int cmid, int cout, void *wt, void *stream)
+{
+    return pair8_pack<false>("f16bf8", w1, w2, cin, cmid, cout, wt, stream);
 }
 
 int xv_tdnn_pair_pool_f16bf8(const void *x, int64_t R, int cin, int cmid, int cout, const void *wt, const float *bias1,
@@ -710,28 +801,24 @@ int xv_tdnn_pair_pool_f16bf8(const void *x, int64_t R, int cin, int cmid, int co
                              const float *bn_scale2, const float *bn_shift2, const float *act_alpha2, int act_kind,
                              const uint8_t *row_valid, float *block_stats, int32_t *status, void *stream)
 {
-    if (R <= 0) return 0;
-    if (!x || !wt || !block_stats) return fail(XV_ERR_BAD_ARG, "tdnn_pair_pool_f16bf8: NULL pointer");
-    if (act_kind < XV_ACT_NONE || act_kind > XV_ACT_PRELU) return fail(XV_ERR_BAD_ARG, "tdnn_pair_pool_f16bf8: unknown act_kind");
-    if ((act_kind == XV_ACT_LRELU || act_kind == XV_ACT_PRELU) && (!act_alpha1 || !act_alpha2))
-        return fail(XV_ERR_BAD_ARG, "tdnn_pair_pool_f16bf8: act_alpha is NULL");
-    if (!pair8_shape_ok(cin, cmid, cout))
-        return fail(XV_ERR_UNSUPPORTED, "tdnn_pair_pool_f16bf8: needs cmid == 512, cin % 32 == 0, cout % 64 == 0, cout <= 4096");
-    if ((((uintptr_t)x) | ((uintptr_t)wt) | ((uintptr_t)block_stats)) & 15)
-        return fail(XV_ERR_BAD_ARG, "tdnn_pair_pool_f16bf8: x, wt and block_stats must be 16-byte aligned");
-    Pair8Params p{};
-    p.x = (const uint8_t *)x; p.R = (long)R; p.n_ks = cin / 32; p.cout = cout; p.n_ct = cout / 64; p.wt = (const uint8_t *)wt;
-    p.b1 = bias1; p.sc1 = bn_scale1; p.sh1 = bn_shift1; p.al1 = act_alpha1;
-    p.b2 = bias2; p.sc2 = bn_scale2; p.sh2 = bn_shift2; p.al2 = act_alpha2;
-    p.act = act_kind; p.valid = row_valid; p.blk = block_stats; p.n_blocks = (long)((R + 7) / 8); p.status = (int *)status;
-    typedef void (*kern_t)(const Pair8Params);
-    const kern_t kerns[3] = {tdnn_pair_pool_f16bf8_kernel<0>, tdnn_pair_pool_f16bf8_kernel<1>, tdnn_pair_pool_f16bf8_kernel<2>};
-    static std::atomic<unsigned long long> lds_done{0};
-    if (const int rc = opt_in_dynamic_lds(lds_done, kerns, P8_LDS_BYTES)) return rc;
-    const int mode = act_kind == XV_ACT_LRELU ? 1 : act_kind == XV_ACT_RELU ? 2 : 0;
-    hipLaunchKernelGGL(kerns[mode], dim3((unsigned)((R + P8_ROWS - 1) / P8_ROWS)), dim3(P8_WAVES * 64), P8_LDS_BYTES,
-                       (hipStream_t)stream, p);
-    return launch_status();
+    return pair8_launch<false>("f16bf8", x, R, cin, cmid, cout, wt, bias1, bn_scale1, bn_shift1, act_alpha1, bias2, bn_scale2, bn_shift2,
+                               act_alpha2, act_kind, row_valid, block_stats, status, stream);
+}
+
+size_t xv_packed_pair_f16mx6_bytes(int cin, int cmid, int cout) { return pair8_packed_bytes(cin, cmid, cout); }
+
+int xv_pack_pair_f16mx6(const float *w1, const float *w2, int cin, int cmid, int cout, void *wt, void *stream)
+{
+    return pair8_pack<true>("f16mx6", w1, w2, cin, cmid, cout, wt, stream);
+}
+
+int xv_tdnn_pair_pool_f16mx6(const void *x, int64_t R, int cin, int cmid, int cout, const void *wt, const float *bias1,
+                             const float *bn_scale1, const float *bn_shift1, const float *act_alpha1, const float *bias2,
+                             const float *bn_scale2, const float *bn_shift2, const float *act_alpha2, int act_kind,
+                             const uint8_t *row_valid, float *block_stats, int32_t *status, void *stream)
+{
+    return pair8_launch<true>("f16mx6", x, R, cin, cmid, cout, wt, bias1, bn_scale1, bn_shift1, act_alpha1, bias2, bn_scale2, bn_shift2,
+                              act_alpha2, act_kind, row_valid, block_stats, status, stream);
 }
 
 }  // extern "C"

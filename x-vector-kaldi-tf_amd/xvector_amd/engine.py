@@ -333,7 +333,7 @@ class DeviceModel(object):
                 wpad[:, :self.feat_dim] = w0
                 self.first = hiplib.pack_first_bf16x3(self._dev(wpad))
             assert not (first_kernel and self.first is None), "first_kernel=True but the topology / precision does not allow it"
-            self.pair = self.pair8 = None
+            self.pair = self.pair8 = self.pair_mx6 = None
             if (pair_kernel is None or pair_kernel) and self.fused_pool and precision == "bf16x3" and len(self.layers) >= 3:
                 La, Lb = self.layers[-2], self.layers[-1]
                 if La["K"] == 1 and Lb["K"] == 1 and hiplib.pair_supported(La["cin"], La["cout"], Lb["cout"]):
@@ -343,6 +343,10 @@ class DeviceModel(object):
                     self.pair = hiplib.pack_pair_bf16x3(wa, wb)
                     if self.f16bf8 and hiplib.pair8_supported(La["cin"], La["cout"], Lb["cout"]):
                         self.pair8 = hiplib.pack_pair_f16bf8(wa, wb)
+                        # the same kernel with the last layer's cross terms on block-scaled e2m3 MFMAs (half their cycles):
+                        # launched in its place wherever its pack exists; pair8 stays "the f16bf8 pair kernel is in use"
+                        if hiplib.pair_mx6_supported(La["cin"], La["cout"], Lb["cout"]):
+                            self.pair_mx6 = hiplib.pack_pair_f16mx6(wa, wb)
             assert not (pair_kernel and self.pair is None), "pair_kernel=True but the topology / precision does not allow it"
             if self.f16bf8:
                 if self.first is None:
@@ -564,7 +568,9 @@ class DeviceModel(object):
             h = y
         if self.pair is not None:
             La, Lb = self.layers[-2], self.layers[-1]
-            if self.pair8 is not None:
+            if self.pair_mx6 is not None:
+                hiplib.tdnn_pair_pool_mx6(h, R, self.pair_mx6, La.pp, Lb.pp, self.act, row_valid, self._last, status)
+            elif self.pair8 is not None:
                 hiplib.tdnn_pair_pool8(h, R, self.pair8, La.pp, Lb.pp, self.act, row_valid, self._last, status)
             else:
                 hiplib.tdnn_pair_pool(h, R, self.pair, La.pp, Lb.pp, self.act, row_valid, self._last)

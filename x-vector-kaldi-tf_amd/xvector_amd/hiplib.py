@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -62,6 +62,9 @@ _SIGNATURES = {
     "xv_packed_pair_f16bf8_bytes": (_sz, [_ci, _ci, _ci]),
     "xv_pack_pair_f16bf8": (_ci, [_vp, _vp, _ci, _ci, _ci, _vp, _vp]),
     "xv_tdnn_pair_pool_f16bf8": (_ci, [_vp, _i64, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp]),
+    "xv_packed_pair_f16mx6_bytes": (_sz, [_ci, _ci, _ci]),
+    "xv_pack_pair_f16mx6": (_ci, [_vp, _vp, _ci, _ci, _ci, _vp, _vp]),
+    "xv_tdnn_pair_pool_f16mx6": (_ci, [_vp, _i64, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp]),
     "xv_fc_bf16x3": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp]),
     "xv_stats_pool_workspace_bytes": (_sz, [_ci, _ci, _ci, _ci]),
     "xv_stats_pool_f32": (_ci, [_vp, _i64, _ci, _vp, _vp, _ci, _ci, _ci, _cf, _vp, _vp, _vp]),
@@ -709,7 +712,7 @@ def pair_supported(cin, cmid, cout):
 
 
 def _pack_pair(arith, cls, w1, w2):
-    """The pair packing of either arithmetic ("bf16x3" / "f16bf8": the suffix of its entry points)."""
+    """The pair packing of an arithmetic ("bf16x3" / "f16bf8" / "f16mx6": the suffix of its entry points)."""
     lib = require_gpu()
     _f32(w1, "w1"); _f32(w2, "w2")
     assert w1.dim() == 2 and w2.dim() == 2 and w1.shape[1] == w2.shape[0]
@@ -718,8 +721,8 @@ def _pack_pair(arith, cls, w1, w2):
 
 
 def _pair_pool(arith, cls, fmt, x, R, w, p1, p2, act, row_valid, block_stats, *status):
-    """The pair launch of either arithmetic: ``w`` a ``cls``, ``x`` a SplitBuf in ``fmt``; ``status``: the extra pointer argument
-    of the f16bf8 entry point."""
+    """The pair launch of an arithmetic: ``w`` a ``cls``, ``x`` a SplitBuf in ``fmt``; ``status``: the extra pointer argument
+    of the f16bf8 and f16mx6 entry points."""
     lib = require_gpu()
     assert isinstance(w, cls)
     xp = _operand(x, w.cin, R, "x", (fmt,))[0]
@@ -752,6 +755,26 @@ def tdnn_pair_pool8(x, R, w, p1, p2, act, row_valid, block_stats, status=None):
     """tdnn_pair_pool in the f16bf8 arithmetic: x: SplitBuf in FMT_SPLIT8; w: PackedPair8; status: int32 device tensor (bit 0:
     the intermediate activation was clamped)."""
     _pair_pool("f16bf8", PackedPair8, FMT_SPLIT8, x, R, w, p1, p2, act, row_valid, block_stats, _ptr(status))
+
+
+class PackedPairMx6(_Packed):
+    """Weights of two consecutive K = 1 layers in the stage order of xv_tdnn_pair_pool_f16mx6 (the second layer's cross-term
+    operands as e2m3 blocks)."""
+    __slots__ = ("wt", "cin", "cmid", "cout")
+
+
+def pair_mx6_supported(cin, cmid, cout):
+    return int(load().xv_packed_pair_f16mx6_bytes(int(cin), int(cmid), int(cout))) > 0
+
+
+def pack_pair_f16mx6(w1, w2):
+    """w1[Cin, Cmid], w2[Cmid, Cout] (device fp32, TF's [in, out] order) -> PackedPairMx6."""
+    return _pack_pair("f16mx6", PackedPairMx6, w1, w2)
+
+
+def tdnn_pair_pool_mx6(x, R, w, p1, p2, act, row_valid, block_stats, status=None):
+    """tdnn_pair_pool8 with the second layer's cross terms on block-scaled e2m3 MFMAs: x: SplitBuf in FMT_SPLIT8; w: PackedPairMx6."""
+    _pair_pool("f16mx6", PackedPairMx6, FMT_SPLIT8, x, R, w, p1, p2, act, row_valid, block_stats, _ptr(status))
 
 
 def tdnn_pair_pool(x, R, w, p1, p2, act, row_valid, block_stats):
