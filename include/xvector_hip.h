@@ -746,6 +746,28 @@ int xv_egs_chunks_f16(const float *x, int ldx, int feat_dim, int64_t x_rows, con
                       const int32_t *chunk_first, const int32_t *chunk_len, const int64_t *chunk_dst, int n_chunks, int max_chunk_len,
                       int cmn_window, int center, int min_window, void *y, int64_t y_elems, void *stream);
 
+/* ---- the extractor's destination-row plan made on the device (csrc/xv_rowplan.hip) ---------------------------
+ * What Extractor.submit_raw computes on the host for xv_cmn_sliding_scatter_f32 (libxvector_host.so: one pass over every frame),
+ * from VAD decisions that already lie in device memory.  Utterances are addressed as in xv_vad_compact_i32 (utt_start[u],
+ * utt_len[u] in frames of a buffer of n_frames rows); they may come in any order and leave gaps.  Integers only, no atomics: the
+ * same bits on every run.  An utterance whose span leaves [0, n_frames) is skipped: nothing is read or written for it (its
+ * voiced_count is 0).  Entries of rank / dst_row outside the listed spans are never written.
+ * xv_voiced_rank_i32  for frame t < utt_len[u], p = utt_start[u] + t: rank[p] = number of voiced frames (vad != 0) of u before t
+ *   when vad[p] != 0, else -1; voiced_count[u] = number of voiced frames of u (= xv_vad_compact_i32's).  vad == NULL: every
+ *   frame is voiced (rank[p] = t, voiced_count[u] = utt_len[u]).
+ * xv_chunk_row_plan_i32  the voiced frames of utterance i, counted from 0, fall into chunks of chunk_size[i] frames; the first
+ *   chunks_kept[i] of them exist and chunk k of the utterance is chunk first_chunk[i] + k of the window, of which this batch
+ *   holds chunks [b0, b1), chunk c at row row_start[c - b0] of the packed batch (row_start: b1 - b0 entries).  With v = rank[p]:
+ *   dst_row[p] = -1 when v < 0 or chunk_size[i] <= 0; else with k = v / size, r = v % size, cid = first_chunk[i] + k:
+ *   dst_row[p] = row_start[cid - b0] + r when k < chunks_kept[i] and b0 <= cid < b1, else -1 (an unvoiced frame, a dropped tail,
+ *   a chunk of another batch).  The device twin of xv_raw_row_plan (csrc/xv_host.cpp), indexed by feature row.
+ * Both: n_utts == 0 returns 0 and launches nothing; a NULL output or a negative n_utts / n_frames is XV_ERR_BAD_ARG. */
+int xv_voiced_rank_i32(const float *vad, const int32_t *utt_start, const int32_t *utt_len, int n_utts, int64_t n_frames,
+                       int32_t *rank, int32_t *voiced_count, void *stream);
+int xv_chunk_row_plan_i32(const int32_t *rank, const int32_t *utt_start, const int32_t *utt_len, const int32_t *chunk_size,
+                          const int32_t *chunks_kept, const int32_t *first_chunk, int n_utts, int64_t n_frames, int32_t b0,
+                          int32_t b1, const int32_t *row_start, int32_t *dst_row, void *stream);
+
 /* ---- compressed feature output: Kaldi CompressedMatrix payloads (csrc/xv_compress.hip) ------------------------
  * What compute-mfcc-feats --compress=true / copy-feats --compress=true do with CompressedMatrix::CopyFromMat (kAutomaticMethod),
  * restated; the format contract and the error bounds of DESIGN.md §8.10 are claimed, byte equality with Kaldi's own writer is not.

@@ -60,7 +60,8 @@ _FLAGS = (
     ("--chunk-size", "chunk_size", int, -1, False, None,
      "If set, extracts xvectors from specified chunk-size, and averages.  If not set, extracts an xvector from all "
      "available features."),
-    ("--feature-rspecifier", "feature_rspecifier", str, None, True, None, "Kaldi rspecifier of the input features."),
+    ("--feature-rspecifier", "feature_rspecifier", str, None, False, None,
+     "Kaldi rspecifier of the input features (required unless --wav-rspecifier is given)."),
     ("--vector-wspecifier", "vector_wspecifier", str, None, True, None,
      "Kaldi wspecifier for the x-vectors (ark, ark pipe, or ark,scp:A,S)."),
     ("--model-dir", "model_dir", str, None, True, None, "Model directory (model.meta + weights + done)."),
@@ -72,7 +73,15 @@ _FLAGS = (
     ("--vad-rspecifier", "vad_rspecifier", str, "", False, None,
      "If set: table of per-frame VAD decisions (same key order as the features); frames with decision 0 are dropped "
      "(select-voiced-frames) after the CMN."),
+    # build-defined extension: x-vectors straight from audio
+    ("--wav-rspecifier", "wav_rspecifier", str, "", False, None,
+     "scp:wav.scp -- extract straight from audio: MFCC and energy VAD are computed on the GPU and stay there (no feature or "
+     "VAD table).  Excludes --feature-rspecifier and --vad-rspecifier; needs --cmn-window > 0; one process only."),
+    ("--mfcc-config", "mfcc_config", str, "", False, None, "With --wav-rspecifier: the compute-mfcc-feats options file (conf/mfcc.conf)."),
+    ("--vad-config", "vad_config", str, "", False, None, "With --wav-rspecifier: the compute-vad options file (conf/vad.conf)."),
 )
+
+WAV_WINDOW_SAMPLES = 1 << 26      # samples per window of the --wav-rspecifier route: the batches of mfcc_vad.py (its WINDOW_SAMPLES)
 
 
 def get_args(argv=None):
@@ -87,7 +96,25 @@ def get_args(argv=None):
         if choices:
             kw["choices"] = list(choices)
         parser.add_argument(flag, **kw)
-    return process_args(parser.parse_args(argv))
+    args = parser.parse_args(argv)
+    # usage errors of the --wav-rspecifier route leave through argparse (exit status 2), before anything is opened
+    if args.wav_rspecifier:
+        if args.feature_rspecifier or args.vad_rspecifier:
+            parser.error("--wav-rspecifier excludes --feature-rspecifier and --vad-rspecifier (the features and the VAD are computed)")
+        if args.cmn_window <= 0:
+            parser.error("--wav-rspecifier needs --cmn-window > 0 (the route is the recipe's CMN + VAD mode)")
+        head, _, path = args.wav_rspecifier.strip().partition(":")
+        if head.replace(" ", "").split(",")[0] != "scp" or not path.strip() or path.strip().endswith("|"):
+            parser.error("--wav-rspecifier: expected scp:wav.scp, got %r" % args.wav_rspecifier)
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            parser.error("--wav-rspecifier runs in one process (WORLD_SIZE=%s): sharding wav.scp across ranks is not supported; "
+                         "split wav.scp and run one job per part" % os.environ["WORLD_SIZE"])
+    else:
+        if not args.feature_rspecifier:
+            parser.error("one of --feature-rspecifier and --wav-rspecifier is required")
+        if args.mfcc_config or args.vad_config:
+            parser.error("--mfcc-config and --vad-config go with --wav-rspecifier")
+    return process_args(args)
 
 
 def process_args(args):
@@ -200,12 +227,31 @@ def _is_scp_table(rspecifier):
     return spec.split(':', 1)[0].replace(' ', '').split(',')[0] == 'scp' and not spec.endswith('|')
 
 
+def _wave_table(args):
+    """The --wav-rspecifier route's input: the wav.scp with the options of its two config files."""
+    from xvector_amd import extract_stream, mfcc
+    opts, vopts = mfcc.MfccOptions(), mfcc.VadOptions()
+    if args.mfcc_config:
+        opts.update(mfcc.read_config(args.mfcc_config))
+    if args.vad_config:
+        vopts.update(mfcc.read_config(args.vad_config))
+    return extract_stream.WaveTable(args.wav_rspecifier.strip().partition(":")[2].strip(), opts, vopts, WAV_WINDOW_SAMPLES)
+
+
 def eval_dnn(args):
     use_gpu = args.use_gpu == 'yes'
     wspecifier, ark, scp = process_wspecifier(args.vector_wspecifier)
     if ark is not None and scp is not None and os.path.exists(scp) and (os.path.exists(ark) or os.path.exists(ark + '.0')):
         logger.info('Both output ark and scp files exist. Return from this call.')
         return
+    if getattr(args, "wav_rspecifier", ""):
+        model = Model()
+        model.prepin_staging = True
+        with _open_output(wspecifier, ark, scp) as output_fid:
+            model.make_embedding(_wave_table(args), output_fid, args.model_dir, args.min_chunk_size, args.chunk_size, use_gpu, logger,
+                                 cmn_window=args.cmn_window, cmn_center=args.cmn_center == 'yes', distributed=False)
+        jobclock.mark("extraction (wav reader -> MFCC -> kernels -> last vector down)")
+        return _rename_outputs(wspecifier, ark, scp)
     # under torchrun (one process per GPU) only rank 0 owns the output table.  An scp feature table is sharded by line
     # range -- every rank reads ONLY its utterances, extracts them as a single process would, and one RCCL gather at the
     # end brings the x-vectors to rank 0; any other rspecifier (ark stream, pipe) is read by every rank and sharded per window
@@ -250,6 +296,11 @@ def eval_dnn(args):
         xdist.finish_process_group()
     if not root:
         return
+    _rename_outputs(wspecifier, ark, scp)
+
+
+def _rename_outputs(wspecifier, ark, scp):
+    """The temporary outputs under their final names (extract_embedding.py:134-148 of the reference)."""
     if ark is not None:
         os.rename(ark + '.tmp.ark', ark)
     if scp is not None and _native_table(wspecifier, ark):

@@ -531,12 +531,21 @@ class Model(object):
         rank reads the same stream and extracts its share of each window (one gather per window to rank 0) unless
         ``distributed=False`` says that the caller sharded the input itself."""
         start_time = time.time()
+        from_wav = isinstance(input_stream, extract_stream.WaveTable)
+        if from_wav:
+            # x-vectors straight from a wav.scp (DESIGN.md §8.13): the table makes its own VAD, the CMN is part of the route, and
+            # one process reads the whole table -- refused before a file is read or a kernel launched
+            from xvector_amd import dist as xdist
+            if vad_stream is not None or cmn_window <= 0:
+                raise ValueError("a WaveTable input takes no vad_stream (it computes the VAD itself) and needs cmn_window > 0")
+            if distributed and xdist.group_shape()[1] > 1:
+                raise ValueError("a WaveTable input is read by one process: sharding wav.scp across ranks is not supported")
         if distributed and vad_stream is None and cmn_window <= 0 and self._extract_byte_ranges(
                 input_stream, output_stream, model_dir, min_chunk_size, chunk_size, use_gpu, logger):
             return
         # three threads (xvector_amd.extract_stream): a reader parses the windows, this one runs them, a writer serialises the
         # vectors.  The reader starts BEFORE the model is loaded: the first arena is read and scanned while the weights are packed
-        reader = extract_stream.WindowReader(self, input_stream, vad_stream)
+        reader = input_stream.start() if from_wav else extract_stream.WindowReader(self, input_stream, vad_stream)
         try:
             try:
                 self._may_borrow = os.environ.get("XVECTOR_MODEL_CACHE", "1") != "0"
@@ -544,6 +553,9 @@ class Model(object):
             finally:
                 self._may_borrow = False
             F_dim = self.device_model.feat_dim
+            if from_wav and input_stream.opts.num_ceps != F_dim:
+                raise ValueError("--num-ceps=%d of the MFCC configuration is not the model's feature dimension %d"
+                                 % (input_stream.opts.num_ceps, F_dim))
             ex = engine.Extractor(self.device_model, min_chunk_size, chunk_size, max_batch_rows=self.max_batch_rows)
             front = None
             if cmn_window > 0 or vad_stream is not None:

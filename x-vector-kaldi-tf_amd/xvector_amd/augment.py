@@ -538,11 +538,12 @@ class Pending(object):
         self.shape = (node.M,)
 
 
-def mfcc_compute(engine, augmenter, keys, items, vad=None, compress=False):
+def mfcc_compute(engine, augmenter, keys, items, vad=None, compress=False, device=False):
     """``mfcc.Mfcc.compute`` over a batch mixing clean waves (int16 arrays) and ``Pending`` entries: the augmented samples are
     written by the GPU straight into the buffer the MFCC kernel reads.  The entries of a batch may come from more than one
     plan (a reader plans an entry before it knows which batch takes it); each plan is evaluated on its own.
-    ``compress``: as ``mfcc.Mfcc.compute``."""
+    ``compress``: as ``mfcc.Mfcc.compute``.  ``device``: ``mfcc.Mfcc.compute_device`` instead (the batch is one window, the
+    results stay on the device; ``vad`` and ``compress`` do not apply)."""
     waves = [np.broadcast_to(np.int16(0), (it.M,)) if isinstance(it, Pending) else it for it in items]
 
     def fill(x, i, j, off):
@@ -555,4 +556,6 @@ def mfcc_compute(engine, augmenter, keys, items, vad=None, compress=False):
         for p in plans:
             ks = [k for k in sel if items[k].plan is p]
             augmenter.run(p, x, [int(off[k - i]) for k in ks], 0 if x.dtype == torch.int16 else 1, tops=[items[k].node for k in ks])
+    if device:
+        return engine.compute_device(keys, waves, fill=fill)
     return engine.compute(keys, waves, vad=vad, fill=fill, compress=compress)

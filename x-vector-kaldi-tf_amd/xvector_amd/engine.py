@@ -137,6 +137,14 @@ def plan_chunk_table(lengths, min_chunk_size, chunk_size):
     return order, c_utt, c_start, c_len, seg
 
 
+def device_plan_table(utt_start, utt_len, order, c_len, seg_start):
+    """What xv_chunk_row_plan_i32 needs per utterance of a window's plan (``order``, ``c_len``, ``seg_start`` of
+    ``plan_chunk_table`` on the voiced counts), as int32 [5, len(order)]: the utterance's first feature row, its frames, the chunk
+    size the plan used for it (= the length of its first chunk), the chunks it keeps and the first of them in the window."""
+    return np.stack([np.asarray(utt_start)[order], np.asarray(utt_len)[order], c_len[seg_start[:-1]], np.diff(seg_start),
+                     seg_start[:-1]]).astype(np.int32)
+
+
 class BatchLayout(object):
     """Row layout of one ragged batch: chunk b owns rows [row_start[b], row_start[b]+row_len[b]); at least ``gap`` zero
     rows precede the first chunk and follow every chunk, and every chunk starts on a multiple of ``align`` rows
@@ -831,6 +839,7 @@ class Extractor(object):
         self.stats = dict(batches=0, chunks=0, frames=0, rows=0)
         self._stage = None
         self._raw_stage = None                         # (submit_raw's own pinned sets, rotated with ``_stage``)
+        self._plan_stage = None                        # (submit_device_raw's: per-utterance and per-chunk tables only)
         self._copy_stream = None
         self._turn = 0
         self._finalizer = None
@@ -1287,6 +1296,97 @@ class Extractor(object):
             self._window_tail(handle, win["compute"], win["P_all"], win["E_all"], seg_start, c_len, win["status"], win["keep"], mats,
                               lambda ex: again(ex)[0])
         return handle, V, vad_dropped
+
+    def submit_device_raw(self, feats, utt_start, utt_len, vad, cmn_window, center=True, min_window=100, ready=None):
+        """``submit_raw`` for RAW features and VAD decisions that already lie in device memory (mfcc.Mfcc.compute_device): feats
+        cuda float32 [>= rows, F], contiguous; utterance u is rows utt_start[u] .. utt_start[u] + utt_len[u] - 1 (host integer
+        arrays); vad cuda float32 [>= rows] (non-zero = voiced) or None (every frame); ``ready``: an event the tensors are complete
+        behind.  The same kernel as ``submit_raw`` normalises and scatters the same rows into the same packed batches -- the
+        x-vectors are the same bits -- but the destination rows are planned on the device (hiplib.voiced_rank once per window,
+        hiplib.chunk_row_plan per batch): the host sees the voiced counts (4 bytes per utterance, the one wait of this call) and
+        does work per utterance and per chunk only; no feature row and no VAD decision is copied anywhere.  The counts are made
+        on the copy stream, so that wait is not queued behind the kernels of the window before.  Returns ``(handle, lengths,
+        vad_dropped)`` as ``submit_raw``; the handle keeps ``feats`` and ``vad`` alive until ``finish``."""
+
+        def again(ex):                                   # this window on another extractor: routed there, or repeated
+            return ex.submit_device_raw(feats, utt_start, utt_len, vad, cmn_window, center, min_window, ready)
+        if self.demoted:
+            owner, out = self._on_twin(again)
+            out[0]["owner"] = owner
+            return out
+        torch, model = self.model.torch, self.model
+        dev, F = model.device, model.feat_dim
+        start = np.asarray(utt_start, dtype=np.int64).reshape(-1)
+        T = np.asarray(utt_len, dtype=np.int64).reshape(-1)
+        n, n_frames = len(T), int(feats.shape[0])
+        assert len(start) == n and feats.dim() == 2 and feats.shape[1] == F, "feats must be [rows, %d] and one (start, length) per utterance" % F
+        assert n == 0 or (start.min() >= 0 and T.min() >= 0 and int((start + T).max()) <= n_frames < 2 ** 31), \
+            "an utterance leaves the %d feature rows" % n_frames
+        assert vad is None or vad.numel() >= n_frames, "vad must hold one decision per feature row"
+        V = np.zeros(n, dtype=np.int64)                       # selected frames per utterance
+        with torch.cuda.device(dev):
+            compute = torch.cuda.current_stream()
+            if self._copy_stream is None:
+                self._copy_stream = torch.cuda.Stream(device=dev)
+            if ready is not None:
+                compute.wait_event(ready)
+            rank = None
+            if n:
+                span_flat, span = self._pinned("span", (2, n), torch.int32)
+                sp = span.numpy()
+                sp[0], sp[1] = start, T
+                cnt_flat, cnt = self._pinned("count", (n,), torch.int32)
+                with torch.cuda.stream(self._copy_stream):
+                    if ready is not None:
+                        self._copy_stream.wait_event(ready)
+                    span_d = span.to(dev, non_blocking=True)
+                    rank, count_d = hiplib.voiced_rank(vad, span_d[0], span_d[1], n_frames)
+                    cnt.copy_(count_d, non_blocking=True)
+                    counted = torch.cuda.Event()
+                    counted.record(self._copy_stream)
+                counted.synchronize()
+                compute.wait_event(counted)
+                V[:] = cnt.numpy()
+                self._unpin("span", span_flat)
+                self._unpin("count", cnt_flat)
+        vad_dropped = (V == 0) if vad is not None else np.zeros(n, dtype=bool)
+        handle, win = self._open_window(V)
+        if win is None:
+            return handle, V, vad_dropped
+        order, bounds, (_, _, c_len, seg_start) = handle["order"], win["bounds"], win["table"]
+        table = device_plan_table(start, T, order, c_len, seg_start)
+        spans = [(int(np.searchsorted(seg_start, b0, side="right")) - 1, int(np.searchsorted(seg_start, b1, side="left")))
+                 for b0, b1, _ in bounds]
+        self._plan_staging(max(hi - lo for lo, hi in spans), max(b1 - b0 for b0, b1, _ in bounds))
+        with torch.cuda.device(dev):
+            dst = torch.empty(n_frames, dtype=torch.int32, device=dev)     # one per window; each batch rewrites its utterances' rows
+            for bi, ((b0, b1, _), (lo, hi)) in enumerate(zip(bounds, spans)):
+                layout = BatchLayout(c_len[b0:b1], model.gap, model.align)
+                nU, max_T = hi - lo, int(table[1, lo:hi].max())
+                st, sx = self._take(self._plan_stage, self._stage)
+                st["utt"].numpy()[:, :nU] = table[:, lo:hi]
+                st["row"].numpy()[:b1 - b0] = layout.row_start
+                layout.row_valid(sx["rv"].numpy())
+
+                def scatter(utt_d, row_d, b0=b0, b1=b1, nU=nU, max_T=max_T, layout=layout):
+                    hiplib.chunk_row_plan(rank, utt_d[0], utt_d[1], utt_d[2], utt_d[3], utt_d[4], n_frames, b0, b1, row_d, dst)
+                    x = torch.zeros((layout.rows, model.in_dim), dtype=torch.float32, device=dev)      # gap rows and padding columns
+                    hiplib.cmn_sliding_scatter(feats, utt_d[0], utt_d[1], nU, max_T, cmn_window, center, min_window, dst, x)
+                    return x
+                st["event"] = sx["event"] = self._launch(handle, win, bi, layout, sx, [st["utt"][:, :nU], st["row"][:b1 - b0]], scatter)
+            win["keep"].append((feats, vad, rank, dst))
+            self._window_tail(handle, win["compute"], win["P_all"], win["E_all"], seg_start, c_len, win["status"], win["keep"], None,
+                              lambda ex: again(ex)[0])
+        return handle, V, vad_dropped
+
+    def _plan_staging(self, nutts, nchunks):
+        """NBUF pinned sets for submit_device_raw: the per-utterance tables int32[5, utts] and the chunks' first rows int32[chunks]."""
+        torch = self.model.torch
+        cur = self._plan_stage
+        if cur is None or cur[0]["utt"].shape[1] < nutts or cur[0]["row"].shape[0] < nchunks:
+            nutts, nchunks = max(nutts, self.PIN_FLOOR[1]), max(nchunks, self.PIN_FLOOR[1], min(self.max_batch_chunks, 8192))
+            self._plan_stage = [dict(utt=torch.zeros((5, nutts), dtype=torch.int32).pin_memory(),
+                                     row=torch.zeros(nchunks, dtype=torch.int32).pin_memory(), event=None) for _ in range(self.NBUF)]
 
     def _raw_staging(self, rows, nutts, feat_dim):
         """NBUF pinned sets for submit_raw: raw features [rows, F], destination rows int32[rows], (start, length) int32[2, utts]."""

@@ -1,5 +1,5 @@
 """The host pipeline of ``Model.make_embedding`` (local/tf/models.py), stage by stage: ``WindowReader`` parses the input into
-windows on a thread of its own, ``Extraction`` carries one call's windows through the front-end and the extractor, and
+windows on a thread of its own (``WaveTable`` in its place when the input is a wav.scp), ``Extraction`` carries one call's windows through the front-end and the extractor, and
 ``VectorWriter`` serialises the finished vectors on a third thread.  The driver loop itself stays in ``make_embedding``."""
 import functools
 import queue
@@ -196,6 +196,89 @@ class WindowReader(object):
             put_unless_cancelled(self._windows, e, self._cancel)
 
 
+class WaveBatch(object):
+    """One window of a ``WaveTable``: the keys and waves of a ``mfcc_vad._planned_batches`` batch, in the place of a window's
+    matrices (it answers what ``make_embedding``'s loop asks of those: no uniform column count, no arenas to give back)."""
+    holders = ()
+    addrs = None
+
+    def __init__(self, table, keys, waves):
+        self.table, self.keys, self.waves = table, keys, waves
+
+    def __len__(self):
+        return len(self.keys)
+
+    def uniform_cols(self):
+        return None
+
+
+class WaveTable(object):
+    """A wav.scp as the ``input_stream`` of ``Model.make_embedding``: x-vectors straight from audio, the MFCC rows and the VAD
+    decisions never leave the device.  The thread interface is ``WindowReader``'s.  The thread does host work
+    only -- it reads the files and their headers, plans ``wav-reverberate`` entries and deals the entries into windows of at most
+    ``window_samples`` samples, with ``mfcc_vad._planned_batches``, i.e. exactly the batches ``compute-mfcc-vad`` would launch --
+    and yields ``(keys, WaveBatch, None)``; the consumer's thread runs ``compute`` (the MFCC engine's launches) and the submit.
+    ``mfcc_opts`` / ``vad_opts``: ``mfcc.MfccOptions`` / ``mfcc.VadOptions``.  ``start`` starts the thread (``make_embedding``
+    calls it once it has accepted its arguments)."""
+
+    def __init__(self, wav_scp, mfcc_opts, vad_opts, window_samples=1 << 26):
+        from . import augment
+        self.path, self.opts, self.vad_opts, self.window_samples = wav_scp, mfcc_opts, vad_opts, int(window_samples)
+        self.opts.check(resample=True)                # (NotImplementedError / ValueError: before anything is read)
+        self._augmenter = augment.Augmenter()
+        self._engine = None
+        self._cancel = threading.Event()
+        self._windows = queue.Queue(maxsize=2)
+        self._thread = None
+
+    def start(self):
+        if self._thread is None:
+            self._thread = threading.Thread(target=self._run, daemon=True)
+            self._thread.start()
+        return self
+
+    def __iter__(self):
+        return self.start()
+
+    def __next__(self):
+        item = self._windows.get()
+        if item is None:
+            raise StopIteration
+        if isinstance(item, BaseException):
+            raise item
+        return item
+
+    def recycle(self, arenas):
+        pass
+
+    def cancel(self):
+        self._cancel.set()
+
+    def close(self):
+        self._cancel.set()
+
+    def _run(self):
+        try:
+            import mfcc_vad
+            for keys, waves in mfcc_vad._planned_batches(self.path, self.opts, self._augmenter, self.window_samples):
+                if not put_unless_cancelled(self._windows, (keys, WaveBatch(self, keys, waves), None), self._cancel):
+                    return
+            put_unless_cancelled(self._windows, None, self._cancel)
+        except BaseException as e:          # noqa: B902 -- forwarded to the consumer (SystemExit of an unreadable entry included)
+            put_unless_cancelled(self._windows, e, self._cancel)
+
+    def compute(self, batch, device):
+        """MFCC + VAD of one window on ``device``: ``mfcc.Mfcc.compute_device``'s result (through ``augment.mfcc_compute`` when the
+        window holds ``wav-reverberate`` entries)."""
+        from . import augment, mfcc
+        if self._engine is None:
+            self._engine = mfcc.Mfcc(self.opts, self.vad_opts, device=device, window_samples=self.window_samples)
+            self._augmenter.device = device
+        if any(isinstance(w, augment.Pending) for w in batch.waves):
+            return augment.mfcc_compute(self._engine, self._augmenter, batch.keys, batch.waves, device=True)
+        return self._engine.compute_device(batch.keys, batch.waves)
+
+
 class VectorWriter(object):
     """A writer thread serialises the records of finished windows (same bytes as write_vec_flt per key), in order, so that
     formatting ~50 k records per window does not sit between two kernel launches (bounded queue: 4 windows).  After an error
@@ -270,10 +353,17 @@ class Extraction(object):
         the keys that go on, their (selected) lengths and a function that yields the vectors."""
         t0 = time.time()
         front, ex = self.front, self.ex
-        if front is not None and front.cmn_window > 0 and self.world == 1 and hasattr(ex, "submit_raw") and \
+        raw = None
+        if isinstance(mats, WaveBatch):
+            # a window of a WaveTable: MFCC + VAD on the device, and the extractor reads the rows where they lie
+            feats, vad, row0, T, ready = mats.table.compute(mats, self.model.device_model.device)
+            raw = ex.submit_device_raw(feats, row0, T, vad, front.cmn_window, front.center, front.min_window, ready)
+        elif front is not None and front.cmn_window > 0 and self.world == 1 and hasattr(ex, "submit_raw") and \
                 engine._host_lib() is not None and (addrs is not None or engine.can_submit_raw(mats, self.model.device_model.feat_dim)):
             # CMN + voiced-frame selection on the device, scattered straight into the packed batches
-            handle, lens, dropped = ex.submit_raw(mats, vads, front.cmn_window, front.center, front.min_window, addrs)
+            raw = ex.submit_raw(mats, vads, front.cmn_window, front.center, front.min_window, addrs)
+        if raw is not None:
+            handle, lens, dropped = raw
             keep = None
             if dropped.any():
                 for i in np.flatnonzero(dropped).tolist():

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -141,6 +141,9 @@ _SIGNATURES = {
     # stages 3-5: training examples
     "xv_vad_compact_i32": (_ci, [_vp, _vp, _vp, _ci, _i64, _vp, _vp, _vp]),
     "xv_egs_chunks_f16": (_ci, [_vp, _ci, _ci, _i64, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _i64, _vp]),
+    # the extractor's destination-row plan from device-resident VAD decisions
+    "xv_voiced_rank_i32": (_ci, [_vp, _vp, _vp, _ci, _i64, _vp, _vp, _vp]),
+    "xv_chunk_row_plan_i32": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp]),
     # compressed feature output
     "xv_cm_payload_bytes": (_i64, [_ci, _ci]),
     "xv_cm_encode_f32": (_ci, [_vp, _i64, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp]),
@@ -1148,6 +1151,45 @@ def vad_compact(vad, utt_start, utt_len):
     rows = torch.full((max(n_frames, 1),), -1, dtype=torch.int32, device=vad.device)
     _check(lib.xv_vad_compact_i32(_ptr(vad), starts, lens, n_utts, n_frames, _ptr(count), _ptr(rows), _stream()), "xv_vad_compact_i32")
     return count, rows
+
+
+def voiced_rank(vad, utt_start, utt_len, n_frames, rank=None, count=None):
+    """xv_voiced_rank_i32: vad[>= n_frames] cuda float32 (non-zero = voiced; None: every frame is voiced), utt_start / utt_len cuda
+    int32 -> (rank[n_frames], voiced_count[n_utts]) cuda int32: rank[utt_start[u] + t] = voiced frames of u before t, -1 for an
+    unvoiced frame.  Entries of ``rank`` outside the utterances' spans are not written (a fresh ``rank`` is uninitialised there)."""
+    import torch
+    lib = require_gpu()
+    i32, n_utts, n_frames = torch.int32, utt_start.numel(), int(n_frames)
+    assert n_frames >= 0 and utt_len.numel() == n_utts
+    if vad is not None:
+        _f32(vad, "vad")
+        assert vad.dim() == 1 and vad.numel() >= n_frames, "vad must hold at least %d decisions" % n_frames
+    dev = utt_start.device
+    if rank is None:
+        rank = torch.empty(max(n_frames, 1), dtype=i32, device=dev)
+    if count is None:
+        count = torch.empty(max(n_utts, 1), dtype=i32, device=dev)
+    _check(lib.xv_voiced_rank_i32(_ptr(vad), _dev(utt_start, i32, "utt_start"), _dev(utt_len, i32, "utt_len"), n_utts, n_frames,
+                                  _dev(rank, i32, "rank", n_frames), _dev(count, i32, "count", n_utts), _stream()), "xv_voiced_rank_i32")
+    return rank, count[:n_utts]
+
+
+def chunk_row_plan(rank, utt_start, utt_len, chunk_size, chunks_kept, first_chunk, n_frames, b0, b1, row_start, dst_row=None):
+    """xv_chunk_row_plan_i32: ``rank`` of voiced_rank + the per-utterance chunk tables (cuda int32, one entry per utterance of
+    utt_start) -> dst_row[n_frames] cuda int32, the row of the packed batch of chunks [b0, b1) (chunk c at row_start[c - b0]) each
+    feature row goes to, or -1.  Only the rows of the listed utterances are written."""
+    import torch
+    lib = require_gpu()
+    i32, n_utts, n_frames = torch.int32, utt_start.numel(), int(n_frames)
+    assert n_frames >= 0 and int(b1) >= int(b0)
+    if dst_row is None:
+        dst_row = torch.empty(max(n_frames, 1), dtype=i32, device=rank.device)
+    _check(lib.xv_chunk_row_plan_i32(_dev(rank, i32, "rank", n_frames), _dev(utt_start, i32, "utt_start"),
+                                     _dev(utt_len, i32, "utt_len", n_utts), _dev(chunk_size, i32, "chunk_size", n_utts),
+                                     _dev(chunks_kept, i32, "chunks_kept", n_utts), _dev(first_chunk, i32, "first_chunk", n_utts),
+                                     n_utts, n_frames, int(b0), int(b1), _dev(row_start, i32, "row_start", int(b1) - int(b0)),
+                                     _dev(dst_row, i32, "dst_row", n_frames), _stream()), "xv_chunk_row_plan_i32")
+    return dst_row
 
 
 def check_chunk_table(table, voiced_counts, feat_dim, y_elems):

@@ -589,7 +589,28 @@ class Mfcc(object):
             self.stats["raw_bytes"] += len(raw)
         return x
 
-    def _launch(self, keys, waves, do_vad, fill=None, compress=False, rates=None):
+    def compute_device(self, keys, waves, rates=None, fill=None):
+        """``compute`` for ONE window whose results stay on the device (``_launch`` without the downloads): everything ``compute``
+        accepts -- plain, resampled and coded waves, the ``fill`` hook -- but the caller does the batching: the waves of a call go
+        up in one sample buffer.  Returns ``(feats, vad, row0, T, ready)``: the cuda tensors feats [max(rows, 1), num_ceps]
+        float32 and vad [max(rows, 1)] float32 (None without VAD options), the host int64 arrays row0 / T (utterance u is rows
+        row0[u] .. row0[u] + T[u] - 1) and an event recorded on this engine's stream behind the last launch: another stream waits
+        for it before it reads the tensors, and keeps them referenced until its own work on them is done."""
+        torch = self.torch
+        rates = self._rates(waves, rates)
+        waves = [w if isinstance(w, CodedWave) else np.asarray(w).reshape(-1) for w in waves]
+        assert len(keys) == len(waves)
+        fill_w = None if fill is None else (lambda x, off: fill(x, 0, len(waves), off))
+        with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
+            y, vad, _, row0, T, _, _ = self._device_pass(keys, waves, self.vad_opts is not None, fill_w, rates)
+            ready = torch.cuda.Event()
+            ready.record(self._stream)
+        return y, vad, row0, T, ready
+
+    def _device_pass(self, keys, waves, do_vad, fill, rates, want_T=False):
+        """Upload + (resample, decode, fill) + MFCC + VAD of one window, on the current stream: the device tensors y, vad (None
+        without ``do_vad``) and lm (None without ``with_logmel``), the host arrays row0 and T, and the device copies of both
+        (d_T: None unless ``do_vad`` or ``want_T``)."""
         torch, opts = self.torch, self.opts
         n = len(waves)
         ns = np.array([w.shape[0] for w in waves], np.int64)
@@ -609,29 +630,37 @@ class Mfcc(object):
             flat = np.concatenate([w.astype(dtype, copy=False) for w in waves]) if n else np.zeros(0, dtype)
         keyv = np.array([dither_key(k, opts.seed) for k in keys], np.uint64).view(np.int64)
         C, B = opts.num_ceps, opts.num_mel_bins
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device, non_blocking=False)  # noqa: E731
+        x = self._upload_parts(waves, rates, res, cod, ns, off) if parts else dev(flat if len(flat) else np.zeros(1, dtype))
+        if fill is not None:
+            fill(x, off)
+        d_off, d_ns, d_row0, d_key = dev(off), dev(ns), dev(row0), dev(keyv)
+        y = torch.empty((max(rows, 1), C), dtype=torch.float32, device=self.device)
+        lm = torch.empty((max(rows, 1), B), dtype=torch.float32, device=self.device) if self.with_logmel else None
+        hiplib.mfcc(x, d_off, d_ns, d_row0, d_key, rows, self._dev, opts, y, lm)
+        d_T = dev(T.astype(np.int32)) if do_vad or want_T else None
+        vad = None
+        if do_vad:
+            vad = torch.empty(max(rows, 1), dtype=torch.float32, device=self.device)
+            hiplib.vad_energy(y, d_row0, d_T, self.vad_opts, vad)
+        self.stats["utterances"] += n
+        self.stats["samples"] += int(ns.sum())
+        self.stats["frames"] += rows
+        self.stats["launches"] += 1
+        return y, vad, lm, row0, T, d_row0, d_T
+
+    def _launch(self, keys, waves, do_vad, fill=None, compress=False, rates=None):
+        torch, C = self.torch, self.opts.num_ceps
         with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
-            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device, non_blocking=False)  # noqa: E731
-            x = self._upload_parts(waves, rates, res, cod, ns, off) if parts else dev(flat if len(flat) else np.zeros(1, dtype))
-            if fill is not None:
-                fill(x, off)
-            d_off, d_ns, d_row0, d_key = dev(off), dev(ns), dev(row0), dev(keyv)
-            y = torch.empty((max(rows, 1), C), dtype=torch.float32, device=self.device)
-            lm = torch.empty((max(rows, 1), B), dtype=torch.float32, device=self.device) if self.with_logmel else None
-            hiplib.mfcc(x, d_off, d_ns, d_row0, d_key, rows, self._dev, opts, y, lm)
-            d_T = dev(T.astype(np.int32)) if do_vad or compress else None
+            y, vad, lm, row0, T, d_row0, d_T = self._device_pass(keys, waves, do_vad, fill, rates, want_T=compress)
+            rows = int(T.sum())
             if do_vad:
-                vad = torch.empty(max(rows, 1), dtype=torch.float32, device=self.device)
-                hiplib.vad_energy(y, d_row0, d_T, self.vad_opts, vad)
                 vad_h = vad[:rows].cpu().numpy()
             if compress:
                 block, records = cm.encode(y, row0, T, C, stream=self._stream, keys=keys, d_row0=d_row0, d_T=d_T)
             else:
                 y_h = y[:rows].cpu().numpy()
             lm_h = lm[:rows].cpu().numpy() if lm is not None else None
-        self.stats["utterances"] += n
-        self.stats["samples"] += int(ns.sum())
-        self.stats["frames"] += rows
-        self.stats["launches"] += 1
         bounds = list(zip(row0.tolist(), (row0 + T).tolist()))
         if compress:
             feats = [p if p.rows else np.zeros((0, C), np.float32) for p in cm.packed(block, records, C)]
