@@ -52,7 +52,7 @@ extern "C" {
 #define XV_ERR_BAD_ARG (-1)
 #define XV_ERR_UNSUPPORTED (-2)
 
-/* Library / ABI version (increments whenever an entry point is added or changed; currently 34). */
+/* Library / ABI version (increments whenever an entry point is added or changed; currently 37). */
 int xv_version(void);
 /* Thread-local description of the last non-zero return. */
 const char *xv_last_error(void);
@@ -885,6 +885,29 @@ int xv_resample_f32(const void *in, int in_format, const int64_t *in_offset, con
 #define XV_DEC_ALAW 3
 int xv_wave_decode(const uint8_t *raw, int64_t raw_bytes, const int64_t *utt, int n_utts, const int64_t *tiles, int64_t n_tiles,
                    void *out, int sample_format, void *stream);
+
+/* ---- sliding-window extraction: the packed rows of overlapping sub-segments (csrc/xv_subseg.hip) --------------
+ * xv_cmn_sliding_scatter_f32 indexed by OUTPUT row, so that one frame may go to several rows: the fp32, packed-row sibling of
+ * xv_egs_chunks_f16.  x[x_rows, ldx]: the raw rows of n_utts utterances (utt_start[u], utt_len[u] in rows; any order, gaps
+ * allowed).  Chunk c is chunk_len[c] consecutive VOICED frames of utterance u = chunk_utt[c] from voiced frame chunk_first[c] on
+ * and goes to rows chunk_row[c] .. chunk_row[c] + chunk_len[c] - 1 of y[y_rows, ldy] (e.g. a zero-filled packed batch).  For
+ * j < chunk_len[c], with t = voiced_row[utt_start[u] + chunk_first[c] + j] (voiced_count, voiced_row: xv_vad_compact_i32's, voiced_row
+ * with x_rows entries; BOTH NULL: every frame is voiced, t = chunk_first[c] + j):
+ *     y[(chunk_row[c] + j) ldy + f] = float(double(x[utt_start[u] + t][f]) - sum_{ws <= s < we} double(x[utt_start[u] + s][f]) / (we - ws))
+ * for f < feat_dim; [ws, we) is the window of xv_cmn_sliding_scatter_f32 around RAW frame t (CMN precedes the selection), the
+ * sum is taken in double precision.  Only columns [0, feat_dim) of the addressed rows are written: gap rows and padding columns
+ * keep their contents.  Chunks may overlap in their sources, come in any order and differ in length (max_chunk_len = the
+ * longest; rows of a chunk past it are not made).  Chunks whose destination rows overlap are the caller's error (both write).
+ * A row is skipped -- no read, no write -- when its utterance is out of range or its span leaves [0, x_rows), its voiced index
+ * lies outside [0, voiced_count[u]), its t outside [0, utt_len[u]), or its destination row outside [0, y_rows).
+ * n_chunks == 0 returns 0 and launches nothing.  XV_ERR_BAD_ARG before any launch: a NULL required pointer, exactly one of
+ * voiced_count / voiced_row NULL, a negative count, feat_dim <= 0, cmn_window <= 0, min_window <= 0, ldx < feat_dim, ldy < feat_dim.
+ * No atomics: the same bits on every run.  Enqueues and returns. */
+int xv_cmn_sliding_gather_f32(const float *x, int ldx, int feat_dim, int64_t x_rows, const int32_t *utt_start, const int32_t *utt_len,
+                              int n_utts, const int32_t *voiced_count, const int32_t *voiced_row, const int32_t *chunk_utt,
+                              const int32_t *chunk_first, const int32_t *chunk_len, const int32_t *chunk_row, int n_chunks,
+                              int max_chunk_len, int cmn_window, int center, int min_window, float *y, int ldy, int64_t y_rows,
+                              void *stream);
 
 #ifdef __cplusplus
 }

@@ -105,4 +105,32 @@ __device__ __forceinline__ float act_fn(float z, float a)
     return MODE == 1 ? fmaxf(a * z, z) : MODE == 2 ? fmaxf(z, 0.f) : fmaxf(z, 0.f) + a * fminf(z, 0.f);
 }
 
+// Kaldi's SlidingWindowCmn window [ws, we) around frame t of an utterance of T frames (the rule is written out at the top of
+// xv_frontend.hip).  Integers only.
+__device__ __forceinline__ void cmn_window_bounds(int t, int T, int window, int center, int min_window, int &ws, int &we)
+{
+    if (center) { ws = t - window / 2; we = ws + window; }
+    else { ws = t - window; we = t + 1; }
+    if (ws < 0) { we -= ws; ws = 0; }
+    if (!center && we > t) we = max(t + 1, min_window);
+    if (we > T) { ws -= we - T; we = T; if (ws < 0) ws = 0; }
+}
+
+// The fp64 sum of col[s * ldx], ws <= s < we, moved right to the window [nws, nwe): the frames that leave are subtracted in
+// ascending order, then the frames that enter are added in ascending order.  One order for every caller: the bits of the sum
+// depend on the path of windows, never on which kernel walks it.
+__device__ __forceinline__ void cmn_window_slide(const float *col, int ldx, int &ws, int &we, int nws, int nwe, double &sum)
+{
+    for (; ws < nws; ++ws) sum -= (double)col[(long)ws * ldx];
+    for (; we < nwe; ++we) sum += (double)col[(long)we * ldx];
+}
+
+// cmn_window_slide for windows that follow an index list (voiced frames): the window moves right by the gap to the previous
+// frame; one that has left the old window behind, or a list that does not ascend, starts its sum afresh.
+__device__ __forceinline__ void cmn_window_move(const float *col, int ldx, int &ws, int &we, int nws, int nwe, double &sum)
+{
+    if (nws >= we || nws < ws || nwe < we) { sum = 0.0; ws = we = nws; }
+    cmn_window_slide(col, ldx, ws, we, nws, nwe, sum);
+}
+
 }  // namespace

@@ -83,13 +83,7 @@ __global__ __launch_bounds__(256) void egs_chunks_kernel(const float *__restrict
     if (dst + (long)j1 * F > y_elems) j1 = (int)min((long)j1, (y_elems - dst) / F);
     if (j0 >= j1) return;
     const int f0 = threadIdx.x & 31;
-    auto bounds = [&](int t, int &ws, int &we) {
-        if (center) { ws = t - window / 2; we = ws + window; }
-        else { ws = t - window; we = t + 1; }
-        if (ws < 0) { we -= ws; ws = 0; }
-        if (!center && we > t) we = max(t + 1, min_window);
-        if (we > T) { ws -= we - T; we = T; if (ws < 0) ws = 0; }
-    };
+    auto bounds = [&](int t, int &ws, int &we) { cmn_window_bounds(t, T, window, center, min_window, ws, we); };
     const int *rows = voiced_row + base + first;
     for (int f = f0; f < F; f += 32) {                 // F <= 32 in every recipe: one trip
         const float *col = x + base * ldx + f;
@@ -102,9 +96,7 @@ __global__ __launch_bounds__(256) void egs_chunks_kernel(const float *__restrict
             bounds(t, nws, nwe);
             // voiced frames ascend, so the window only moves right: by the gap to the previous voiced frame.  A window that has left
             // the old one behind (or an index list that does not ascend) starts its sum afresh.
-            if (nws >= we || nws < ws || nwe < we) { sum = 0.0; ws = we = nws; }
-            for (; ws < nws; ++ws) sum -= (double)col[(long)ws * ldx];
-            for (; we < nwe; ++we) sum += (double)col[(long)we * ldx];
+            cmn_window_move(col, ldx, ws, we, nws, nwe, sum);
             float v = (float)((double)col[(long)t * ldx] - sum / (double)(we - ws));
             // Two roundings, as the reference's float32 features cast with astype(float16): the compiler would otherwise fold
             // double -> float -> half into ONE rounding from the double (seen in the ISA: a software f64 -> f16 sequence), which

@@ -36,13 +36,7 @@ __global__ __launch_bounds__(256) void cmn_sliding_scatter_kernel(const float *_
     const int b = min(a + SEG, T);
     const int f0 = threadIdx.x & 31;
     const long base = utt_start[u];
-    auto bounds = [&](int t, int &ws, int &we) {
-        if (center) { ws = t - window / 2; we = ws + window; }
-        else { ws = t - window; we = t + 1; }
-        if (ws < 0) { we -= ws; ws = 0; }
-        if (!center && we > t) we = max(t + 1, min_window);
-        if (we > T) { ws -= we - T; we = T; if (ws < 0) ws = 0; }
-    };
+    auto bounds = [&](int t, int &ws, int &we) { cmn_window_bounds(t, T, window, center, min_window, ws, we); };
     for (int f = f0; f < F; f += 32) {                 // F <= 32 in every recipe: one trip
         const float *col = x + base * ldx + f;
         int ws, we;
@@ -53,8 +47,7 @@ __global__ __launch_bounds__(256) void cmn_sliding_scatter_kernel(const float *_
             int nws, nwe;
             bounds(t, nws, nwe);
             // the window only ever moves right, by at most one frame at each end
-            for (; ws < nws; ++ws) sum -= (double)col[(long)ws * ldx];
-            for (; we < nwe; ++we) sum += (double)col[(long)we * ldx];
+            cmn_window_slide(col, ldx, ws, we, nws, nwe, sum);
             const int dst = dst_row[base + t];
             if (dst >= 0) y[(long)dst * ldy + f] = (float)((double)col[(long)t * ldx] - sum / (double)(we - ws));
         }

@@ -79,6 +79,15 @@ _FLAGS = (
      "VAD table).  Excludes --feature-rspecifier and --vad-rspecifier; needs --cmn-window > 0; one process only."),
     ("--mfcc-config", "mfcc_config", str, "", False, None, "With --wav-rspecifier: the compute-mfcc-feats options file (conf/mfcc.conf)."),
     ("--vad-config", "vad_config", str, "", False, None, "With --wav-rspecifier: the compute-vad options file (conf/vad.conf)."),
+    # build-defined extension: one x-vector per sliding window of an utterance
+    ("--window", "window", int, 0, False, None,
+     "If > 0: sliding-window extraction -- one x-vector per sub-segment of this many frames, written under <utt>-<first>-<end>; "
+     "--chunk-size is ignored.  150 with --period 75 is Kaldi's 1.5 s every 0.75 s at a 10 ms shift.  One process only."),
+    ("--period", "period", int, 0, False, None, "With --window: frames between the starts of two sub-segments (0: = --window)."),
+    ("--frame-shift", "frame_shift", float, None, False, None,
+     "With --subsegments-file: milliseconds per frame (10 when not given).  Not with --wav-rspecifier: the MFCC configuration's value is used."),
+    ("--subsegments-file", "subsegments_file", str, "", False, None,
+     "With --window: also write '<key> <utt> <start s> <end s>' per vector to this file (a Kaldi segments file)."),
 )
 
 WAV_WINDOW_SAMPLES = 1 << 26      # samples per window of the --wav-rspecifier route: the batches of mfcc_vad.py (its WINDOW_SAMPLES)
@@ -97,6 +106,28 @@ def get_args(argv=None):
             kw["choices"] = list(choices)
         parser.add_argument(flag, **kw)
     args = parser.parse_args(argv)
+    # usage errors of the sliding mode leave through argparse (exit status 2), before anything is opened
+    if args.window < 0 or args.period < 0:
+        parser.error("--window and --period are frame counts: not negative")
+    if args.window == 0:
+        if args.period:
+            parser.error("--period goes with --window")
+        if args.subsegments_file:
+            parser.error("--subsegments-file goes with --window")
+    else:
+        if args.period > args.window:
+            parser.error("--period %d is larger than --window %d: frames between two sub-segments would be skipped" % (args.period, args.window))
+        if args.window < args.min_chunk_size:
+            parser.error("--window %d is shorter than --min-chunk-size %d: no sub-segment could be kept" % (args.window, args.min_chunk_size))
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            parser.error("--window runs in one process (WORLD_SIZE=%s): split the input and run one job per part" % os.environ["WORLD_SIZE"])
+        args.period = args.period or args.window
+    if args.wav_rspecifier and args.frame_shift is not None:
+        parser.error("--frame-shift is not accepted with --wav-rspecifier: the MFCC configuration's --frame-shift is used")
+    if args.frame_shift is None:
+        args.frame_shift = 10.0
+    if args.frame_shift <= 0:
+        parser.error("--frame-shift must be positive")
     # usage errors of the --wav-rspecifier route leave through argparse (exit status 2), before anything is opened
     if args.wav_rspecifier:
         if args.feature_rspecifier or args.vad_rspecifier:
@@ -238,18 +269,34 @@ def _wave_table(args):
     return extract_stream.WaveTable(args.wav_rspecifier.strip().partition(":")[2].strip(), opts, vopts, WAV_WINDOW_SAMPLES)
 
 
+def _sliding(args, subsegments_fid):
+    """make_embedding's keyword arguments of the sliding mode (none without --window)."""
+    if not getattr(args, "window", 0):
+        return {}
+    return dict(window=args.window, period=args.period or args.window, subsegments=subsegments_fid, frame_shift=args.frame_shift)
+
+
 def eval_dnn(args):
     use_gpu = args.use_gpu == 'yes'
     wspecifier, ark, scp = process_wspecifier(args.vector_wspecifier)
     if ark is not None and scp is not None and os.path.exists(scp) and (os.path.exists(ark) or os.path.exists(ark + '.0')):
         logger.info('Both output ark and scp files exist. Return from this call.')
         return
+    # --subsegments-file: written under a temporary name and renamed at the end, like the ark and the scp
+    sub_path = getattr(args, "subsegments_file", "") if getattr(args, "window", 0) else ""
+    with (open(sub_path + '.tmp', 'wt') if sub_path else _Null()) as sub_fid:
+        _extract(args, use_gpu, wspecifier, ark, scp, _sliding(args, sub_fid))
+    if sub_path and int(os.environ.get("RANK", "0")) == 0:
+        os.rename(sub_path + '.tmp', sub_path)
+
+
+def _extract(args, use_gpu, wspecifier, ark, scp, sliding):
     if getattr(args, "wav_rspecifier", ""):
         model = Model()
         model.prepin_staging = True
         with _open_output(wspecifier, ark, scp) as output_fid:
             model.make_embedding(_wave_table(args), output_fid, args.model_dir, args.min_chunk_size, args.chunk_size, use_gpu, logger,
-                                 cmn_window=args.cmn_window, cmn_center=args.cmn_center == 'yes', distributed=False)
+                                 cmn_window=args.cmn_window, cmn_center=args.cmn_center == 'yes', distributed=False, **sliding)
         jobclock.mark("extraction (wav reader -> MFCC -> kernels -> last vector down)")
         return _rename_outputs(wspecifier, ark, scp)
     # under torchrun (one process per GPU) only rank 0 owns the output table.  An scp feature table is sharded by line
@@ -258,6 +305,7 @@ def eval_dnn(args):
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     root = rank == 0
     grouped = world > 1 or (os.environ.get("XV_FORCE_DIST") == "1" and "RANK" in os.environ)     # the latter: 1-rank group (tests)
+    grouped = grouped and not sliding              # (the sliding mode is a one-process mode: no group, no sharding)
     if grouped and _is_scp_table(args.feature_rspecifier) and (not args.vad_rspecifier or _is_scp_table(args.vad_rspecifier)) and \
             _native_table(wspecifier, ark) and os.environ.get("XVECTOR_SHARD_OUTPUT", "gather") == "files":
         return _extract_into_shard_files(args, use_gpu, ark, scp, rank, world)
@@ -286,7 +334,7 @@ def eval_dnn(args):
         with (collector if presharded else _open_output(wspecifier, ark, scp) if root else _Discard()) as output_fid:
             model.make_embedding(input_fid if feats is None else feats, output_fid, args.model_dir, args.min_chunk_size,
                                  args.chunk_size, use_gpu, logger, vad_stream=vad, cmn_window=args.cmn_window,
-                                 cmn_center=args.cmn_center == 'yes', distributed=not presharded)
+                                 cmn_center=args.cmn_center == 'yes', distributed=not presharded, **sliding)
     jobclock.mark("extraction (reader -> kernels -> last vector down)")
     if presharded:
         _gather_and_write(model, collector, shard_keys, wspecifier, ark, scp, rank, world)

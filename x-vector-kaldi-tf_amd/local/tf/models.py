@@ -522,16 +522,35 @@ class Model(object):
 
     # -- the hot path ------------------------------------------------------------------------------
     def make_embedding(self, input_stream, output_stream, model_dir, min_chunk_size, chunk_size, use_gpu, logger,
-                       vad_stream=None, cmn_window=0, cmn_center=True, distributed=True):
+                       vad_stream=None, cmn_window=0, cmn_center=True, distributed=True, window=0, period=0, subsegments=None,
+                       frame_shift=10.0):
         """Build-defined extension (defaults = the reference's behaviour): with ``cmn_window > 0`` and/or a
         ``vad_stream`` (ark stream or (key, vector) iterator, same key order as the features) the sliding-window CMN and
         the VAD frame selection that extract_xvectors.sh:68 runs as Kaldi binaries are done on the GPU first, so
         ``input_stream`` can carry raw features.  ``input_stream`` may also be a (key, matrix) iterator or a table with a
         ``blocks()`` method (kaldi_io.MatScp).  Under torchrun every
         rank reads the same stream and extracts its share of each window (one gather per window to rank 0) unless
-        ``distributed=False`` says that the caller sharded the input itself."""
+        ``distributed=False`` says that the caller sharded the input itself.
+
+        ``window`` > 0 (frames): sliding mode -- one x-vector per sub-segment of ``window`` frames cut every
+        ``period`` frames (0: = window) instead of one per utterance, ``chunk_size`` ignored; sub-segment [first, end) of ``<utt>``
+        is written under ``<utt>-<first>-<end>`` (8 digits each).  ``subsegments``: a text stream that gets one line per vector,
+        ``<key> <utt> <start s> <end s>`` (a Kaldi segments file), frames turned into seconds with ``frame_shift`` milliseconds (a
+        WaveTable input: its MFCC configuration's).  One process only."""
         start_time = time.time()
         from_wav = isinstance(input_stream, extract_stream.WaveTable)
+        sliding = int(window or 0) > 0
+        if sliding:
+            from xvector_amd import dist as xdist
+            if distributed and xdist.group_shape()[1] > 1:
+                raise ValueError("sliding-window extraction (window > 0) runs in one process: split the input and run one job per part")
+            period = int(period) if period else int(window)
+            if not 1 <= period <= int(window):
+                raise ValueError("period must lie in [1, window] (period %d, window %d)" % (period, window))
+            if int(window) < int(min_chunk_size):
+                raise ValueError("window %d is shorter than min_chunk_size %d" % (window, min_chunk_size))
+        elif period or subsegments is not None:
+            raise ValueError("period and subsegments go with window > 0")
         if from_wav:
             # x-vectors straight from a wav.scp (DESIGN.md §8.13): the table makes its own VAD, the CMN is part of the route, and
             # one process reads the whole table -- refused before a file is read or a kernel launched
@@ -540,7 +559,7 @@ class Model(object):
                 raise ValueError("a WaveTable input takes no vad_stream (it computes the VAD itself) and needs cmn_window > 0")
             if distributed and xdist.group_shape()[1] > 1:
                 raise ValueError("a WaveTable input is read by one process: sharding wav.scp across ranks is not supported")
-        if distributed and vad_stream is None and cmn_window <= 0 and self._extract_byte_ranges(
+        if distributed and not sliding and vad_stream is None and cmn_window <= 0 and self._extract_byte_ranges(
                 input_stream, output_stream, model_dir, min_chunk_size, chunk_size, use_gpu, logger):
             return
         # three threads (xvector_amd.extract_stream): a reader parses the windows, this one runs them, a writer serialises the
@@ -556,7 +575,8 @@ class Model(object):
             if from_wav and input_stream.opts.num_ceps != F_dim:
                 raise ValueError("--num-ceps=%d of the MFCC configuration is not the model's feature dimension %d"
                                  % (input_stream.opts.num_ceps, F_dim))
-            ex = engine.Extractor(self.device_model, min_chunk_size, chunk_size, max_batch_rows=self.max_batch_rows)
+            ex = engine.Extractor(self.device_model, min_chunk_size, chunk_size, max_batch_rows=self.max_batch_rows,
+                                  window=int(window) if sliding else None, period=period if sliding else None)
             front = None
             if cmn_window > 0 or vad_stream is not None:
                 front = frontend.FrontEnd(self.device_model.device, cmn_window, cmn_center)     # cmn_window <= 0: selection only
@@ -586,7 +606,8 @@ class Model(object):
                 # range): behave as a single process and leave the exchange to the caller
                 rank, world = 0, 1
 
-            writer = extract_stream.VectorWriter(output_stream)
+            writer = extract_stream.VectorWriter(output_stream, subsegments,
+                                                 input_stream.opts.frame_shift if from_wav else frame_shift)
             run = extract_stream.Extraction(self, ex, front, writer, logger, min_chunk_size, chunk_size, rank, world)
             # software pipeline of depth 2 over the windows: the host work of window i+1 (packing, H2D, launches) is issued
             # before the vectors of window i are awaited and written, so the GPU never waits for the writer
@@ -624,8 +645,9 @@ class Model(object):
                 "; demoted to bf16x3 at window %d" % st["demoted_at_window"] if ex.demoted else ""))
         self.last_stats = dict(st, demoted=bool(getattr(ex, "demoted", False)),
                                selection=dict(getattr(self.device_model, "selection", None) or {}))
-        logger.info("Processed %d features of average size %d frames. Done %d and failed %d" %
-                    (run.total_segments, st["frames"] / max(run.total_segments, 1), run.num_success, run.num_fail))
+        logger.info("Processed %d features of average size %d frames. Done %d and failed %d%s" %
+                    (run.total_segments, st["frames"] / max(run.total_segments, 1), run.num_success, run.num_fail,
+                     "; wrote %d sub-segment vectors" % run.num_vectors if sliding else ""))
         logger.info("Total time for neural network computations is %.2f minutes." % (run.compute_time / 60.0))
         logger.info("Elapsed time for extracting whole embeddings is %.2f minutes." %
                     ((time.time() - start_time) / 60.0))

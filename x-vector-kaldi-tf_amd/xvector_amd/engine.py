@@ -137,6 +137,49 @@ def plan_chunk_table(lengths, min_chunk_size, chunk_size):
     return order, c_utt, c_start, c_len, seg
 
 
+def plan_subsegments(num_rows, min_chunk_size, window, period):
+    """[(start, length), ...] of the sliding-window sub-segments of an utterance of ``num_rows`` frames (one x-vector each, nothing
+    is averaged), or None when the utterance is rejected by the rule of ``plan_chunks`` (zero length / shorter than
+    ``min_chunk_size``).  Sub-segment k starts at ``k * period`` and has ``min(window, num_rows - k * period)`` frames; sub-segment
+    0 always exists; sub-segment k >= 1 exists only while the one before it did not reach the end of the utterance and while it
+    has at least ``min_chunk_size`` frames (a shorter last piece is dropped, as the reference drops its short tail chunk).  All
+    sizes in frames: Kaldi's 1.5 s every 0.75 s are 150 / 75 at a 10 ms shift."""
+    if not 1 <= period <= window:
+        raise ValueError("sub-segments need 1 <= period <= window (period %d, window %d)" % (period, window))
+    if num_rows == 0 or num_rows < min_chunk_size:
+        return None
+    plan = [(0, min(window, num_rows))]
+    k = 1
+    while (k - 1) * period + window < num_rows:
+        length = min(window, num_rows - k * period)
+        if length < min_chunk_size:
+            break                                   # (what would follow is shorter still)
+        plan.append((k * period, length))
+        k += 1
+    return plan
+
+
+def plan_subsegment_table(lengths, min_chunk_size, window, period):
+    """``plan_subsegments`` for many utterances at once, as the flat chunk table of ``plan_chunk_table`` (same five arrays:
+    utterances that yield a sub-segment ordered by length, stably, and their sub-segments in order).  Vectorised."""
+    if not 1 <= period <= window:
+        raise ValueError("sub-segments need 1 <= period <= window (period %d, window %d)" % (period, window))
+    T = np.asarray(lengths, dtype=np.int64)
+    valid = np.flatnonzero((T > 0) & (T >= min_chunk_size))
+    order = valid[np.argsort(T[valid], kind="stable")]
+    To = T[order]
+    kmax = np.where(To > window, -(-(To - window) // period), 0)          # index of the last sub-segment that may exist
+    last = np.minimum(window, To - kmax * period)                         # ... and its length; all before it are full windows
+    kept = kmax + 1 - ((kmax > 0) & (last < min_chunk_size))
+    seg = np.zeros(len(order) + 1, np.int64)
+    np.cumsum(kept, out=seg[1:])
+    c_utt = np.repeat(order, kept)
+    idx = np.arange(int(seg[-1]), dtype=np.int64) - np.repeat(seg[:-1], kept)
+    c_start = idx * period
+    c_len = np.where(idx == np.repeat(kmax, kept), np.repeat(last, kept), window)
+    return order, c_utt, c_start, c_len, seg
+
+
 def device_plan_table(utt_start, utt_len, order, c_len, seg_start):
     """What xv_chunk_row_plan_i32 needs per utterance of a window's plan (``order``, ``c_len``, ``seg_start`` of
     ``plan_chunk_table`` on the voiced counts), as int32 [5, len(order)]: the utterance's first feature row, its frames, the chunk
@@ -820,13 +863,28 @@ class Extractor(object):
     PROBE_ROWS = 16384           # run-time accuracy check: this many rows of a window's first batch are repeated on the bf16x3 twin
     PROBE_EVERY = 64             # ... for the first window of an extractor and every 64th after it
 
-    def __init__(self, model, min_chunk_size, chunk_size, max_batch_rows=262144, max_batch_chunks=8192, accuracy_probe=None):
+    def __init__(self, model, min_chunk_size, chunk_size, max_batch_rows=262144, max_batch_chunks=8192, accuracy_probe=None,
+                 window=None, period=None):
         """accuracy_probe (f16bf8 models; default on, XVECTOR_ACCURACY_PROBE=0 turns it off): the leading (= shortest) chunks of
         the first batch of a window -- the packed rows are already in HBM -- also run through the bf16x3 twin, and ``finish``
         compares the two sets of chunk vectors.  Beyond DATA_PROBE_LIMIT the extractor is DEMOTED: the window is repeated on
         the twin and every later window goes there directly.  The load-time probe (``select_model``) sees the weights on
-        synthetic input; this one sees them on the caller's features."""
+        synthetic input; this one sees them on the caller's features.
+
+        window / period (frames): sliding mode -- one x-vector per sub-segment of ``plan_subsegments`` instead
+        of one averaged vector per utterance; ``chunk_size`` is ignored, ``period`` defaults to ``window``.  ``finish`` then
+        returns (vectors, spans) per utterance.  ``window=None``: everything as without the argument."""
         self.model = model
+        self.window = self.period = None
+        if window is not None:
+            self.window = int(window)
+            self.period = self.window if period is None else int(period)
+            if self.period < 1 or self.period > self.window:
+                raise ValueError("period must lie in [1, window] (period %d, window %d)" % (self.period, self.window))
+            if self.window < int(min_chunk_size):
+                raise ValueError("window %d is shorter than min_chunk_size %d" % (self.window, int(min_chunk_size)))
+        elif period is not None:
+            raise ValueError("period without window")
         if accuracy_probe is None:
             accuracy_probe = os.environ.get("XVECTOR_ACCURACY_PROBE", "1") != "0"
         self.accuracy_probe = bool(accuracy_probe) and model.f16bf8
@@ -840,6 +898,7 @@ class Extractor(object):
         self._stage = None
         self._raw_stage = None                         # (submit_raw's own pinned sets, rotated with ``_stage``)
         self._plan_stage = None                        # (submit_device_raw's: per-utterance and per-chunk tables only)
+        self._sub_stage = None                         # (sliding mode of the two raw routes: chunk and utterance tables)
         self._copy_stream = None
         self._turn = 0
         self._finalizer = None
@@ -971,7 +1030,8 @@ class Extractor(object):
         return bounds
 
     def extract(self, mats, addrs=None):
-        """mats: list of float32 [T, F] arrays.  Returns a list of float32[E] (or None) per input."""
+        """mats: list of float32 [T, F] arrays.  Returns a list of float32[E] (or None) per input; in sliding mode a list of
+        (vectors, spans) (or None), see ``finish``."""
         return self.finish(self.submit(mats, addrs))
 
     def submit(self, mats, addrs=None):
@@ -1017,7 +1077,10 @@ class Extractor(object):
                     layout.pack([mats[l_utt[i]][l_start[i]:l_start[i] + l_len[i]] for i in range(b0, b1)], st["x"].numpy())
                     layout.row_valid(st["rv"].numpy())
                 st["event"] = self._launch(handle, win, bi, layout, st, [st["x"][:layout.rows]], lambda x: x)
-            self._window_tail(handle, win["compute"], win["P_all"], win["E_all"], seg_start, c_len, win["status"], win["keep"], mats, again)
+            # (sliding mode: a sub-segment's span is its rows of the input matrix)
+            spans = None if self.window is None else np.stack([c_start, c_start + c_len], axis=1).astype(np.int32)
+            self._window_tail(handle, win["compute"], win["P_all"], win["E_all"], seg_start, c_len, win["status"], win["keep"], mats, again,
+                              spans)
         return handle
 
     def _open_window(self, lens):
@@ -1081,7 +1144,10 @@ class Extractor(object):
         are length-homogeneous) and its batch boundaries (the rows dealt evenly to the fewest batches within max_batch_rows /
         max_batch_chunks; a single chunk may exceed the row budget).  Returns
         ``(handle, (c_utt, c_start, c_len, seg_start), bounds)``; bounds is None for a window without a chunk."""
-        order, c_utt, c_start, c_len, seg_start = plan_chunk_table(lens, self.min_chunk_size, self.chunk_size)
+        if self.window is not None:      # sliding mode: overlapping sub-segments, one vector each (chunk_size plays no part)
+            order, c_utt, c_start, c_len, seg_start = plan_subsegment_table(lens, self.min_chunk_size, self.window, self.period)
+        else:
+            order, c_utt, c_start, c_len, seg_start = plan_chunk_table(lens, self.min_chunk_size, self.chunk_size)
         nch = len(c_utt)
         handle = dict(n=len(lens), order=order, nch=nch)
         bounds = None
@@ -1098,12 +1164,24 @@ class Extractor(object):
         self.stats["frames"] += int(layout.row_len.sum())
         self.stats["rows"] += layout.rows
 
-    def _window_tail(self, handle, compute, P_all, E_all, seg_start, c_len, status, keep, mats, redo):
+    def _window_tail(self, handle, compute, P_all, E_all, seg_start, c_len, status, keep, mats, redo, spans=None):
         """Behind the last batch of a window (on its device, ``compute`` its stream): ONE segment-level pass and ONE chunk
-        average over all its chunks, the asynchronous D2H copy of the x-vectors, and what ``finish`` waits for and releases."""
+        average over all its chunks, the asynchronous D2H copy of the x-vectors, and what ``finish`` waits for and releases.
+        Sliding mode: the rows of ``E_all`` come down as they are (no chunk average: ``len * e / len`` is not always ``e``), with
+        ``spans`` -- int32 [chunks, 2] on the host, or a pinned tensor a copy on ``compute`` is filling."""
         torch, model = self.model.torch, self.model
         dev, order = model.device, handle["order"]
         model.segment_level(P_all, E_all)
+        if self.window is not None:
+            host_flat, host = self._pinned("xvec", tuple(E_all.shape), torch.float32)
+            host.copy_(E_all, non_blocking=True)
+            self._end_probe(handle, E_all)
+            self._watch(handle, status, redo)
+            done = torch.cuda.Event()
+            done.record(compute)
+            handle.update(host=host, done=done, keep=(keep, E_all, P_all, mats), pinned=(None, host_flat), spans=spans,
+                          seg_start=np.asarray(seg_start, dtype=np.int64))
+            return
         # (pinned + copy stream: a pageable H2D copy here would block the host until every kernel of the window is done)
         tail_np = np.concatenate([np.asarray(seg_start, dtype=np.int32), c_len.astype(np.int32)])
         tail_flat, tail = self._pinned("tail", tail_np.shape, torch.int32)
@@ -1134,7 +1212,7 @@ class Extractor(object):
         """The extractor of the model's bf16x3 twin (out-of-range windows, windows after a demotion)."""
         if self._fallback_ex is None:
             self._fallback_ex = Extractor(self.model.fallback(), self.min_chunk_size, self.chunk_size, self.max_batch_rows,
-                                          self.max_batch_chunks)
+                                          self.max_batch_chunks, window=self.window, period=self.period)
         return self._fallback_ex
 
     def _on_twin(self, submit):
@@ -1251,6 +1329,10 @@ class Extractor(object):
         handle, win = self._open_window(V)
         if win is None:
             return handle, V, vad_dropped
+        if self.window is not None:
+            self._submit_raw_subsegments(handle, win, mats, addrs, T, V, cand, voiced, cmn_window, center, min_window,
+                                         lambda ex: again(ex)[0])
+            return handle, V, vad_dropped
         order, bounds, (_, _, c_len, seg_start) = handle["order"], win["bounds"], win["table"]
         kept = np.ascontiguousarray(np.diff(seg_start), dtype=np.int64)                  # chunks per utterance of `order`
         first_len = np.ascontiguousarray(c_len[seg_start[:-1]], dtype=np.int64)          # = the chunk size the plan used for the utterance
@@ -1340,7 +1422,13 @@ class Extractor(object):
                     if ready is not None:
                         self._copy_stream.wait_event(ready)
                     span_d = span.to(dev, non_blocking=True)
-                    rank, count_d = hiplib.voiced_rank(vad, span_d[0], span_d[1], n_frames)
+                    if self.window is None:
+                        rank, count_d = hiplib.voiced_rank(vad, span_d[0], span_d[1], n_frames)
+                    elif vad is not None:
+                        # sliding mode: the voiced-row lists (xv_vad_compact_i32) in the place of the ranks; the same counts
+                        count_d, vrow_d = hiplib.vad_compact(vad, span_d[0], span_d[1])
+                    else:
+                        count_d, vrow_d = span_d[1], None
                     cnt.copy_(count_d, non_blocking=True)
                     counted = torch.cuda.Event()
                     counted.record(self._copy_stream)
@@ -1352,6 +1440,10 @@ class Extractor(object):
         vad_dropped = (V == 0) if vad is not None else np.zeros(n, dtype=bool)
         handle, win = self._open_window(V)
         if win is None:
+            return handle, V, vad_dropped
+        if self.window is not None:
+            self._submit_device_subsegments(handle, win, feats, vad, start, span_d, None if vad is None else count_d,
+                                            None if vad is None else vrow_d, cmn_window, center, min_window, lambda ex: again(ex)[0])
             return handle, V, vad_dropped
         order, bounds, (_, _, c_len, seg_start) = handle["order"], win["bounds"], win["table"]
         table = device_plan_table(start, T, order, c_len, seg_start)
@@ -1379,6 +1471,112 @@ class Extractor(object):
                               lambda ex: again(ex)[0])
         return handle, V, vad_dropped
 
+    # -- sliding mode on the two raw routes: xv_cmn_sliding_gather_f32 in the place of the scatter and its row plans --------------
+    def _sub_staging(self, nutts, nchunks):
+        """NBUF pinned sets for the sliding mode of the raw routes: the batch's chunk table int32[4, chunks] (utterance, first voiced
+        frame, length, first batch row) and, for submit_raw, its utterances int32[3, utts] (first raw row, frames, voiced frames)."""
+        torch = self.model.torch
+        cur = self._sub_stage
+        if cur is None or cur[0]["utt"].shape[1] < nutts or cur[0]["tab"].shape[1] < nchunks:
+            nutts, nchunks = max(nutts, self.PIN_FLOOR[1]), max(nchunks, self.PIN_FLOOR[1], min(self.max_batch_chunks, 8192))
+            self._sub_stage = [dict(utt=torch.zeros((3, nutts), dtype=torch.int32).pin_memory(),
+                                    tab=torch.zeros((4, nchunks), dtype=torch.int32).pin_memory(), event=None) for _ in range(self.NBUF)]
+
+    def _submit_raw_subsegments(self, handle, win, mats, addrs, T, V, cand, voiced, cmn_window, center, min_window, redo):
+        """The batches of ``submit_raw`` in sliding mode.  A frame may lie in several sub-segments, so nothing is scattered: the
+        utterance's voiced-row list goes up where the destination rows go otherwise (4 bytes per frame), and every batch gathers its
+        rows with its chunk table.  ``voiced``: the flags of the utterances ``cand`` back to back (None: every frame)."""
+        torch, model = self.model.torch, self.model
+        dev, F, lib, n = model.device, model.feat_dim, _host_lib(), len(T)
+        order, bounds, (c_utt, c_start, c_len, seg_start) = handle["order"], win["bounds"], win["table"]
+        # every utterance's list of voiced frames, back to back in utterance order: u's is vrow[voff[u] : voff[u] + V[u]]
+        voff = np.cumsum(V) - V
+        if voiced is None:
+            vrow = np.arange(int(V.sum()), dtype=np.int64) - np.repeat(voff, V)
+        else:
+            fstart = np.zeros(n, dtype=np.int64)                     # where the utterance's flags start in `voiced`
+            fstart[cand] = np.cumsum(T[cand]) - T[cand]
+            vrow = np.flatnonzero(voiced) - np.repeat(fstart, V)
+        at = voff[c_utt] + c_start
+        chunk_spans = np.stack([vrow[at], vrow[at + c_len - 1] + 1], axis=1).astype(np.int32)      # RAW frames: first, one past the last
+        spans = [(int(np.searchsorted(seg_start, b0, side="right")) - 1, int(np.searchsorted(seg_start, b1, side="left")))
+                 for b0, b1, _ in bounds]
+        self._raw_staging(max(int(T[order[lo:hi]].sum()) for lo, hi in spans), max(hi - lo for lo, hi in spans), F)
+        self._sub_staging(max(hi - lo for lo, hi in spans), max(b1 - b0 for b0, b1, _ in bounds))
+        with torch.cuda.device(dev):
+            for bi, ((b0, b1, _), (lo, hi)) in enumerate(zip(bounds, spans)):
+                layout = BatchLayout(c_len[b0:b1], model.gap, model.align)
+                U = order[lo:hi]
+                Tb, Vb = T[U], V[U]
+                nU, nb, rows_in = len(U), b1 - b0, int(Tb.sum())
+                ustart = np.zeros(nU, dtype=np.int64)
+                np.cumsum(Tb[:-1], out=ustart[1:])
+                st, ss, sx = self._take(self._raw_stage, self._sub_stage, self._stage)
+                src_b, len_b, start_b = addrs[U], Tb.astype(np.int32), ustart.astype(np.int32)      # (kept alive across the call)
+                rc = lib.xv_pack_rows_f32(src_b.ctypes.data, len_b.ctypes.data, start_b.ctypes.data, nU, F,
+                                          st["raw"].numpy().ctypes.data, F, rows_in, None, self.PACK_THREADS)
+                assert rc == 0, "xv_pack_rows_f32 rejected the raw layout"
+                # voiced_row of the batch's utterances, each list at its utterance's first raw row (the entries behind a list are
+                # never read: the kernel stops at the voiced count)
+                within = np.arange(int(Vb.sum()), dtype=np.int64) - np.repeat(np.cumsum(Vb) - Vb, Vb)
+                st["dst"].numpy()[np.repeat(ustart, Vb) + within] = vrow[np.repeat(voff[U], Vb) + within]
+                um = ss["utt"].numpy()
+                um[0, :nU], um[1, :nU], um[2, :nU] = ustart, Tb, Vb
+                tb = ss["tab"].numpy()
+                tb[0, :nb] = np.searchsorted(seg_start, np.arange(b0, b1), side="right") - 1 - lo      # utterance within the batch
+                tb[1, :nb], tb[2, :nb], tb[3, :nb] = c_start[b0:b1], c_len[b0:b1], layout.row_start
+                layout.row_valid(sx["rv"].numpy())
+
+                def gather(raw_d, vrow_d, utt_d, tab_d, layout=layout):
+                    x = torch.zeros((layout.rows, model.in_dim), dtype=torch.float32, device=dev)      # gap rows and padding columns
+                    hiplib.cmn_sliding_gather(raw_d, utt_d[0], utt_d[1], utt_d[2], vrow_d, tab_d[0], tab_d[1], tab_d[2], tab_d[3],
+                                              layout.max_len, cmn_window, center, min_window, x)
+                    return x
+                st["event"] = ss["event"] = sx["event"] = self._launch(
+                    handle, win, bi, layout, sx, [st["raw"][:rows_in], st["dst"][:rows_in], ss["utt"][:, :nU], ss["tab"][:, :nb]], gather)
+            self._window_tail(handle, win["compute"], win["P_all"], win["E_all"], seg_start, c_len, win["status"], win["keep"], mats, redo,
+                              chunk_spans)
+
+    def _submit_device_subsegments(self, handle, win, feats, vad, start, span_d, count_d, vrow_d, cmn_window, center, min_window, redo):
+        """The batches of ``submit_device_raw`` in sliding mode: per batch the chunk table goes up and xv_cmn_sliding_gather_f32 reads
+        ``feats`` where they lie.  ``span_d``: (first row, frames) of every utterance on the device; ``count_d`` / ``vrow_d``:
+        xv_vad_compact_i32's results (None without a VAD).  The spans are gathered from ``vrow_d`` and come down with the vectors."""
+        torch, model = self.model.torch, self.model
+        dev = model.device
+        bounds, (c_utt, c_start, c_len, seg_start) = win["bounds"], win["table"]
+        nch = handle["nch"]
+        self._sub_staging(0, max(b1 - b0 for b0, b1, _ in bounds))
+        with torch.cuda.device(dev):
+            for bi, (b0, b1, _) in enumerate(bounds):
+                layout = BatchLayout(c_len[b0:b1], model.gap, model.align)
+                nb = b1 - b0
+                ss, sx = self._take(self._sub_stage, self._stage)
+                tb = ss["tab"].numpy()
+                tb[0, :nb], tb[1, :nb], tb[2, :nb], tb[3, :nb] = c_utt[b0:b1], c_start[b0:b1], c_len[b0:b1], layout.row_start
+                layout.row_valid(sx["rv"].numpy())
+
+                def gather(tab_d, layout=layout):
+                    x = torch.zeros((layout.rows, model.in_dim), dtype=torch.float32, device=dev)      # gap rows and padding columns
+                    hiplib.cmn_sliding_gather(feats, span_d[0], span_d[1], count_d, vrow_d, tab_d[0], tab_d[1], tab_d[2], tab_d[3],
+                                              layout.max_len, cmn_window, center, min_window, x)
+                    return x
+                ss["event"] = sx["event"] = self._launch(handle, win, bi, layout, sx, [ss["tab"][:, :nb]], gather)
+            if vrow_d is None:
+                chunk_spans = np.stack([c_start, c_start + c_len], axis=1).astype(np.int32)
+            else:
+                at = start[c_utt] + c_start
+                idx_flat, idx = self._pinned("span_idx", (2, nch), torch.int64)
+                idx.numpy()[0], idx.numpy()[1] = at, at + c_len - 1
+                (idx_d,), _ = self._upload(win["compute"], idx)
+                sp_d = torch.stack([vrow_d[idx_d[0]], vrow_d[idx_d[1]] + 1], dim=1)
+                span_flat, chunk_spans = self._pinned("spans", (nch, 2), torch.int32)
+                chunk_spans.copy_(sp_d, non_blocking=True)
+                handle["span_flat"] = span_flat
+                win["keep"].append((idx, idx_d, sp_d, idx_flat))
+            win["keep"].append((feats, vad, span_d, count_d, vrow_d))
+            self._window_tail(handle, win["compute"], win["P_all"], win["E_all"], seg_start, c_len, win["status"], win["keep"], None, redo,
+                              chunk_spans)
+
     def _plan_staging(self, nutts, nchunks):
         """NBUF pinned sets for submit_device_raw: the per-utterance tables int32[5, utts] and the chunks' first rows int32[chunks]."""
         torch = self.model.torch
@@ -1402,12 +1600,50 @@ class Extractor(object):
         """The pinned chunk table and x-vector buffer of a window go round again (nobody may still hold rows of ``host``)."""
         pinned = handle.pop("pinned", None)
         if pinned is not None:
-            self._unpin("tail", pinned[0])
+            if pinned[0] is not None:
+                self._unpin("tail", pinned[0])
             self._unpin("xvec", pinned[1])
+        span_flat = handle.pop("span_flat", None)
+        if span_flat is not None:
+            self._unpin("spans", span_flat)
+
+    def _finish_subsegments(self, handle, host_out, as_array):
+        """``finish`` in sliding mode, behind the wait: the rows of the window's chunk table back in input order."""
+        n, E = handle["n"], self.model.embed_dim
+        counts = np.zeros(n, dtype=np.int64)
+        nch = handle["nch"]
+        if nch:
+            order, seg = handle["order"], handle["seg_start"]
+            counts[order] = np.diff(seg)
+            spans = handle["spans"]
+            spans = spans if isinstance(spans, np.ndarray) else spans.numpy()
+        if as_array:
+            offsets = np.zeros(n + 1, dtype=np.int64)
+            np.cumsum(counts, out=offsets[1:])
+            if not nch:
+                return np.zeros((0, E), np.float32), np.zeros((0, 2), np.int32), offsets
+            ko = np.argsort(order, kind="stable")                     # the plan's utterances in input order
+            src = np.repeat(seg[:-1][ko] - offsets[:-1][order[ko]], np.diff(seg)[ko]) + np.arange(nch, dtype=np.int64)
+            vecs, sp = host_out[src], np.ascontiguousarray(spans[src], dtype=np.int32)
+            self._release(handle)                                     # the vectors and spans were copied out
+            return vecs, sp, offsets
+        results = [None] * n
+        if nch:
+            # (no ``_release``: the rows handed out alias the pinned buffer)
+            sp = np.array(spans, dtype=np.int32)
+            for k, u in enumerate(order.tolist()):
+                results[u] = (host_out[seg[k]:seg[k + 1]], sp[seg[k]:seg[k + 1]])
+        return results
 
     def finish(self, handle, as_array=False):
         """Wait for a submitted window and return its x-vectors in input order: a list with None for rejected utterances,
-        or with ``as_array`` the pair (float32 [n, E] array, bool [n] mask of the utterances that produced a vector)."""
+        or with ``as_array`` the pair (float32 [n, E] array, bool [n] mask of the utterances that produced a vector).
+
+        Sliding mode (``window`` given): per input utterance None (rejected) or ``(vectors float32 [n_k, E], spans int32
+        [n_k, 2])``, ``spans[k] = (first, end)`` with end exclusive -- rows of the input matrix on the table route, RAW frame
+        indices on the raw routes (the sub-segment's first voiced frame and one past its last).  With ``as_array`` the triple
+        ``(vectors float32 [M, E], spans int32 [M, 2], offsets int64 [n + 1])``: the M sub-segments of the window in input order,
+        those of utterance i in rows ``offsets[i]:offsets[i + 1]`` (none for a rejected one)."""
         owner = handle.get("owner")
         if owner is not None and owner is not self:
             return owner.finish(handle, as_array)             # a window of a demoted extractor: it ran on the twin
@@ -1433,6 +1669,8 @@ class Extractor(object):
                 handle.pop("redo", None)
             host_out = handle["host"].numpy()
             handle["keep"] = None
+        if self.window is not None:
+            return self._finish_subsegments(handle, host_out if handle["nch"] else None, as_array)
         if as_array:
             full = np.zeros((n, self.model.embed_dim), dtype=np.float32)
             valid = np.zeros(n, dtype=bool)

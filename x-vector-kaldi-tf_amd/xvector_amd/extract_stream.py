@@ -279,13 +279,28 @@ class WaveTable(object):
         return self._engine.compute_device(batch.keys, batch.waves)
 
 
+def subsegment_key(utt, first, end):
+    """The key of the x-vector of frames [first, end) of ``utt`` (sliding mode): fixed-width numbers, so that the keys of an
+    utterance sort in the order of their first frames."""
+    return "%s-%08d-%08d" % (utt, first, end)
+
+
+def subsegment_line(key, utt, first, end, frame_shift):
+    """One line of the subsegments file, the layout of a Kaldi ``segments`` file: ``<key> <utt> <start s> <end s>``;
+    ``frame_shift`` in milliseconds."""
+    return "%s %s %.3f %.3f\n" % (key, utt, first * frame_shift / 1000.0, end * frame_shift / 1000.0)
+
+
 class VectorWriter(object):
     """A writer thread serialises the records of finished windows (same bytes as write_vec_flt per key), in order, so that
     formatting ~50 k records per window does not sit between two kernel launches (bounded queue: 4 windows).  After an error
     it keeps draining, so that the producer never blocks; ``check`` re-raises the error in the caller."""
 
-    def __init__(self, output_stream):
+    def __init__(self, output_stream, subsegments=None, frame_shift=10.0):
+        """subsegments (sliding mode): a text stream that gets one line per vector whose ``put`` names its sub-segment, in the
+        layout of a Kaldi ``segments`` file; ``frame_shift`` in milliseconds turns frame indices into seconds."""
         self._out, self._q, self.error = output_stream, queue.Queue(maxsize=4), None
+        self._sub, self._shift = subsegments, float(frame_shift)
         self._thread = threading.Thread(target=self._run, daemon=True)
         self._thread.start()
 
@@ -299,11 +314,15 @@ class VectorWriter(object):
                 continue
             try:
                 kaldi_io.write_vec_flt_batch(self._out, item[0], item[1])
+                if self._sub is not None and item[2] is not None:
+                    self._sub.write("".join(subsegment_line(k, u, f, e, self._shift) for k, u, (f, e) in
+                                            zip(item[0], item[2][0], item[2][1].tolist())))
             except BaseException as e:          # noqa: B902 -- forwarded to the caller
                 self.error = e
 
-    def put(self, keys, vecs):
-        self._q.put((keys, vecs))
+    def put(self, keys, vecs, subsegments=None):
+        """subsegments: None, or (utterance key per vector, spans int [n, 2]) for the subsegments file."""
+        self._q.put((keys, vecs, subsegments))
 
     def check(self):
         if self.error is not None:
@@ -325,9 +344,31 @@ class Extraction(object):
         self.total_segments = self.num_fail = self.num_success = 0
         self.compute_time = 0.0
         self.stash = []
+        # sliding mode (the extractor has a ``window``): one vector per sub-segment, keys expanded by ``emit_subsegments``
+        self.sliding = getattr(ex, "window", None) is not None
+        self.num_vectors = 0
 
-    def _finish(self, handle, keep=None, shards=None):
+    def _finish_subsegments(self, handle, keep, voiced_rows):
+        """Sliding mode: (vectors, spans, offsets) of the utterances ``keep`` (None: all) -- ``Extractor.finish(as_array=True)``.
+        ``voiced_rows`` (the host front-end in front of the table route): per utterance None or its voiced frames, through
+        which spans counted in selected rows become RAW frame indices, as on the raw routes."""
+        vecs, spans, off = self.ex.finish(handle, as_array=True)
+        if keep is not None:
+            counts = np.diff(off)[keep]
+            src = np.repeat(off[:-1][keep] - (np.cumsum(counts) - counts), counts) + np.arange(int(counts.sum()), dtype=np.int64)
+            vecs, spans = vecs[src], spans[src]
+            off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        if voiced_rows is not None:
+            for i, rows in enumerate(voiced_rows):
+                if rows is not None and off[i + 1] > off[i]:
+                    sp = spans[off[i]:off[i + 1]]
+                    spans[off[i]:off[i + 1]] = np.stack([rows[sp[:, 0]], rows[sp[:, 1] - 1] + 1], axis=1)
+        return vecs, spans, off
+
+    def _finish(self, handle, keep=None, shards=None, voiced_rows=None):
         """The vectors of a submitted window: (vectors, valid) of the utterances ``keep`` (None: all), or this rank's share."""
+        if self.sliding:
+            return self._finish_subsegments(handle, keep, voiced_rows)
         full, valid = self.ex.finish(handle, as_array=True)
         if shards is not None:
             return "shard", shards, full
@@ -372,15 +413,21 @@ class Extraction(object):
                 keys, lens = [keys[i] for i in keep.tolist()], lens[keep]
             result = functools.partial(self._finish, handle, keep)
         else:
+            voiced_rows = None
             if front is not None:
                 kept = []
-                for key, m in zip(keys, front.apply(mats, vads)):
+                for i, (key, m) in enumerate(zip(keys, front.apply(mats, vads))):
                     if m is None:      # select-voiced-frames: VAD length mismatch or no voiced frame -> nothing written
                         self._warn_unvoiced(key)
                     else:
-                        kept.append((key, m))
-                keys, mats, addrs = [k for k, _ in kept], [m for _, m in kept], None
+                        kept.append((key, m, i))
+                if self.sliding and vads is not None:
+                    # the spans of the table route count selected rows: the voiced frames they stand for (see _finish_subsegments)
+                    voiced_rows = [None if vads[i] is None else np.flatnonzero(np.asarray(vads[i]).reshape(-1) != 0) for _, _, i in kept]
+                keys, mats, addrs = [k for k, _, _ in kept], [m for _, m, _ in kept], None
             result = self.submit_window(mats, addrs)
+            if voiced_rows is not None:
+                result = functools.partial(result.func, *result.args, voiced_rows=voiced_rows)
             lens = mats.lengths if hasattr(mats, "lengths") else np.fromiter((m.shape[0] for m in mats), dtype=np.int64, count=len(mats))
         self.compute_time += time.time() - t0
         return keys, lens, result
@@ -398,6 +445,8 @@ class Extraction(object):
         t0 = time.time()
         out = result()
         self.compute_time += time.time() - t0
+        if self.sliding:
+            return self.emit_subsegments(keys, lens, *out)
         if len(out) == 3:                     # multi-GPU: this rank's share of the window; exchanged once, at the end
             self.stash.append((keys, lens, out[1], out[2]))
             # XVECTOR_EXCHANGE_WINDOWS=N (default 0 = the single gather at the very end): exchange -- and let rank 0 write --
@@ -415,16 +464,32 @@ class Extraction(object):
         self.model._exchange_shards(self.stash, self.rank, self.world, self.min_chunk_size, self.chunk_size, self.emit)
         del self.stash[:]
 
+    def _warn_rejected(self, keys, lens, valid):
+        for i in np.flatnonzero(~valid).tolist():
+            if lens[i] == 0:
+                self.logger.warning("Zero-length utterance: '%s'" % keys[i])
+            else:
+                self.logger.warning("Minimum chunk size of %d is greater than the number of rows in utterance: %s" %
+                                    (self.min_chunk_size, keys[i]))
+        self.num_fail += int((~valid).sum())
+
+    def emit_subsegments(self, keys, lens, vecs, spans, offsets):
+        """``emit`` in sliding mode: the same warnings; sub-segment k of ``<utt>`` goes out under ``subsegment_key(utt, first, end)``
+        of its span (strictly increasing ``first`` within an utterance: unique and sorted), with its line of the subsegments file."""
+        counts = np.diff(offsets)
+        valid = counts > 0
+        if not valid.all():
+            self._warn_rejected(keys, lens, valid)
+        utts = [k for k, c in zip(keys, counts.tolist()) for _ in range(c)]
+        out_keys = [subsegment_key(u, f, e) for u, (f, e) in zip(utts, spans.tolist())]
+        self.writer.put(out_keys, vecs, (utts, spans))
+        self.num_success += int(valid.sum())
+        self.num_vectors += len(out_keys)
+
     def emit(self, keys, lens, vecs, valid):
         """Warn about rejected utterances, hand the rest to the writer thread."""
         if not valid.all():
-            for i in np.flatnonzero(~valid).tolist():
-                if lens[i] == 0:
-                    self.logger.warning("Zero-length utterance: '%s'" % keys[i])
-                else:
-                    self.logger.warning("Minimum chunk size of %d is greater than the number of rows in utterance: %s" %
-                                        (self.min_chunk_size, keys[i]))
-            self.num_fail += int((~valid).sum())
+            self._warn_rejected(keys, lens, valid)
             keys = [k for k, ok in zip(keys, valid.tolist()) if ok]
             vecs = vecs[valid]
         self.writer.put(keys, vecs)             # written by the writer thread, in order

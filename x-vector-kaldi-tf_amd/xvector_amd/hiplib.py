@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -152,6 +152,9 @@ _SIGNATURES = {
     "xv_resample_f32": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     # SPHERE audio (G.711, big-endian PCM) decoded in front of the MFCC kernel
     "xv_wave_decode": (_ci, [_vp, _i64, _vp, _ci, _vp, _i64, _vp, _ci, _vp]),
+    # sliding-window extraction: the packed rows of overlapping sub-segments
+    "xv_cmn_sliding_gather_f32": (_ci, [_vp, _ci, _ci, _i64, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp,
+                                        _ci, _i64, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)      # tests check the header declares exactly these and the .so exports all of them
 
@@ -1136,6 +1139,28 @@ def cmn_sliding_scatter(x, utt_start, utt_len, n_utts, max_len, cmn_window, cent
                                           _dev(utt_len, i32, "utt_len", n_utts), int(n_utts), int(max_len), int(cmn_window),
                                           1 if center else 0, int(min_window), _dev(dst_row, i32, "dst_row", x.shape[0]), _ptr(y),
                                           y.stride(0), _stream()), "xv_cmn_sliding_scatter_f32")
+
+
+def cmn_sliding_gather(x, utt_start, utt_len, voiced_count, voiced_row, chunk_utt, chunk_first, chunk_len, chunk_row, max_chunk_len,
+                       cmn_window, center, min_window, y):
+    """xv_cmn_sliding_gather_f32: raw rows x[x_rows, F] (cuda float32, row stride >= F) -> rows of y[y_rows, >= F] (cuda float32): chunk
+    c = chunk_len[c] voiced frames of utterance chunk_utt[c] from voiced frame chunk_first[c] on, normalised (sliding-window CMN over
+    the RAW frames) and written to rows chunk_row[c] .. of y.  All tables cuda int32; voiced_count / voiced_row are vad_compact's, or
+    both None when every frame is voiced.  The kernel checks every row against x, the voiced counts and y (see include/xvector_hip.h)."""
+    import torch
+    lib = require_gpu()
+    _f32_rows(x, "x"); _f32_rows(y, "y")
+    i32 = torch.int32
+    n_utts, n_chunks = utt_start.numel(), chunk_utt.numel()
+    assert (voiced_count is None) == (voiced_row is None), "voiced_count and voiced_row go together"
+    _check(lib.xv_cmn_sliding_gather_f32(_ptr(x), x.stride(0), x.shape[1], x.shape[0], _dev(utt_start, i32, "utt_start"),
+                                         _dev(utt_len, i32, "utt_len", n_utts), n_utts,
+                                         None if voiced_count is None else _dev(voiced_count, i32, "voiced_count", n_utts),
+                                         None if voiced_row is None else _dev(voiced_row, i32, "voiced_row", x.shape[0]),
+                                         _dev(chunk_utt, i32, "chunk_utt"), _dev(chunk_first, i32, "chunk_first", n_chunks),
+                                         _dev(chunk_len, i32, "chunk_len", n_chunks), _dev(chunk_row, i32, "chunk_row", n_chunks),
+                                         n_chunks, int(max_chunk_len), int(cmn_window), 1 if center else 0, int(min_window), _ptr(y),
+                                         y.stride(0), y.shape[0], _stream()), "xv_cmn_sliding_gather_f32")
 
 
 def vad_compact(vad, utt_start, utt_len):
