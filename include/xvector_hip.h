@@ -52,7 +52,7 @@ extern "C" {
 #define XV_ERR_BAD_ARG (-1)
 #define XV_ERR_UNSUPPORTED (-2)
 
-/* Library / ABI version (increments whenever an entry point is added or changed; currently 37). */
+/* Library / ABI version (increments whenever an entry point is added or changed; currently 38). */
 int xv_version(void);
 /* Thread-local description of the last non-zero return. */
 const char *xv_last_error(void);
@@ -556,6 +556,19 @@ int xv_cmn_sliding_scatter_f32(const float *x, int ldx, int feat_dim, const int3
  *   of XV_BACKEND_KSTEP, <= 1024 (else XV_ERR_UNSUPPORTED).
  * xv_score_pairs_f32  scores[i] = the same expression for the trial (e_idx[i], t_idx[i]), as an fmaf chain k ascending from 0:
  *   bit-identical to the cell of xv_score_matrix_f32, whatever the other trials of the list.
+ * xv_score_blocks_f32  block-diagonal self-scoring of ragged groups of rows (diarization: every recording's sub-segments against
+ *   each other).  E, T [n_rows, ldk] and r [n_rows] (may be NULL) as for xv_score_matrix_f32.  Device tables:
+ *   grp_row0 [n_groups + 1] (int32 prefix sums: group g is rows [grp_row0[g], grp_row0[g + 1]), n_g >= 1 of them) and grp_score0
+ *   [n_groups] (int64 element offsets into scores, multiples of 4).  Group g's n_g x n_g matrix lies at scores + grp_score0[g] with
+ *   row stride ld_g = (n_g + 3) & ~3; its cell (i, j) = sum_k E[row0 + i, k] T[row0 + j, k] + r[row0 + i] holds the SAME BITS as the
+ *   cell xv_score_matrix_f32 writes for those two rows (one tile body serves both).  Columns [n_g, ld_g) and everything between
+ *   the blocks are not written.  max_n: an upper bound of every n_g (it sizes the grid: tiles x groups, workgroups past a group's
+ *   own tiles exit); scores_elems: the elements of scores.  One launch per 65535 groups, no synchronisation.
+ *   A group out of contract (n_g < 1, n_g > max_n, rows outside [0, n_rows), an offset that is negative or no multiple of 4, a
+ *   block of n_g * ld_g elements past scores_elems) is skipped whole: nothing is read or written for it, and the device word
+ *   *status receives 1.  The caller zeroes *status and reads it back with the results.
+ *   XV_ERR_BAD_ARG, nothing launched: a NULL pointer (r excepted), n_groups, max_n, n_rows or scores_elems below 1, kpad / ldk /
+ *   alignment as for xv_score_matrix_f32 (scores 16-byte aligned too), misaligned tables.  kpad > 1024: XV_ERR_UNSUPPORTED.
  * xv_topk_row_stats_f32  AS-norm cohort statistics: for each row i < n_rows of scores (row i = scores[i*ld .. i*ld + n_cols)),
  *   mean[i] and std[i] = the mean and the POPULATION standard deviation (divisor top_n) of the top_n largest values of the row,
  *   taken as a multiset (ties at the threshold are counted by multiplicity).  Exact selection: an MSB-first radix select on
@@ -574,6 +587,9 @@ int xv_backend_prepare_f32(const float *x, int64_t ldx, int n_rows, int dim_in, 
                            int64_t ldo, float *r, void *stream);
 int xv_score_matrix_f32(const float *e, const float *t, int64_t ldk, int kpad, int n_enrol, int n_test, const float *r,
                         float *scores, int64_t ld_scores, void *stream);
+int xv_score_blocks_f32(const float *e, const float *t, int64_t ldk, int kpad, int n_rows, const float *r, const int32_t *grp_row0,
+                        const int64_t *grp_score0, int n_groups, int max_n, float *scores, int64_t scores_elems, int32_t *status,
+                        void *stream);
 int xv_score_pairs_f32(const float *e, const float *t, int64_t ldk, int kpad, const int32_t *e_idx, const int32_t *t_idx,
                        int64_t n_trials, const float *r, float *scores, void *stream);
 int xv_topk_row_stats_f32(const float *scores, int64_t ld, int n_rows, int n_cols, int top_n, float *mean, float *std,
@@ -627,6 +643,39 @@ int xv_ahc_average_f64(const float *scores, int64_t ld, int n, double threshold,
                        int32_t *merge_b, double *merge_score, int32_t *n_merges, int32_t *labels, void *workspace,
                        size_t workspace_bytes, void *stream);
 size_t xv_ahc_average_workspace_bytes(int n);
+
+/* ---- diarization: one clustering problem per recording (csrc/xv_cluster.hip) ------------------------------
+ * xv_ahc_average_batch_f64  n_groups independent xv_ahc_average_f64 problems in ONE launch, one workgroup per group.  Per-group
+ *   inputs, all in device memory: grp_row0 [n_groups + 1] and grp_score0 [n_groups] as for xv_score_blocks_f32 (group g's score
+ *   block at scores + grp_score0[g], row stride (n_g + 3) & ~3, only its strict upper triangle is read); grp_ws0 [n_groups]
+ *   (int64 byte offsets into the workspace, multiples of 8, each slice xv_ahc_average_batch_workspace_bytes(n_g) bytes);
+ *   threshold [n_groups] (fp64); min_clusters [n_groups] (int32).
+ *   Semantics: those of xv_ahc_average_f64 above, word for word.  Group g's merges, merge scores, n_merges[g] and labels are
+ *     bit-identical to a single-problem call on its block; slot indices are local to the group.  They do not depend on the other
+ *     groups, the group's position in the batch, the workspace contents or what ran before.
+ *   Outputs need no tables of their own: merge_a, merge_b, merge_score have n_rows entries, group g owns
+ *     [grp_row0[g], grp_row0[g] + n_g - 1) and only the first n_merges[g] of those are written; labels [n_rows] holds group g's
+ *     labels at grp_row0[g] + i; n_merges [n_groups].
+ *   Structure: a group's init, first row caches, merges and labels all run inside its workgroup, between s_barriers; no
+ *     cooperative launch, no grid barrier, no workgroup waits on another, no floating-point atomics.  The merge loop is bounded
+ *     by construction (m < n_g - min_clusters), so non-finite scores cannot make it spin (their result is unspecified).  The call
+ *     enqueues one launch and does NOT synchronise.  Workgroups tend to start in group order (speed alone depends on it) and
+ *     a large group runs much longer than a small one: the CALLER puts large groups first, so that the longest do not start last.
+ *   XV_ERR_BAD_ARG, nothing launched: a NULL or misaligned pointer (scores 16 bytes; grp_score0, grp_ws0, threshold, merge_score
+ *     and the workspace 8; the rest 4), n_groups, n_rows or scores_elems below 1, max_n < 1, workspace_bytes of 0.
+ *     max_n > XV_AHC_BATCH_MAX_N: XV_ERR_UNSUPPORTED.
+ *   Device side: a group that breaks its contract (n_g outside [1, max_n], rows outside [0, n_rows), a score block as refused by
+ *     xv_score_blocks_f32, min_clusters outside [1, n_g], a NaN threshold, a workspace slice that is negative, misaligned or
+ *     ends past workspace_bytes) is skipped whole: nothing of it is read or written, and *status receives 1.  The caller zeroes
+ *     *status and reads it back with the results.
+ * xv_ahc_average_batch_workspace_bytes  the bytes of ONE group's slice, 8 n^2 + 24 n + 64 (0 for n outside
+ *   [1, XV_AHC_BATCH_MAX_N]). */
+#define XV_AHC_BATCH_MAX_N 4096
+int xv_ahc_average_batch_f64(const float *scores, int64_t scores_elems, const int32_t *grp_row0, const int64_t *grp_score0,
+                             const int64_t *grp_ws0, const double *threshold, const int32_t *min_clusters, int n_groups, int max_n,
+                             int n_rows, int32_t *merge_a, int32_t *merge_b, double *merge_score, int32_t *n_merges, int32_t *labels,
+                             int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+size_t xv_ahc_average_batch_workspace_bytes(int n);
 
 /* Stage 1 of the recipe: MFCC features and the energy VAD (compute-mfcc-feats / compute-vad; csrc/xv_mfcc.hip).
  * xv_mfcc_f32  MFCC rows of n_utts utterances in one launch.  samples: every utterance's samples back to back, int16

@@ -6,11 +6,13 @@
 // The PLDA log-likelihood ratio of Kaldi's Plda::LogLikelihoodRatio is one dot product of length K = 2d plus a per-enrolment
 // constant:
 //     enrolment row [ (a/v) z , 1/v - 1/w ]    test row [ t , -t^2/2 ]    r_e = -1/2 sum a^2 z^2 / v + 1/2 sum (log w - log v)
-// with a = n psi / (n psi + 1), v = 1 + psi / (n psi + 1), w = 1 + psi.  Four kernels:
+// with a = n psi / (n psi + 1), v = 1 + psi / (n psi + 1), w = 1 + psi.  Five kernels:
 //   backend_prepare_kernel   x -> operand rows: (x - mu), LDA, length norm, PLDA transform, PLDA length norm, side packing.
 //                            32 rows per workgroup; both products on v_mfma_f32_32x32x2_f32 (exact fp32), the rows stay in LDS
 //                            between the two products and the two norms.
 //   score_matrix_kernel      S = E T^T + r on v_mfma_f32_32x32x2_f32, 128 x 128 tiles, one accumulator per score, k ascending.
+//   score_blocks_kernel      the same tile body (score_tile) over ragged groups of rows: each group against itself, every
+//                            group's matrix from one launch (diarization).
 //   score_pairs_kernel       one trial per thread: an fmaf chain over k ascending from 0, then + r.
 //   topk_row_stats_kernel    AS-norm cohort statistics: mean and population std of the top-N scores of each row, by an exact
 //                            MSB-first radix select on order-preserving keys (rows of <= 32768 columns staged in LDS), fp64 sums.
@@ -215,16 +217,15 @@ constexpr int SM_UNITS = (SM_BM + SM_BN) * (SM_BK / 8) / SM_NT;     // 8-float p
 
 // LDS image of 8 consecutive k of one row: [k0 k2 k4 k6 | k1 k3 k5 k7], so that a lane of half h reads ONE f32x4 at
 // 8 kk + 4 h and finds k = 8 kk + 2 s + h in element s: the MFMA of step s then sums k = 2s (lanes 0-31) and 2s + 1 (32-63).
-__global__ __launch_bounds__(SM_NT, 2) void score_matrix_kernel(const float *__restrict__ E, const float *__restrict__ T, int ldk,
-                                                                int kpad, int Ne, int Nt, const float *__restrict__ r,
-                                                                float *__restrict__ S, long lds)
+// The tile body of both dense kernels: the 128 x 128 tile at (e0, t0) of S = E T^T + r.  smem: (SM_BM + SM_BN) * SM_LDK floats.
+__device__ __forceinline__ void score_tile(const float *__restrict__ E, const float *__restrict__ T, int ldk, int kpad, int Ne, int Nt,
+                                           const float *__restrict__ r, float *__restrict__ S, long lds, long e0, long t0,
+                                           f32x4 *smem)
 {
-    __shared__ f32x4 smem[(SM_BM + SM_BN) * SM_LDK / 4];
     float *As = reinterpret_cast<float *>(smem);
     float *Bs = As + SM_BM * SM_LDK;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wr = wave >> 1, wc = wave & 1;
-    const long e0 = (long)blockIdx.y * SM_BM, t0 = (long)blockIdx.x * SM_BN;
 
     f32x4 reg[SM_UNITS][2];
     auto load = [&](int k0) {
@@ -298,6 +299,40 @@ __global__ __launch_bounds__(SM_NT, 2) void score_matrix_kernel(const float *__r
     put(acc01, 0, 1);
     put(acc10, 1, 0);
     put(acc11, 1, 1);
+}
+
+__global__ __launch_bounds__(SM_NT, 2) void score_matrix_kernel(const float *__restrict__ E, const float *__restrict__ T, int ldk,
+                                                                int kpad, int Ne, int Nt, const float *__restrict__ r,
+                                                                float *__restrict__ S, long lds)
+{
+    __shared__ f32x4 smem[(SM_BM + SM_BN) * SM_LDK / 4];
+    score_tile(E, T, ldk, kpad, Ne, Nt, r, S, lds, (long)blockIdx.y * SM_BM, (long)blockIdx.x * SM_BN, smem);
+}
+
+// Block-diagonal self-scoring of ragged groups: workgroup (tile, group).  Group g = g0 + blockIdx.y is rows
+// [grp_row0[g], grp_row0[g + 1]) of E, T and r; its n x n matrix goes to S + grp_score0[g] with row stride (n + 3) & ~3.  A tile
+// past the group's own tiles exits; a group that breaks the contract of xv_score_blocks_f32 is skipped whole (nothing of it is read
+// or written) and *status = 1.  Every test below is uniform over the workgroup.
+__global__ __launch_bounds__(SM_NT, 2) void score_blocks_kernel(const float *__restrict__ E, const float *__restrict__ T, int ldk,
+                                                                int kpad, int n_rows, const float *__restrict__ r,
+                                                                const int32_t *__restrict__ grp_row0,
+                                                                const int64_t *__restrict__ grp_score0, int g0, int max_n,
+                                                                float *__restrict__ S, long scores_elems, int32_t *status)
+{
+    __shared__ f32x4 smem[(SM_BM + SM_BN) * SM_LDK / 4];
+    const int g = g0 + blockIdx.y;
+    const long row0 = grp_row0[g], n = (long)grp_row0[g + 1] - row0;
+    const long off = grp_score0[g], ld = (n + 3) & ~3L;
+    if (n < 1 || n > max_n || row0 < 0 || row0 + n > n_rows || off < 0 || (off & 3) || off > scores_elems ||
+        n * ld > scores_elems - off) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) *status = 1;
+        return;
+    }
+    const int tiles = (int)((n + SM_BM - 1) / SM_BM);
+    if ((int)blockIdx.x >= tiles * tiles) return;
+    const int by = blockIdx.x / tiles, bx = blockIdx.x % tiles;
+    score_tile(E + row0 * ldk, T + row0 * ldk, ldk, kpad, (int)n, (int)n, r ? r + row0 : nullptr, S + off, ld, (long)by * SM_BM,
+               (long)bx * SM_BN, smem);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -500,6 +535,27 @@ extern "C" int xv_score_matrix_f32(const float *e, const float *t, int64_t ldk, 
     hipLaunchKernelGGL(score_matrix_kernel, dim3((n_test + SM_BN - 1) / SM_BN, (unsigned)gy), dim3(SM_NT), 0, (hipStream_t)stream, e, t,
                        (int)ldk, kpad, n_enrol, n_test, r, scores, (long)ld_scores);
     return launch_status("score_matrix_kernel");
+}
+
+extern "C" int xv_score_blocks_f32(const float *e, const float *t, int64_t ldk, int kpad, int n_rows, const float *r,
+                                   const int32_t *grp_row0, const int64_t *grp_score0, int n_groups, int max_n, float *scores,
+                                   int64_t scores_elems, int32_t *status, void *stream)
+{
+    if (!e || !t || !grp_row0 || !grp_score0 || !scores || !status || n_groups < 1 || max_n < 1 || n_rows < 1 || scores_elems < 1)
+        return fail(XV_ERR_BAD_ARG, "score_blocks: NULL pointer, or n_groups, max_n, n_rows or scores_elems below 1");
+    if (kpad <= 0 || kpad % KSTEP || ldk < kpad || ldk % 4 || (((uintptr_t)e | (uintptr_t)t | (uintptr_t)scores) & 15) ||
+        ((uintptr_t)grp_row0 & 3) || ((uintptr_t)grp_score0 & 7) || ((uintptr_t)status & 3))
+        return fail(XV_ERR_BAD_ARG, "score_blocks: bad argument");
+    if (kpad > 1024) return fail(XV_ERR_UNSUPPORTED, "score_blocks: K <= 1024 only");
+    const long tiles = ((long)max_n + SM_BM - 1) / SM_BM;
+    if (tiles * tiles > 0x7fffffffL) return fail(XV_ERR_UNSUPPORTED, "score_blocks: max_n too large for one launch");
+    for (int g0 = 0; g0 < n_groups; g0 += 65535) {                   // grid.y holds at most 65535 groups
+        const int ng = n_groups - g0 < 65535 ? n_groups - g0 : 65535;
+        hipLaunchKernelGGL(score_blocks_kernel, dim3((unsigned)(tiles * tiles), (unsigned)ng), dim3(SM_NT), 0, (hipStream_t)stream, e, t,
+                           (int)ldk, kpad, n_rows, r, grp_row0, grp_score0, g0, max_n, scores, (long)scores_elems, status);
+        if (const int rc = launch_status("score_blocks_kernel")) return rc;
+    }
+    return 0;
 }
 
 extern "C" int xv_score_pairs_f32(const float *e, const float *t, int64_t ldk, int kpad, const int32_t *e_idx, const int32_t *t_idx,

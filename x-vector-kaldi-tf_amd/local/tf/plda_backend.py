@@ -20,6 +20,13 @@
                against themselves and their average-linkage agglomerative clustering both run on the GPU; with --lda the
                vectors first go through stage 8's chain there, as in adapt-plda.  Writes one ``utt cluster`` line per vector.
                Turn utt2cluster into a spk2utt, fit an in-domain model with compute-plda --lda, mix it with interpolate-plda
+  diarize      ivector-plda-scoring-dense | agglomerative-cluster --reco2utt [--reco2num-spk] | diarization/make_rttm.py
+               (DESIGN.md §8.15): [--mean mean.vec] [--lda transform.mat] [--threshold t] [--reco2num-spk FILE] [--rttm OUT.rttm]
+               [--rttm-channel c] plda <vectors> <segments> <labels-out>.  <segments> is what extract_embedding.py
+               --subsegments-file writes (``key reco start end``; any Kaldi segments file).  The vectors are grouped by recording;
+               every recording's PLDA score matrix comes from one launch and every recording's average-linkage clustering runs in
+               a workgroup of its own, all at once.  Writes ``key label`` lines (labels 1..K per recording) and, with --rttm, the
+               speaker turns
   interpolate-plda   [--alpha a] plda_out plda_in plda: (1 - a) plda_out + a plda_in on the models' covariances and means (host)
   compute-eer  compute-eer <file of "score target|nontarget" lines, or ->   (prints the EER in percent)
 
@@ -201,6 +208,157 @@ def cmd_cluster(args):
                 (n, dim, len(distinct), int((counts == 1).sum())))
 
 
+def parse_ms(tok):
+    """A time in seconds -> integer milliseconds."""
+    return int(round(1000 * float(tok)))
+
+
+def read_segments(path):
+    """A Kaldi segments file -> [(key, reco, start ms, end ms)] in file order.  SystemExit on a malformed line, a repeated key or
+    end < start."""
+    out, seen = [], set()
+    with open(path, "rt") as f:
+        for ln, line in enumerate(f, 1):
+            parts = line.split()
+            if not parts:
+                continue
+            if len(parts) < 4:
+                raise SystemExit("%s:%d: expected <key> <reco> <start> <end>, got %r" % (path, ln, line.strip()))
+            try:
+                t0, t1 = parse_ms(parts[2]), parse_ms(parts[3])
+            except (ValueError, OverflowError):
+                raise SystemExit("%s:%d: bad times %r %r" % (path, ln, parts[2], parts[3]))
+            if t1 < t0:
+                raise SystemExit("%s:%d: segment %s ends before it starts (%s < %s)" % (path, ln, parts[0], parts[3], parts[2]))
+            if parts[0] in seen:
+                raise SystemExit("%s:%d: key %s appears twice" % (path, ln, parts[0]))
+            seen.add(parts[0])
+            out.append((parts[0], parts[1], t0, t1))
+    return out
+
+
+def group_segments(segments, have):
+    """Group the segments that have a vector by recording: -> (recos, groups, n_missing).  recos: the recordings in order of first
+    appearance; groups[r]: the indices into ``segments`` of recording r's lines, in file order (they need not be contiguous);
+    n_missing: lines whose key is not in ``have``, which are skipped."""
+    recos, index, groups, missing = [], {}, [], 0
+    for i, (key, reco, _, _) in enumerate(segments):
+        if key not in have:
+            missing += 1
+            continue
+        if reco not in index:
+            index[reco] = len(recos)
+            recos.append(reco)
+            groups.append([])
+        groups[index[reco]].append(i)
+    return recos, groups, missing
+
+
+def number_labels(slots):
+    """Cluster slots of one recording's vectors, in the recording's order -> labels 1..K, the clusters numbered by their first
+    member (the kernel names a cluster by its first member, so this is the rank rule of ``cluster``, applied per recording)."""
+    number = {}
+    return [number.setdefault(s, len(number) + 1) for s in np.asarray(slots).tolist()]
+
+
+def rttm_text(recos, channel=0):
+    """The RTTM of recos = [(reco, [(start ms, end ms, key, label)])], the recordings in the given order.  Per recording: sort by
+    (start, end, key); where consecutive segments of different labels overlap, both meet at the midpoint (end + start) // 2;
+    consecutive segments of one label that touch or overlap merge (the end is the maximum); pieces of no length are dropped."""
+    lines = []
+    for reco, segs in recos:
+        segs = sorted(segs, key=lambda s: (s[0], s[1], s[2]))
+        start = [s[0] for s in segs]
+        end = [s[1] for s in segs]
+        label = [s[3] for s in segs]
+        for i in range(len(segs) - 1):
+            if label[i] != label[i + 1] and end[i] > start[i + 1]:
+                end[i] = start[i + 1] = (end[i] + start[i + 1]) // 2
+        pieces = []
+        for t0, t1, l in zip(start, end, label):
+            if pieces and pieces[-1][2] == l and t0 <= pieces[-1][1]:
+                pieces[-1][1] = max(pieces[-1][1], t1)
+            else:
+                pieces.append([t0, t1, l])
+        for t0, t1, l in pieces:
+            if t1 > t0:
+                lines.append("SPEAKER %s %d %7.3f %7.3f <NA> <NA> %s <NA> <NA>\n" % (reco, channel, t0 / 1000.0, (t1 - t0) / 1000.0, l))
+    return "".join(lines)
+
+
+def _write_renamed(path, text):
+    with open(path + ".tmp", "wt") as f:
+        f.write(text)
+    os.replace(path + ".tmp", path)
+
+
+def cmd_diarize(args):
+    from xvector_amd import backend, hiplib
+    if np.isnan(args.threshold):
+        raise SystemExit("--threshold must be a number, got %r" % args.threshold)
+    if args.rttm_channel < 0:
+        raise SystemExit("--rttm-channel must not be negative, got %d" % args.rttm_channel)
+    segments = read_segments(args.segments)
+    num_spk = {}
+    if args.reco2num_spk:
+        for reco, v in read_table(args.reco2num_spk).items():
+            try:
+                num_spk[reco] = int(v[0])
+            except (IndexError, ValueError):
+                raise SystemExit("%s: no speaker count for recording %s" % (args.reco2num_spk, reco))
+            if num_spk[reco] < 1:
+                raise SystemExit("%s: the speaker count of recording %s must be at least 1, got %d" %
+                                 (args.reco2num_spk, reco, num_spk[reco]))
+    hiplib.require_gpu()                                 # no CPU fallback: fail before reading the model or the vectors
+    plda = backend.read_plda(args.plda)
+    vectors = read_vectors(args.vectors)
+    if not vectors:
+        raise SystemExit("no vectors in %s: nothing to diarize, no labels written" % args.vectors)
+    recos, groups, missing = group_segments(segments, vectors)
+    listed = set(segments[i][0] for g in groups for i in g)
+    for k in vectors:
+        if k not in listed:
+            raise SystemExit("vector %s has no line in %s: no labels written" % (k, args.segments))
+    if missing:
+        logger.warning("%d segments of %s have no vector: skipped" % (missing, args.segments))
+    keys = [segments[i][0] for g in groups for i in g]
+    x = _stack(vectors, keys)
+    t = backend.read_transform(args.lda) if args.lda else None
+    if t is not None and t.shape[1] not in (x.shape[1], x.shape[1] + 1):
+        raise SystemExit("%s has %d columns, the vectors have dimension %d" % (args.lda, t.shape[1], x.shape[1]))
+    dim = x.shape[1] if t is None else t.shape[0]
+    if dim != plda.dim:
+        raise SystemExit("the vectors have dimension %d%s, the PLDA %d: no labels written" %
+                         (dim, " after the LDA" if t is not None else "", plda.dim))
+    mean = kaldi_io.read_vec_flt(args.mean).astype(np.float32) if args.mean else None
+    if mean is not None and mean.shape[0] != x.shape[1]:
+        raise SystemExit("%s has dimension %d, the vectors %d: no labels written" % (args.mean, mean.shape[0], x.shape[1]))
+    sizes = [len(g) for g in groups]
+    counts = None
+    if num_spk:
+        counts = [num_spk.get(r) for r in recos]
+        for r, n, k in zip(recos, sizes, counts):
+            if k is not None and k > n:
+                logger.warning("recording %s: %d speakers asked for, %d vectors: using %d" % (r, k, n, n))
+    try:
+        slots, _ = backend.diarize(x, sizes, plda, mean=mean, transform=t, threshold=args.threshold, num_spk=counts)
+    except ValueError as e:
+        raise SystemExit("%s: no labels written" % e)
+    label_of, by_reco, n_speakers, at = {}, [], 0, 0
+    for reco, g in zip(recos, groups):
+        labels = number_labels(slots[at:at + len(g)])
+        at += len(g)
+        n_speakers += max(labels)
+        by_reco.append((reco, [(segments[i][2], segments[i][3], segments[i][0], l) for i, l in zip(g, labels)]))
+        for i, l in zip(g, labels):
+            label_of[i] = l
+    _write_renamed(args.labels_out, "".join("%s %d\n" % (segments[i][0], label_of[i]) for i in sorted(label_of)))
+    if args.rttm:
+        _write_renamed(args.rttm, rttm_text(by_reco, args.rttm_channel))
+    logger.info("Diarized %d recordings: %d vectors of dimension %d into %d speakers (%d segments without a vector skipped)" %
+                (len(recos), len(keys), dim, n_speakers, missing))
+
+
 def cmd_interpolate_plda(args):
     from xvector_amd import backend
     if not (np.isfinite(args.alpha) and 0.0 <= args.alpha <= 1.0):
@@ -338,6 +496,15 @@ def main(argv=None):
     p.add_argument("--prefix", default="c", help="cluster names are <prefix><rank>")
     p.add_argument("plda"); p.add_argument("vectors"); p.add_argument("utt2cluster")
     p.set_defaults(fn=cmd_cluster)
+    p = sub.add_parser("diarize", help="per-recording PLDA scoring, average-linkage clustering and RTTM")
+    p.add_argument("--mean", help="mean.vec: subtract it first (ivector-subtract-global-mean)")
+    p.add_argument("--lda", help="transform.mat: transform-vec + ivector-normalize-length after the mean")
+    p.add_argument("--threshold", type=float, default=0.0, help="stop when no pair of clusters has an average score this large")
+    p.add_argument("--reco2num-spk", help="lines <reco> <count>: these recordings stop at exactly that many clusters")
+    p.add_argument("--rttm", help="write the speaker turns here")
+    p.add_argument("--rttm-channel", type=int, default=0)
+    p.add_argument("plda"); p.add_argument("vectors"); p.add_argument("segments"); p.add_argument("labels_out")
+    p.set_defaults(fn=cmd_diarize)
     p = sub.add_parser("interpolate-plda", help="a PLDA between two")
     p.add_argument("--alpha", type=float, default=0.5, help="weight of plda_in, in [0, 1]")
     p.add_argument("--binary", type=lambda s: s.lower() in ("true", "1"), default=True)

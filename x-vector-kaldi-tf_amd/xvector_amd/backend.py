@@ -6,6 +6,9 @@
   adapt_plda     ivector-adapt-plda: unsupervised adaptation of a Plda to those moments   (host, fp64)
   cluster_vectors / ahc   clustering-based adaptation: the N x N PLDA score matrix of unlabelled vectors and its
                  average-linkage agglomerative clustering, both on the device (xv_score_matrix_f32, xv_ahc_average_f64)
+  diarize / score_blocks / ahc_batch   diarization: one such problem per recording, all recordings' score
+                 blocks from one launch (xv_score_blocks_f32) and one workgroup per recording's dendrogram
+                 (xv_ahc_average_batch_f64)
   interpolate_plda   a Plda between two (the out-of-domain model and the one fitted on the clusters)   (host, fp64)
   read_plda / write_plda, read_transform / write_transform   Kaldi's <Plda> object and transform.mat, binary and text
   prepare        ivector-subtract-global-mean | transform-vec | ivector-normalize-length | Plda::TransformIvector on the GPU
@@ -530,6 +533,232 @@ def cluster_vectors(x, plda, mean=None, transform=None, threshold=0.0, num_clust
         raise ValueError("cluster_vectors: %d vectors exceed %d, the limit of xv_ahc_average_f64" % (n, hiplib.AHC_MAX_N))
     s = score_matrix_self(x, plda, mean, transform, device)
     return ahc(s[:, :n], threshold, num_clusters)
+
+
+# ------------------------------------------------------------------------------------------------
+# diarization: one small clustering problem per recording, all of them in one batch
+# ------------------------------------------------------------------------------------------------
+class GroupTables(object):
+    """The ragged-batch tables of xv_score_blocks_f32 / xv_ahc_average_batch_f64 for groups of ``sizes`` rows, in that order:
+    row0 int32 [G + 1] (prefix sums), ld int64 [G] (the row stride of a group's score block, its size rounded up to a multiple of
+    4), score0 int64 [G] (element offsets of the blocks, packed back to back) and scores_elems; row0_d / score0_d are their device
+    copies and status the device word both kernels report a skipped group in (zeroed here)."""
+
+    def __init__(self, sizes, device=None):
+        self.sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
+        if self.sizes.size < 1 or int(self.sizes.min()) < 1:
+            raise ValueError("every group needs at least one row, and there must be a group")
+        if int(self.sizes.sum()) > np.iinfo(np.int32).max:
+            raise ValueError("too many rows for int32 row offsets")
+        self.row0 = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int32)
+        self.ld = (self.sizes + 3) & ~3
+        elems = self.sizes * self.ld
+        self.score0 = np.concatenate([[0], np.cumsum(elems)[:-1]]).astype(np.int64)
+        self.scores_elems = int(elems.sum())
+        self.n_rows = int(self.row0[-1])
+        self.max_n = int(self.sizes.max())
+        self.row0_d = self.score0_d = self.status = None
+        if device is not None:
+            import torch
+            self.row0_d = torch.as_tensor(self.row0, device=device)
+            self.score0_d = torch.as_tensor(self.score0, device=device)
+            self.status = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def block(self, scores, g):
+        """Group g's [n, n] view of the packed scores (a device tensor or a host array)."""
+        n, ld, o = int(self.sizes[g]), int(self.ld[g]), int(self.score0[g])
+        return scores[o:o + n * ld].reshape(n, ld)[:, :n]
+
+
+def size_order(sizes):
+    """(order, inverse): order lists the groups by size, descending (equal sizes keep their order), as the device wants them --
+    workgroups tend to start in group order and the largest group runs longest (only speed depends on it); inverse[g] is the position of group g in order."""
+    order = np.argsort(-np.asarray(sizes, dtype=np.int64), kind="stable")
+    inverse = np.empty_like(order)
+    inverse[order] = np.arange(order.size)
+    return order, inverse
+
+
+def plan_ahc_batch(sizes, max_bytes=AHC_MAX_BYTES, max_batch_n=hiplib.AHC_BATCH_MAX_N):
+    """Cut the group list into calls of xv_ahc_average_batch_f64: -> (calls, routed).  calls: a list of (g_lo, g_hi, ws0, nbytes):
+    groups [g_lo, g_hi) in one call, ws0 int64 [g_hi - g_lo] their byte offsets into a workspace of nbytes <= max_bytes.  A call
+    is a run of consecutive groups, because a group's rows are found by a prefix-sum table.  routed: the groups above max_batch_n,
+    which go through the single-problem ``ahc`` on their block.  A group whose own workspace exceeds max_bytes is an error."""
+    max_batch_n = min(int(max_batch_n), hiplib.AHC_BATCH_MAX_N)
+    calls, routed = [], []
+    lo, offs, total = None, [], 0
+
+    def close(hi):
+        if lo is not None:
+            calls.append((lo, hi, np.asarray(offs, dtype=np.int64), total))
+
+    for g, n in enumerate(np.asarray(sizes, dtype=np.int64).tolist()):
+        if n > max_batch_n:
+            close(g)
+            lo, offs, total = None, [], 0
+            routed.append(g)
+            if hiplib.ahc_average_workspace_bytes(n) > max_bytes:
+                raise ValueError("ahc_batch: a group of %d items needs a workspace of more than max_bytes = %d" % (n, max_bytes))
+            continue
+        need = hiplib.ahc_average_batch_workspace_bytes(n)
+        if need > max_bytes:
+            raise ValueError("ahc_batch: a group of %d items needs a workspace of %d bytes, more than max_bytes = %d" %
+                             (n, need, max_bytes))
+        if lo is not None and total + need > max_bytes:
+            close(g)
+            lo, offs, total = None, [], 0
+        if lo is None:
+            lo = g
+        offs.append(total)
+        total += need
+    close(len(sizes))
+    return calls, routed
+
+
+def _nonfinite_upper(scores, tables):
+    """A device bool: does the strict upper triangle of any group's block hold a value that is not finite?  No host sync."""
+    import torch
+    dev = scores.device
+    n_d = torch.as_tensor(tables.sizes, device=dev)
+    ld_d = torch.as_tensor(tables.ld, device=dev)
+    bad = torch.zeros((), dtype=torch.bool, device=dev)
+    for lo in range(0, scores.numel(), _FINITE_CHECK_ELEMS):
+        chunk = scores[lo:lo + _FINITE_CHECK_ELEMS]
+        idx = torch.arange(lo, lo + chunk.numel(), device=dev)
+        g = torch.searchsorted(tables.score0_d, idx, right=True) - 1
+        inside = g >= 0
+        g = g.clamp_(min=0)
+        local = idx - tables.score0_d[g]
+        i, j = local // ld_d[g], local % ld_d[g]
+        upper = inside & (j > i) & (j < n_d[g]) & (i < n_d[g])
+        bad = bad | (upper & ~torch.isfinite(chunk)).any()
+    return bad
+
+
+def score_blocks(x, group_sizes, plda, mean=None, transform=None, device="cuda:0"):
+    """Every group's PLDA score matrix from one launch (xv_score_blocks_f32): x[N, D] raw vectors, group g the next
+    group_sizes[g] rows.  The chain is that of ``score_matrix_self`` (two prepare calls over all rows, one-utterance enrolments),
+    and a block holds the bits ``score_matrix_self`` gives that group's rows.  -> (scores, tables): the packed float32 device
+    blocks and their GroupTables; tables.status stays on the device (``ahc_batch`` downloads it with its results)."""
+    import torch
+    hiplib.require_gpu()
+    tables = GroupTables(group_sizes, device)
+    n = len(x)
+    if n != tables.n_rows:
+        raise ValueError("score_blocks: %d vectors, but the group sizes add up to %d" % (n, tables.n_rows))
+    ln = transform is not None
+    E, r = prepare(x, hiplib.SIDE_ENROL, np.ones(n, np.int32), mean, transform, plda, ln, device)
+    T, _ = prepare(x, hiplib.SIDE_TEST, None, mean, transform, plda, ln, device)
+    scores = torch.empty(tables.scores_elems, dtype=torch.float32, device=device)
+    hiplib.score_blocks(E, T, r, tables.row0_d, tables.score0_d, tables.max_n, scores, tables.status)
+    return scores, tables
+
+
+def ahc_batch(scores, tables, thresholds, min_clusters, max_bytes=AHC_MAX_BYTES, max_batch_n=hiplib.AHC_BATCH_MAX_N):
+    """Average-linkage clustering of every group's block of the packed ``scores`` (what ``score_blocks`` returns), one workgroup
+    per group (xv_ahc_average_batch_f64).  thresholds float [G] and min_clusters int [G] are each group's stop rule, as in
+    ``ahc``.  The group list is cut into calls whose workspaces fit max_bytes; a group above max_batch_n goes through ``ahc`` on
+    its block (identical results by the kernels' contract).  Put large groups first (``diarize`` does): workgroups start in group
+    order.  One download at the end: results, the kernels' status word and the finite check of the upper triangles.
+    -> (labels, merges): per group, in the given order, labels int32[n_g] (the local slot of each item's cluster) and
+    (a int32[M], b int32[M], score float64[M])."""
+    import torch
+    hiplib.require_gpu()
+    G = tables.sizes.size
+    thr = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+    minc = np.asarray(min_clusters, dtype=np.int64).reshape(-1)
+    if thr.size != G or minc.size != G:
+        raise ValueError("ahc_batch: %d groups, %d thresholds, %d min_clusters" % (G, thr.size, minc.size))
+    if np.isnan(thr).any():
+        raise ValueError("ahc_batch: a threshold is NaN")
+    if (minc < 1).any() or (minc > tables.sizes).any():
+        raise ValueError("ahc_batch: min_clusters must be in 1..n for every group")
+    if not (isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dim() == 1 and scores.dtype == torch.float32 and
+            scores.numel() >= tables.scores_elems):
+        raise ValueError("ahc_batch: scores must be the packed float32 device blocks of the tables")
+    calls, routed = plan_ahc_batch(tables.sizes, max_bytes, max_batch_n)
+    dev = scores.device
+    n_rows = tables.n_rows
+    with torch.cuda.device(dev):
+        nonfinite = _nonfinite_upper(scores, tables)
+        # a, b, labels, n_merges in one int32 buffer: one download
+        ints = torch.empty(3 * n_rows + G, dtype=torch.int32, device=dev)
+        m_a, m_b, lab, cnt = ints[:n_rows], ints[n_rows:2 * n_rows], ints[2 * n_rows:3 * n_rows], ints[3 * n_rows:]
+        m_s = torch.empty(n_rows, dtype=torch.float64, device=dev)
+        if calls:
+            ws = torch.empty(max(c[3] for c in calls), dtype=torch.uint8, device=dev)
+            ws0 = torch.as_tensor(np.concatenate([c[2] for c in calls]), device=dev)
+            thr_d = torch.as_tensor(thr, device=dev)
+            minc_d = torch.as_tensor(minc.astype(np.int32), device=dev)
+            at = 0
+            for lo, hi, _, _ in calls:
+                hiplib.ahc_average_batch(scores, tables.row0_d[lo:hi + 1], tables.score0_d[lo:hi], ws0[at:at + hi - lo], thr_d[lo:hi],
+                                         minc_d[lo:hi], int(tables.sizes[lo:hi].max()), m_a, m_b, m_s, cnt[lo:hi], lab, tables.status,
+                                         ws)
+                at += hi - lo
+        flags = torch.cat([tables.status.to(torch.int32), nonfinite.to(torch.int32).reshape(1)])
+        ints_h, m_s_h, flags_h = ints.cpu().numpy(), m_s.cpu().numpy(), flags.cpu().numpy()
+    if flags_h[1]:
+        raise ValueError("ahc_batch: the upper triangle of a group's score matrix holds a value that is not finite")
+    if flags_h[0]:
+        raise hiplib.XvectorHipError("ahc_batch: a kernel skipped a group that broke its contract (status %d)" % flags_h[0])
+    labels, merges = [None] * G, [None] * G
+    for g in routed:
+        labels[g], merges[g] = ahc(tables.block(scores, g), float(thr[g]), int(minc[g]), max_bytes)
+    a_h, b_h, lab_h, cnt_h = ints_h[:n_rows], ints_h[n_rows:2 * n_rows], ints_h[2 * n_rows:3 * n_rows], ints_h[3 * n_rows:]
+    for g in range(G):
+        if labels[g] is None:
+            r0, r1, m = int(tables.row0[g]), int(tables.row0[g + 1]), int(cnt_h[g])
+            labels[g] = lab_h[r0:r1].copy()
+            merges[g] = (a_h[r0:r0 + m].copy(), b_h[r0:r0 + m].copy(), m_s_h[r0:r0 + m].copy())
+    return labels, merges
+
+
+def diarize(x, group_sizes, plda, mean=None, transform=None, threshold=0.0, num_spk=None, device="cuda:0"):
+    """Cluster every recording's vectors on their own: x[N, D] raw vectors, recording g the next group_sizes[g] rows.  The
+    recordings are sorted by size, descending, for the device, scored against themselves in one launch (``score_blocks``) and
+    clustered one workgroup each (``ahc_batch``); the results come back in the caller's order.  threshold: the stop rule of every
+    recording; num_spk (None, or one entry per recording, None or a count): a recording with a count stops at exactly
+    min(count, n_g) clusters instead.  -> (labels int32[N]: the local slot of each vector's cluster within its recording,
+    merges: per recording (a, b, score))."""
+    hiplib.require_gpu()
+    sizes = np.asarray(group_sizes, dtype=np.int64).reshape(-1)
+    thr, minc = diarize_stop_rules(sizes, threshold, num_spk)
+    x = np.asarray(x, dtype=np.float32)
+    if sizes.size < 1 or int(sizes.min()) < 1 or x.ndim != 2 or int(sizes.sum()) != x.shape[0]:
+        raise ValueError("diarize: x must be [N, D] and the group sizes, all at least 1, must add up to N")
+    order, _ = size_order(sizes)
+    row0 = np.concatenate([[0], np.cumsum(sizes)])
+    rows = np.concatenate([np.arange(row0[g], row0[g + 1]) for g in order])
+    scores, tables = score_blocks(x[rows], sizes[order], plda, mean, transform, device)
+    lab_sorted, merges_sorted = ahc_batch(scores, tables, thr[order], minc[order])
+    labels = np.empty(x.shape[0], dtype=np.int32)
+    labels[rows] = np.concatenate(lab_sorted)
+    merges = [None] * sizes.size
+    for k, g in enumerate(order.tolist()):
+        merges[g] = merges_sorted[k]
+    return labels, merges
+
+
+def diarize_stop_rules(sizes, threshold=0.0, num_spk=None):
+    """(thresholds float64 [G], min_clusters int64 [G]) of ``diarize``: the common threshold and 1, or for a recording with a
+    speaker count -inf and min(count, n_g)."""
+    sizes = np.asarray(sizes, dtype=np.int64)
+    threshold = float(threshold)
+    if np.isnan(threshold):
+        raise ValueError("diarize: the threshold is NaN")
+    thr = np.full(sizes.size, threshold)
+    minc = np.ones(sizes.size, dtype=np.int64)
+    if num_spk is not None:
+        if len(num_spk) != sizes.size:
+            raise ValueError("diarize: %d recordings, %d speaker counts" % (sizes.size, len(num_spk)))
+        for g, k in enumerate(num_spk):
+            if k is not None:
+                if int(k) < 1:
+                    raise ValueError("diarize: a speaker count must be at least 1, got %r" % (k,))
+                thr[g] = -np.inf
+                minc[g] = min(int(k), int(sizes[g]))
+    return thr, minc
 
 
 DENSE_MAX_BYTES = 1 << 30          # the dense score matrix of one trial list is at most this large

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -120,6 +120,7 @@ _SIGNATURES = {
     # PLDA / cosine scoring back-end
     "xv_backend_prepare_f32": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp, _vp, _i64, _vp, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _i64, _vp, _vp]),
     "xv_score_matrix_f32": (_ci, [_vp, _vp, _i64, _ci, _ci, _ci, _vp, _vp, _i64, _vp]),
+    "xv_score_blocks_f32": (_ci, [_vp, _vp, _i64, _ci, _ci, _vp, _vp, _vp, _ci, _ci, _vp, _i64, _vp, _vp]),
     "xv_score_pairs_f32": (_ci, [_vp, _vp, _i64, _ci, _vp, _vp, _i64, _vp, _vp, _vp]),
     "xv_topk_row_stats_f32": (_ci, [_vp, _i64, _ci, _ci, _ci, _vp, _vp, _vp]),
     # moments for PLDA adaptation
@@ -128,6 +129,9 @@ _SIGNATURES = {
     # clustering for PLDA adaptation
     "xv_ahc_average_f64": (_ci, [_vp, _i64, _ci, ctypes.c_double, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "xv_ahc_average_workspace_bytes": (_sz, [_ci]),
+    # diarization: one clustering problem per recording
+    "xv_ahc_average_batch_f64": (_ci, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "xv_ahc_average_batch_workspace_bytes": (_sz, [_ci]),
     "xv_mfcc_f32": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _ci, _i64, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _ci, _vp, _ci, _ci, _ci, _ci,
                           _cf, _cf, _ci, _ci, _ci, _cf, _vp, _i64, _vp, _i64, _vp]),
     "xv_vad_energy_f32": (_ci, [_vp, _i64, _vp, _vp, _ci, _cf, _cf, _ci, _cf, _vp, _vp]),
@@ -171,6 +175,7 @@ SIDE_PLAIN, SIDE_ENROL, SIDE_TEST, SIDE_COSINE = 0, 1, 2, 3
 MOMENT_SLAB = 2048                # XV_MOMENT_SLAB: rows per partial of xv_moment_stats_f64
 MOMENT_DIM_MAX = 256
 AHC_MAX_N = 32768                  # XV_AHC_MAX_N: items of one xv_ahc_average_f64 call
+AHC_BATCH_MAX_N = 4096             # XV_AHC_BATCH_MAX_N: items of one group of xv_ahc_average_batch_f64
 
 _lib = None
 
@@ -1296,6 +1301,23 @@ def score_matrix(e, t, r, out):
                                    _stream()), "xv_score_matrix_f32")
 
 
+def score_blocks(e, t, r, grp_row0, grp_score0, max_n, out, status):
+    """Block-diagonal self-scoring of ragged groups of rows (xv_score_blocks_f32; see include/xvector_hip.h): group g is rows
+    [grp_row0[g], grp_row0[g + 1]) of e, t and r, its n_g x n_g matrix goes to out + grp_score0[g] with row stride
+    (n_g + 3) & ~3, each cell with the bits score_matrix gives those two rows.  grp_row0: int32 [G + 1], grp_score0: int64 [G],
+    out: float32 1-D, status: int32 [1] (zeroed by the caller, 1 after a group out of contract was skipped), all on the device."""
+    import torch
+    lib = require_gpu()
+    _f32_rows(e, "e"); _f32_rows(t, "t"); _f32(out, "out")
+    assert e.shape == t.shape and e.stride(0) == t.stride(0)
+    assert r is None or _f32(r, "r").numel() >= e.shape[0]
+    n_groups = grp_score0.numel()
+    _check(lib.xv_score_blocks_f32(_ptr(e), _ptr(t), e.stride(0), e.shape[1], e.shape[0], _ptr(r),
+                                   _dev(grp_row0, torch.int32, "grp_row0", n_groups + 1), _dev(grp_score0, torch.int64, "grp_score0"),
+                                   n_groups, int(max_n), _ptr(out), out.numel(), _dev(status, torch.int32, "status", 1), _stream()),
+           "xv_score_blocks_f32")
+
+
 def score_pairs(e, t, r, e_idx, t_idx, out):
     """out[i] = e[e_idx[i]] . t[t_idx[i]] + r[e_idx[i]]: bit-identical to the cell of score_matrix.  The kernel reads the rows the
     indices name, so their range is checked here first.  e and t may be slices of wider buffers, as for score_matrix."""
@@ -1375,6 +1397,35 @@ def ahc_average(scores, threshold, min_clusters, merge_a, merge_b, merge_score, 
                                   _dev(merge_a, i32, "merge_a", n - 1), _dev(merge_b, i32, "merge_b", n - 1),
                                   _dev(merge_score, torch.float64, "merge_score", n - 1), _dev(n_merges, i32, "n_merges", 1),
                                   _dev(labels, i32, "labels", n), _ptr(workspace), _nbytes(workspace), _stream()), "xv_ahc_average_f64")
+
+
+def ahc_average_batch_workspace_bytes(n):
+    return int(load().xv_ahc_average_batch_workspace_bytes(int(n)))
+
+
+def ahc_average_batch(scores, grp_row0, grp_score0, grp_ws0, threshold, min_clusters, max_n, merge_a, merge_b, merge_score, n_merges,
+                      labels, status, workspace):
+    """G independent average-linkage problems in one launch, one workgroup each (xv_ahc_average_batch_f64; see
+    include/xvector_hip.h).  scores: float32 1-D, the packed blocks score_blocks writes; grp_row0: int32 [G + 1]; grp_score0,
+    grp_ws0: int64 [G] (element offsets into scores, byte offsets into workspace); threshold: float64 [G]; min_clusters: int32 [G].
+    merge_a, merge_b: int32 [>= n_rows]; merge_score: float64 [>= n_rows]; n_merges: int32 [>= G]; labels: int32 [>= n_rows] with
+    n_rows = len(labels); status: int32 [1], zeroed by the caller.  Everything is on the device and written there: nothing is read
+    back and the stream is not synchronised.  Put large groups first: workgroups tend to start in group order (only speed depends on it)."""
+    import torch
+    lib = require_gpu()
+    _f32(scores, "scores")
+    n_groups = grp_score0.numel()
+    n_rows = labels.numel()
+    i32, i64, f64 = torch.int32, torch.int64, torch.float64
+    assert workspace.is_cuda and workspace.is_contiguous()
+    _check(lib.xv_ahc_average_batch_f64(_ptr(scores), scores.numel(), _dev(grp_row0, i32, "grp_row0", n_groups + 1),
+                                        _dev(grp_score0, i64, "grp_score0"), _dev(grp_ws0, i64, "grp_ws0", n_groups),
+                                        _dev(threshold, f64, "threshold", n_groups), _dev(min_clusters, i32, "min_clusters", n_groups),
+                                        n_groups, int(max_n), n_rows, _dev(merge_a, i32, "merge_a", n_rows),
+                                        _dev(merge_b, i32, "merge_b", n_rows), _dev(merge_score, f64, "merge_score", n_rows),
+                                        _dev(n_merges, i32, "n_merges", n_groups), _dev(labels, i32, "labels"),
+                                        _dev(status, i32, "status", 1), _ptr(workspace), _nbytes(workspace), _stream()),
+           "xv_ahc_average_batch_f64")
 
 
 def mfcc(samples, utt_offset, utt_samples, utt_row0, utt_key, total_rows, tables, opts, feats, logmel=None):
