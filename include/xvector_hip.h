@@ -81,6 +81,14 @@ int xv_pack_weights_f32(const float *w, int kred, int cout, float *wp, void *str
 int xv_fold_bn_f32(const float *gamma, const float *beta, const float *mean, const float *var, float eps,
                    int c, float *scale, float *shift, void *stream);
 
+/* Move a producer layer's BN shift into its consumer (one-off at load; see tap_bias of xv_tdnn_layer_f16bf8).  w[K, Cin, Cout]
+ * are the consumer's fp32 weights, shift[Cin] the producer's:
+ *     tap_bias[t][o] = sum_c shift[c] * w[t][c][o]          ([K][Cout]; may be NULL when only the sum is wanted, e.g. K = 1)
+ *     bias_full[o]   = bias[o] + sum_t tap_bias[t][o]       (bias may be NULL = 0)
+ * accumulated in fp64 in a fixed order (taps, then input channels, ascending) and rounded to fp32 once. */
+int xv_fold_shift_taps_f32(const float *w, const float *shift, const float *bias, int K, int cin, int cout, float *tap_bias,
+                           float *bias_full, void *stream);
+
 /* Frame-level TDNN layer over a whole ragged batch.  Replaces, per layer,
  *   tf.nn.conv1d(stride 1, SAME) / tf.nn.convolution(dilation_rate)  local/tf/models.py:60, :579-580
  *   + tf.nn.bias_add (:61) + relu|leaky_relu|prelu (:64, :912, tf_block.py:38-47)
@@ -257,6 +265,12 @@ int xv_tdnn_pair_pool_bf16x3(const void *x, int64_t R, int cin, int cmid, int co
  * xv_tdnn_layer_f16bf8: x in XV_FMT_SPLIT8; y in XV_FMT_F32 (row stride ldy), XV_FMT_SPLIT (to feed a bf16x3 consumer such
  *   as xv_tdnn_pair_pool_bf16x3) or XV_FMT_SPLIT8; K in {1,3,5,7}, 2 <= (K-1)*dilation <= 8 for K > 1.
  * xv_tdnn_layer_pool_f16bf8: the xv_tdnn_layer_pool_bf16x3 contract (block statistics instead of y).
+ * tap_bias (both; NULL = none; K > 1, Cout % 8 == 0, 16-byte aligned -- else XV_ERR_UNSUPPORTED): a per-row bias.  When the
+ *   producer of x stored scale * act(z + b) without its BN shift (so that a ReLU's zeros stay zero bits in x), the shift's share
+ *   of this layer is the constant tap_bias[t][o] (xv_fold_shift_taps_f32) for every tap t that falls on a frame, and nothing
+ *   for a tap that falls on a gap row (row_valid == 0) or outside [0, R), where SAME padding reads zeros:
+ *     z[r,o] = bias[o] - sum_{t missing at r} tap_bias[t][o] + sum_t sum_c x[r + (t-(K-1)/2)*dilation, c] * w[t,c,o]
+ *   with bias = the layer's own bias + sum_t tap_bias[t] (bias_full of xv_fold_shift_taps_f32).
  * xv_tdnn_first_f16bf8: xv_tdnn_first_bf16x3 (bf16x3 arithmetic on the fp32 feature rows, same packed weights) writing
  *   XV_FMT_SPLIT8 rows.  xv_split8_encode_f32 / xv_split8_decode_f32: tooling and tests (decode returns hi + xl8 / 2^11). */
 #define XV_FMT_SPLIT8 2
@@ -266,10 +280,11 @@ int xv_split8_encode_f32(const float *x, int64_t R, int c, int ldx, void *xs, in
 int xv_split8_decode_f32(const void *xs, int64_t R, int c, float *x, int ldx, void *stream);
 int xv_tdnn_layer_f16bf8(const void *x, int64_t R, int cin, const void *wt, const float *bias, const float *bn_scale,
                          const float *bn_shift, int act_kind, const float *act_alpha, int K, int dilation, int cout,
-                         const uint8_t *row_valid, void *y, int y_format, int ldy, int32_t *status, void *stream);
+                         const uint8_t *row_valid, const float *tap_bias, void *y, int y_format, int ldy, int32_t *status,
+                         void *stream);
 int xv_tdnn_layer_pool_f16bf8(const void *x, int64_t R, int cin, const void *wt, const float *bias, const float *bn_scale,
                               const float *bn_shift, int act_kind, const float *act_alpha, int K, int dilation, int cout,
-                              const uint8_t *row_valid, float *block_stats, void *stream);
+                              const uint8_t *row_valid, const float *tap_bias, float *block_stats, void *stream);
 int xv_tdnn_first_f16bf8(const float *x, int64_t R, int cin, int ldx, const void *wt, const float *bias, const float *bn_scale,
                          const float *bn_shift, int act_kind, const float *act_alpha, int K, int dilation, int cout,
                          const uint8_t *row_valid, void *y, int32_t *status, void *stream);

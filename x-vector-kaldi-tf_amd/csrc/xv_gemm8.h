@@ -30,6 +30,7 @@ struct Gemm8Params {
     int cin, xchunks;
     const uint8_t *wt;    // tiled f16bf8 weights
     const float *bias, *scale, *shift;
+    const float *tapbias; // [K][cout] or NULL: see gemm8_tap_flags
     int act;
     const float *alpha;
     int K, dil, cout;
@@ -40,6 +41,57 @@ struct Gemm8Params {
     int *status;          // bit 0 is set when a split8 output had to be clamped (may be NULL)
     int n_mt, n_nt, n_chunks;
 };
+
+// The per-row bias (tapbias != NULL).  The producer of x stored u = scale * act(z + b) WITHOUT its BN shift, so that the ReLU's
+// zeros reach the MFMAs as zero bits; the shift's share of this layer, c_t[o] = sum_c shift[c] * w[t][c][o], is a constant per
+// tap wherever tap t falls on a frame: the caller passes bias + sum_t c_t as ``bias`` and the table c_t as ``tapbias``.  A tap
+// that falls on a gap row or outside [0, R) (SAME padding: x is 0 there, shift and all) must not contribute: the epilogue takes
+// its c_t out again.  Row flags, one byte per tile row in LDS: bit 0 = the row is valid, bit 1 + t = tap t of a valid row is
+// missing.  (K <= 7 taps and the flag: eight bits.)  Without a table the byte is row_valid's, as before.
+// The kernels fill the flags of a table launch behind the issue of their prologue DMA: K independent byte loads (clamped addresses, no
+// branch between them) that share the DMA's latency, instead of K dependent ones in front of it.
+template <int KT>
+__device__ __forceinline__ uint8_t gemm8_tap_flags(const Gemm8Params &p, long gr, int left)
+{
+    bool inside[KT];
+    long q[KT];
+#pragma unroll
+    for (int t = 0; t < KT; ++t) {
+        q[t] = gr - left + (long)t * p.dil;
+        inside[t] = q[t] >= 0 && q[t] < p.R;
+    }
+    unsigned f = 0;
+    if (p.valid) {
+        uint8_t v[KT];
+#pragma unroll
+        for (int t = 0; t < KT; ++t) v[t] = p.valid[inside[t] ? q[t] : 0];       // (R > 0: row 0 exists)
+#pragma unroll
+        for (int t = 0; t < KT; ++t) f |= (inside[t] && v[t]) ? 0u : 2u << t;
+    } else {
+#pragma unroll
+        for (int t = 0; t < KT; ++t) f |= inside[t] ? 0u : 2u << t;
+    }
+    return (f & (2u << (KT / 2))) ? (uint8_t)0 : (uint8_t)(f | 1u);              // the centre tap is the row itself
+}
+
+// tv[j] = 8 channels (from gc0) of the accumulators of tile row lr(j): minus the constants of the row's missing taps.  A
+// divergent loop over the set bits -- about one row in fifty at 300-frame chunks has any.
+template <class RowOf>
+__device__ __forceinline__ void gemm8_drop_missing_taps(const Gemm8Params &p, const uint8_t *Ms, int gc0, f32x4 (&tv)[8][2], RowOf &&lr)
+{
+    if (gc0 + 8 > p.cout) return;                       // (columns past Cout of a 128-column tile: nothing is stored for them)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        unsigned m = Ms[lr(j)] >> 1;
+        while (m) {
+            const int t = __builtin_ctz(m);
+            m &= m - 1;
+            const float *c = p.tapbias + (size_t)t * p.cout + gc0;
+            tv[j][0] -= *reinterpret_cast<const f32x4 *>(c);
+            tv[j][1] -= *reinterpret_cast<const f32x4 *>(c + 4);
+        }
+    }
+}
 
 // the 256 x 256 workgroup tile of xv_gemm8_wide.hip / xv_gemm8_wide16.hip: LDS = [operand buffers | epilogue fp32 tile of 128
 // rows (aliased)] [row mask] [epilogue params]
@@ -96,6 +148,8 @@ __device__ __forceinline__ void wide_epilogue(const Gemm8Params &p, char *lds, c
     };
     auto process = [&](int h) {
         const long mh = m0 + h * 128;
+        if (p.tapbias)                                  // (in a branch of its own: the straight path keeps its registers)
+            gemm8_drop_missing_taps(p, Ms + h * 128, gc0, tv, [&](int j) { return POOL ? (tid >> 5) * 8 + j : (tid >> 5) + 16 * j; });
         if constexpr (POOL) {
             const int blk = tid >> 5;                   // 16 blocks of 8 rows
             if (mh + blk * 8 >= p.R) return;

@@ -106,6 +106,8 @@ __global__ __launch_bounds__(WM * 128, 2) void tdnn_gemm_f16bf8_kernel(const Gem
     for (int j = 0; j < RING; ++j) dma_b(j, j);
     dma_a_slab(0);
     if (KT == 1 && n_stages > 1) dma_a_slab(1);
+    if constexpr (KT > 1)
+        if (p.tapbias && tid < BM) Ms[tid] = gemm8_tap_flags<KT>(p, m0 + tid, left);        // (xv_gemm8.h)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
@@ -315,6 +317,8 @@ __global__ __launch_bounds__(WM * 128, 2) void tdnn_gemm_f16bf8_kernel(const Gem
             tv[j][1] = *reinterpret_cast<const f32x4 *>(T + lr * T_LD + cg * 8 + 4);
             keep[j] = Ms[lr] ? 1.f : 0.f;
         }
+        if constexpr (KT > 1)
+            if (p.tapbias) gemm8_drop_missing_taps(p, Ms, gc0, tv, [&](int j) { return blk * 8 + j; });
         __builtin_amdgcn_sched_barrier(0);
         by_mode([&](auto MODE) {
 #pragma unroll
@@ -363,6 +367,8 @@ __global__ __launch_bounds__(WM * 128, 2) void tdnn_gemm_f16bf8_kernel(const Gem
             tv[j][1] = *reinterpret_cast<const f32x4 *>(T + lr * T_LD + cg * 8 + 4);
             keep[j] = Ms[lr] ? 1.f : 0.f;
         }
+        if constexpr (KT > 1)
+            if (p.tapbias) gemm8_drop_missing_taps(p, Ms, gc0, tv, [&](int j) { return (tid >> 4) + (NT / 16) * j; });
         __builtin_amdgcn_sched_barrier(0);
         if (p.y_format != XV_FMT_F32 && n0 + BN <= p.cout) {
             // hidden layers: full-width tile into a split format.  Rows >= R of the last tile land in the buffer's zero
@@ -488,6 +494,12 @@ int launch_gemm8(const Gemm8Params &p0, hipStream_t st)
         return fail(XV_ERR_UNSUPPORTED, "tdnn_f16bf8: supports K in {1,3,5,7} with (K-1)*dilation <= 8");
     if ((p.act == XV_ACT_LRELU || p.act == XV_ACT_PRELU) && !p.alpha) return fail(XV_ERR_BAD_ARG, "tdnn_f16bf8: act_alpha is NULL");
     if ((((uintptr_t)p.x) | ((uintptr_t)p.wt)) & 15) return fail(XV_ERR_BAD_ARG, "tdnn_f16bf8: input and packed weights must be 16-byte aligned");
+    if (p.tapbias) {
+        // a K = 1 layer has no neighbours and its kernels no per-row bias: its share of the producer's shift is all in ``bias``
+        if (p.K == 1) return fail(XV_ERR_UNSUPPORTED, "tdnn_f16bf8: a K = 1 layer takes no tap_bias table");
+        // the epilogue reads 8 channels of a tap with two 16-byte loads
+        if ((p.cout & 7) || (((uintptr_t)p.tapbias) & 15)) return fail(XV_ERR_UNSUPPORTED, "tdnn_f16bf8: tap_bias needs Cout % 8 == 0 and 16-byte alignment");
+    }
     p.n_chunks = (p.cin + BK - 1) / BK;
     p.xchunks = p.n_chunks;
     if (p.y) {
@@ -652,7 +664,7 @@ int xv_split8_decode_f32(const void *xs, int64_t R, int c, float *x, int ldx, vo
 
 int xv_tdnn_layer_f16bf8(const void *x, int64_t R, int cin, const void *wt, const float *bias, const float *bn_scale,
                          const float *bn_shift, int act_kind, const float *act_alpha, int K, int dilation, int cout,
-                         const uint8_t *row_valid, void *y, int y_format, int ldy, int32_t *status, void *stream)
+                         const uint8_t *row_valid, const float *tap_bias, void *y, int y_format, int ldy, int32_t *status, void *stream)
 {
     if (!x || !wt || !y) return fail(XV_ERR_BAD_ARG, "tdnn_f16bf8: NULL pointer");
     if (act_kind < XV_ACT_NONE || act_kind > XV_ACT_PRELU) return fail(XV_ERR_BAD_ARG, "tdnn_f16bf8: unknown act_kind");
@@ -661,14 +673,14 @@ int xv_tdnn_layer_f16bf8(const void *x, int64_t R, int cin, const void *wt, cons
     Gemm8Params p{};
     p.x = (const uint8_t *)x; p.R = (long)R; p.cin = cin; p.wt = (const uint8_t *)wt;
     p.bias = bias; p.scale = bn_scale; p.shift = bn_shift; p.act = act_kind; p.alpha = act_alpha;
-    p.K = K; p.dil = dilation; p.cout = cout; p.valid = row_valid;
+    p.K = K; p.dil = dilation; p.cout = cout; p.valid = row_valid; p.tapbias = tap_bias;
     p.y = y; p.y_format = y_format; p.ldy = ldy; p.status = (int *)status;
     return launch_gemm8(p, (hipStream_t)stream);
 }
 
 int xv_tdnn_layer_pool_f16bf8(const void *x, int64_t R, int cin, const void *wt, const float *bias, const float *bn_scale,
                               const float *bn_shift, int act_kind, const float *act_alpha, int K, int dilation, int cout,
-                              const uint8_t *row_valid, float *block_stats, void *stream)
+                              const uint8_t *row_valid, const float *tap_bias, float *block_stats, void *stream)
 {
     if (!x || !wt || !block_stats) return fail(XV_ERR_BAD_ARG, "tdnn_pool_f16bf8: NULL pointer");
     if (act_kind < XV_ACT_NONE || act_kind > XV_ACT_PRELU) return fail(XV_ERR_BAD_ARG, "tdnn_pool_f16bf8: unknown act_kind");
@@ -676,7 +688,7 @@ int xv_tdnn_layer_pool_f16bf8(const void *x, int64_t R, int cin, const void *wt,
     Gemm8Params p{};
     p.x = (const uint8_t *)x; p.R = (long)R; p.cin = cin; p.wt = (const uint8_t *)wt;
     p.bias = bias; p.scale = bn_scale; p.shift = bn_shift; p.act = act_kind; p.alpha = act_alpha;
-    p.K = K; p.dil = dilation; p.cout = cout; p.valid = row_valid;
+    p.K = K; p.dil = dilation; p.cout = cout; p.valid = row_valid; p.tapbias = tap_bias;
     p.blk = block_stats; p.y_format = XV_FMT_F32;
     return launch_gemm8(p, (hipStream_t)stream);
 }

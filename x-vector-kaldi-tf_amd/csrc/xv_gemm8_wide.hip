@@ -80,6 +80,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_f16bf8_wide_kernel(const Gem
         }
         for (int piece = wave; piece < NP; piece += NW) XV_GLDS16(abase + (size_t)piece * 8 * xrow_bytes, Abuf + piece * 1024);
     }
+    if (p.tapbias && tid < W_BM) Ms[tid] = gemm8_tap_flags<KT>(p, m0 + tid, left);         // (xv_gemm8.h)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 

@@ -121,6 +121,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_f16bf8_wide16_kernel(const G
         for (int piece = wave; piece < NP; piece += NW) XV_BLDS16(xrs, Abuf + piece * 1024, xvoff, piece * 8 * (int)xrow_bytes, 0);
     }
     wsoff += (n_pairs > 1) ? 2 * B_BYTES : 0;          // -> pair 1
+    if (p.tapbias && tid < W_BM) Ms[tid] = gemm8_tap_flags<KT>(p, m0 + tid, left);         // (xv_gemm8.h)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 

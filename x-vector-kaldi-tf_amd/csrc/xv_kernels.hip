@@ -847,6 +847,24 @@ __global__ void fold_bn_kernel(const float *gamma, const float *beta, const floa
     shift[i] = beta[i] - ms;
 }
 
+// The share of a producer's BN shift in its consumer's pre-activation (xv_fold_shift_taps_f32): one thread per output channel,
+// taps and input channels in ascending order, fp64 throughout.  tap[t][o] = sum_c shift[c] * w[t][c][o];
+// bias_full[o] = bias[o] + sum_t tap[t][o] (from the unrounded sums).
+__global__ void fold_shift_taps_kernel(const float *__restrict__ w, const float *__restrict__ shift, const float *__restrict__ bias,
+                                       int K, int cin, int cout, float *__restrict__ tap, float *__restrict__ bias_full)
+{
+    const int o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= cout) return;
+    double total = bias ? (double)bias[o] : 0.0;
+    for (int t = 0; t < K; ++t) {
+        double acc = 0.0;
+        for (int c = 0; c < cin; ++c) acc += (double)shift[c] * (double)w[((size_t)t * cin + c) * cout + o];
+        if (tap) tap[(size_t)t * cout + o] = (float)acc;
+        total += acc;
+    }
+    bias_full[o] = (float)total;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -859,7 +877,7 @@ void xv_internal_gemm3_tile_rows(int value);      // xv_gemm3.hip
 void xv_internal_gemm8_tile_rows(int value);      // xv_gemm8.hip
 void xv_internal_first_tiles(int tiles);          // xv_first.hip
 
-int xv_version(void) { return 38; }
+int xv_version(void) { return 39; }
 
 int xv_set_tuning(int key, int value)
 {
@@ -899,6 +917,15 @@ int xv_fold_bn_f32(const float *gamma, const float *beta, const float *mean, con
     if (!gamma || !beta || !mean || !var || !scale || !shift || c <= 0) return fail(XV_ERR_BAD_ARG, "fold_bn: bad argument");
     hipLaunchKernelGGL(fold_bn_kernel, dim3((c + 255) / 256), dim3(256), 0, (hipStream_t)stream, gamma, beta, mean, var, eps, c, scale, shift);
     return launch_status("fold_bn_kernel");
+}
+
+int xv_fold_shift_taps_f32(const float *w, const float *shift, const float *bias, int K, int cin, int cout, float *tap_bias,
+                           float *bias_full, void *stream)
+{
+    if (!w || !shift || !bias_full || K <= 0 || cin <= 0 || cout <= 0) return fail(XV_ERR_BAD_ARG, "fold_shift_taps: bad argument");
+    hipLaunchKernelGGL(fold_shift_taps_kernel, dim3((cout + 63) / 64), dim3(64), 0, (hipStream_t)stream, w, shift, bias, K, cin, cout,
+                       tap_bias, bias_full);
+    return launch_status("fold_shift_taps_kernel");
 }
 
 int xv_tdnn_layer_f32(const float *x, int64_t R, int cin, int ldx, const float *wp, const float *bias,

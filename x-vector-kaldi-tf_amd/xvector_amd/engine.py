@@ -244,6 +244,36 @@ class BatchLayout(object):
 
 
 # ------------------------------------------------------------------------------------------------
+# BN shifts folded into the consumer's bias (f16bf8 ReLU models)
+# ------------------------------------------------------------------------------------------------
+# A hidden layer ends in v = scale * relu(z + b) + shift.  Stored as u = scale * relu(z + b), almost half of the activations
+# are exact zeros in every plane of the split8 format, which the power-limited MFMAs of the next layer turn into clock.  The
+# shift moves into the consumer exactly: z'[r] = sum_t u[r + (t - left) d] W[t] + sum_t valid[r + (t - left) d] c_t, with
+# c_t = shift . W[t] a [K, Cout] table -- a constant b + sum_t c_t wherever all K taps fall on frames, less the c_t of the taps
+# that fall on gap rows or outside the batch (SAME padding reads zeros there, not the shift).  These two functions are the host
+# form of that algebra in fp64 (tests, debugging); the model computes the same table on the device (hiplib.fold_shift_taps) and
+# the f16bf8 GEMM epilogues apply it per row (tap_bias of xv_tdnn_layer_f16bf8).
+def shift_tap_table(w3d, shift):
+    """c_t[K, Cout] = shift[Cin] . w3d[t] in fp64: what the producer's BN shift adds to the consumer's pre-activation per tap."""
+    return np.einsum("c,kco->ko", np.asarray(shift, np.float64), np.asarray(w3d, np.float64))
+
+
+def folded_row_bias(bias, taps, row_valid, dilation):
+    """Per-row bias [R, Cout] (fp64) of a consumer that reads activations stored without their shift: ``bias`` plus ``taps[t]``
+    for every tap t of row r whose source row r + (t - (K - 1) / 2) * dilation is a frame of the batch (row_valid, 0 outside)."""
+    taps = np.asarray(taps, np.float64)
+    K = taps.shape[0]
+    v = np.asarray(row_valid, np.float64).reshape(-1)
+    R = v.shape[0]
+    halo = (K - 1) // 2 * int(dilation)
+    vp = np.concatenate([np.zeros(halo), v, np.zeros(halo)])
+    out = np.tile(np.asarray(bias, np.float64), (R, 1))
+    for t in range(K):
+        out += vp[t * int(dilation): t * int(dilation) + R, None] * taps[t][None, :]
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # device model
 # ------------------------------------------------------------------------------------------------
 class _ColumnView(object):
@@ -284,7 +314,7 @@ class DeviceModel(object):
     POOL_SPLIT_ROWS = 512
 
     def __init__(self, weights, topo, device="cuda:0", embedding_index=0, precision="bf16x3", fused_pool=None, pair_kernel=None,
-                 first_kernel=None):
+                 first_kernel=None, fold_shift=None):
         """precision: "fp32" = exact fp32 MFMA GEMMs; "bf16x3" = split-precision bf16 MFMA GEMMs (fp32-class
         accuracy, ~3e-6 rel-L2 on the x-vector; see include/xvector_hip.h).  fused_pool (default: on; fp32 needs a last layer whose
         width is a multiple of 4; never with attention pooling): the last frame-level layer reduces its output to 8-row block
@@ -293,7 +323,9 @@ class DeviceModel(object):
         fused_pool when the last two layers have kernel size 1 and a shape xv_tdnn_pair_pool_bf16x3 supports; False: off;
         True: required): those two layers and the block statistics run as one launch whose
         intermediate activation stays in registers.  first_kernel (None, False or True, as pair_kernel): layer 0 of a bf16x3
-        model on xv_tdnn_first_bf16x3 when its shape allows."""
+        model on xv_tdnn_first_bf16x3 when its shape allows.  fold_shift (None, the default: on where supported -- f16bf8 models
+        with ReLU whose K > 1 layers behind layer 0 are a multiple of 8 channels wide; False: off; True: required): the frame-level layers store their activations without the BN shift, which
+        moves into the next layer's bias (see shift_tap_table), so that the f16bf8 GEMMs read the ReLU's zeros as zeros."""
         import torch
         hiplib.require_gpu()
         assert precision in ("fp32", "fp32tc", "bf16x3", "f16bf8")
@@ -407,6 +439,17 @@ class DeviceModel(object):
                     sc = "frame_level_info_layer-%d" % i
                     self.layers[i]["wp8"] = hiplib.pack_weights_f16bf8(self._wdev(weights, sc + "/w:0"))
                 self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+            # (only ReLU leaves zeros to gain: the other activations keep today's path)
+            # (and the GEMM epilogues read 8 channels of a tap's constants at a time: every K > 1 consumer's width a multiple of 8)
+            can_fold = self.f16bf8 and self.act == tp.ACT_RELU and all(L["cout"] % 8 == 0 for L in self.layers[1:] if L["K"] > 1)
+            self.fold_shift = can_fold and (fold_shift is None or bool(fold_shift))
+            assert not (fold_shift and not self.fold_shift), \
+                "fold_shift=True needs an f16bf8 model with ReLU whose K > 1 layers behind layer 0 have widths that are multiples of 8"
+            if self.fold_shift:
+                for i in range(1, len(self.layers)):
+                    L = self.layers[i]
+                    w = self._wdev(weights, "frame_level_info_layer-%d/w:0" % i)
+                    L["tapbias"], L["fbias"] = hiplib.fold_shift_taps(w, self.layers[i - 1]["shift"], L["bias"], table=L["K"] > 1)
             self.embed = []
             for j in range(len(topo["embedding_sizes"])):
                 sc = "embed_layer-%d" % j
@@ -597,37 +640,53 @@ class DeviceModel(object):
         n = len(self.layers)
         bufs = (self._ping, self._pong)
         S8, S3 = hiplib.FMT_SPLIT8, hiplib.FMT_SPLIT
+        fold = self.fold_shift
+
+        def pp(i):
+            """(bias, scale, shift, alpha) of layer i; folded: its producer's shift in the bias, its own left to its consumer
+            (the last layer's acts on the pooled block means and stays)."""
+            L = self.layers[i]
+            if not fold:
+                return L.pp
+            return L["fbias"] if i else L["bias"], L["scale"], L["shift"] if i == n - 1 else None, L["alpha"]
+
+        def ep(i):
+            b, sc, sh, al = pp(i)
+            return b, sc, sh, self.act, al
+
+        def taps(i):
+            return self.layers[i].get("tapbias") if fold else None
         L = self.layers[0]
         stop = n - 2 if self.pair is not None else n - 1        # layers [1, stop) run on xv_tdnn_layer_f16bf8
         pair_fmt = S8 if self.pair8 is not None else S3         # what the pair kernel in use reads
         h = bufs[0].view(L["cout"], pair_fmt if (self.pair is not None and stop == 1) else S8)
         mark("start")
         if self.first is not None:
-            hiplib.tdnn_first(x, R, self.first, *L.ep(self.act), L["dil"], row_valid, h, status)
+            hiplib.tdnn_first(x, R, self.first, *ep(0), L["dil"], row_valid, h, status)
             mark("layer 0: tdnn_first_kernel (bf16x3)")
         else:
             # a first layer the dedicated kernel does not take: the general bf16x3 GEMM into fp32 rows, then one encoding pass
             y32 = self._l0_rows[:R]
-            hiplib.tdnn_layer(x, L["wp"], *L.ep(self.act), L["K"], L["dil"], row_valid, y32, rows=R)
+            hiplib.tdnn_layer(x, L["wp"], *ep(0), L["K"], L["dil"], row_valid, y32, rows=R)
             hiplib.split_encode(y32, h, rows=R, status=status if h.fmt == S8 else None)
             mark("layer 0: tdnn_gemm_bf16x3_kernel + split encode")
         for i in range(1, stop):
             L = self.layers[i]
             y = bufs[i & 1].view(L["cout"], pair_fmt if (self.pair is not None and i == stop - 1) else S8)
-            hiplib.tdnn_layer8(h, R, L["wp8"], *L.ep(self.act), L["dil"], row_valid, y, status)
+            hiplib.tdnn_layer8(h, R, L["wp8"], *ep(i), L["dil"], row_valid, y, status, tapbias=taps(i))
             mark("layer %d: tdnn_gemm_f16bf8 (K=%d, %d -> %d)" % (i, L["K"], L["cin"], L["cout"]))
             h = y
         if self.pair is not None:
-            La, Lb = self.layers[-2], self.layers[-1]
+            pa, pb = pp(n - 2), pp(n - 1)                # (two K = 1 layers: the fold is in their biases, nothing else changes)
             if self.pair_mx6 is not None:
-                hiplib.tdnn_pair_pool_mx6(h, R, self.pair_mx6, La.pp, Lb.pp, self.act, row_valid, self._last, status)
+                hiplib.tdnn_pair_pool_mx6(h, R, self.pair_mx6, pa, pb, self.act, row_valid, self._last, status)
             elif self.pair8 is not None:
-                hiplib.tdnn_pair_pool8(h, R, self.pair8, La.pp, Lb.pp, self.act, row_valid, self._last, status)
+                hiplib.tdnn_pair_pool8(h, R, self.pair8, pa, pb, self.act, row_valid, self._last, status)
             else:
-                hiplib.tdnn_pair_pool(h, R, self.pair, La.pp, Lb.pp, self.act, row_valid, self._last)
+                hiplib.tdnn_pair_pool(h, R, self.pair, pa, pb, self.act, row_valid, self._last)
         else:
             L = self.layers[-1]
-            hiplib.tdnn_layer_pool8(h, R, L["wp8"], *L.ep(self.act), L["dil"], row_valid, self._last)
+            hiplib.tdnn_layer_pool8(h, R, L["wp8"], *ep(n - 1), L["dil"], row_valid, self._last, tapbias=taps(n - 1))
         mark("layers %d+%d + pooling statistics: %s" % (n - 2, n - 1, "tdnn_pair_pool_f16bf8_kernel" if self.pair8 is not None else
                                                         "tdnn_pair_pool_kernel (bf16x3)") if self.pair is not None else
              "layer %d + pooling statistics: tdnn_gemm_f16bf8 POOL" % (n - 1))
@@ -741,7 +800,7 @@ def _max_rel_l2(a, b):
     return float(np.nan_to_num(r, nan=np.inf).max()) if len(r) else 0.0
 
 
-def select_model(weights, topo, device="cuda:0", embedding_index=0, precision="f16bf8", probe=None):
+def select_model(weights, topo, device="cuda:0", embedding_index=0, precision="f16bf8", probe=None, fold_shift=None):
     """``DeviceModel`` in the fastest arithmetic, not faster than ``precision``, that the accuracy probe admits for THESE weights:
     f16bf8 -> (its x-vectors of the probe batch differ from bf16x3's by more than PROBE_LIMIT_F16BF8, or are not finite, or left
     the fp16 range) -> bf16x3 -> (differs from the exact-fp32 kernels by more than PROBE_LIMIT_BF16X3) -> the exact rung.  The
@@ -750,10 +809,12 @@ def select_model(weights, topo, device="cuda:0", embedding_index=0, precision="f
     on all 22 checkpoints of profiles/r05_fp32tc_accuracy_sweep.txt and 1.3x faster; bit-identical to ``fp32`` on a topology the
     Toom-Cook kernel does not cover) -- a demoted model does not fall to the slowest form.  XVECTOR_EXACT_RUNG=fp32 (or a request
     of ``precision="fp32"``) keeps the direct contraction, the literal statement of local/tf/models.py:60.
-    ``model.selection`` reports what was measured.  ``probe=False`` (or XVECTOR_ACCURACY_PROBE=0) takes ``precision`` as given."""
+    ``model.selection`` reports what was measured.  ``probe=False`` (or XVECTOR_ACCURACY_PROBE=0) takes ``precision`` as given.
+    ``fold_shift``: as DeviceModel's (the f16bf8 candidate only); left at None, a folded candidate that fails its probe is tried
+    unfolded before the model is demoted (``selection["fold_shift"]`` is then False)."""
     if probe is None:
         probe = os.environ.get("XVECTOR_ACCURACY_PROBE", "1") != "0"
-    model = DeviceModel(weights, topo, device, embedding_index, precision)
+    model = DeviceModel(weights, topo, device, embedding_index, precision, fold_shift=fold_shift)
     sel = dict(requested=precision, selected=model.arithmetic, probed=False)
     model.selection = sel
     if not probe or not model.f16bf8:
@@ -769,6 +830,19 @@ def select_model(weights, topo, device="cuda:0", embedding_index=0, precision="f
                probe_frames=int(np.sum(batch[2])))
     if err <= PROBE_LIMIT_F16BF8 and not clamped:
         return model
+    if model.fold_shift and fold_shift is None:
+        # The fold costs accuracy (uncentred operands: DESIGN 9.7) for a per-cent of the step; the step down to bf16x3 costs a
+        # quarter of it.  A checkpoint that misses the limit folded gets the unfolded f16bf8 arithmetic before it is demoted.
+        plain = DeviceModel(weights, topo, device, embedding_index, precision, fold_shift=False)
+        got = plain.probe_vectors(batch)
+        clamped2 = int(plain.status.item()) != 0
+        plain.status.zero_()
+        err2 = _max_rel_l2(got, ref)
+        sel.update(folded_f16bf8_vs_bf16x3=err, f16bf8_vs_bf16x3=err2, probe_left_fp16_range=clamped2, fold_shift=False)
+        if err2 <= PROBE_LIMIT_F16BF8 and not clamped2:
+            plain._fallback = twin
+            plain.selection = sel
+            return plain
     rung = "fp32" if os.environ.get("XVECTOR_EXACT_RUNG", "fp32tc") == "fp32" else "fp32tc"
     exact = DeviceModel(weights, topo, device, embedding_index, rung)
     err3 = _max_rel_l2(ref, exact.probe_vectors(batch))

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 38
+ABI_VERSION = 39
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -21,6 +21,7 @@ _SIGNATURES = {
     "xv_set_tuning": (_ci, [_ci, _ci]),
     "xv_pack_weights_f32": (_ci, [_vp, _ci, _ci, _vp, _vp]),
     "xv_fold_bn_f32": (_ci, [_vp, _vp, _vp, _vp, _cf, _ci, _vp, _vp, _vp]),
+    "xv_fold_shift_taps_f32": (_ci, [_vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp]),
     "xv_tdnn_layer_f32": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _vp]),
     "xv_packed_weights_rows_f32_floats": (_sz, [_ci, _ci, _ci, _ci]),
     "xv_pack_weights_rows_f32": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp, _vp]),
@@ -56,8 +57,8 @@ _SIGNATURES = {
     "xv_pack_weights_f16bf8": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp]),
     "xv_split8_encode_f32": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp, _vp]),
     "xv_split8_decode_f32": (_ci, [_vp, _i64, _ci, _vp, _ci, _vp]),
-    "xv_tdnn_layer_f16bf8": (_ci, [_vp, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _vp, _vp]),
-    "xv_tdnn_layer_pool_f16bf8": (_ci, [_vp, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "xv_tdnn_layer_f16bf8": (_ci, [_vp, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _ci, _ci, _vp, _vp]),
+    "xv_tdnn_layer_pool_f16bf8": (_ci, [_vp, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
     "xv_tdnn_first_f16bf8": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
     "xv_packed_pair_f16bf8_bytes": (_sz, [_ci, _ci, _ci]),
     "xv_pack_pair_f16bf8": (_ci, [_vp, _vp, _ci, _ci, _ci, _vp, _vp]),
@@ -691,25 +692,36 @@ def pack_weights_f16bf8(w3d):
                        (_f32(w3d, "w"),), w3d.shape)
 
 
-def tdnn_layer8(x, R, w, bias, scale, shift, act, alpha, dilation, row_valid, y, status=None):
+def _tap_bias(tapbias, w):
+    """The [K, Cout] table of fold_shift_taps for the layer packed as ``w`` (None: none)."""
+    if tapbias is not None:
+        _f32(tapbias, "tapbias")
+        assert tuple(tapbias.shape) == (w.K, w.cout), "tapbias must be [K, Cout] = [%d, %d]" % (w.K, w.cout)
+    return _ptr(tapbias)
+
+
+def tdnn_layer8(x, R, w, bias, scale, shift, act, alpha, dilation, row_valid, y, status=None, tapbias=None):
     """f16bf8 layer.  x: SplitBuf in FMT_SPLIT8; y: contiguous fp32 tensor [>=R, C] or SplitBuf of either format; w: Packed8;
-    status: int32 device tensor whose bit 0 is set when a FMT_SPLIT8 output had to be clamped (None: not reported)."""
+    status: int32 device tensor whose bit 0 is set when a FMT_SPLIT8 output had to be clamped (None: not reported);
+    tapbias: the per-tap constants of fold_shift_taps when x was stored without its BN shift (``bias`` is then bias_full)."""
     lib = require_gpu()
     assert isinstance(w, Packed8)
     xp = _operand(x, w.cin, R, "x", (FMT_SPLIT8,))[0]
     yp, ldy, yfmt = _operand(y, w.cout, R, "y", (FMT_F32, FMT_SPLIT, FMT_SPLIT8))
     _check(lib.xv_tdnn_layer_f16bf8(xp, int(R), w.cin, _ptr(w.wt), _ptr(bias), _ptr(scale), _ptr(shift), int(act), _ptr(alpha), w.K,
-                                    int(dilation), w.cout, _valid(row_valid, R), yp, yfmt, ldy, _ptr(status), _stream()),
+                                    int(dilation), w.cout, _valid(row_valid, R), _tap_bias(tapbias, w), yp, yfmt, ldy, _ptr(status),
+                                    _stream()),
            "xv_tdnn_layer_f16bf8")
 
 
-def tdnn_layer_pool8(x, R, w, bias, scale, shift, act, alpha, dilation, row_valid, block_stats):
-    """tdnn_layer_pool in the f16bf8 arithmetic (x: SplitBuf in FMT_SPLIT8, w: Packed8)."""
+def tdnn_layer_pool8(x, R, w, bias, scale, shift, act, alpha, dilation, row_valid, block_stats, tapbias=None):
+    """tdnn_layer_pool in the f16bf8 arithmetic (x: SplitBuf in FMT_SPLIT8, w: Packed8; tapbias: as tdnn_layer8)."""
     lib = require_gpu()
     assert isinstance(w, Packed8)
     xp = _operand(x, w.cin, R, "x", (FMT_SPLIT8,))[0]
     _check(lib.xv_tdnn_layer_pool_f16bf8(xp, int(R), w.cin, _ptr(w.wt), _ptr(bias), _ptr(scale), _ptr(shift), int(act), _ptr(alpha), w.K,
-                                         int(dilation), w.cout, _valid(row_valid, R), _block_stats(block_stats, R, w.cout), _stream()),
+                                         int(dilation), w.cout, _valid(row_valid, R), _tap_bias(tapbias, w),
+                                         _block_stats(block_stats, R, w.cout), _stream()),
            "xv_tdnn_layer_pool_f16bf8")
 
 
@@ -811,6 +823,21 @@ def fold_bn(gamma, beta, mean, var, eps):
                               _ptr(_f32(var, "var")), float(eps), c, _ptr(scale), _ptr(shift), _stream()),
            "xv_fold_bn_f32")
     return scale, shift
+
+
+def fold_shift_taps(w3d, shift, bias=None, table=True):
+    """The share of a producer's BN ``shift[Cin]`` in the consumer with weights ``w3d[K, Cin, Cout]`` (device fp32):
+    (tap[K, Cout] or None, bias_full[Cout]) with tap[t] = shift . w3d[t] and bias_full = bias + sum_t tap[t], in fp64."""
+    lib = require_gpu()
+    _f32(w3d, "w"); _f32(shift, "shift")
+    K, cin, cout = (int(v) for v in w3d.shape)
+    assert shift.numel() == cin and (bias is None or _f32(bias, "bias").numel() == cout)
+    import torch
+    tap = torch.empty((K, cout), dtype=torch.float32, device=w3d.device) if table else None
+    full = torch.empty(cout, dtype=torch.float32, device=w3d.device)
+    _check(lib.xv_fold_shift_taps_f32(_ptr(w3d), _ptr(shift), _ptr(bias), K, cin, cout, _ptr(tap), _ptr(full), _stream()),
+           "xv_fold_shift_taps_f32")
+    return tap, full
 
 
 def tdnn_layer(x, wp, bias, scale, shift, act, alpha, K, dilation, row_valid, y, y_preact=None, rows=None):
