@@ -1,5 +1,7 @@
 """MFCC + energy VAD on the GPU (csrc/xv_mfcc.hip) against the fp64 oracle (tests/mfcc_ref.py) under the propagated fp32 bound
-of DESIGN.md §8.6, the bitwise independence of a frame from its batch, exact VAD decisions, and the stage-1 CLI end to end."""
+of DESIGN.md §8.6, the bitwise independence of a frame from its batch, exact VAD decisions, and the stage-1 CLI end to end.  The
+oracle computes with the product's fp32 tables; tests/test_mfcc_cpu.py pins those against independent fp64 definitions."""
+import ctypes
 import os
 import subprocess
 import sys
@@ -106,6 +108,194 @@ def test_every_window_and_raw_energy_false(env, window):
     named = signals(env["synthetic"], 8000, 5)[:4]
     check(env, recipe_opts(env["mfcc"], window_type=window), named)
     check(env, recipe_opts(env["mfcc"], window_type=window, raw_energy=False, energy_floor=1.0), named)
+
+
+# The kernel's option space (xv_mfcc_f32 takes padded 128 .. 1024, up to 128 bins and cepstra): the smallest configurations that
+# reach each branch the recipe and the 16 kHz defaults leave out.  (base, options, (frame length, shift, padded), what it reaches)
+OPTION_CASES = {
+    "pad128_full": ("kaldi", dict(sample_frequency=8000, frame_length=16, num_mel_bins=13, num_ceps=13, low_freq=20, high_freq=3700,
+                                  snip_edges=False), (128, 80, 128)),           # H/2 = 32 butterflies, no zero padding, reflection
+    "pad128_short": ("kaldi", dict(sample_frequency=8000, frame_length=10, frame_shift=10, num_mel_bins=10, num_ceps=7, low_freq=100),
+                     (80, 80, 128)),                                            # a partial second lane trip; ceps < bins
+    "pad1024": ("kaldi", dict(sample_frequency=32000, frame_length=25, num_mel_bins=80, num_ceps=80, high_freq=-400),
+                (800, 320, 1024)),                                              # 16 v[] slots, two lane trips of mel and DCT
+    "pad1024_full": ("kaldi", dict(sample_frequency=16000, frame_length=64, num_mel_bins=128, num_ceps=128, low_freq=0,
+                                   snip_edges=False), (1024, 160, 1024)),       # the limits of all three constants at once
+    "65x65": ("kaldi", dict(num_mel_bins=65, num_ceps=65), (400, 160, 512)),    # one lane in the second trip
+    "flags_off": ("recipe", dict(remove_dc_offset=False, preemphasis_coefficient=0, use_energy=False, cepstral_lifter=0),
+                  (200, 80, 256)),                                              # c0 is the DCT's row 0, held by the cepstra bound
+    "floor": ("recipe", dict(energy_floor=1e6, raw_energy=True), (200, 80, 256)),
+    "gaps_nosnip": ("kaldi", dict(sample_frequency=8000, frame_length=20, frame_shift=25, snip_edges=False), (160, 200, 256)),
+    "gaps_snip": ("kaldi", dict(sample_frequency=8000, frame_length=20, frame_shift=25, snip_edges=True), (160, 200, 256)),
+}
+OPTION_RUNS = [(name, 0.0) for name in OPTION_CASES] + [("pad1024", 1.0), ("pad1024_full", 1.0)]
+
+
+@pytest.mark.parametrize("name,dither", OPTION_RUNS, ids=["%s-dither%g" % r for r in OPTION_RUNS])
+def test_option_space(env, name, dither):
+    mfcc, syn = env["mfcc"], env["synthetic"]
+    base, kw, geometry = OPTION_CASES[name]
+    opts = (recipe_opts(mfcc) if base == "recipe" else mfcc.MfccOptions()).update(list(kw.items()) + [("dither", dither), ("seed", 5)])
+    L = opts.frame_length_samples
+    assert (L, opts.frame_shift_samples, opts.padded_length) == geometry
+    fs = int(opts.sample_frequency)
+    named = [(n, w[:int(0.6 * fs)]) for n, w in signals(syn, fs, 6)[:4]]
+    sp = syn.speech_like_wave(2 * L, fs, 8)
+    named += [("len%d" % n, sp[:n]) for n in (0, 1, L - 1, L, L + 1)]
+    if name == "floor":
+        named.append(("silence", np.zeros(int(0.6 * fs), np.int16)))
+    _, _, feats, _ = check(env, opts, named)
+    if name == "floor":
+        c0 = feats[-1][:, 0]
+        want = np.log(1e6)
+        assert c0.shape[0] > 0 and (c0 == c0[0]).all() and abs(float(c0[0]) - want) <= float(np.spacing(np.float32(want)))
+        assert feats[2][:, 0].min() > want + 1                   # the clipped square is far above the floor: both sides are met
+
+
+def _direct(env, opts, x, ns, keys):
+    """hiplib.mfcc on one sample buffer (int16 or float32): -> (feats [rows, C], logmel [rows, B], first rows, frame counts)."""
+    torch, mfcc, hiplib = env["torch"], env["mfcc"], env["hiplib"]
+    dev = mfcc.MfccTables(opts).to_device("cuda:0")
+    ns = np.asarray(ns, np.int64)
+    T = opts.num_frames(ns)
+    row0 = np.concatenate([[0], np.cumsum(T)[:-1]]).astype(np.int64)
+    rows = int(T.sum())
+    cuda = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    off = np.concatenate([[0], np.cumsum(ns)[:-1]]).astype(np.int64)
+    keyv = np.array([mfcc.dither_key(k, opts.seed) for k in keys], np.uint64).view(np.int64)
+    feats = torch.full((rows, opts.num_ceps), float("nan"), device="cuda")
+    lm = torch.full((rows, opts.num_mel_bins), float("nan"), device="cuda")
+    hiplib.mfcc(cuda(x), cuda(off), cuda(ns), cuda(row0), cuda(keyv), rows, dev, opts, feats, lm)
+    return feats.cpu().numpy(), lm.cpu().numpy(), row0, T
+
+
+def test_sample_formats(env):
+    """The same integer samples as int16 and as fp32 give the same bits; fp32 non-integers stay within the bounds of the oracle
+    fed the same fp32 values."""
+    mfcc, syn = env["mfcc"], env["synthetic"]
+    opts = recipe_opts(mfcc, dither=1.0, seed=13)
+    waves = [syn.speech_like_wave(n, 8000, 40 + n) for n in (4000, 0, 199, 2501)]
+    waves.append(np.where(np.arange(1000) % 24 < 12, 32767, -32768).astype(np.int16))
+    x = np.concatenate(waves)
+    ns, keys = [w.shape[0] for w in waves], ["fmt%d" % i for i in range(len(waves))]
+    f16, l16, _, T = _direct(env, opts, x, ns, keys)
+    f32, l32, _, _ = _direct(env, opts, x.astype(np.float32), ns, keys)
+    assert f16.shape[0] == int(T.sum()) > 0 and np.isfinite(f16).all() and np.isfinite(l16).all()
+    assert np.array_equal(f16.view(np.uint32), f32.view(np.uint32)) and np.array_equal(l16.view(np.uint32), l32.view(np.uint32))
+    scaled = (waves[0].astype(np.float64) * 0.37).astype(np.float32)
+    assert (scaled != np.rint(scaled)).any()
+    check(env, opts, [("scaled", scaled), ("scaled-short", scaled[:201])])
+
+
+def test_vad_through_a_strided_matrix(env):
+    """xv_vad_energy_f32 on column 0 of a [rows, 23] matrix (row stride 23; compute_vad only ever feeds stride 1): three
+    utterances at non-zero first rows, one of them empty; the other columns and the rows of no utterance are NaN."""
+    torch, mfcc, hiplib = env["torch"], env["mfcc"], env["hiplib"]
+    rng = np.random.default_rng(17)
+    row0 = np.array([5, 102, 110], np.int64)
+    T = np.array([97, 0, 300], np.int32)
+    rows, canary = 410, 29
+    m = np.full((rows + canary, 23), np.nan, np.float32)
+    c0s = [(rng.standard_normal(int(t)) * 4 + 12).astype(np.float32) for t in T]
+    for r, c in zip(row0, c0s):
+        m[r:r + len(c), 0] = c
+    d_m = torch.from_numpy(m).cuda()
+    assert d_m.stride(0) == 23
+    for v in (recipe_vad(mfcc), mfcc.VadOptions(vad_frames_context=5, vad_proportion_threshold=0.5)):
+        out = torch.full((rows + canary,), float("nan"), device="cuda")
+        hiplib.vad_energy(d_m, torch.from_numpy(row0).cuda(), torch.from_numpy(T).cuda(), v, out)
+        got = out.cpu().numpy()
+        written = np.zeros(rows + canary, bool)
+        for r, c in zip(row0, c0s):
+            assert np.array_equal(got[r:r + len(c)], mfcc_ref.vad(c, v))
+            written[r:r + len(c)] = True
+        assert np.isnan(got[~written]).all() and written.sum() == 397
+
+
+BAD_ARG, UNSUPPORTED = -1, -2             # XV_ERR_BAD_ARG, XV_ERR_UNSUPPORTED of include/xvector_hip.h
+POISON = 0x7FC0BEEF
+
+
+def test_refused_mfcc_arguments_leave_the_output_alone(env):
+    torch, mfcc, hiplib = env["torch"], env["mfcc"], env["hiplib"]
+    lib = hiplib.load()
+    opts = recipe_opts(mfcc, dither=0.0)
+    tb = mfcc.MfccTables(opts).to_device("cuda:0")
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    n = 2000
+    rows = int(opts.num_frames(n))
+    x = dev(env["synthetic"].speech_like_wave(n, 8000, 2))
+    one = lambda v: dev(np.array([v], np.int64))  # noqa: E731
+    # buffers wide enough for every refused shape, should a check be missing
+    feats = dev(np.full((rows + 8, 256), POISON, np.uint32).view(np.float32))
+    lm = dev(np.full((rows + 8, 256), POISON, np.uint32).view(np.float32))
+    good = dict(samples=x, sample_format=0, utt_offset=one(0), utt_samples=one(n), utt_row0=one(0), utt_key=one(1), n_utts=1,
+                total_rows=rows, window=tb["window"], mel_first=tb["mel_first"], mel_len=tb["mel_len"], mel_w=tb["mel_w"],
+                num_bins=23, mel_ld=int(tb["mel_w"].shape[1]), lifter_dct=tb["lifter_dct"], num_ceps=23, twiddle=tb["twiddle"],
+                frame_length=200, frame_shift=80, padded_length=256, snip_edges=0, dither=0.0, preemph_coeff=0.97, remove_dc=1,
+                use_energy=1, raw_energy=1, energy_floor=0.0, feats=feats, ld_feats=256, logmel=lm, ld_logmel=256, stream=None)
+
+    def call(**kw):
+        a = dict(good, **kw)
+        return lib.xv_mfcc_f32(*[ctypes.c_void_p(v.data_ptr()) if isinstance(v, torch.Tensor) else v for v in a.values()])
+
+    def untouched():
+        torch.cuda.synchronize()
+        return all(bool((t.cpu().numpy().view(np.uint32) == POISON).all()) for t in (feats, lm))
+
+    refused = [(dict(padded_length=64, frame_length=50), UNSUPPORTED), (dict(padded_length=2048), UNSUPPORTED),
+               (dict(padded_length=384), UNSUPPORTED), (dict(num_bins=129), UNSUPPORTED),
+               (dict(num_ceps=24), BAD_ARG), (dict(frame_length=257), BAD_ARG), (dict(frame_length=0), BAD_ARG),
+               (dict(frame_shift=0), BAD_ARG), (dict(ld_feats=22), BAD_ARG), (dict(ld_logmel=22), BAD_ARG),
+               (dict(dither=-1.0), BAD_ARG), (dict(sample_format=2), BAD_ARG), (dict(n_utts=-1), BAD_ARG),
+               (dict(total_rows=-1), BAD_ARG)]
+    pointers = ("samples", "utt_offset", "utt_samples", "utt_row0", "utt_key", "window", "mel_first", "mel_len", "mel_w",
+                "lifter_dct", "twiddle", "feats")
+    refused += [({p: None}, BAD_ARG) for p in pointers]
+    for kw, code in refused:
+        assert call(**kw) == code, (kw, lib.xv_last_error())
+        assert b"mfcc" in lib.xv_last_error(), kw
+    assert untouched()
+    # no rows: nothing to do, whatever the pointers
+    assert call(total_rows=0, **{p: None for p in pointers}) == 0 and call(total_rows=0, n_utts=0) == 0
+    assert untouched()
+    # a narrow log-mel stride is fine without a log-mel buffer; and the call with nothing wrong writes exactly its rows
+    assert call(logmel=None, ld_logmel=0) == 0 and call() == 0
+    torch.cuda.synchronize()
+    f, l = feats.cpu().numpy(), lm.cpu().numpy()
+    assert np.isfinite(f[:rows, :23]).all() and np.isfinite(l[:rows, :23]).all()
+    for a in (f, l):
+        assert (a[rows:].view(np.uint32) == POISON).all() and (a[:, 23:].view(np.uint32) == POISON).all()
+
+
+def test_refused_vad_arguments_leave_the_output_alone(env):
+    torch, hiplib = env["torch"], env["hiplib"]
+    lib = hiplib.load()
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    c0 = np.linspace(0, 20, 60).astype(np.float32)
+    good = dict(feats=dev(c0), ld=1, utt_row0=dev(np.array([0, 40], np.int64)), n_frames=dev(np.array([40, 20], np.int32)), n_utts=2,
+                energy_threshold=5.0, energy_mean_scale=0.5, frames_context=2, proportion_threshold=0.6,
+                out=dev(np.full(64, POISON, np.uint32).view(np.float32)), stream=None)
+
+    def call(**kw):
+        a = dict(good, **kw)
+        return lib.xv_vad_energy_f32(*[ctypes.c_void_p(v.data_ptr()) if isinstance(v, torch.Tensor) else v for v in a.values()])
+
+    def poison_left():
+        torch.cuda.synchronize()
+        return int((good["out"].cpu().numpy().view(np.uint32) == POISON).sum())
+
+    for kw in (dict(frames_context=-1), dict(ld=0), dict(n_utts=-1), dict(feats=None), dict(utt_row0=None), dict(n_frames=None),
+               dict(out=None)):
+        assert call(**kw) == BAD_ARG, (kw, lib.xv_last_error())
+        assert b"vad_energy" in lib.xv_last_error(), kw
+    assert call(n_utts=0) == 0 and call(n_utts=0, feats=None, out=None) == 0
+    assert poison_left() == 64
+    assert call() == 0
+    assert poison_left() == 4
+    vopts = env["mfcc"].VadOptions(vad_frames_context=2)
+    got = good["out"].cpu().numpy()
+    assert np.array_equal(got[:40], mfcc_ref.vad(c0[:40], vopts)) and np.array_equal(got[40:60], mfcc_ref.vad(c0[40:], vopts))
 
 
 def test_silence_without_dither_is_the_floor(env):

@@ -1,5 +1,6 @@
-"""Host side of the MFCC + VAD front-end (no GPU): the oracle's frame geometry, the mel-table support, Philox against the
-Random123 known-answer vectors, the --config parser, the WAV reader and the CLI's argument errors."""
+"""Host side of the MFCC + VAD front-end (no GPU): the oracle's frame geometry, the mel-table support, every table (window, mel
+bank, lifter x DCT, twiddles) against fp64 definitions written without the product, Philox against the Random123 known-answer
+vectors, the --config parser, the WAV reader and the CLI's argument errors."""
 import os
 import struct
 import subprocess
@@ -98,6 +99,153 @@ def test_tables():
     assert t.window.dtype == np.float32 and t.window.shape == (200,) and t.window[0] == 0 and abs(t.window[100] - 1) < 1e-3
     assert t.lifter_dct.shape == (23, 23) and abs(t.lifter_dct[0, 0] - np.sqrt(1 / 23)) < 1e-7
     assert t.twiddle.shape == (128, 2) and t.twiddle[64, 0] == np.float32(np.cos(-np.pi / 2)) and t.twiddle[64, 1] == -1
+
+
+# ------------------------------------------------------------------------------------------------
+# the tables against definitions written without the product (mfcc_ref.window64 / mel_dense64 / lifter_dct64 / twiddle64)
+# ------------------------------------------------------------------------------------------------
+# (sample frequency, frame length in ms) -> (samples, padded): every padded length at every rate, with and without zero padding
+GEOMETRY = {(8000, 10): (80, 128), (8000, 16): (128, 128), (8000, 25): (200, 256), (8000, 64): (512, 512), (8000, 100): (800, 1024),
+            (16000, 8): (128, 128), (16000, 10): (160, 256), (16000, 25): (400, 512), (16000, 32): (512, 512), (16000, 64): (1024, 1024),
+            (32000, 3): (96, 128), (32000, 8): (256, 256), (32000, 12): (384, 512), (32000, 25): (800, 1024), (32000, 32): (1024, 1024)}
+WINDOWS = [(w, 0.42) for w in mfcc.WINDOW_TYPES] + [("blackman", 0.40)]
+BINS = (10, 13, 23, 40, 65, 80, 128)
+ABS0 = 1e-14            # entries that are exactly 0 in one statement and ~1e-15 in the other (cos pi/2)
+# reference against scipy, both fp64: a cosine's argument of size x, formed by a few roundings, is off by a few x 2^-53, and the
+# cosine moves by as much.  Windows: x <= 4 pi, amplitude <= 1.  DCT: the reference reduces its angle below 2 pi, amplitude
+# sqrt(2/B) <= 0.45, and scipy's FFT-based transform of a unit vector is as exact; the same allowance serves.
+WIN_TOL = 8 * 4 * np.pi * 2.0 ** -53
+DCT_TOL = WIN_TOL
+
+
+def _geometry(fs, ms, **kw):
+    o = mfcc.MfccOptions(sample_frequency=fs, frame_length=ms, **kw)
+    assert (o.frame_length_samples, o.padded_length) == GEOMETRY[(fs, ms)]
+    return o
+
+
+def _rounded_once(table, ref):
+    """An fp32 table formed in fp64 and rounded once lies within half an fp32 ulp of the independent fp64 value."""
+    assert table.dtype == np.float32 and table.shape == ref.shape
+    err = np.abs(table.astype(np.float64) - ref)
+    bound = mfcc_ref.half_ulp32(ref) + ABS0
+    assert (err <= bound).all(), (float((err / bound).max()), np.unravel_index(np.argmax(err / bound), err.shape))
+
+
+@pytest.mark.parametrize("window,coeff", WINDOWS)
+@pytest.mark.parametrize("fs,ms", sorted(GEOMETRY))
+def test_window_against_the_definition(fs, ms, window, coeff):
+    o = _geometry(fs, ms, window_type=window, blackman_coeff=coeff)
+    _rounded_once(mfcc.window_function(o), mfcc_ref.window64(window, o.frame_length_samples, coeff))
+
+
+@pytest.mark.parametrize("Q", [0.0, 22.0, 30.0])
+@pytest.mark.parametrize("B", BINS)
+def test_lifter_dct_against_the_definition(B, Q):
+    for C in sorted({1, 13, B}):
+        if C > B:
+            continue
+        o = mfcc.MfccOptions(num_mel_bins=B, num_ceps=C, cepstral_lifter=Q)
+        _rounded_once(mfcc.lifter_dct(o), mfcc_ref.lifter_dct64(B, C, Q))
+
+
+@pytest.mark.parametrize("fs,ms", sorted(GEOMETRY))
+def test_twiddles_against_the_definition(fs, ms):
+    o = _geometry(fs, ms)
+    _rounded_once(mfcc.twiddles(o), mfcc_ref.twiddle64(o.padded_length))
+
+
+def test_tables_object_holds_the_builders_output():
+    """``MfccTables`` (what is uploaded) is the builders' output, bit for bit."""
+    o = _geometry(32000, 25, num_mel_bins=80, num_ceps=80, high_freq=-400.0, window_type="blackman", blackman_coeff=0.40)
+    t = mfcc.MfccTables(o)
+    f, w, n = mfcc.mel_banks(o)
+    for got, want in ((t.window, mfcc.window_function(o)), (t.lifter_dct, mfcc.lifter_dct(o)), (t.twiddle, mfcc.twiddles(o)),
+                      (t.mel_first, f), (t.mel_w, w), (t.mel_len, n)):
+        assert got.dtype == want.dtype and np.array_equal(got, want)
+
+
+def _mel_dense32(first, w, length, half):
+    B = len(first)
+    assert w.dtype == np.float32 and w.shape[0] == B and w.shape[1] == int(length.max())
+    W = np.zeros((half, B), np.float64)
+    inside = np.zeros((half, B), bool)
+    for b in range(B):
+        f, n = int(first[b]), int(length[b])
+        assert n >= 1 and f >= 0 and f + n <= half, (b, f, n)
+        assert not w[b, n:].any(), b                                  # nothing past the band's length
+        W[f:f + n, b] = w[b, :n]
+        inside[f:f + n, b] = True
+    return W, inside
+
+
+@pytest.mark.parametrize("fs,ms", sorted(GEOMETRY))
+def test_mel_bank_against_the_definition(fs, ms):
+    """The fp32 bank (Kaldi forms it in fp32) against the fp64 definition.  Bound: a mel value of size up to mel(high), rounded
+    to fp32 (2^-24 relative), divided by the band's half-width delta, times 8 for the few operations involved, plus 2 roundings of
+    the weight itself: 2^-24 (2 + 8 mel(high) / delta)."""
+    N = GEOMETRY[(fs, ms)][1]
+    accepted = refused = 0
+    worst = 0.0
+    for B in BINS:
+        for low in (0.0, 20.0, 300.0):
+            for high in (0.0, -400.0, 3700.0):
+                o = _geometry(fs, ms, num_mel_bins=B, low_freq=low, high_freq=high)
+                W64 = mfcc_ref.mel_dense64(fs, N, B, low, high)
+                mlo, mhi = mfcc_ref.mel_range64(fs, low, high)
+                bound = 2.0 ** -24 * (2.0 + 8.0 * mhi / ((mhi - mlo) / (B + 1)))
+                what = (fs, N, B, low, high)
+                try:
+                    first, w, length = mfcc.mel_banks(o)
+                except ValueError as e:
+                    # a refusal is right only where the definition leaves some band without a bin too
+                    assert "has no FFT bin" in str(e) and (W64.max(axis=0) <= bound).any(), what
+                    refused += 1
+                    continue
+                accepted += 1
+                W32, inside = _mel_dense32(first, w, length, N // 2)
+                err = np.abs(W32 - W64)
+                worst = max(worst, float(err.max() / bound))
+                assert (err <= bound).all(), (what, float(err.max() / bound))
+                assert (W32 >= 0).all() and (W32 <= 1).all(), what
+                assert (W64[(W32 > 0) != (W64 > 0)] < bound).all(), what       # the supports differ only in negligible weights
+                assert (W64[~inside] < bound).all(), what                      # and nothing of weight lies outside a stored row
+                assert (W32.max(axis=0) > 0).all(), what
+    print("mel bank fs %d N %d: worst error / bound %.3f, %d accepted, %d refused" % (fs, N, worst, accepted, refused))
+    assert accepted >= 9                                                       # the grid is not refused away
+
+
+def test_too_many_mel_bins_are_refused():
+    with pytest.raises(ValueError, match=r"mel band \d+ has no FFT bin"):
+        mfcc.mel_banks(mfcc.MfccOptions(num_mel_bins=128))
+    with pytest.raises(ValueError, match=r"mel band \d+ has no FFT bin"):
+        mfcc.MfccTables(mfcc.MfccOptions(num_mel_bins=128))
+
+
+def test_reference_dct_against_scipy():
+    fft = pytest.importorskip("scipy.fft")
+    for B in BINS:
+        for C in sorted({1, 13, B}):
+            if C <= B:
+                want = fft.dct(np.eye(B), type=2, norm="ortho", axis=0)[:C]
+                assert np.abs(mfcc_ref.dct64(B, C) - want).max() <= DCT_TOL
+                assert np.array_equal(mfcc_ref.lifter_dct64(B, C, 0.0), mfcc_ref.dct64(B, C))
+    # the lifter: 1 at k = 0, 1 + Q/2 at k = Q/2, 1 again at k = Q
+    assert mfcc_ref.lifter64(23, 22.0)[0] == 1.0 and mfcc_ref.lifter64(23, 22.0)[11] == 12.0
+    assert abs(mfcc_ref.lifter64(23, 22.0)[22] - 1.0) <= 1e-14 and mfcc_ref.lifter64(31, 30.0)[15] == 16.0
+
+
+def test_reference_windows_against_scipy():
+    windows = pytest.importorskip("scipy.signal.windows")
+    for L in sorted({v[0] for v in GEOMETRY.values()}):
+        hann = windows.hann(L)                                                 # symmetric, as Kaldi's
+        assert np.abs(mfcc_ref.window64("hanning", L) - hann).max() <= WIN_TOL
+        assert np.abs(mfcc_ref.window64("hamming", L) - windows.hamming(L)).max() <= WIN_TOL
+        assert np.abs(mfcc_ref.window64("blackman", L, 0.42) - windows.blackman(L)).max() <= WIN_TOL
+        assert np.abs(mfcc_ref.window64("povey", L) - np.maximum(hann, 0.0) ** 0.85).max() <= WIN_TOL
+        assert (mfcc_ref.window64("rectangular", L) == 1.0).all()
+        sine = mfcc_ref.window64("sine", L)                                    # scipy's cosine window is another one
+        assert np.abs(sine * sine - hann).max() <= WIN_TOL                       # sin^2(pi x) = 1/2 - 1/2 cos(2 pi x)
 
 
 def test_wav_reader_formats():

@@ -261,9 +261,11 @@ def mel_banks(opts):
 def lifter_dct(opts):
     """Rows 0 .. num_ceps - 1 of Kaldi's DCT-II matrix times the cepstral lifter, fp64 -> fp32."""
     B, C = opts.num_mel_bins, opts.num_ceps
-    k = np.arange(C, dtype=np.float64)[:, None]
-    n = np.arange(B, dtype=np.float64)[None, :]
-    d = math.sqrt(2.0 / B) * np.cos(math.pi / B * (n + 0.5) * k)
+    k = np.arange(C, dtype=np.int64)[:, None]
+    n = np.arange(B, dtype=np.int64)[None, :]
+    # cos(pi (2n + 1) k / 2B) with the angle reduced to [0, 2 pi) in integers: an entry that is 0 stays below 1e-16 (unreduced,
+    # the rounding of an angle near 400 leaves 1e-14 there, times a lifter of up to 1 + Q/2)
+    d = math.sqrt(2.0 / B) * np.cos(math.pi * (((2 * n + 1) * k) % (4 * B)).astype(np.float64) / (2.0 * B))
     d[0, :] = math.sqrt(1.0 / B)
     Q = opts.cepstral_lifter
     if Q != 0:
