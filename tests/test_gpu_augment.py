@@ -102,6 +102,11 @@ def check(env, tmp_path, name, x, rir=None, noises=(), snrs=(), times=(), **opts
     err = np.abs(y - yr)
     WORST["waveform"] = max(WORST.get("waveform", 0.0), float((err / bound).max()))
     assert (err <= bound).all(), (name, float((err / bound).max()))
+    if rir is not None and not noises and len(x) * len(rir) <= 5e7:
+        # reverberation alone, within the oracle's direct form: the convolution is exact (int16 taps / 32768, partial sums below
+        # 2^53 on the 2^-15 grid), so the waveform equals the integer convolution bit for bit
+        exact = np.convolve(np.asarray(x, np.int64), np.asarray(rir, np.int64)).astype(np.float64) * 2.0 ** -15
+        assert np.array_equal(y, exact), (name, np.flatnonzero(y != exact)[:8])
     # int16: equal except where the oracle's value lies within the propagated bound of a truncation boundary
     assert got.dtype == np.int16 and got.shape == ref["out"].shape, name
     pre = ref["pre"]
