@@ -52,7 +52,7 @@ extern "C" {
 #define XV_ERR_BAD_ARG (-1)
 #define XV_ERR_UNSUPPORTED (-2)
 
-/* Library / ABI version (increments whenever an entry point is added or changed; currently 38). */
+/* Library / ABI version (increments whenever an entry point is added or changed; currently 40). */
 int xv_version(void);
 /* Thread-local description of the last non-zero return. */
 const char *xv_last_error(void);
@@ -691,6 +691,70 @@ int xv_ahc_average_batch_f64(const float *scores, int64_t scores_elems, const in
                              int n_rows, int32_t *merge_a, int32_t *merge_b, double *merge_score, int32_t *n_merges, int32_t *labels,
                              int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 size_t xv_ahc_average_batch_workspace_bytes(int n);
+
+/* ---- diarization: per-recording PCA and the PLDA projected into it (csrc/xv_pca.hip) -----------------------
+ * What ivector-plda-scoring-dense --target-energy does per recording (EstPca, TransformIvectors, Plda::ApplyTransform).  The rule
+ * below was written down from memory of Kaldi's source, not checked against it: the rule AS WRITTEN HERE is the contract.
+ * xv_pca_plda_groups_f64  for every group g (rows [grp_row0[g], grp_row0[g + 1]) of y [n_rows, ldy] fp32, n_g >= 1 of them; the
+ *   rows are the vectors after mean subtraction, LDA and length normalisation), all in fp64, one workgroup per group:
+ *   1. C = (1/n) sum_i y_i y_i^T - m m^T, m = (1/n) sum_i y_i; every sum runs over the rows in ascending order.
+ *   2. The eigenpairs of C.  Eigenvalues descending, ties to the smaller column index of the iteration; every eigenvector's
+ *      sign is chosen so that its first component of largest magnitude is positive.
+ *   3. total = sum of the eigenvalues (descending order); k = the smallest count with (l_1 + .. + l_k) / total > target_energy
+ *      (k = dim if none); p_g = min(k + 1, dim) -- Kaldi's loop steps once past the count it summed.
+ *   4. A_g [p_g, dim] = the first p_g eigenvectors as rows.  Vectors are projected WITHOUT centring: u = A_g y.
+ *   5. With the global model (mean mu, transform P, psi) and within = P^-1 P^-T, between = P^-1 diag(psi) P^-T (formed by the
+ *      caller): mu_g = A_g mu, W_g = A_g within A_g^T, B_g = A_g between A_g^T; W_g = L L^T (Cholesky), T1 = L^-1, the eigenpairs of
+ *      T1 B_g T1^T descending (V), P_g = V^T T1, psi_g = max(eigenvalue, 0).
+ *   Outputs (device memory): grp_dim [n_groups] int32 = p_g; grp_info [n_groups] int32: 0 = PCA applied, 1 = fallback for energy,
+ *     2 = fallback for non-convergence; eigvals [n_groups, dim]: the eigenvalues of C, descending (zeros when info is 1 by a
+ *     non-finite or non-positive trace, or when the PCA's own iteration did not converge); pca [n_groups, dim, dim] (may be
+ *     NULL: not written): rows < p_g hold A_g; grp_psi [n_groups, dim]: psi_g in the first p_g entries; grp_map
+ *     [n_groups, dim, dim]: rows < p_g hold M_g = P_g A_g; grp_off [n_groups, dim]: c_g = -P_g mu_g in the first p_g entries.
+ *     So z = M_g y + c_g.  Rows and entries at p_g and beyond are not written.
+ *   Fallback: total (or the trace of C) not finite or not > 0 (one vector, identical vectors): info 1; an eigen-iteration that
+ *     does not converge within XV_PCA_MAX_SWEEPS sweeps, or a W_g that is not positive definite: info 2.  Such a group holds the
+ *     global model: p_g = dim, grp_map = transform and grp_psi = psi as exact copies, grp_off[i] = -(sum_k P[i, k] mu[k]) with
+ *     rounded products added in ascending k from a zero start, pca = the identity.
+ *   Eigen-solver: cyclic Jacobi in a fixed rotation order, a round-robin tournament over m = dim rounded up to even players (the
+ *     circle method: step r < m - 1 pairs (m - 1, r) and ((r + k) mod (m - 1), (r - k) mod (m - 1)), 0 < k < m / 2; a pair
+ *     holding the index dim, for odd dim, sits out).  The disjoint rotations of a step are applied together.  At the head of
+ *     every sweep the iteration stops as converged if max_{i != j} |a_ij| <= 2^-58 max_i |a_ii|; at most XV_PCA_MAX_SWEEPS sweeps
+ *     run.  One device function serves the dim x dim problem of step 2 and the p_g x p_g problem of step 5.
+ *   Determinism: no floating-point atomics, every value has one writer and every sum one order; the bits of a group's outputs
+ *     depend on its own rows, dim, target_energy and the model only: not on the other groups, the group's position, the
+ *     workspace contents or what ran before.  The iterate lives in LDS (dim * (dim + 1) doubles, 129 KiB at dim 128: small
+ *     problems share a CU), the accumulated eigenvectors in the group's workspace slice.  No cooperative launch, no workgroup
+ *     waits on another, every loop is bounded by construction.  One launch; the call does NOT synchronise.
+ *   XV_ERR_BAD_ARG, nothing launched: n_groups, n_rows or dim below 1, ldy < dim, a target_energy outside (0, 1] or NaN, a NULL
+ *     pointer (pca excepted) or a misaligned one (fp64 arrays and the workspace 8 bytes, the rest 4), a workspace smaller than
+ *     xv_pca_plda_groups_workspace_bytes(n_groups, dim).  dim > XV_PCA_MAX_DIM: XV_ERR_UNSUPPORTED.
+ *   Device side: a group with n_g < 1 or rows outside [0, n_rows) is skipped whole: nothing of it is read or written, and
+ *     *status receives 1.  The caller zeroes *status and reads it back with the results.
+ * xv_pca_plda_groups_workspace_bytes  the bytes of that workspace, n_groups * 4 * dim^2 * 8 (0 for arguments the call refuses).
+ * xv_backend_prepare_groups_f32  the grouped twin of xv_backend_prepare_f32's PLDA stage: for every row of y [n_rows, ldy] in
+ *   group g (the tables above; max_n: an upper bound of every n_g, it sizes the grid), with p = grp_dim[g]:
+ *     z_i = sum_k (float)M_g[i, k] y[k] + (float)c_g[i], i < p   (an fmaf chain, k ascending from a zero start, c added after it)
+ *     z *= sqrt(p / sum_i z_i^2 / ((float)psi_g[i] + 1))          (Plda::TransformIvector, one utterance; a zero sum: scale 1)
+ *     side XV_SIDE_ENROL: the enrolment row of xv_backend_prepare_f32 with n = 1 and psi_g in columns [0, 2 p), r written;
+ *          XV_SIDE_TEST:  the test row in columns [0, 2 p), r (may be NULL) written as exactly 0.
+ *   Columns [2 p, ldo) receive exact zeros, so xv_score_blocks_f32 scores these rows unchanged with kpad = ldo.  The bits of a
+ *   row depend on its values and its group's tables only, not on ldy, ldo or the other rows.
+ *   XV_ERR_BAD_ARG, nothing launched: a side other than ENROL / TEST, counts below 1, ldy < dim, ldo < 2 dim or no multiple of
+ *     XV_BACKEND_KSTEP, a NULL (r excepted) or misaligned pointer.  dim > XV_PCA_MAX_DIM: XV_ERR_UNSUPPORTED.
+ *   Device side: a group with n_g outside [1, max_n], rows outside [0, n_rows) or grp_dim outside [1, dim] is skipped whole and
+ *     *status receives 1. */
+#define XV_PCA_MAX_DIM 128
+#define XV_PCA_MAX_SWEEPS 30
+int xv_pca_plda_groups_f64(const float *y, int64_t ldy, int n_rows, const int32_t *grp_row0, int n_groups, int dim,
+                           double target_energy, const double *mean, const double *within, const double *between,
+                           const double *transform, const double *psi, int32_t *grp_dim, int32_t *grp_info, double *eigvals,
+                           double *pca, double *grp_psi, double *grp_map, double *grp_off, int32_t *status, void *workspace,
+                           size_t workspace_bytes, void *stream);
+size_t xv_pca_plda_groups_workspace_bytes(int n_groups, int dim);
+int xv_backend_prepare_groups_f32(const float *y, int64_t ldy, int n_rows, const int32_t *grp_row0, int n_groups, int max_n, int dim,
+                                  const int32_t *grp_dim, const double *grp_psi, const double *grp_map, const double *grp_off,
+                                  int side, float *out, int64_t ldo, float *r, int32_t *status, void *stream);
 
 /* Stage 1 of the recipe: MFCC features and the energy VAD (compute-mfcc-feats / compute-vad; csrc/xv_mfcc.hip).
  * xv_mfcc_f32  MFCC rows of n_utts utterances in one launch.  samples: every utterance's samples back to back, int16

@@ -298,6 +298,10 @@ def cmd_diarize(args):
         raise SystemExit("--threshold must be a number, got %r" % args.threshold)
     if args.rttm_channel < 0:
         raise SystemExit("--rttm-channel must not be negative, got %d" % args.rttm_channel)
+    try:
+        backend.check_target_energy(args.target_energy)
+    except ValueError:
+        raise SystemExit("--target-energy must be in (0, 1], got %r" % args.target_energy)
     segments = read_segments(args.segments)
     num_spk = {}
     if args.reco2num_spk:
@@ -340,8 +344,13 @@ def cmd_diarize(args):
         for r, n, k in zip(recos, sizes, counts):
             if k is not None and k > n:
                 logger.warning("recording %s: %d speakers asked for, %d vectors: using %d" % (r, k, n, n))
+    pca = {}
     try:
-        slots, _ = backend.diarize(x, sizes, plda, mean=mean, transform=t, threshold=args.threshold, num_spk=counts)
+        if backend.target_energy_is_one(args.target_energy):
+            slots, _ = backend.diarize(x, sizes, plda, mean=mean, transform=t, threshold=args.threshold, num_spk=counts)
+        else:
+            slots, _ = backend.diarize(x, sizes, plda, mean=mean, transform=t, threshold=args.threshold, num_spk=counts,
+                                       target_energy=args.target_energy, pca_report=pca)
     except ValueError as e:
         raise SystemExit("%s: no labels written" % e)
     label_of, by_reco, n_speakers, at = {}, [], 0, 0
@@ -357,6 +366,12 @@ def cmd_diarize(args):
         _write_renamed(args.rttm, rttm_text(by_reco, args.rttm_channel))
     logger.info("Diarized %d recordings: %d vectors of dimension %d into %d speakers (%d segments without a vector skipped)" %
                 (len(recos), len(keys), dim, n_speakers, missing))
+    if pca:
+        info = pca["info"]
+        logger.info("Per-recording PCA at target energy %g: mean retained dimension %.2f of %d; %d recordings fell back to the "
+                    "global model (%d without energy, %d without convergence)" %
+                    (args.target_energy, float(pca["dim"].mean()), dim, int((info != 0).sum()), int((info == 1).sum()),
+                     int((info == 2).sum())))
 
 
 def cmd_interpolate_plda(args):
@@ -501,6 +516,10 @@ def main(argv=None):
     p.add_argument("--lda", help="transform.mat: transform-vec + ivector-normalize-length after the mean")
     p.add_argument("--threshold", type=float, default=0.0, help="stop when no pair of clusters has an average score this large")
     p.add_argument("--reco2num-spk", help="lines <reco> <count>: these recordings stop at exactly that many clusters")
+    p.add_argument("--target-energy", type=float, default=1.0,
+                   help="ivector-plda-scoring-dense --target-energy, in (0, 1]: score every recording in the PCA subspace of its own "
+                        "vectors that holds this share of their variance, under the PLDA projected into it (the callhome recipe "
+                        "passes 0.1).  The default here is 1.0 -- no PCA, the scores of earlier versions -- where Kaldi's is 0.5")
     p.add_argument("--rttm", help="write the speaker turns here")
     p.add_argument("--rttm-channel", type=int, default=0)
     p.add_argument("plda"); p.add_argument("vectors"); p.add_argument("segments"); p.add_argument("labels_out")

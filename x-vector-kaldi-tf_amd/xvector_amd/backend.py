@@ -9,6 +9,9 @@
   diarize / score_blocks / ahc_batch   diarization: one such problem per recording, all recordings' score
                  blocks from one launch (xv_score_blocks_f32) and one workgroup per recording's dendrogram
                  (xv_ahc_average_batch_f64)
+  est_pca / Plda.apply_transform / pca_plda_groups   the per-recording PCA of ivector-plda-scoring-dense --target-energy and the
+                 PLDA projected into it: fp64 on the host, and every recording's eigenproblems side by side on
+                 the device (xv_pca_plda_groups_f64, xv_backend_prepare_groups_f32) behind diarize / score_blocks(target_energy=)
   interpolate_plda   a Plda between two (the out-of-domain model and the one fitted on the clusters)   (host, fp64)
   read_plda / write_plda, read_transform / write_transform   Kaldi's <Plda> object and transform.mat, binary and text
   prepare        ivector-subtract-global-mean | transform-vec | ivector-normalize-length | Plda::TransformIvector on the GPU
@@ -111,6 +114,21 @@ class Plda(object):
     @property
     def dim(self):
         return self.mean.shape[0]
+
+    def covariances(self):
+        """(within, between) = (P^-1 P^-T, P^-1 diag(psi) P^-T), the model's two covariances (float64)."""
+        inv = np.linalg.inv(self.transform)
+        return inv @ inv.T, (inv * self.psi) @ inv.T
+
+    def apply_transform(self, A, covariances=None):
+        """Kaldi's Plda::ApplyTransform: the model of the vectors u = A y, A [p, d] (DESIGN.md §8.16).  mean A mu, covariances
+        A W A^T and A B A^T, diagonalised again as ``plda_from_covariances`` does.  covariances: what ``covariances()`` returned,
+        for callers that project one model many times.  -> Plda of dimension p."""
+        A = np.asarray(A, dtype=np.float64)
+        if A.ndim != 2 or A.shape[1] != self.dim or not 1 <= A.shape[0] <= self.dim:
+            raise ValueError("apply_transform: the transform must be [p, %d] with 1 <= p <= %d" % (self.dim, self.dim))
+        W, B = self.covariances() if covariances is None else covariances
+        return plda_from_covariances(A @ self.mean, A @ B @ A.T, A @ W @ A.T)
 
 
 def _spk_stats(x, groups):
@@ -615,6 +633,142 @@ def plan_ahc_batch(sizes, max_bytes=AHC_MAX_BYTES, max_batch_n=hiplib.AHC_BATCH_
     return calls, routed
 
 
+# ---- per-recording PCA (ivector-plda-scoring-dense --target-energy) ----
+PCA_MAX_BYTES = 1 << 30            # the per-group tables and workspace of one xv_pca_plda_groups_f64 call are at most this large
+PCA_INFO_NAMES = ("PCA applied", "fallback: no energy", "fallback: no convergence")
+
+
+def target_energy_is_one(target_energy):
+    """Kaldi's ApproxEqual(target_energy, 1.0, 0.001): the PCA is skipped altogether."""
+    t = float(target_energy)
+    return abs(t - 1.0) <= 0.001 * (abs(t) + 1.0)
+
+
+def check_target_energy(target_energy):
+    """The target energy as a float; ValueError unless it is in (0, 1] or approximately 1."""
+    t = float(target_energy)
+    if not np.isfinite(t) or not (target_energy_is_one(t) or 0.0 < t <= 1.0):
+        raise ValueError("the target energy must be in (0, 1], got %r" % (target_energy,))
+    return t
+
+
+def energy_dim(eigvals, target_energy):
+    """The retained dimension of the energy rule for eigenvalues sorted descending: with k the smallest count whose share
+    (l_1 + .. + l_k) / total exceeds target_energy (d if none), p = min(k + 1, d) -- Kaldi's loop steps once past the count it
+    summed.  None (the fallback) when the total is not finite or not > 0."""
+    s = np.asarray(eigvals, dtype=np.float64)
+    total = 0.0
+    for v in s.tolist():
+        total += v
+    if not (np.isfinite(total) and total > 0.0):
+        return None
+    cum, k = 0.0, s.size
+    for i, v in enumerate(s.tolist()):
+        cum += v
+        if cum / total > target_energy:
+            k = i + 1
+            break
+    return min(k + 1, s.size)
+
+
+def order_eigenpairs(s, u):
+    """(eigenvalues descending, eigenvectors as ROWS): ties go to the smaller original column index, and every eigenvector's sign
+    is fixed so that its first component of largest magnitude is positive."""
+    s = np.asarray(s, dtype=np.float64)
+    o = np.argsort(-s, kind="stable")
+    rows = np.asarray(u, dtype=np.float64)[:, o].T.copy()
+    at = np.argmax(np.abs(rows), axis=1)
+    rows[rows[np.arange(rows.shape[0]), at] < 0] *= -1.0
+    return s[o], rows
+
+
+def est_pca(y, target_energy):
+    """Kaldi's EstPca on one recording's rows y[n, d]: C = (1/n) sum y y^T - m m^T in float64, its eigenpairs
+    ordered by ``order_eigenpairs``, the retained dimension by ``energy_dim``.  The vectors are NOT centred when projected:
+    u = A y.  -> (A [p, d], eigvals [d] descending), or None for the fallback to the global model."""
+    y = np.asarray(y, dtype=np.float64)
+    if y.ndim != 2 or y.shape[0] < 1:
+        raise ValueError("est_pca: y must be [n, d] with n >= 1")
+    n = y.shape[0]
+    m = y.sum(axis=0) / n
+    C = y.T @ y / n - np.outer(m, m)
+    if not np.all(np.isfinite(C)):
+        return None
+    s, rows = order_eigenpairs(*np.linalg.eigh((C + C.T) / 2))
+    p = energy_dim(s, target_energy)
+    if p is None:
+        return None
+    return rows[:p], s
+
+
+def host_pca_tables(y, group_sizes, plda, target_energy):
+    """The per-group tables of xv_pca_plda_groups_f64 from ``est_pca`` and ``Plda.apply_transform`` on the host, one recording
+    after the other (the NumPy route xv_pca_plda_groups_f64 is measured against): -> dict(dim int32 [G], info int32 [G],
+    psi [G, d], map [G, d, d], off [G, d]) with z = map y + off; a fallback group holds the global model."""
+    y = np.asarray(y, dtype=np.float64)
+    sizes = np.asarray(group_sizes, dtype=np.int64)
+    G, d = sizes.size, plda.dim
+    out = dict(dim=np.full(G, d, np.int32), info=np.zeros(G, np.int32), psi=np.zeros((G, d)), map=np.zeros((G, d, d)),
+               off=np.zeros((G, d)))
+    at = 0
+    cov = plda.covariances()
+    for g, n in enumerate(sizes.tolist()):
+        est = est_pca(y[at:at + n, :d], target_energy)
+        at += n
+        if est is None:
+            out["info"][g] = 1
+            out["psi"][g], out["map"][g], out["off"][g] = plda.psi, plda.transform, -(plda.transform @ plda.mean)
+            continue
+        A = est[0]
+        pg = plda.apply_transform(A, cov)
+        p = A.shape[0]
+        out["dim"][g] = p
+        out["psi"][g, :p] = pg.psi
+        out["map"][g, :p] = pg.transform @ A
+        out["off"][g, :p] = -(pg.transform @ pg.mean)
+    return out
+
+
+def plan_pca_groups(n_groups, dim, max_bytes=PCA_MAX_BYTES, keep_pca=False):
+    """Cut n_groups groups into calls of xv_pca_plda_groups_f64 whose per-group tables and workspace fit max_bytes:
+    -> (groups per call, [(g_lo, g_hi)]).  One group alone above max_bytes is an error."""
+    per = 8 * (3 * dim + (2 if keep_pca else 1) * dim * dim) + hiplib.pca_plda_groups_workspace_bytes(1, dim)
+    if per > max_bytes:
+        raise ValueError("pca_plda_groups: one group of dimension %d needs %d bytes, more than max_bytes = %d" % (dim, per, max_bytes))
+    step = int(min(n_groups, max_bytes // per))
+    return step, [(lo, min(lo + step, n_groups)) for lo in range(0, n_groups, step)]
+
+
+def pca_plda_groups(y_rows, tables, plda, target_energy, grp_dim, grp_info, max_bytes=PCA_MAX_BYTES, keep_pca=False):
+    """Every group's PCA and projected PLDA on the device (xv_pca_plda_groups_f64).  y_rows: float32 device rows [N, >= d], the
+    vectors after mean subtraction, LDA and length normalisation (``prepare(..., SIDE_PLAIN, plda=None)``); tables: their
+    GroupTables; grp_dim, grp_info: int32 device tensors [G] that receive every group's retained dimension and 0 / 1 / 2 (PCA
+    applied / fallback for energy / fallback for non-convergence).  The fp64 model is uploaded once.  The group list is cut into
+    calls whose tables and workspace fit max_bytes (``plan_pca_groups``); this GENERATOR yields, per call,
+    (g_lo, g_hi, dict(eigvals [g, d], psi [g, d], map [g, d, d], off [g, d], pca [g, d, d] or None)) -- float64 device tensors
+    that the next call overwrites, so the consumer launches what reads them (``hiplib.backend_prepare_groups``) before it asks
+    for the next.  Nothing is synchronised or read back: a skipped group shows in tables.status."""
+    import torch
+    hiplib.require_gpu()
+    target_energy = check_target_energy(target_energy)
+    d, G = plda.dim, tables.sizes.size
+    if d > hiplib.PCA_MAX_DIM:
+        raise ValueError("pca_plda_groups: dimension %d exceeds %d, the limit of xv_pca_plda_groups_f64" % (d, hiplib.PCA_MAX_DIM))
+    step, calls = plan_pca_groups(G, d, max_bytes, keep_pca)
+    dev = y_rows.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    W, B = plda.covariances()
+    model = [torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev) for a in (plda.mean, W, B, plda.transform, plda.psi)]
+    with torch.cuda.device(dev):
+        t = dict(eigvals=torch.empty((step, d), **f64), psi=torch.empty((step, d), **f64), map=torch.empty((step, d, d), **f64),
+                 off=torch.empty((step, d), **f64), pca=torch.empty((step, d, d), **f64) if keep_pca else None)
+        ws = torch.empty(hiplib.pca_plda_groups_workspace_bytes(step, d), dtype=torch.uint8, device=dev)
+        for lo, hi in calls:
+            hiplib.pca_plda_groups(y_rows, tables.row0_d[lo:hi + 1], d, min(target_energy, 1.0), *model, grp_dim[lo:hi], grp_info[lo:hi],
+                                   t["eigvals"], t["pca"], t["psi"], t["map"], t["off"], tables.status, ws)
+            yield lo, hi, {k: (None if v is None else v[:hi - lo]) for k, v in t.items()}
+
+
 def _nonfinite_upper(scores, tables):
     """A device bool: does the strict upper triangle of any group's block hold a value that is not finite?  No host sync."""
     import torch
@@ -635,33 +789,61 @@ def _nonfinite_upper(scores, tables):
     return bad
 
 
-def score_blocks(x, group_sizes, plda, mean=None, transform=None, device="cuda:0"):
+def score_blocks(x, group_sizes, plda, mean=None, transform=None, device="cuda:0", target_energy=1.0, pca_max_bytes=PCA_MAX_BYTES):
     """Every group's PLDA score matrix from one launch (xv_score_blocks_f32): x[N, D] raw vectors, group g the next
     group_sizes[g] rows.  The chain is that of ``score_matrix_self`` (two prepare calls over all rows, one-utterance enrolments),
     and a block holds the bits ``score_matrix_self`` gives that group's rows.  -> (scores, tables): the packed float32 device
-    blocks and their GroupTables; tables.status stays on the device (``ahc_batch`` downloads it with its results)."""
+    blocks and their GroupTables; tables.status stays on the device (``ahc_batch`` downloads it with its results).
+
+    target_energy below 1 (ivector-plda-scoring-dense --target-energy): every group is scored under its own
+    PCA and projected PLDA instead -- one PLAIN prepare without the PLDA, ``pca_plda_groups``, the grouped prepare for both
+    sides, then the same scorer.  tables.pca is then the int32 device tensor [2 G] of the retained dimensions followed by the
+    0 / 1 / 2 fallback codes (None on the default route, which is the code above unchanged)."""
     import torch
     hiplib.require_gpu()
+    target_energy = check_target_energy(target_energy)
+    use_pca = not target_energy_is_one(target_energy)
+    if use_pca and plda.dim > hiplib.PCA_MAX_DIM:
+        raise ValueError("score_blocks: the per-recording PCA handles dimensions up to %d, the PLDA has %d" %
+                         (hiplib.PCA_MAX_DIM, plda.dim))
     tables = GroupTables(group_sizes, device)
+    tables.pca = None
     n = len(x)
     if n != tables.n_rows:
         raise ValueError("score_blocks: %d vectors, but the group sizes add up to %d" % (n, tables.n_rows))
     ln = transform is not None
-    E, r = prepare(x, hiplib.SIDE_ENROL, np.ones(n, np.int32), mean, transform, plda, ln, device)
-    T, _ = prepare(x, hiplib.SIDE_TEST, None, mean, transform, plda, ln, device)
+    if use_pca:
+        d, G = plda.dim, tables.sizes.size
+        Y, _ = prepare(x, hiplib.SIDE_PLAIN, None, mean, transform, None, ln, device)
+        if Y.shape[1] < d:
+            raise ValueError("PLDA dim %d != vector dim %d" % (d, Y.shape[1]))
+        E = torch.empty((n, kpad_for(2 * d)), dtype=torch.float32, device=device)
+        T = torch.empty_like(E)
+        r = torch.empty(n, dtype=torch.float32, device=device)
+        tables.pca = torch.empty(2 * G, dtype=torch.int32, device=device)
+        grp_dim, grp_info = tables.pca[:G], tables.pca[G:]
+        for lo, hi, t in pca_plda_groups(Y, tables, plda, target_energy, grp_dim, grp_info, pca_max_bytes):
+            mx = int(tables.sizes[lo:hi].max())
+            for side, out, rr in ((hiplib.SIDE_ENROL, E, r), (hiplib.SIDE_TEST, T, None)):
+                hiplib.backend_prepare_groups(Y, tables.row0_d[lo:hi + 1], mx, d, grp_dim[lo:hi], t["psi"], t["map"], t["off"], side, out,
+                                              rr, tables.status)
+    else:
+        E, r = prepare(x, hiplib.SIDE_ENROL, np.ones(n, np.int32), mean, transform, plda, ln, device)
+        T, _ = prepare(x, hiplib.SIDE_TEST, None, mean, transform, plda, ln, device)
     scores = torch.empty(tables.scores_elems, dtype=torch.float32, device=device)
     hiplib.score_blocks(E, T, r, tables.row0_d, tables.score0_d, tables.max_n, scores, tables.status)
     return scores, tables
 
 
-def ahc_batch(scores, tables, thresholds, min_clusters, max_bytes=AHC_MAX_BYTES, max_batch_n=hiplib.AHC_BATCH_MAX_N):
+def ahc_batch(scores, tables, thresholds, min_clusters, max_bytes=AHC_MAX_BYTES, max_batch_n=hiplib.AHC_BATCH_MAX_N, extra=None):
     """Average-linkage clustering of every group's block of the packed ``scores`` (what ``score_blocks`` returns), one workgroup
     per group (xv_ahc_average_batch_f64).  thresholds float [G] and min_clusters int [G] are each group's stop rule, as in
     ``ahc``.  The group list is cut into calls whose workspaces fit max_bytes; a group above max_batch_n goes through ``ahc`` on
     its block (identical results by the kernels' contract).  Put large groups first (``diarize`` does): workgroups start in group
     order.  One download at the end: results, the kernels' status word and the finite check of the upper triangles.
     -> (labels, merges): per group, in the given order, labels int32[n_g] (the local slot of each item's cluster) and
-    (a int32[M], b int32[M], score float64[M])."""
+    (a int32[M], b int32[M], score float64[M]).  extra (an int32 device tensor, e.g. tables.pca): it rides on that download, and
+    the result is (labels, merges, extra as NumPy)."""
     import torch
     hiplib.require_gpu()
     G = tables.sizes.size
@@ -696,7 +878,8 @@ def ahc_batch(scores, tables, thresholds, min_clusters, max_bytes=AHC_MAX_BYTES,
                                          minc_d[lo:hi], int(tables.sizes[lo:hi].max()), m_a, m_b, m_s, cnt[lo:hi], lab, tables.status,
                                          ws)
                 at += hi - lo
-        flags = torch.cat([tables.status.to(torch.int32), nonfinite.to(torch.int32).reshape(1)])
+        flags = torch.cat([tables.status.to(torch.int32), nonfinite.to(torch.int32).reshape(1)] +
+                          ([] if extra is None else [extra.to(torch.int32).reshape(-1)]))
         ints_h, m_s_h, flags_h = ints.cpu().numpy(), m_s.cpu().numpy(), flags.cpu().numpy()
     if flags_h[1]:
         raise ValueError("ahc_batch: the upper triangle of a group's score matrix holds a value that is not finite")
@@ -711,17 +894,26 @@ def ahc_batch(scores, tables, thresholds, min_clusters, max_bytes=AHC_MAX_BYTES,
             r0, r1, m = int(tables.row0[g]), int(tables.row0[g + 1]), int(cnt_h[g])
             labels[g] = lab_h[r0:r1].copy()
             merges[g] = (a_h[r0:r0 + m].copy(), b_h[r0:r0 + m].copy(), m_s_h[r0:r0 + m].copy())
+    if extra is not None:
+        return labels, merges, flags_h[2:].copy()
     return labels, merges
 
 
-def diarize(x, group_sizes, plda, mean=None, transform=None, threshold=0.0, num_spk=None, device="cuda:0"):
+def diarize(x, group_sizes, plda, mean=None, transform=None, threshold=0.0, num_spk=None, device="cuda:0", target_energy=1.0,
+            pca_report=None):
     """Cluster every recording's vectors on their own: x[N, D] raw vectors, recording g the next group_sizes[g] rows.  The
     recordings are sorted by size, descending, for the device, scored against themselves in one launch (``score_blocks``) and
     clustered one workgroup each (``ahc_batch``); the results come back in the caller's order.  threshold: the stop rule of every
     recording; num_spk (None, or one entry per recording, None or a count): a recording with a count stops at exactly
     min(count, n_g) clusters instead.  -> (labels int32[N]: the local slot of each vector's cluster within its recording,
-    merges: per recording (a, b, score))."""
+    merges: per recording (a, b, score)).
+
+    target_energy below 1: every recording is scored under its own PCA and projected PLDA (``score_blocks``); the default, 1.0,
+    is the route without a PCA, unchanged.  pca_report (a dict, optional) then receives 'dim' and 'info', int32 [G] in the
+    caller's order: each recording's retained dimension and 0 / 1 / 2 (PCA applied / fallback for energy / for non-convergence);
+    they come down with ``ahc_batch``'s download."""
     hiplib.require_gpu()
+    target_energy = check_target_energy(target_energy)
     sizes = np.asarray(group_sizes, dtype=np.int64).reshape(-1)
     thr, minc = diarize_stop_rules(sizes, threshold, num_spk)
     x = np.asarray(x, dtype=np.float32)
@@ -730,8 +922,18 @@ def diarize(x, group_sizes, plda, mean=None, transform=None, threshold=0.0, num_
     order, _ = size_order(sizes)
     row0 = np.concatenate([[0], np.cumsum(sizes)])
     rows = np.concatenate([np.arange(row0[g], row0[g + 1]) for g in order])
-    scores, tables = score_blocks(x[rows], sizes[order], plda, mean, transform, device)
-    lab_sorted, merges_sorted = ahc_batch(scores, tables, thr[order], minc[order])
+    if target_energy_is_one(target_energy):
+        scores, tables = score_blocks(x[rows], sizes[order], plda, mean, transform, device)
+        lab_sorted, merges_sorted = ahc_batch(scores, tables, thr[order], minc[order])
+    else:
+        scores, tables = score_blocks(x[rows], sizes[order], plda, mean, transform, device, target_energy)
+        lab_sorted, merges_sorted, pca = ahc_batch(scores, tables, thr[order], minc[order], extra=tables.pca)
+        if pca_report is not None:
+            G = sizes.size
+            pca_report["dim"] = np.empty(G, np.int32)
+            pca_report["info"] = np.empty(G, np.int32)
+            pca_report["dim"][order] = pca[:G]
+            pca_report["info"][order] = pca[G:]
     labels = np.empty(x.shape[0], dtype=np.int32)
     labels[rows] = np.concatenate(lab_sorted)
     merges = [None] * sizes.size

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 39
+ABI_VERSION = 40
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -133,6 +133,11 @@ _SIGNATURES = {
     # diarization: one clustering problem per recording
     "xv_ahc_average_batch_f64": (_ci, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "xv_ahc_average_batch_workspace_bytes": (_sz, [_ci]),
+    # diarization: per-recording PCA and the PLDA projected into it
+    "xv_pca_plda_groups_f64": (_ci, [_vp, _i64, _ci, _vp, _ci, _ci, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, _sz, _vp]),
+    "xv_pca_plda_groups_workspace_bytes": (_sz, [_ci, _ci]),
+    "xv_backend_prepare_groups_f32": (_ci, [_vp, _i64, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _i64, _vp, _vp, _vp]),
     "xv_mfcc_f32": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _ci, _i64, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _ci, _vp, _ci, _ci, _ci, _ci,
                           _cf, _cf, _ci, _ci, _ci, _cf, _vp, _i64, _vp, _i64, _vp]),
     "xv_vad_energy_f32": (_ci, [_vp, _i64, _vp, _vp, _ci, _cf, _cf, _ci, _cf, _vp, _vp]),
@@ -177,6 +182,8 @@ MOMENT_SLAB = 2048                # XV_MOMENT_SLAB: rows per partial of xv_momen
 MOMENT_DIM_MAX = 256
 AHC_MAX_N = 32768                  # XV_AHC_MAX_N: items of one xv_ahc_average_f64 call
 AHC_BATCH_MAX_N = 4096             # XV_AHC_BATCH_MAX_N: items of one group of xv_ahc_average_batch_f64
+PCA_MAX_DIM = 128                  # XV_PCA_MAX_DIM: the vector dimension of xv_pca_plda_groups_f64
+PCA_MAX_SWEEPS = 30                # XV_PCA_MAX_SWEEPS: the sweep cap of its Jacobi iteration
 
 _lib = None
 
@@ -1453,6 +1460,58 @@ def ahc_average_batch(scores, grp_row0, grp_score0, grp_ws0, threshold, min_clus
                                         _dev(n_merges, i32, "n_merges", n_groups), _dev(labels, i32, "labels"),
                                         _dev(status, i32, "status", 1), _ptr(workspace), _nbytes(workspace), _stream()),
            "xv_ahc_average_batch_f64")
+
+
+def pca_plda_groups_workspace_bytes(n_groups, dim):
+    return int(load().xv_pca_plda_groups_workspace_bytes(int(n_groups), int(dim)))
+
+
+def pca_plda_groups(y, grp_row0, dim, target_energy, mean, within, between, transform, psi, grp_dim, grp_info, eigvals, pca, grp_psi,
+                    grp_map, grp_off, status, workspace=None):
+    """Per-group PCA and the PLDA projected into it (xv_pca_plda_groups_f64; see include/xvector_hip.h).  y: float32 rows
+    [n_rows, >= dim] (its row stride is passed as ldy); grp_row0: int32 [G + 1]; the model mean, psi: float64 [dim], within,
+    between, transform: float64 [dim, dim].  Outputs, all on the device: grp_dim, grp_info: int32 [G]; eigvals, grp_psi, grp_off:
+    float64 [G, dim]; pca (or None), grp_map: float64 [G, dim, dim]; status: int32 [1], zeroed by the caller.  Nothing is read
+    back and the stream is not synchronised.  workspace: pca_plda_groups_workspace_bytes(G, dim) bytes (None: allocated here)."""
+    import torch
+    lib = require_gpu()
+    _rows2d(y, "y")
+    i32, f64 = torch.int32, torch.float64
+    G = grp_dim.numel()
+    dim = int(dim)
+    assert y.shape[1] >= dim
+    need = lib.xv_pca_plda_groups_workspace_bytes(G, dim)
+    if workspace is None:
+        workspace = _ws(need, y.device)
+    assert workspace.is_cuda and workspace.is_contiguous()
+    _check(lib.xv_pca_plda_groups_f64(_ptr(y), y.stride(0), y.shape[0], _dev(grp_row0, i32, "grp_row0", G + 1), G, dim,
+                                      float(target_energy), _dev(mean, f64, "mean", dim), _dev(within, f64, "within", dim * dim),
+                                      _dev(between, f64, "between", dim * dim), _dev(transform, f64, "transform", dim * dim),
+                                      _dev(psi, f64, "psi", dim), _dev(grp_dim, i32, "grp_dim"), _dev(grp_info, i32, "grp_info", G),
+                                      _dev(eigvals, f64, "eigvals", G * dim), None if pca is None else _dev(pca, f64, "pca", G * dim * dim),
+                                      _dev(grp_psi, f64, "grp_psi", G * dim), _dev(grp_map, f64, "grp_map", G * dim * dim),
+                                      _dev(grp_off, f64, "grp_off", G * dim), _dev(status, i32, "status", 1), _ptr(workspace),
+                                      _nbytes(workspace), _stream()), "xv_pca_plda_groups_f64")
+
+
+def backend_prepare_groups(y, grp_row0, max_n, dim, grp_dim, grp_psi, grp_map, grp_off, side, out, r, status):
+    """The grouped twin of backend_prepare's PLDA stage (xv_backend_prepare_groups_f32; see include/xvector_hip.h): every row of
+    y [n_rows, >= dim] through its group's z = M_g y + c_g, the PLDA length norm with psi_g and p_g, and the operand row of
+    ``side`` (SIDE_ENROL | SIDE_TEST) in out[n_rows, ldo] with exact zeros past 2 p_g; r: float32 [n_rows] or None."""
+    import torch
+    lib = require_gpu()
+    _rows2d(y, "y"); _f32_rows(out, "out")
+    i32, f64 = torch.int32, torch.float64
+    G = grp_dim.numel()
+    dim = int(dim)
+    n_rows = y.shape[0]
+    assert y.shape[1] >= dim and out.shape[0] >= n_rows and out.shape[1] == out.stride(0)
+    assert r is None or _f32(r, "r").numel() >= n_rows
+    _check(lib.xv_backend_prepare_groups_f32(_ptr(y), y.stride(0), n_rows, _dev(grp_row0, i32, "grp_row0", G + 1), G, int(max_n), dim,
+                                             _dev(grp_dim, i32, "grp_dim"), _dev(grp_psi, f64, "grp_psi", G * dim),
+                                             _dev(grp_map, f64, "grp_map", G * dim * dim), _dev(grp_off, f64, "grp_off", G * dim),
+                                             int(side), _ptr(out), out.stride(0), _ptr(r), _dev(status, i32, "status", 1), _stream()),
+           "xv_backend_prepare_groups_f32")
 
 
 def mfcc(samples, utt_offset, utt_samples, utt_row0, utt_key, total_rows, tables, opts, feats, logmel=None):
