@@ -1,8 +1,12 @@
 // EXPERIMENT: (1) operand layout of v_mfma_scale_f32_32x32x64_f8f6f4 with bf8 (e5m2) operands, (2) MFMA-only throughput of the
 // shipped bf16x3 pattern (24 x bf16 32x32x16 per 32-channel stage and wave) against the candidate "f16 + bf8 cross terms"
 // pattern (8 x f16 32x32x16 + 4 x MX 32x32x64) with register-resident operands, (3) the e2m3 conversion instruction and the
-// per-lane scale bytes of the same MFMA with 6-bit operands (cbsz:2 blgp:2).
-//   hipcc --offload-arch=gfx950 -O3 -o mx_probe mx_probe.hip && ./mx_probe [fp6]
+// per-lane scale bytes of the same MFMA with 6-bit operands (cbsz:2 blgp:2), (4) the same for v_mfma_scale_f32_16x16x128_f8f6f4:
+// operands, result, the map from every lane's scale byte to the elements it acts on, and the instruction's issue rate.
+//   hipcc --offload-arch=gfx950 -O3 -o mx_probe mx_probe.hip && ./mx_probe [fp6 | fp6x16]
+// RESULT of (4) (MI355X): H16 below holds exactly; every lane's byte (picked by op_sel, the other bytes ignored) acts on that lane's
+// own 32 elements, on both operands; 17.0 shader clocks per instruction with e2m3 operands against 32.0 with bf8 (one wave per
+// SIMD, 16 independent accumulator tiles, tied asm; the builtin's untied form measured 29.5 -- accumulator copies, not the pipe).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -379,8 +383,169 @@ static int fp6_probe()
     return bad;
 }
 
+// ---- (4) the same questions for v_mfma_scale_f32_16x16x128_f8f6f4 with cbsz:2 blgp:2 ("fp6x16" as the only argument) ------------------
+// Hypothesis H16: lane l supplies row / column (l & 15) and the 32 values of K block (l >> 4); element e of an A lane meets element e
+// of the B lane of the same block; D (4 floats per lane) = column (l & 15), rows 4 (l >> 4) + i.  Which lane's scale byte acts on
+// which elements is NOT assumed (mx16_probe.hip: with bf8 operands the four K blocks' scales do not come from the four lanes that
+// hold them): it is mapped, element by element, with a one-hot operand and a different byte in each of the four lane groups.
+typedef float f32x4p __attribute__((ext_vector_type(4)));
+
+template <int OPA, int OPB>
+__global__ void fp6x16_mfma_kernel(const float *xa, const float *xb, const int *sa, const int *sb, float *D)
+{
+    const int lane = threadIdx.x;
+    f32x16 a0, a1, b0, b1;
+    for (int i = 0; i < 16; ++i) {
+        a0[i] = xa[lane * 32 + i]; a1[i] = xa[lane * 32 + 16 + i];
+        b0[i] = xb[lane * 32 + i]; b1[i] = xb[lane * 32 + 16 + i];
+    }
+    const u32x6 ra = cvt_fp6(a0, a1, 1.f);
+    const u32x6 rb = cvt_fp6(b0, b1, 1.f);
+    const i32x8 A = {(int)ra[0], (int)ra[1], (int)ra[2], (int)ra[3], (int)ra[4], (int)ra[5], 0, 0};
+    const i32x8 B = {(int)rb[0], (int)rb[1], (int)rb[2], (int)rb[3], (int)rb[4], (int)rb[5], 0, 0};
+    const int va = (sa[lane] << (8 * OPA)) | (0x88888888 & ~(0xff << (8 * OPA)));
+    const int vb = (sb[lane] << (8 * OPB)) | (0x88888888 & ~(0xff << (8 * OPB)));
+    f32x4p c = {0.f, 0.f, 0.f, 0.f};
+    c = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(A, B, c, 2, 2, OPA, va, OPB, vb);
+    for (int i = 0; i < 4; ++i) D[(4 * (lane >> 4) + i) * 16 + (lane & 15)] = c[i];
+}
+
+// one wave per SIMD, 16 independent accumulator tiles, register operands: shader clocks per instruction at an idle chip's clock
+template <int FMT>    // 1: bf8 (cbsz:1 blgp:1)   2: e2m3 (cbsz:2 blgp:2)
+__global__ __launch_bounds__(256) void fp6x16_cycles_kernel(const int *src, float *out, long long *clk, int iters)
+{
+    i32x8 a, b;
+    for (int j = 0; j < 8; ++j) { a[j] = src[threadIdx.x * 16 + j]; b[j] = src[threadIdx.x * 16 + 8 + j]; }
+    const u32x6 a6 = {(unsigned)a[0], (unsigned)a[1], (unsigned)a[2], (unsigned)a[3], (unsigned)a[4], (unsigned)a[5]};
+    const u32x6 b6 = {(unsigned)b[0], (unsigned)b[1], (unsigned)b[2], (unsigned)b[3], (unsigned)b[4], (unsigned)b[5]};
+    int va = 127, vb = 127;
+    asm volatile("" : "+v"(va), "+v"(vb));
+    f32x4p acc[16];
+    for (int t = 0; t < 16; ++t) acc[t] = (f32x4p){0.f, 0.f, 0.f, 0.f};
+    const long long t0 = clock64(), w0 = wall_clock64();
+    for (int it = 0; it < iters; ++it)
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            // (tied asm, as in xv_gemm8_wide16.hip: the builtin has no tied form and the loop filled up with accumulator copies)
+            if constexpr (FMT == 1)
+                asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0] cbsz:1 blgp:1" : "+v"(acc[t]) : "v"(a), "v"(b), "v"(va), "v"(vb));
+            else
+                asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0] cbsz:2 blgp:2" : "+v"(acc[t]) : "v"(a6), "v"(b6), "v"(va), "v"(vb));
+        }
+    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+    float s = 0.f;
+    for (int t = 0; t < 16; ++t) s += acc[t][0] + acc[t][1] + acc[t][2] + acc[t][3];
+    const long long t1 = clock64(), w1 = wall_clock64();
+    if (s == 12345.678f) out[threadIdx.x] = s;
+    if ((threadIdx.x & 63) == 0) { clk[threadIdx.x >> 6] = t1 - t0; clk[4 + (threadIdx.x >> 6)] = w1 - w0; }
+}
+
+static int fp6x16_probe()
+{
+    int bad = 0;
+    float *dxa, *dxb, *dD; int *dsa, *dsb;
+    CK(hipMalloc(&dxa, 64 * 32 * 4)); CK(hipMalloc(&dxb, 64 * 32 * 4)); CK(hipMalloc(&dD, 256 * 4));
+    CK(hipMalloc(&dsa, 64 * 4)); CK(hipMalloc(&dsb, 64 * 4));
+    std::vector<float> xa(64 * 32), xb(64 * 32), D(256);
+    std::vector<int> sa(64, 127), sb(64, 127);
+    auto launch = [&](int opa, int opb) {
+        CK(hipMemcpy(dxa, xa.data(), xa.size() * 4, hipMemcpyHostToDevice));
+        CK(hipMemcpy(dxb, xb.data(), xb.size() * 4, hipMemcpyHostToDevice));
+        CK(hipMemcpy(dsa, sa.data(), 256, hipMemcpyHostToDevice));
+        CK(hipMemcpy(dsb, sb.data(), 256, hipMemcpyHostToDevice));
+        if (opa == 0 && opb == 0) fp6x16_mfma_kernel<0, 0><<<1, 64>>>(dxa, dxb, dsa, dsb, dD);
+        else fp6x16_mfma_kernel<2, 1><<<1, 64>>>(dxa, dxb, dsa, dsb, dD);
+        CK(hipMemcpy(D.data(), dD, 1024, hipMemcpyDeviceToHost));
+    };
+    // (a) operands and result under uniform scales: grid values, every product and sum exact
+    const float grid[] = {0.f, 0.125f, 0.5f, 1.f, 1.5f, 2.f, 3.f, 4.f, 6.f, 7.5f, 0.875f, 1.125f};
+    srand(16);
+    for (auto &v : xa) v = grid[rand() % 12] * (rand() & 1 ? 1.f : -1.f);
+    for (auto &v : xb) v = grid[rand() % 12] * (rand() & 1 ? 1.f : -1.f);
+    const std::vector<float> ra = xa, rb = xb;
+    // block_of(side, g, e): the lane group whose scale byte acts on source element e of a lane of group g; -1: the lane's own (H16)
+    int map[2][4][32];
+    auto check = [&](const char *what, bool mapped, int bit) {
+        double worst = 0, ref_max = 0;
+        for (int i = 0; i < 16; ++i)
+            for (int j = 0; j < 16; ++j) {
+                double ref = 0;
+                for (int g = 0; g < 4; ++g)
+                    for (int e = 0; e < 32; ++e) {
+                        const int ga = mapped ? map[0][g][e] : g, gb = mapped ? map[1][g][e] : g;
+                        ref += (double)ra[(i + 16 * g) * 32 + e] * rb[(j + 16 * g) * 32 + e] * ldexp(1.0, sa[i + 16 * ga] - 127 + sb[j + 16 * gb] - 127);
+                    }
+                worst = fmax(worst, fabs((double)(float)ref - D[i * 16 + j]));
+                ref_max = fmax(ref_max, fabs(ref));
+            }
+        printf("fp6 16x16x128 %-52s max |D - ref| = %g (max |ref| %g)  %s\n", what, worst, ref_max, worst == 0 ? "EXACT" : "MISMATCH");
+        if (worst != 0) bad |= bit;
+    };
+    launch(0, 0);
+    check("H16 operands / result, uniform scales:", false, 1);
+    for (int l = 0; l < 64; ++l) sa[l] = 126 + (l & 15) % 3;
+    launch(0, 0);
+    check("scale A differs per ROW (same in the four groups):", false, 2);
+    for (int l = 0; l < 64; ++l) { sa[l] = 127; sb[l] = 126 + (l & 15) % 3; }
+    launch(0, 0);
+    check("scale B differs per COLUMN:", false, 4);
+    // (b) the scale map: one-hot element e in every lane of group g (all 16 rows), the other operand all ones, byte 127 + b in group b
+    for (int side = 0; side < 2; ++side) {
+        std::vector<float> &hot = side ? xb : xa, &ones = side ? xa : xb;
+        std::vector<int> &sh = side ? sb : sa, &so = side ? sa : sb;
+        for (auto &v : ones) v = 1.f;
+        for (int l = 0; l < 64; ++l) { sh[l] = 127 + (l >> 4); so[l] = 127; }
+        printf("scale map, operand %c (source element e of the conversion: 0-15 first source, 16-31 second): group of the lane whose byte acts\n", side ? 'B' : 'A');
+        for (int g = 0; g < 4; ++g) {
+            printf("  lanes %2d-%2d:", 16 * g, 16 * g + 15);
+            for (int e = 0; e < 32; ++e) {
+                for (auto &v : hot) v = 0.f;
+                for (int i = 0; i < 16; ++i) hot[(i + 16 * g) * 32 + e] = 1.f;
+                launch(0, 0);
+                int b = -2;
+                for (int k = 0; k < 256; ++k) {
+                    const int bk = D[k] == 1.f ? 0 : D[k] == 2.f ? 1 : D[k] == 4.f ? 2 : D[k] == 8.f ? 3 : -1;
+                    b = (b == -2 || b == bk) ? bk : -1;
+                }
+                map[side][g][e] = b < 0 ? g : b;
+                if (b < 0) bad |= 8;
+                printf(" %c", b < 0 ? '?' : '0' + b);
+            }
+            printf("\n");
+        }
+    }
+    // (c) the map on random data: per-lane scales on both sides (close together: the blocks' sums are not added in one rounding), byte picked by op_sel
+    xa = ra; xb = rb;
+    for (int l = 0; l < 64; ++l) { sa[l] = 126 + rand() % 3; sb[l] = 127 + rand() % 2; }
+    launch(0, 0);
+    check("mapped scales, per-lane bytes A and B:", true, 16);
+    launch(2, 1);
+    check("mapped scales, bytes 2 / 1 by op_sel, decoys elsewhere:", true, 32);
+    bool own = true;
+    for (int s = 0; s < 2; ++s) for (int g = 0; g < 4; ++g) for (int e = 0; e < 32; ++e) own &= map[s][g][e] == g;
+    printf("scale map: %s\n", own ? "every lane's byte acts on that lane's own 32 elements" : "NOT the lane's own byte everywhere (table above)");
+    // (d) cycles
+    int *dsrc; float *dout; long long *dclk;
+    CK(hipMalloc(&dsrc, 256 * 16 * 4)); CK(hipMalloc(&dout, 1024)); CK(hipMalloc(&dclk, 64));
+    CK(hipMemset(dsrc, 0x11, 256 * 16 * 4));
+    const int iters = 20000;
+    for (int rep = 0; rep < 2; ++rep)
+        for (int fmt = 1; fmt <= 2; ++fmt) {
+            if (fmt == 1) fp6x16_cycles_kernel<1><<<1, 256>>>(dsrc, dout, dclk, iters);
+            else fp6x16_cycles_kernel<2><<<1, 256>>>(dsrc, dout, dclk, iters);
+            long long clk[8];
+            CK(hipMemcpy(clk, dclk, 64, hipMemcpyDeviceToHost));
+            printf("16x16x128 %s: %.2f clock64 ticks, %.2f wall_clock64 ticks (10 ns) per instruction (clock64 of the four waves: %.2f %.2f %.2f %.2f)\n",
+                   fmt == 1 ? "bf8 " : "e2m3", clk[0] / (16.0 * iters), clk[4] / (16.0 * iters), clk[0] / (16.0 * iters), clk[1] / (16.0 * iters),
+                   clk[2] / (16.0 * iters), clk[3] / (16.0 * iters));
+        }
+    printf("fp6x16 probe: %s (mask %d)\n", bad ? "SURPRISE" : "all as hypothesised", bad);
+    return bad;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "fp6x16")) return fp6x16_probe() ? 1 : 0;
     // ---- e2m3 conversion and scale semantics ("fp6" as the only argument: this part alone) ----
     const int fp6_bad = fp6_probe();
     if (argc > 1 && !strcmp(argv[1], "fp6")) return fp6_bad ? 1 : 0;

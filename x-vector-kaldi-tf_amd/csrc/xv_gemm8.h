@@ -5,7 +5,7 @@
 // namespace, so a kernel's symbol name does not depend on the file that defines it.
 #pragma once
 #include "xv_device.h"
-#include "xv_split8.h"
+#include "xv_split6.h"
 
 namespace {
 
@@ -25,7 +25,8 @@ __device__ __forceinline__ void for_taps(F &f)
 }
 
 struct Gemm8Params {
-    const uint8_t *x;     // split8 buffer, row 0
+    const uint8_t *x;     // split8 / split6 buffer, row 0
+    int x_format;         // XV_FMT_SPLIT8, or XV_FMT_SPLIT6 (the wide16 kernels' MX6 form only)
     long R;
     int cin, xchunks;
     const uint8_t *wt;    // tiled f16bf8 weights
@@ -35,7 +36,7 @@ struct Gemm8Params {
     const float *alpha;
     int K, dil, cout;
     const uint8_t *valid;
-    void *y;              // fp32 rows, bf16 split buffer or split8 buffer
+    void *y;              // fp32 rows, bf16 split buffer, split8 or split6 buffer (the last: the wide16 kernels only)
     int y_format, ldy, ychunks;
     float *blk;           // POOL: per-8-row-block (mean, M2) planes
     int *status;          // bit 0 is set when a split8 output had to be clamped (may be NULL)
@@ -103,12 +104,106 @@ constexpr int W_TILE = 128 * W_TLD * 4;                    // 133120
 constexpr int W_MASK_OFF = W_OPER > W_TILE ? W_OPER : W_TILE;
 constexpr size_t W_LDS_BYTES = (size_t)W_MASK_OFF + W_BM + 4 * W_BN * sizeof(float);
 
+// XV_FMT_SPLIT6 output of the 256 x 256 kernels (instantiated by the 16 x 16 MFMA form: wide_epilogue<POOL, true>).  An e2m3
+// block is the 16 channels x {lo', c} of one row and needs them in ONE lane (v_cvt_scalef32_2xpk16_fp6_f32), so a thread takes 4 rows x 16 channels of the 128-row half -- rows (tid >> 4) + 32 j, block
+// tid & 15 of the tile's 16 -- instead of wide_epilogue's 8 rows x 8 channels: the same 64 tile values, read as four 16-byte
+// pieces per row.  The column parameters are read from LDS where they are used (64 registers otherwise).  Bias, missing-tap
+// constants, mask, activation, BN scale / shift, amax / status as in wide_epilogue; a masked row is written as zeros (elements 0).
+template <class WriteTile>
+__device__ __forceinline__ void wide_epilogue_split6(const Gemm8Params &p, char *lds, const uint8_t *Ms, const float *Ps, long m0, int n0,
+                                                     int tid, int wr, WriteTile &&write_tile)
+{
+    float *T = reinterpret_cast<float *>(lds);
+    const int cg = tid & 15, r0 = tid >> 4;
+    const int gc0 = n0 + cg * 16;
+    const f32x4 *P4 = reinterpret_cast<const f32x4 *>(Ps) + cg * 4;
+    float amax = 0.f;
+    f32x4 tv[4][4];
+    float keep[4];
+    auto read_tile = [&](int h) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int lr = r0 + 32 * j;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) tv[j][q] = *reinterpret_cast<const f32x4 *>(T + lr * W_TLD + cg * 16 + 4 * q);
+            keep[j] = Ms[h * 128 + lr] ? 1.f : 0.f;
+        }
+    };
+    auto process = [&](int h) {
+        const long mh = m0 + h * 128;
+        if (p.tapbias) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                unsigned m = Ms[h * 128 + r0 + 32 * j] >> 1;
+                while (m) {
+                    const int t = __builtin_ctz(m);
+                    m &= m - 1;
+                    const f32x4 *c = reinterpret_cast<const f32x4 *>(p.tapbias + (size_t)t * p.cout + gc0);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) tv[j][q] -= c[q];
+                }
+            }
+        }
+        const int c = cg & 1;                            // block of the 32-channel slab gc0 >> 5
+        char *ybase = reinterpret_cast<char *>(p.y) + (size_t)(gc0 >> 5) * SROW;
+        const size_t yrow = (size_t)p.ychunks * SROW;
+        auto rows = [&](auto MODE) {
+            constexpr int mode = decltype(MODE)::value;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long gr = mh + r0 + 32 * j;
+                float v[16];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const f32x4 b = P4[q], sc = P4[W_BN / 4 + q], sh = P4[2 * W_BN / 4 + q], al = P4[3 * W_BN / 4 + q];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float z = tv[j][q][i] + b[i];
+                        const float a = mode == 1 ? fmaxf(al[i] * z, z) : mode == 2 ? fmaxf(z, 0.f) : fmaxf(z, 0.f) + al[i] * fminf(z, 0.f);
+                        v[4 * q + i] = keep[j] != 0.f ? a * sc[i] + sh[i] : 0.f;
+                    }
+                }
+                xv_f16x8 h0, h1;
+                xv_u32x6 x6;
+                int e8m0;
+                xv_split6_encode16<true>(v, h0, h1, x6, e8m0, amax);
+                const int sw = (int)(gr >> 1) & 7;
+                char *row = ybase + (size_t)gr * yrow;
+                *reinterpret_cast<xv_f16x8 *>(row + (((2 * c) ^ sw) << 4)) = h0;
+                *reinterpret_cast<xv_f16x8 *>(row + (((2 * c + 1) ^ sw) << 4)) = h1;
+                *reinterpret_cast<xv_i32x4 *>(row + (((4 + c) ^ sw) << 4)) = (xv_i32x4){(int)x6[0], (int)x6[1], (int)x6[2], (int)x6[3]};
+                // (the 2^-11 of the cross terms rides in the activation side's byte; XV_SPLIT6_E8M0_MIN keeps it positive)
+                *reinterpret_cast<xv_i32x4 *>(row + (((6 + c) ^ sw) << 4)) = (xv_i32x4){(int)x6[4], (int)x6[5], e8m0 - XV_SPLIT6_LO_EXP, 0};
+            }
+        };
+        if (p.act == XV_ACT_LRELU) rows(std::integral_constant<int, 1>{});
+        else if (p.act == XV_ACT_RELU) rows(std::integral_constant<int, 2>{});
+        else rows(std::integral_constant<int, 0>{});
+    };
+    __syncthreads();                                    // (the sequence of wide_epilogue)
+    if (wr == 0) write_tile(T);
+    __syncthreads();
+    read_tile(0);
+    __syncthreads();
+    if (wr == 1) write_tile(T);
+    __builtin_amdgcn_sched_barrier(0);
+    process(0);
+    __syncthreads();
+    read_tile(1);
+    __builtin_amdgcn_sched_barrier(0);
+    process(1);
+    if (amax > XV_SPLIT8_MAX && p.status) atomicOr(p.status, 1);
+}
+
 // Epilogue of the 256 x 256 kernels (both MFMA shapes), 128 rows at a time through an fp32 tile that re-uses the operand area:
 // write_tile(T) puts the calling wave's 128 x 64 accumulators into the tile of its half.
-template <bool POOL, class WriteTile>
+template <bool POOL, bool Y6 = false, class WriteTile>
 __device__ __forceinline__ void wide_epilogue(const Gemm8Params &p, char *lds, const uint8_t *Ms, const float *Ps, long m0, int n0,
                                               int tid, int wr, WriteTile &&write_tile)
 {
+    // (a compile-time choice: as a run-time branch beside the other formats it cost every !POOL kernel 70 spilled registers in
+    // the epilogue, the SPLIT8 launches included)
+    if constexpr (Y6) return wide_epilogue_split6(p, lds, Ms, Ps, m0, n0, tid, wr, write_tile);
     float *T = reinterpret_cast<float *>(lds);
     const int cg = tid & 31;                            // 8-channel group of the 256-column tile
     const int gc0 = n0 + cg * 8;

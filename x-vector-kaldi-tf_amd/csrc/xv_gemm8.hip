@@ -530,6 +530,11 @@ int launch_gemm8(const Gemm8Params &p0, hipStream_t st)
         else if (wide_ok && (want == 512 || want == 1024 || (want == 0 && wide_pays))) wm = 8;
         else if (want == 256 || (want == 0 && p.K >= 5 && big_enough)) wm = 4;
     }
+    // the e2m3 forms exist in the 16 x 16 MFMA kernel only: split6 input in its main loop, split6 output in its form of wide_epilogue
+    if (p.x_format == XV_FMT_SPLIT6 && wm != 16)
+        return fail(XV_ERR_UNSUPPORTED, "tdnn_f16mx6: needs an even number of 32-channel slabs, K in {3,5,7}, Cout % 256 == 0 and a split-format or pooled output");
+    if (p.y && p.y_format == XV_FMT_SPLIT6 && (wm != 16 || p.blk))
+        return fail(XV_ERR_UNSUPPORTED, "tdnn_f16bf8: XV_FMT_SPLIT6 output needs the 16 x 16 MFMA form of the 256 x 256 tile (an even number of slabs, K in {3,5,7}, Cout % 256 == 0)");
     if (wm >= 8) {
         p.n_nt = p.cout / W_BN;
         p.n_mt = (int)((p.R + W_BM - 1) / W_BM);
@@ -575,6 +580,97 @@ __global__ void pack_weights_f16bf8_kernel(const float *__restrict__ w, int K, i
     uint8_t *t = wt + tile * B_BYTES + n * 64 + ((g ^ ((n >> 2) & 3)) << 4);
     *reinterpret_cast<xv_f16x8 *>(t) = hi;
     *reinterpret_cast<xv_i32x4 *>(t + B_PLANE) = x8;
+}
+
+// The same tiles with the 8-bit plane as e2m3 blocks (xv_split6.h): column n, block c = channels 16c..16c+15 of the slab; slot c of the
+// plane = dwords 0-3 of [clamp(w) | 2^11 lo], slot 2+c = [dword 4 | dword 5 | E8M0 byte | 0] -- the two 16-byte reads a lane of
+// tdnn_gemm_f16bf8_wide16_kernel makes for K block (item, c).  The fp16 plane is xv_pack_weights_f16bf8's, bit for bit.
+__global__ void pack_weights_f16mx6_kernel(const float *__restrict__ w, int K, int cin, int cout, int n_chunks,
+                                           uint8_t *__restrict__ wt, size_t total)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;      // one (tile, col, block)
+    if (i >= total) return;
+    const int c = (int)(i & 1);
+    const int n = (int)((i >> 1) & 127);
+    const size_t tile = i >> 8;
+    const int tap = (int)(tile % K);
+    const int chunk = (int)((tile / K) % n_chunks);
+    const int nt = (int)(tile / ((size_t)K * n_chunks));
+    const int gn = nt * 128 + n;
+    float v[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int ch = chunk * 32 + c * 16 + e;
+        v[e] = (ch < cin && gn < cout) ? w[((size_t)tap * cin + ch) * cout + gn] : 0.f;
+    }
+    xv_f16x8 h0, h1;
+    xv_u32x6 x6;
+    int e8m0;
+    float amax = 0.f;
+    xv_split6_encode16<false>(v, h0, h1, x6, e8m0, amax);
+    const int sw = (n >> 2) & 3;
+    uint8_t *t = wt + tile * B_BYTES + n * 64;
+    *reinterpret_cast<xv_f16x8 *>(t + (((2 * c) ^ sw) << 4)) = h0;
+    *reinterpret_cast<xv_f16x8 *>(t + (((2 * c + 1) ^ sw) << 4)) = h1;
+    *reinterpret_cast<xv_i32x4 *>(t + B_PLANE + ((c ^ sw) << 4)) = (xv_i32x4){(int)x6[0], (int)x6[1], (int)x6[2], (int)x6[3]};
+    *reinterpret_cast<xv_i32x4 *>(t + B_PLANE + (((2 + c) ^ sw) << 4)) = (xv_i32x4){(int)x6[4], (int)x6[5], e8m0, 0};
+}
+
+// fp32 rows -> split6 / back (tests and tooling).  Element k of a block sits at bits [6k, 6k + 6) of its six dwords; the conversion
+// instruction puts its first source's value i at element XV_SPLIT6_ELEM(0, i), its second source's at XV_SPLIT6_ELEM(1, i).
+__global__ void split6_encode_kernel(const float *__restrict__ x, long R, int c, int ldx, uint8_t *__restrict__ xs, int chunks,
+                                     int *status)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;      // one (row, slab, block)
+    if (i >= (size_t)R * chunks * 2) return;
+    const int b = (int)(i & 1);
+    const int ch = (int)((i >> 1) % chunks);
+    const long r = (long)(i / ((size_t)2 * chunks));
+    float v[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int cc = ch * 32 + b * 16 + e;
+        v[e] = cc < c ? x[(size_t)r * ldx + cc] : 0.f;
+    }
+    xv_f16x8 h0, h1;
+    xv_u32x6 x6;
+    int e8m0;
+    float amax = 0.f;
+    xv_split6_encode16<true>(v, h0, h1, x6, e8m0, amax);
+    const int sw = (int)(r >> 1) & 7;
+    uint8_t *row = xs + ((size_t)r * chunks + ch) * SROW;
+    *reinterpret_cast<xv_f16x8 *>(row + (((2 * b) ^ sw) << 4)) = h0;
+    *reinterpret_cast<xv_f16x8 *>(row + (((2 * b + 1) ^ sw) << 4)) = h1;
+    *reinterpret_cast<xv_i32x4 *>(row + (((4 + b) ^ sw) << 4)) = (xv_i32x4){(int)x6[0], (int)x6[1], (int)x6[2], (int)x6[3]};
+    *reinterpret_cast<xv_i32x4 *>(row + (((6 + b) ^ sw) << 4)) = (xv_i32x4){(int)x6[4], (int)x6[5], e8m0 - XV_SPLIT6_LO_EXP, 0};
+    if (amax > XV_SPLIT8_MAX && status) atomicOr(status, 1);
+}
+
+__global__ void split6_decode_kernel(const uint8_t *__restrict__ xs, long R, int c, int chunks, float *__restrict__ x,
+                                     float *__restrict__ cq, int ldx)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)R * c) return;
+    const long r = (long)(i / c);
+    const int cc = (int)(i - (size_t)r * c);
+    const int ch = cc >> 5, k = cc & 31, b = k >> 4, e = k & 15;
+    const int sw = (int)(r >> 1) & 7;
+    const uint8_t *row = xs + ((size_t)r * chunks + ch) * SROW;
+    const _Float16 h = *reinterpret_cast<const _Float16 *>(row + (((k >> 3) ^ sw) << 4) + (k & 7) * 2);
+    const uint32_t *lo4 = reinterpret_cast<const uint32_t *>(row + (((4 + b) ^ sw) << 4));
+    const uint32_t *hi4 = reinterpret_cast<const uint32_t *>(row + (((6 + b) ^ sw) << 4));
+    const uint32_t d[7] = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], 0u};
+    const float scale = __builtin_bit_cast(float, (hi4[2] & 0xffu) << 23);       // 2^(byte - 127): the 2^-11 is in the byte
+    auto elem = [&](int pos) {
+        const int bit = 6 * pos;
+        const uint64_t w2 = (uint64_t)d[bit >> 5] | ((uint64_t)d[(bit >> 5) + 1] << 32);
+        const uint32_t code = (uint32_t)(w2 >> (bit & 31)) & 63u;
+        const int ex = (code >> 3) & 3, m = code & 7;
+        const float mag = ex == 0 ? m * 0.125f : (1.f + m * 0.125f) * (float)(1 << (ex - 1));
+        return (code & 32u) ? -mag : mag;
+    };
+    x[(size_t)r * ldx + cc] = (float)h + elem(XV_SPLIT6_ELEM(0, e)) * scale;
+    if (cq) cq[(size_t)r * ldx + cc] = elem(XV_SPLIT6_ELEM(1, e)) * scale * XV_SPLIT8_LO_SCALE;
 }
 
 // fp32 rows -> split8 (tests / tooling; the layers write the format themselves)
@@ -640,6 +736,48 @@ int xv_pack_weights_f16bf8(const float *w, int K, int cin, int cout, void *wt, v
     return launch_status("pack_weights_f16bf8_kernel");
 }
 
+size_t xv_packed_weights_f16mx6_bytes(int K, int cin, int cout)
+{
+    // what the 16 x 16 MFMA form of the 256 x 256 tile takes (launch_gemm8): an even number of slabs, K in {3,5,7}, Cout % 256 == 0
+    if ((K != 3 && K != 5 && K != 7) || cin <= 0 || cout <= 0 || (cout & 255) || (((cin + BK - 1) / BK) & 1)) return 0;
+    return xv_packed_weights_f16bf8_bytes(K, cin, cout);
+}
+
+int xv_pack_weights_f16mx6(const float *w, int K, int cin, int cout, void *wt, void *stream)
+{
+    if (!w || !wt) return fail(XV_ERR_BAD_ARG, "pack_weights_f16mx6: bad argument");
+    if (((uintptr_t)wt) & 15) return fail(XV_ERR_BAD_ARG, "pack_weights_f16mx6: wt must be 16-byte aligned");
+    const size_t bytes = xv_packed_weights_f16mx6_bytes(K, cin, cout);
+    if (!bytes) return fail(XV_ERR_UNSUPPORTED, "pack_weights_f16mx6: needs K in {3,5,7}, an even number of 32-channel slabs and Cout % 256 == 0");
+    const int n_chunks = (cin + BK - 1) / BK;
+    const size_t total = bytes / 64;                   // one thread per block of 16 channels (32 + 32 bytes)
+    hipLaunchKernelGGL(pack_weights_f16mx6_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, K,
+                       cin, cout, n_chunks, (uint8_t *)wt, total);
+    return launch_status("pack_weights_f16mx6_kernel");
+}
+
+int xv_split6_encode_f32(const float *x, int64_t R, int c, int ldx, void *xs, int32_t *status, void *stream)
+{
+    if (R <= 0) return 0;
+    if (!x || !xs || c <= 0 || ldx < c) return fail(XV_ERR_BAD_ARG, "split6_encode: bad argument");
+    if (((uintptr_t)xs) & 15) return fail(XV_ERR_BAD_ARG, "split6_encode: xs must be 16-byte aligned");
+    const int chunks = (c + 31) / 32;
+    const size_t n = (size_t)R * chunks * 2;
+    hipLaunchKernelGGL(split6_encode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, (long)R, c, ldx,
+                       (uint8_t *)xs, chunks, (int *)status);
+    return launch_status("split6_encode_kernel");
+}
+
+int xv_split6_decode_f32(const void *xs, int64_t R, int c, float *x, float *cq, int ldx, void *stream)
+{
+    if (R <= 0) return 0;
+    if (!x || !xs || c <= 0 || ldx < c) return fail(XV_ERR_BAD_ARG, "split6_decode: bad argument");
+    const size_t n = (size_t)R * c;
+    hipLaunchKernelGGL(split6_decode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const uint8_t *)xs, (long)R, c, (c + 31) / 32, x, cq, ldx);
+    return launch_status("split6_decode_kernel");
+}
+
 int xv_split8_encode_f32(const float *x, int64_t R, int c, int ldx, void *xs, int32_t *status, void *stream)
 {
     if (R <= 0) return 0;
@@ -662,20 +800,37 @@ int xv_split8_decode_f32(const void *xs, int64_t R, int c, float *x, int ldx, vo
     return launch_status("split8_decode_kernel");
 }
 
-int xv_tdnn_layer_f16bf8(const void *x, int64_t R, int cin, const void *wt, const float *bias, const float *bn_scale,
-                         const float *bn_shift, int act_kind, const float *act_alpha, int K, int dilation, int cout,
-                         const uint8_t *row_valid, const float *tap_bias, void *y, int y_format, int ldy, int32_t *status, void *stream)
+// the layer with x in ``x_format`` (XV_FMT_SPLIT8: xv_tdnn_layer_f16bf8; XV_FMT_SPLIT6: xv_tdnn_layer_f16mx6)
+static int tdnn_layer8(int x_format, const void *x, int64_t R, int cin, const void *wt, const float *bias, const float *bn_scale,
+                       const float *bn_shift, int act_kind, const float *act_alpha, int K, int dilation, int cout,
+                       const uint8_t *row_valid, const float *tap_bias, void *y, int y_format, int ldy, int32_t *status, void *stream)
 {
     if (!x || !wt || !y) return fail(XV_ERR_BAD_ARG, "tdnn_f16bf8: NULL pointer");
     if (act_kind < XV_ACT_NONE || act_kind > XV_ACT_PRELU) return fail(XV_ERR_BAD_ARG, "tdnn_f16bf8: unknown act_kind");
-    if (y_format != XV_FMT_F32 && y_format != XV_FMT_SPLIT && y_format != XV_FMT_SPLIT8)
+    if (y_format != XV_FMT_F32 && y_format != XV_FMT_SPLIT && y_format != XV_FMT_SPLIT8 && y_format != XV_FMT_SPLIT6)
         return fail(XV_ERR_BAD_ARG, "tdnn_f16bf8: unknown tensor format");
     Gemm8Params p{};
-    p.x = (const uint8_t *)x; p.R = (long)R; p.cin = cin; p.wt = (const uint8_t *)wt;
+    p.x = (const uint8_t *)x; p.x_format = x_format; p.R = (long)R; p.cin = cin; p.wt = (const uint8_t *)wt;
     p.bias = bias; p.scale = bn_scale; p.shift = bn_shift; p.act = act_kind; p.alpha = act_alpha;
     p.K = K; p.dil = dilation; p.cout = cout; p.valid = row_valid; p.tapbias = tap_bias;
     p.y = y; p.y_format = y_format; p.ldy = ldy; p.status = (int *)status;
     return launch_gemm8(p, (hipStream_t)stream);
+}
+
+int xv_tdnn_layer_f16bf8(const void *x, int64_t R, int cin, const void *wt, const float *bias, const float *bn_scale,
+                         const float *bn_shift, int act_kind, const float *act_alpha, int K, int dilation, int cout,
+                         const uint8_t *row_valid, const float *tap_bias, void *y, int y_format, int ldy, int32_t *status, void *stream)
+{
+    return tdnn_layer8(XV_FMT_SPLIT8, x, R, cin, wt, bias, bn_scale, bn_shift, act_kind, act_alpha, K, dilation, cout, row_valid, tap_bias,
+                       y, y_format, ldy, status, stream);
+}
+
+int xv_tdnn_layer_f16mx6(const void *x, int64_t R, int cin, const void *wt, const float *bias, const float *bn_scale,
+                         const float *bn_shift, int act_kind, const float *act_alpha, int K, int dilation, int cout,
+                         const uint8_t *row_valid, const float *tap_bias, void *y, int y_format, int ldy, int32_t *status, void *stream)
+{
+    return tdnn_layer8(XV_FMT_SPLIT6, x, R, cin, wt, bias, bn_scale, bn_shift, act_kind, act_alpha, K, dilation, cout, row_valid, tap_bias,
+                       y, y_format, ldy, status, stream);
 }
 
 int xv_tdnn_layer_pool_f16bf8(const void *x, int64_t R, int cin, const void *wt, const float *bias, const float *bn_scale,
@@ -689,7 +844,7 @@ int xv_tdnn_layer_pool_f16bf8(const void *x, int64_t R, int cin, const void *wt,
     p.x = (const uint8_t *)x; p.R = (long)R; p.cin = cin; p.wt = (const uint8_t *)wt;
     p.bias = bias; p.scale = bn_scale; p.shift = bn_shift; p.act = act_kind; p.alpha = act_alpha;
     p.K = K; p.dil = dilation; p.cout = cout; p.valid = row_valid; p.tapbias = tap_bias;
-    p.blk = block_stats; p.y_format = XV_FMT_F32;
+    p.x_format = XV_FMT_SPLIT8; p.blk = block_stats; p.y_format = XV_FMT_F32;
     return launch_gemm8(p, (hipStream_t)stream);
 }
 

@@ -23,6 +23,19 @@
 //     barrier 2 [X, H0 of the next pair landed]                   -> DMA H1 of the next pair, halo pieces
 //     phase D   16 scaled MFMAs (quarters 2, 3)        | read BH, AH q0 of the next pair's item 0
 // Needs an even number of slabs, K in {3, 5, 7}, Cout % 256 == 0, split-format or POOL output (else the 32 x 32 form).
+//
+// MX6 form (x in XV_FMT_SPLIT6, weights from xv_pack_weights_f16mx6: xv_tdnn_layer_f16mx6).  The cross terms in block-scaled e2m3
+// (xv_split6.h): the same two 16-byte reads per fragment at the same addresses -- slot 4 + kc = dwords 0-3 of block kc of the item's
+// slab (channels 16 kc .. 16 kc + 15, [2^11 lo | c] on the activation side, [c | 2^11 lo] on the weight side), slot 6 + kc = [dword 4 |
+// dword 5 | E8M0 byte | 0], read as 8 + 4 bytes -- and the scaled MFMA with cbsz:2 blgp:2 takes the six element registers of either
+// fragment and byte 0 of its scale dword as that lane's block scale, in place of the two constant scale registers.  Nothing else
+// in the loop changes: phases, barriers, DMA, accumulation order, no conversion, no extra VALU.  What the instruction does at this
+// shape (tools/experiments/mx_probe.hip part 4, MI355X): lane l supplies row / column l & 15 and the 32 elements of K block
+// l >> 4, element e of an A lane meets element e of the B lane of the same block, and the scale byte (picked by op_sel, other
+// bytes ignored) of EVERY lane acts on that lane's own 32 elements -- on both operands, exact on grid data with per-lane bytes.
+// (mx16_probe.hip's mismatch with per-K-block bytes was on bf8 operands and is not re-examined here.)  Issue rate with register
+// operands, one wave per SIMD: 17 shader clocks per instruction against 32 for the bf8 form -- a pair's 32 scaled MFMAs take
+// 544 instead of 1024 of its 2048 cycles.
 #include "xv_gemm8.h"
 
 namespace {
@@ -45,7 +58,10 @@ __device__ __forceinline__ void call_kth(F0 &&f0, Fs &&...fs)
         XV_BLDS16(rsrc, lptr, voff, soff, (imm) + 3072);                                                        \
     } while (0)
 
-template <int KT, bool POOL>
+typedef int xv_i32x2 __attribute__((ext_vector_type(2)));
+typedef int xv_i32x6 __attribute__((ext_vector_type(6)));
+
+template <int KT, bool POOL, bool MX6, bool Y6>
 __global__ __launch_bounds__(512, 2) void tdnn_gemm_f16bf8_wide16_kernel(const Gemm8Params p)
 {
     static_assert(KT == 3 || KT == 5 || KT == 7, "pairs of (slab, tap) items over two slabs: K odd");
@@ -156,6 +172,11 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_f16bf8_wide16_kernel(const G
     // enough: X jobs never follow each other (two H jobs lie between them and cover the refill), H jobs come in twos.
     xv_f16x8 AH[2][2], BH[4];
     xv_i32x4 AXl[2], AXh[2], BXl[4], BXh[4];             // a 32-byte 8-bit fragment = two 16-byte reads
+    // MX6: the slot-6 piece is read as 8 + 4 bytes, [dword 4 | dword 5] and the scale dword.  The instruction wants its six element
+    // registers as ONE tuple: a 16-byte and an 8-byte result coalesce into one, while the first two registers of a 16-byte (or
+    // 12-byte) result cannot be the tail of a six-register tuple -- read that way every B fragment was copied, 24 v_mov per pair.
+    xv_i32x2 AXm[2], BXm[4];
+    int AXs[2], BXs[4];
     auto cat = [](xv_i32x4 u, xv_i32x4 v) { return __builtin_shufflevector(u, v, 0, 1, 2, 3, 4, 5, 6, 7); };
     // The MFMAs are TIED inline asm (dst = srcC).  The compiler has no tied form of the 16 x 16 MFMAs (only the shapes with more
     // than four passes have one): left to the builtins its register allocator let the 32 accumulator tiles wander -- 82 % of the
@@ -164,12 +185,21 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_f16bf8_wide16_kernel(const G
     // by s_waitcnt, which the compiler still inserts per register), from an MFMA at least 8 MFMAs back, or from a constant.
     // asm volatile statements also keep their order among themselves and against memory operations, so the interleave of MFMAs,
     // fragment reads and LDS-DMA below IS the source order (no sched_group_barrier needed, none possible).
+    // MX6: the scale registers come from ds_read as well (the third dword of the slot-6 reads).  The nearest MFMA-to-MFMA dependence
+    // is still 8 MFMAs: an H job follows the X job of its quarter directly (J9 -> J10, J11 -> J12), tile k of one 8 instructions
+    // behind tile k of the other.  With the 4-pass e2m3 instruction those are 7 x 16 = 112 cycles between the issue of a scaled
+    // MFMA and the fp16 MFMA that reads its result as srcC, against a result latency of 4 passes plus a few cycles: it holds.
     auto mfma_h = [&](f32x4 &c, const xv_f16x8 &a, const xv_f16x8 &b) {
         asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
     };
     auto mfma_x = [&](f32x4 &c, const xv_i32x8 &a, const xv_i32x8 &b) {
         asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0] cbsz:1 blgp:1"
                      : "+v"(c) : "v"(a), "v"(b), "v"(scale_a), "v"(scale_b));
+    };
+    auto cat6 = [](xv_i32x4 u, xv_i32x2 v) { return __builtin_shufflevector(u, __builtin_shufflevector(v, v, 0, 1, -1, -1), 0, 1, 2, 3, 4, 5); };
+    auto mfma_x6 = [&](f32x4 &c, const xv_i32x6 &a, const xv_i32x6 &b, int sa, int sb) {       // (byte 0 of sa / sb: the lane's block scales)
+        asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0] cbsz:2 blgp:2"
+                     : "+v"(c) : "v"(a), "v"(b), "v"(sa), "v"(sb));
     };
     // job = 8 MFMAs of a quarter (two row tiles x four column tiles), interleaved one to one with up to 8 fragment reads
     auto job_h = [&](auto SET, auto Q, auto &&...loads) {
@@ -185,7 +215,8 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_f16bf8_wide16_kernel(const G
         constexpr int q = decltype(Q)::value;
         auto step = [&](auto KK) {
             constexpr int k = decltype(KK)::value;
-            mfma_x(acc[2 * q + (k & 1)][k >> 1], cat(AXl[k & 1], AXh[k & 1]), cat(BXl[k >> 1], BXh[k >> 1]));
+            if constexpr (MX6) mfma_x6(acc[2 * q + (k & 1)][k >> 1], cat6(AXl[k & 1], AXm[k & 1]), cat6(BXl[k >> 1], BXm[k >> 1]), AXs[k & 1], BXs[k >> 1]);
+            else mfma_x(acc[2 * q + (k & 1)][k >> 1], cat(AXl[k & 1], AXh[k & 1]), cat(BXl[k >> 1], BXh[k >> 1]));
             if constexpr (k < (int)sizeof...(loads)) call_kth<k>(loads...);
         };
         for_taps<0, 8>(step);
@@ -201,7 +232,14 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_f16bf8_wide16_kernel(const G
         return [&, px, q] { XV_LD(AXl[decltype(R)::value], xv_i32x4, px, q * 32 * SROW + decltype(R)::value * 16 * SROW); };
     };
     auto ld_axh = [&](auto R, const char *px2, int q) {
-        return [&, px2, q] { XV_LD(AXh[decltype(R)::value], xv_i32x4, px2, q * 32 * SROW + decltype(R)::value * 16 * SROW); };
+        return [&, px2, q] {
+            if constexpr (MX6) {
+                XV_LD(AXm[decltype(R)::value], xv_i32x2, px2, q * 32 * SROW + decltype(R)::value * 16 * SROW);
+                XV_LD(AXs[decltype(R)::value], int, px2, q * 32 * SROW + decltype(R)::value * 16 * SROW + 8);
+            } else {
+                XV_LD(AXh[decltype(R)::value], xv_i32x4, px2, q * 32 * SROW + decltype(R)::value * 16 * SROW);
+            }
+        };
     };
     // (opaque: else the compiler splits off the region base -- 0x10800 and up, too large for an offset field -- and keeps
     // "lane part + region + 1024 j" in a register per j)
@@ -210,7 +248,16 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_f16bf8_wide16_kernel(const G
     const char *const pBH = lds + pbh_o, *const pBX = lds + pbx_o, *const pBX2 = lds + pbx2_o;
     auto ld_bh = [&](auto J, int par) { return [&, par] { XV_LD(BH[decltype(J)::value], xv_f16x8, pBH, par * B_BYTES + decltype(J)::value * 1024); }; };
     auto ld_bxl = [&](auto J) { return [&] { XV_LD(BXl[decltype(J)::value], xv_i32x4, pBX, decltype(J)::value * 1024); }; };
-    auto ld_bxh = [&](auto J) { return [&] { XV_LD(BXh[decltype(J)::value], xv_i32x4, pBX2, decltype(J)::value * 1024); }; };
+    auto ld_bxh = [&](auto J) {
+        return [&] {
+            if constexpr (MX6) {
+                XV_LD(BXm[decltype(J)::value], xv_i32x2, pBX2, decltype(J)::value * 1024);
+                XV_LD(BXs[decltype(J)::value], int, pBX2, decltype(J)::value * 1024 + 8);
+            } else {
+                XV_LD(BXh[decltype(J)::value], xv_i32x4, pBX2, decltype(J)::value * 1024);
+            }
+        };
+    };
     typedef std::integral_constant<int, 0> I0;
     typedef std::integral_constant<int, 1> I1;
     typedef std::integral_constant<int, 2> I2;
@@ -354,19 +401,23 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_f16bf8_wide16_kernel(const G
 #pragma unroll
                 for (int e = 0; e < 4; ++e) T[(16 * i + rows4[e]) * W_TLD + col + 16 * j] = acc[i][j][e];
     };
-    wide_epilogue<POOL>(p, lds, Ms, Ps, m0, n0, tid, wr, write_tile);
+    wide_epilogue<POOL, Y6>(p, lds, Ms, Ps, m0, n0, tid, wr, write_tile);
 }
 
 typedef void (*gemm8_fn)(const Gemm8Params);
 struct WideKernel {
     int kt;
-    bool pool;
+    bool pool, mx6, y6;      // y6: XV_FMT_SPLIT6 output (a compile-time form of the epilogue: wide_epilogue)
     gemm8_fn fn;
 };
+#define XV_W16(KT, POOL, MX6, Y6) {KT, POOL, MX6, Y6, tdnn_gemm_f16bf8_wide16_kernel<KT, POOL, MX6, Y6>}
+#define XV_W16_K(POOL, MX6, Y6) XV_W16(3, POOL, MX6, Y6), XV_W16(5, POOL, MX6, Y6), XV_W16(7, POOL, MX6, Y6)
 const WideKernel WIDE16_KERNELS[] = {
-    {3, false, tdnn_gemm_f16bf8_wide16_kernel<3, false>}, {5, false, tdnn_gemm_f16bf8_wide16_kernel<5, false>}, {7, false, tdnn_gemm_f16bf8_wide16_kernel<7, false>},
-    {3, true, tdnn_gemm_f16bf8_wide16_kernel<3, true>},   {5, true, tdnn_gemm_f16bf8_wide16_kernel<5, true>},   {7, true, tdnn_gemm_f16bf8_wide16_kernel<7, true>},
+    XV_W16_K(false, false, false), XV_W16_K(true, false, false), XV_W16_K(false, true, false),
+    XV_W16_K(false, false, true),  XV_W16_K(false, true, true),      // (no pooled MX6 form: no entry point asks for one)
 };
+#undef XV_W16_K
+#undef XV_W16
 
 }  // namespace
 
@@ -374,7 +425,9 @@ int launch_gemm8_wide16(const Gemm8Params &p, hipStream_t st)
 {
     const WideKernel *k = nullptr;
     for (const WideKernel &e : WIDE16_KERNELS)
-        if (e.kt == p.K && e.pool == (p.blk != nullptr)) k = &e;
+        if (e.kt == p.K && e.pool == (p.blk != nullptr) && e.mx6 == (p.x_format == XV_FMT_SPLIT6) &&
+            e.y6 == (!p.blk && p.y_format == XV_FMT_SPLIT6))
+            k = &e;
     if (!k) return fail(XV_ERR_UNSUPPORTED, "tdnn_f16bf8: no kernel for this configuration");
     static std::atomic<unsigned long long> lds_done{0};
     if (const int rc = opt_in_dynamic_lds(lds_done, WIDE16_KERNELS, [](const WideKernel &e) { return std::make_pair(e.fn, W_LDS_BYTES); })) return rc;

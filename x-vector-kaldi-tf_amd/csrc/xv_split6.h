@@ -15,15 +15,24 @@
 // carries it in the bf8 form.  e2m3 has one mantissa bit more than e5m2; its narrow exponent range does no harm because inside
 // a block only the large elements matter to the absolute error of a dot product (tools/experiments/cross_term_mx6_sim.py).
 //
+// The same holds for v_mfma_scale_f32_16x16x128_f8f6f4 (row / column l & 15, K block l >> 4, every lane's own byte: mx_probe part 4),
+// which tdnn_gemm_f16bf8_wide16_kernel's MX6 form runs on rows stored in HBM: XV_FMT_SPLIT6 (include/xvector_hip.h), a block = 16
+// CONSECUTIVE channels of a 32-channel slab, written by the producing layer's epilogue (wide_epilogue_split6 in xv_gemm8.h).
+//
 // Both sides are encoded by the same instruction, v_cvt_scalef32_2xpk16_fp6_f32 (32 floats / scale -> six dwords), so the
 // order of the elements inside the six dwords agrees by construction.
 #pragma once
 #include "xv_split8.h"
 
+// position, among the 32 six-bit elements of the result (element k = bits [6k, 6k + 6) of the six dwords), of value i of source
+// s (0 / 1) of v_cvt_scalef32_2xpk16_fp6_f32 -- for code that READS a block's bits (xv_split6_decode_f32); the MFMA never needs it
+#define XV_SPLIT6_ELEM(s, i) (2 * (i) + (s))
+
 typedef unsigned xv_u32x6 __attribute__((ext_vector_type(6)));
 typedef float xv_f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int XV_SPLIT6_E8M0_MIN = 16;                // floor of a block's byte (a block of denormals: its elements round to 0)
+constexpr int XV_SPLIT6_LO_EXP = 11;                  // the 2^-11 of the cross terms: subtracted from the byte an activation block STORES (XV_FMT_SPLIT6)
 
 // The E8M0 byte of 1 / s for the block maximum m >= 0 (finite): m = f 2^e with 1 <= f < 2 gives 1 / s = 2^(e-2) for f <= 1.875
 // and 2^(e-1) above -- the carry of (mantissa + 0x0fffff) into the exponent field is exactly "f > 1.875".

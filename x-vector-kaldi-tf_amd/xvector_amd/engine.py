@@ -314,7 +314,7 @@ class DeviceModel(object):
     POOL_SPLIT_ROWS = 512
 
     def __init__(self, weights, topo, device="cuda:0", embedding_index=0, precision="bf16x3", fused_pool=None, pair_kernel=None,
-                 first_kernel=None, fold_shift=None):
+                 first_kernel=None, fold_shift=None, layer_mx6=None):
         """precision: "fp32" = exact fp32 MFMA GEMMs; "bf16x3" = split-precision bf16 MFMA GEMMs (fp32-class
         accuracy, ~3e-6 rel-L2 on the x-vector; see include/xvector_hip.h).  fused_pool (default: on; fp32 needs a last layer whose
         width is a multiple of 4; never with attention pooling): the last frame-level layer reduces its output to 8-row block
@@ -325,7 +325,10 @@ class DeviceModel(object):
         intermediate activation stays in registers.  first_kernel (None, False or True, as pair_kernel): layer 0 of a bf16x3
         model on xv_tdnn_first_bf16x3 when its shape allows.  fold_shift (None, the default: on where supported -- f16bf8 models
         with ReLU whose K > 1 layers behind layer 0 are a multiple of 8 channels wide; False: off; True: required): the frame-level layers store their activations without the BN shift, which
-        moves into the next layer's bias (see shift_tap_table), so that the f16bf8 GEMMs read the ReLU's zeros as zeros."""
+        moves into the next layer's bias (see shift_tap_table), so that the f16bf8 GEMMs read the ReLU's zeros as zeros.
+        layer_mx6 (None, the default: on where supported; False: off; True: required): a hidden f16bf8 layer i >= 2 in front of the
+        pair kernel whose shape xv_tdnn_layer_f16mx6 takes, fed by an f16bf8 layer that runs the same kernel form, forms its cross
+        terms on block-scaled e2m3 MFMAs at half their cycles; its producer writes FMT_SPLIT6 rows into the same buffer."""
         import torch
         hiplib.require_gpu()
         assert precision in ("fp32", "fp32tc", "bf16x3", "f16bf8")
@@ -439,6 +442,21 @@ class DeviceModel(object):
                     sc = "frame_level_info_layer-%d" % i
                     self.layers[i]["wp8"] = hiplib.pack_weights_f16bf8(self._wdev(weights, sc + "/w:0"))
                 self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+            # the e2m3 form of a hidden layer: both it and its producer must run the 16 x 16 MFMA form of the 256 x 256 tile (the
+            # producer's epilogue writes the 6-bit rows, layer 0's kernel does not); the layer in front of the pair kernel keeps
+            # writing what that kernel reads
+            self.mx6_layers = set()
+            if self.f16bf8 and (layer_mx6 is None or layer_mx6):
+                def takes(j):
+                    Lj = self.layers[j]
+                    return hiplib.layer_mx6_supported(Lj["K"], Lj["dil"], Lj["cin"], Lj["cout"])
+                for i in range(2, n - 2 if self.pair is not None else n - 1):
+                    if takes(i) and takes(i - 1):
+                        self.layers[i]["wp6"] = hiplib.pack_weights_f16mx6(self._wdev(weights, "frame_level_info_layer-%d/w:0" % i))
+                        self.mx6_layers.add(i)
+            self.layer_mx6 = bool(self.mx6_layers)
+            assert not (layer_mx6 and not self.layer_mx6), \
+                "layer_mx6=True needs an f16bf8 model with a K in {3,5,7} layer (Cin % 64 == 0, Cout % 256 == 0) behind another one"
             # (only ReLU leaves zeros to gain: the other activations keep today's path)
             # (and the GEMM epilogues read 8 channels of a tap's constants at a time: every K > 1 consumer's width a multiple of 8)
             can_fold = self.f16bf8 and self.act == tp.ACT_RELU and all(L["cout"] % 8 == 0 for L in self.layers[1:] if L["K"] > 1)
@@ -639,7 +657,7 @@ class DeviceModel(object):
                 marks.append((label, ev))
         n = len(self.layers)
         bufs = (self._ping, self._pong)
-        S8, S3 = hiplib.FMT_SPLIT8, hiplib.FMT_SPLIT
+        S8, S3, S6 = hiplib.FMT_SPLIT8, hiplib.FMT_SPLIT, hiplib.FMT_SPLIT6
         fold = self.fold_shift
 
         def pp(i):
@@ -672,8 +690,10 @@ class DeviceModel(object):
             mark("layer 0: tdnn_gemm_bf16x3_kernel + split encode")
         for i in range(1, stop):
             L = self.layers[i]
-            y = bufs[i & 1].view(L["cout"], pair_fmt if (self.pair is not None and i == stop - 1) else S8)
-            hiplib.tdnn_layer8(h, R, L["wp8"], *ep(i), L["dil"], row_valid, y, status, tapbias=taps(i))
+            y = bufs[i & 1].view(L["cout"], pair_fmt if (self.pair is not None and i == stop - 1) else
+                                 S6 if i + 1 in self.mx6_layers else S8)
+            # (one launcher for both forms: the weight pack says which kernel reads h)
+            hiplib.tdnn_layer8(h, R, L["wp6" if i in self.mx6_layers else "wp8"], *ep(i), L["dil"], row_valid, y, status, tapbias=taps(i))
             mark("layer %d: tdnn_gemm_f16bf8 (K=%d, %d -> %d)" % (i, L["K"], L["cin"], L["cout"]))
             h = y
         if self.pair is not None:
@@ -800,7 +820,7 @@ def _max_rel_l2(a, b):
     return float(np.nan_to_num(r, nan=np.inf).max()) if len(r) else 0.0
 
 
-def select_model(weights, topo, device="cuda:0", embedding_index=0, precision="f16bf8", probe=None, fold_shift=None):
+def select_model(weights, topo, device="cuda:0", embedding_index=0, precision="f16bf8", probe=None, fold_shift=None, layer_mx6=None):
     """``DeviceModel`` in the fastest arithmetic, not faster than ``precision``, that the accuracy probe admits for THESE weights:
     f16bf8 -> (its x-vectors of the probe batch differ from bf16x3's by more than PROBE_LIMIT_F16BF8, or are not finite, or left
     the fp16 range) -> bf16x3 -> (differs from the exact-fp32 kernels by more than PROBE_LIMIT_BF16X3) -> the exact rung.  The
@@ -811,10 +831,13 @@ def select_model(weights, topo, device="cuda:0", embedding_index=0, precision="f
     of ``precision="fp32"``) keeps the direct contraction, the literal statement of local/tf/models.py:60.
     ``model.selection`` reports what was measured.  ``probe=False`` (or XVECTOR_ACCURACY_PROBE=0) takes ``precision`` as given.
     ``fold_shift``: as DeviceModel's (the f16bf8 candidate only); left at None, a folded candidate that fails its probe is tried
-    unfolded before the model is demoted (``selection["fold_shift"]`` is then False)."""
+    unfolded before the model is demoted (``selection["fold_shift"]`` is then False).  ``layer_mx6``: as DeviceModel's; left at
+    None, a candidate with an e2m3 layer that misses the limit (unfolded too, where that applies) is tried once more without it before
+    the model is demoted.  ``selection["layer_mx6"]`` (of a
+    probed model) records which form runs."""
     if probe is None:
         probe = os.environ.get("XVECTOR_ACCURACY_PROBE", "1") != "0"
-    model = DeviceModel(weights, topo, device, embedding_index, precision, fold_shift=fold_shift)
+    model = DeviceModel(weights, topo, device, embedding_index, precision, fold_shift=fold_shift, layer_mx6=layer_mx6)
     sel = dict(requested=precision, selected=model.arithmetic, probed=False)
     model.selection = sel
     if not probe or not model.f16bf8:
@@ -826,14 +849,15 @@ def select_model(weights, topo, device="cuda:0", embedding_index=0, precision="f
     twin = model.fallback()
     ref = twin.probe_vectors(batch)
     err = _max_rel_l2(got, ref)
-    sel.update(probed=True, f16bf8_vs_bf16x3=err, f16bf8_limit=PROBE_LIMIT_F16BF8, probe_left_fp16_range=clamped,
+    sel.update(probed=True, layer_mx6=model.layer_mx6, f16bf8_vs_bf16x3=err, f16bf8_limit=PROBE_LIMIT_F16BF8, probe_left_fp16_range=clamped,
                probe_frames=int(np.sum(batch[2])))
     if err <= PROBE_LIMIT_F16BF8 and not clamped:
         return model
+    last, last_err = model, err                          # the f16bf8 candidate probed last
     if model.fold_shift and fold_shift is None:
         # The fold costs accuracy (uncentred operands: DESIGN 9.7) for a per-cent of the step; the step down to bf16x3 costs a
         # quarter of it.  A checkpoint that misses the limit folded gets the unfolded f16bf8 arithmetic before it is demoted.
-        plain = DeviceModel(weights, topo, device, embedding_index, precision, fold_shift=False)
+        plain = DeviceModel(weights, topo, device, embedding_index, precision, fold_shift=False, layer_mx6=layer_mx6)
         got = plain.probe_vectors(batch)
         clamped2 = int(plain.status.item()) != 0
         plain.status.zero_()
@@ -843,6 +867,19 @@ def select_model(weights, topo, device="cuda:0", embedding_index=0, precision="f
             plain._fallback = twin
             plain.selection = sel
             return plain
+        last, last_err = plain, err2
+    if last.layer_mx6 and layer_mx6 is None:
+        # ... and the last candidate with that layer's cross terms back in bf8, before the arithmetic itself is given up
+        bf8 = DeviceModel(weights, topo, device, embedding_index, precision, fold_shift=last.fold_shift, layer_mx6=False)
+        got = bf8.probe_vectors(batch)
+        clamped3 = int(bf8.status.item()) != 0
+        bf8.status.zero_()
+        err_bf8 = _max_rel_l2(got, ref)
+        sel.update(mx6_f16bf8_vs_bf16x3=last_err, f16bf8_vs_bf16x3=err_bf8, probe_left_fp16_range=clamped3, layer_mx6=False)
+        if err_bf8 <= PROBE_LIMIT_F16BF8 and not clamped3:
+            bf8._fallback = twin
+            bf8.selection = sel
+            return bf8
     rung = "fp32" if os.environ.get("XVECTOR_EXACT_RUNG", "fp32tc") == "fp32" else "fp32tc"
     exact = DeviceModel(weights, topo, device, embedding_index, rung)
     err3 = _max_rel_l2(ref, exact.probe_vectors(batch))

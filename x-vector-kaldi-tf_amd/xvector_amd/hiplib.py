@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 40
+ABI_VERSION = 41
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -66,6 +66,12 @@ _SIGNATURES = {
     "xv_packed_pair_f16mx6_bytes": (_sz, [_ci, _ci, _ci]),
     "xv_pack_pair_f16mx6": (_ci, [_vp, _vp, _ci, _ci, _ci, _vp, _vp]),
     "xv_tdnn_pair_pool_f16mx6": (_ci, [_vp, _i64, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp]),
+    # a hidden layer's cross terms on e2m3 MFMAs: the XV_FMT_SPLIT6 activation format, its weights and its layer
+    "xv_packed_weights_f16mx6_bytes": (_sz, [_ci, _ci, _ci]),
+    "xv_pack_weights_f16mx6": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp]),
+    "xv_split6_encode_f32": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp, _vp]),
+    "xv_split6_decode_f32": (_ci, [_vp, _i64, _ci, _vp, _vp, _ci, _vp]),
+    "xv_tdnn_layer_f16mx6": (_ci, [_vp, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _ci, _ci, _vp, _vp]),
     "xv_fc_bf16x3": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp]),
     "xv_stats_pool_workspace_bytes": (_sz, [_ci, _ci, _ci, _ci]),
     "xv_stats_pool_f32": (_ci, [_vp, _i64, _ci, _vp, _vp, _ci, _ci, _ci, _cf, _vp, _vp, _vp]),
@@ -168,7 +174,7 @@ _SIGNATURES = {
 }
 SYMBOLS = tuple(_SIGNATURES)      # tests check the header declares exactly these and the .so exports all of them
 
-FMT_F32, FMT_SPLIT, FMT_SPLIT8 = 0, 1, 2
+FMT_F32, FMT_SPLIT, FMT_SPLIT8, FMT_SPLIT6 = 0, 1, 2, 3
 SPLIT_PAD_BEFORE, SPLIT_PAD_AFTER = 8, 264
 TUNE_TILE_ROWS = 1
 TUNE_FIRST_TILES = 2
@@ -511,7 +517,7 @@ class PackPlan(object):
 
 class SplitBuf(object):
     """Device buffer in a split activation format (``fmt``: FMT_SPLIT = bf16 hi/lo planes, FMT_SPLIT8 = fp16 hi + bf8
-    cross bytes; same geometry) with the zero padding rows the layer kernels may read
+    cross bytes, FMT_SPLIT6 = fp16 hi + e2m3 cross blocks; same geometry) with the zero padding rows the layer kernels may read
     (rows [-SPLIT_PAD_BEFORE, rows + SPLIT_PAD_AFTER))."""
 
     def __init__(self, rows, channels, device, fmt=FMT_SPLIT):
@@ -522,8 +528,8 @@ class SplitBuf(object):
         self.ptr = self.base.data_ptr() + SPLIT_PAD_BEFORE * self.row_bytes      # row 0
 
     def view(self, channels, fmt=None):
-        """Same storage seen as a buffer of ``channels`` channels per row (<= allocated width), optionally in the other
-        split format (all-zero bytes are zeros in both)."""
+        """Same storage seen as a buffer of ``channels`` channels per row (<= allocated width), optionally in another
+        split format (all-zero bytes are zeros in all of them)."""
         v = object.__new__(SplitBuf)
         v.rows, v.channels, v.base = self.rows, int(channels), self.base
         v.fmt = self.fmt if fmt is None else int(fmt)
@@ -534,24 +540,31 @@ class SplitBuf(object):
 
 
 def split_encode(x, buf, rows=None, status=None):
-    """fp32 rows x[R, C] -> buf (SplitBuf, either format; ``status``: int32 device tensor, FMT_SPLIT8 only)."""
+    """fp32 rows x[R, C] -> buf (SplitBuf, any format; ``status``: int32 device tensor, FMT_SPLIT8 / FMT_SPLIT6 only)."""
     lib = require_gpu()
     _f32(x, "x")
     R = x.shape[0] if rows is None else int(rows)
     assert R <= buf.rows and x.shape[1] == buf.channels
-    if buf.fmt == FMT_SPLIT8:
-        _check(lib.xv_split8_encode_f32(_ptr(x), R, x.shape[1], x.stride(0), ctypes.c_void_p(buf.ptr), _ptr(status), _stream()),
-               "xv_split8_encode_f32")
+    if buf.fmt in (FMT_SPLIT8, FMT_SPLIT6):
+        name = "xv_split8_encode_f32" if buf.fmt == FMT_SPLIT8 else "xv_split6_encode_f32"
+        _check(getattr(lib, name)(_ptr(x), R, x.shape[1], x.stride(0), ctypes.c_void_p(buf.ptr), _ptr(status), _stream()), name)
         return
     _check(lib.xv_split_encode_f32(_ptr(x), R, x.shape[1], x.stride(0), ctypes.c_void_p(buf.ptr), _stream()), "xv_split_encode_f32")
 
 
-def split_decode(buf, rows, out=None):
-    """SplitBuf -> fp32 tensor [rows, C]."""
+def split_decode(buf, rows, out=None, cq=None):
+    """SplitBuf -> fp32 tensor [rows, C].  ``cq`` (FMT_SPLIT6 only): a tensor like ``out`` (same row stride) that receives the
+    dequantised second cross-term operand."""
     import torch
     lib = require_gpu()
     if out is None:
         out = torch.empty((rows, buf.channels), dtype=torch.float32, device=buf.base.device)
+    if buf.fmt == FMT_SPLIT6:
+        assert cq is None or (cq.shape == out.shape and cq.stride(0) == out.stride(0))
+        _check(lib.xv_split6_decode_f32(ctypes.c_void_p(buf.ptr), int(rows), buf.channels, _ptr(out), _ptr(cq), out.stride(0), _stream()),
+               "xv_split6_decode_f32")
+        return out
+    assert cq is None
     name = "xv_split8_decode_f32" if buf.fmt == FMT_SPLIT8 else "xv_split_decode_f32"
     _check(getattr(lib, name)(ctypes.c_void_p(buf.ptr), int(rows), buf.channels, _ptr(out), out.stride(0), _stream()), name)
     return out
@@ -708,17 +721,50 @@ def _tap_bias(tapbias, w):
 
 
 def tdnn_layer8(x, R, w, bias, scale, shift, act, alpha, dilation, row_valid, y, status=None, tapbias=None):
-    """f16bf8 layer.  x: SplitBuf in FMT_SPLIT8; y: contiguous fp32 tensor [>=R, C] or SplitBuf of either format; w: Packed8;
+    """f16bf8 layer.  x: SplitBuf in FMT_SPLIT8; y: contiguous fp32 tensor [>=R, C] or SplitBuf of any format (FMT_SPLIT6: the
+    16 x 16 MFMA form of the 256 x 256 tile only -- layer_mx6_supported); w: Packed8 -- or PackedMx6 with x in FMT_SPLIT6: the
+    same layer with its cross terms on e2m3 MFMAs (tdnn_layer_mx6);
     status: int32 device tensor whose bit 0 is set when a FMT_SPLIT8 output had to be clamped (None: not reported);
     tapbias: the per-tap constants of fold_shift_taps when x was stored without its BN shift (``bias`` is then bias_full)."""
     lib = require_gpu()
-    assert isinstance(w, Packed8)
-    xp = _operand(x, w.cin, R, "x", (FMT_SPLIT8,))[0]
-    yp, ldy, yfmt = _operand(y, w.cout, R, "y", (FMT_F32, FMT_SPLIT, FMT_SPLIT8))
-    _check(lib.xv_tdnn_layer_f16bf8(xp, int(R), w.cin, _ptr(w.wt), _ptr(bias), _ptr(scale), _ptr(shift), int(act), _ptr(alpha), w.K,
-                                    int(dilation), w.cout, _valid(row_valid, R), _tap_bias(tapbias, w), yp, yfmt, ldy, _ptr(status),
-                                    _stream()),
-           "xv_tdnn_layer_f16bf8")
+    assert isinstance(w, (Packed8, PackedMx6))
+    if isinstance(w, PackedMx6):
+        return _layer8("xv_tdnn_layer_f16mx6", FMT_SPLIT6, lib, x, R, w, bias, scale, shift, act, alpha, dilation, row_valid, y, status, tapbias)
+    _layer8("xv_tdnn_layer_f16bf8", FMT_SPLIT8, lib, x, R, w, bias, scale, shift, act, alpha, dilation, row_valid, y, status, tapbias)
+
+
+def _layer8(name, xfmt, lib, x, R, w, bias, scale, shift, act, alpha, dilation, row_valid, y, status, tapbias):
+    """The launch tdnn_layer8 and tdnn_layer_mx6 share: entry point ``name`` with x in ``xfmt``."""
+    xp = _operand(x, w.cin, R, "x", (xfmt,))[0]
+    yp, ldy, yfmt = _operand(y, w.cout, R, "y", (FMT_F32, FMT_SPLIT, FMT_SPLIT8, FMT_SPLIT6))
+    _check(getattr(lib, name)(xp, int(R), w.cin, _ptr(w.wt), _ptr(bias), _ptr(scale), _ptr(shift), int(act), _ptr(alpha), w.K,
+                              int(dilation), w.cout, _valid(row_valid, R), _tap_bias(tapbias, w), yp, yfmt, ldy, _ptr(status),
+                              _stream()), name)
+
+
+class PackedMx6(_Packed):
+    """Tiled f16mx6 weights of one layer (xv_pack_weights_f16mx6) + the shape they were packed for."""
+    __slots__ = ("wt", "K", "cin", "cout")
+
+
+def layer_mx6_supported(K, dilation, cin, cout):
+    """Shapes xv_tdnn_layer_f16mx6 takes: those of the 16 x 16 MFMA form of the 256 x 256 tile."""
+    return f16bf8_supported(K, dilation) and int(load().xv_packed_weights_f16mx6_bytes(int(K), int(cin), int(cout))) > 0
+
+
+def pack_weights_f16mx6(w3d):
+    """w3d: [K, Cin, Cout] fp32 (TF layout) -> PackedMx6."""
+    lib = require_gpu()
+    return _pack_bytes(lib.xv_packed_weights_f16mx6_bytes, lib.xv_pack_weights_f16mx6, "xv_pack_weights_f16mx6", PackedMx6,
+                       (_f32(w3d, "w"),), w3d.shape, unsupported="K = %d, %d -> %d")
+
+
+def tdnn_layer_mx6(x, R, w, bias, scale, shift, act, alpha, dilation, row_valid, y, status=None, tapbias=None):
+    """tdnn_layer8 with the cross terms on block-scaled e2m3 MFMAs: x: SplitBuf in FMT_SPLIT6 (written by a layer's epilogue);
+    w: PackedMx6; y: a SplitBuf of any format."""
+    lib = require_gpu()
+    assert isinstance(w, PackedMx6)
+    _layer8("xv_tdnn_layer_f16mx6", FMT_SPLIT6, lib, x, R, w, bias, scale, shift, act, alpha, dilation, row_valid, y, status, tapbias)
 
 
 def tdnn_layer_pool8(x, R, w, bias, scale, shift, act, alpha, dilation, row_valid, block_stats, tapbias=None):
