@@ -780,6 +780,69 @@ int xv_backend_prepare_groups_f32(const float *y, int64_t ldy, int n_rows, const
                                   const int32_t *grp_dim, const double *grp_psi, const double *grp_map, const double *grp_off,
                                   int side, float *out, int64_t ldo, float *r, int32_t *status, void *stream);
 
+/* ---- diarization: VBx resegmentation of every recording's vectors (csrc/xv_vbx.hip) -------------------------
+ * A variational-Bayes HMM over the x-vector sequence of one recording (Landini et al., "Bayesian HMM clustering of x-vector
+ * sequences"): one state per speaker, speaker means drawn from the PLDA's between-class prior, initialised from a clustering's
+ * labels; speakers the data do not support fade out.  The rule below was written down from memory of BUT's VBx.py / vbhmm.py, not
+ * checked against them: the rule AS WRITTEN HERE is the contract.
+ * xv_vbx_groups_f64  for every group g (rows [grp_row0[g], grp_row0[g + 1]) of y [n_rows, ldy] fp32, T = n_g >= 1 of them, the
+ *   rows after mean subtraction, LDA and length normalisation; D = dim), one workgroup per group, all arithmetic in fp64.
+ *   Inputs of a group: its rows, visited in time order through row_of_t (int32 [n_rows]; entry grp_row0[g] + t is the row index,
+ *     local to the group, of the group's t-th vector in time; a permutation of [0, n_g); NULL = the identity); an initial label
+ *     l in [0, S) per ROW (init_label [n_rows], indexed like y); S = grp_spk[g], 1 <= S <= max_spk <= XV_VBX_MAX_SPK; the global
+ *     PLDA mu = plda_mean [D], P = transform [D, D], Phi = psi [D]; the scalars Fa = fa > 0, Fb = fb > 0 (both finite), loopP =
+ *     loop_prob in [0, 1), smooth = init_smoothing >= 0 (finite), max_iters in [1, XV_VBX_MAX_ITERS], eps = epsilon (any value but
+ *     NaN; -inf: never stop early).  y_t below is the row of the t-th vector in time, l_t its initial label.
+ *   1. z_t = P (y_t - mu) (no length scaling: this is not Plda::TransformIvector); rho_t = z_t o sqrt(Phi);
+ *      G_t = -1/2 (sum_d z_td^2 + D ln 2 pi).
+ *   2. gamma_ts = e^smooth / (e^smooth + S - 1) for s = l_t and 1 / (e^smooth + S - 1) otherwise; pi_s = 1 / S.
+ *   3. Iteration i = 0, 1, ...:
+ *        N_s = sum_t gamma_ts;  invL_sd = 1 / (1 + (Fa/Fb) N_s Phi_d);  alpha_sd = (Fa/Fb) invL_sd sum_t gamma_ts rho_td
+ *        l_ts = Fa (sum_d rho_td alpha_sd - 1/2 sum_d (invL_sd + alpha_sd^2) Phi_d + G_t);  m_t = max_s l_ts;  b_ts = exp(l_ts - m_t)
+ *        forward:  v_0s = pi_s b_0s;  v_ts = (loopP a_{t-1,s} + (1 - loopP) pi_s) b_ts, t >= 1;  c_t = sum_s v_ts;  a_ts = v_ts / c_t
+ *                  (the transition loopP I + (1 - loopP) 1 pi^T, used in its structure: a step costs O(S))
+ *        backward: beta_{T-1,s} = 1;  w_s = b_{t+1,s} beta_{t+1,s};  beta_ts = (loopP w_s + (1 - loopP) sum_j pi_j w_j) / c_{t+1}
+ *        gamma_ts = a_ts beta_ts
+ *        ELBO_i = sum_t (ln c_t + m_t) + (Fb/2) sum_sd (ln invL_sd - invL_sd - alpha_sd^2 + 1)
+ *        pi'_s = gamma_0s + (1 - loopP) pi_s sum_{t >= 1} b_ts beta_ts / c_t;  pi = pi' / sum_s pi'_s
+ *                  (pi_s = 0 is legal: no logarithm of pi is taken anywhere)
+ *        stop after this iteration if i > 0 and ELBO_i - ELBO_{i-1} < eps, or at max_iters.
+ *   4. label_t = argmax_s gamma_ts, ties to the smallest s: a slot of the initial labelling (the caller renumbers).
+ *   Outputs (device memory), per ROW like y: labels [n_rows] int32; gamma [n_rows, max_spk] (may be NULL: not written), columns
+ *     < S; per group: pi [n_groups, max_spk], entries < S; elbo [n_groups, max_iters]: ELBO_0 .. of the iterations that ran, the
+ *     entries past grp_iters[g] are not written; grp_iters [n_groups]; grp_info [n_groups].
+ *   Fallback: a c_t, an ELBO or a pi normaliser that is zero or not finite (a NaN in a row, a negative psi) gives info 2: the
+ *     group's labels are then its initial labels, its other outputs are unspecified but lie inside its own slices.  Otherwise
+ *     info 0.  Every loop is bounded by T, S, D and max_iters, whatever the values.
+ *   Structure: z / rho are formed once into the group's workspace slice; the two products of an iteration, sum_t gamma_ts rho_td
+ *     and sum_d rho_td alpha_sd, and z itself run on v_mfma_f64_16x16x4_f64, their 16 x 16 output tiles dealt to the workgroup's
+ *     waves, each tile one chain over its whole summation index in ascending groups of 4; the forward and backward chains run in
+ *     one wave, one lane per speaker (hence the cap of 64), with one cross-lane butterfly sum (xor 1, 2, 4, ... below the power of
+ *     two that holds S) and one division per step and no exp / log inside; a, b, beta and c live in LDS when (3 S + 1) T doubles
+ *     fit, in the workspace slice otherwise, with the same bits either way.
+ *   Determinism: no floating-point atomics, every sum has one order; the bits of a group's outputs depend on its own rows,
+ *     labels, time order, S, the model and the scalars only: not on the other groups, its position in the batch, ldy, max_spk
+ *     (beyond the layout of gamma and pi), the workspace contents or what ran before.  Bit equality with a host evaluation is not
+ *     claimed: exp and log differ by library.  No cooperative launch, no workgroup waits on another.  One launch; the call does
+ *     NOT synchronise.
+ *   XV_ERR_BAD_ARG, nothing launched: n_groups, n_rows or dim below 1, ldy < dim, max_spk outside [1, XV_VBX_MAX_SPK], max_iters
+ *     outside [1, XV_VBX_MAX_ITERS], a scalar outside its range above or NaN, a NULL pointer (row_of_t and gamma excepted) or a
+ *     misaligned one (fp64 arrays and the workspace 8 bytes, the rest 4), a workspace smaller than
+ *     xv_vbx_groups_workspace_bytes(n_rows, n_groups, dim, max_spk).  dim > XV_PCA_MAX_DIM: XV_ERR_UNSUPPORTED.
+ *   Device side: a group with n_g < 1, rows outside [0, n_rows), grp_spk outside [1, max_spk], an initial label outside [0, S) or
+ *     a row_of_t entry outside [0, n_g) is skipped whole: nothing of it is written, nothing of its rows is read, and *status
+ *     receives 1.  The caller zeroes *status and reads it back with the results.
+ * xv_vbx_groups_workspace_bytes  the bytes of that workspace, 8 (n_rows (dp + 3 + 3 max_spk) + n_groups 2 max_spk dp) with dp =
+ *   dim rounded up to a multiple of 4 (0 for arguments the call refuses). */
+#define XV_VBX_MAX_SPK 64
+#define XV_VBX_MAX_ITERS 100
+int xv_vbx_groups_f64(const float *y, int64_t ldy, int n_rows, const int32_t *grp_row0, int n_groups, int dim,
+                      const int32_t *row_of_t, const int32_t *init_label, const int32_t *grp_spk, int max_spk,
+                      const double *plda_mean, const double *transform, const double *psi, double fa, double fb, double loop_prob,
+                      double init_smoothing, int max_iters, double epsilon, int32_t *labels, double *gamma, double *pi, double *elbo,
+                      int32_t *grp_iters, int32_t *grp_info, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+size_t xv_vbx_groups_workspace_bytes(int n_rows, int n_groups, int dim, int max_spk);
+
 /* Stage 1 of the recipe: MFCC features and the energy VAD (compute-mfcc-feats / compute-vad; csrc/xv_mfcc.hip).
  * xv_mfcc_f32  MFCC rows of n_utts utterances in one launch.  samples: every utterance's samples back to back, int16
  *   (sample_format 0) or fp32 (1); utterance u has utt_samples[u] samples from element utt_offset[u], its frames go to rows

@@ -8,7 +8,12 @@ With --target-energy F below 1: backend.diarize under every r
 device stage on its own (xv_pca_plda_groups_f64, every call of backend.pca_plda_groups), its share of the diarize call, and the host
 route beside it: backend.host_pca_tables (est_pca + Plda.apply_transform per recording in NumPy, one host thread) feeding the same
 grouped prepare and scorer.  At the default, 1.0, the tool's figures come from the unchanged path.
-    python tools/diarize_bench.py [--loop] [--reps R] [--dim D] [--target-energy F] [G:n ...]
+With --vbx: speakers take turns of 5 sub-segments (VBx models time), backend.diarize with and without
+vbx={} and their difference, xv_vbx_groups_f64 on its own (every call of backend.vbx_groups, its download included), and the host
+route beside it: backend.vbx_host looped over the recordings in NumPy, one host thread.  --threshold T sets the clustering's stop
+rule (a high one over-splits: more initial speakers).  --vbx-probe: one recording of T = 4096, S = 16 at d = 128 and at d = 4, 10
+iterations -- the two MFMA products shrink 32-fold with d, the one-wave chains do not, so the pair shows the chains' share.
+    python tools/diarize_bench.py [--loop] [--reps R] [--dim D] [--target-energy F] [--vbx [--threshold T]] [--vbx-probe] [G:n ...]
                                                             (default shapes 256:200 2048:100, R = 3, D = 64, the best is printed)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -107,6 +112,87 @@ def pca_main(shapes, reps, target_energy):
         sys.stdout.flush()
 
 
+def planted_turns(G, n, seed=0, turn=5):
+    """``planted`` with the speakers taking turns of ``turn`` vectors in a fixed cycle instead of a shuffle."""
+    from xvector_amd import backend
+    rng = np.random.default_rng(seed)
+    psi = np.sort(rng.uniform(2.0, 12.0, DIM))[::-1]
+    spk = np.tile((np.arange(n) // turn) % SPK, (G, 1))
+    centres = rng.standard_normal((G, SPK, DIM)) * np.sqrt(psi)
+    x = centres[np.arange(G)[:, None], spk] + rng.standard_normal((G, n, DIM))
+    return x.reshape(G * n, DIM).astype(np.float32), spk, backend.Plda(np.zeros(DIM), np.eye(DIM), psi)
+
+
+def vbx_main(shapes, reps, threshold):
+    """The --vbx route: diarize with and without VBx, the kernel on its own, the host loop of vbx_host."""
+    import torch
+    from xvector_amd import backend, hiplib
+    hiplib.require_gpu()
+    x, _, plda = planted_turns(4, 50)
+    backend.diarize(x, [50] * 4, plda, threshold=threshold, vbx={})          # warm-up: code objects, allocator
+    print("| G | n | d | diarize(): wall ms | device-event ms | diarize(vbx={}): wall ms | device-event ms | difference: wall ms "
+          "| vbx_groups alone: wall ms (device-event ms) | host vbx_host loop: wall ms (ms / recording) | speakers before -> after "
+          "| mean iterations | info 2 | planted partitions before -> after |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+    for G, n in shapes:
+        x, spk, plda = planted_turns(G, n)
+        sizes = [n] * G
+        w0, d0, (lab0, _) = best(lambda: backend.diarize(x, sizes, plda, threshold=threshold), reps)
+        rep = {}
+        w1, d1, (lab1, _) = best(lambda: backend.diarize(x, sizes, plda, threshold=threshold, vbx={}, vbx_report=rep), reps)
+        ok0 = sum(same_partition(lab0[g * n:(g + 1) * n], spk[g]) for g in range(G))
+        ok1 = sum(same_partition(lab1[g * n:(g + 1) * n], spk[g]) for g in range(G))
+        Y, _ = backend.prepare(x, hiplib.SIDE_PLAIN, None, None, None, None, False)
+        tables = backend.GroupTables(sizes, Y.device)
+        init = np.concatenate([backend.compact_labels(lab0[g * n:(g + 1) * n])[0] for g in range(G)])
+        run = np.flatnonzero(rep["ran"])
+        if run.size == 0:
+            print("| %d | %d | %d | %.1f | %.1f | %.1f | %.1f | %.1f | no recording has at most %d clusters: lower --threshold |"
+                  % (G, n, plda.dim, w0, d0, w1, d1, w1 - w0, hiplib.VBX_MAX_SPK))
+            continue
+        if run.size < G:                                         # the stage alone and the host loop: the recordings that ran
+            rows = np.concatenate([np.arange(g * n, (g + 1) * n) for g in run])
+            Y, init = Y[torch.as_tensor(rows, device=Y.device)], init[rows]
+            tables = backend.GroupTables([n] * run.size, Y.device)
+        wk, dk, res = best(lambda: backend.vbx_groups(Y, tables, init, plda), reps)
+        Yh = Y.cpu().numpy()
+
+        def host_loop():
+            return [backend.vbx_host(Yh[g * n:(g + 1) * n], init[g * n:(g + 1) * n], plda) for g in range(run.size)]
+        wh, _, host = min((timed(host_loop) for _ in range(min(reps, 2))), key=lambda r: r[0])
+        same = sum(np.array_equal(host[g]["labels"], res["labels"][g * n:(g + 1) * n]) and host[g]["iters"] == res["iters"][g]
+                   for g in range(run.size))
+        print("| %d | %d | %d | %.1f | %.1f | %.1f | %.1f | %.1f | %.1f (%.2f) | %.0f (%.2f) | %.2f -> %.2f | %.2f | %d | %d -> %d of %d |"
+              % (G, n, plda.dim, w0, d0, w1, d1, w1 - w0, wk, dk, wh, wh / run.size, float(rep["spk_before"].mean()),
+                 float(rep["spk_after"].mean()), float(rep["iters"][run].mean()) if run.size else 0.0, int((rep["info"] == 2).sum()),
+                 ok0, ok1, G))
+        print("  (recordings VBx ran on: %d of %d; those whose labels and iteration count agree between the kernel and the host "
+              "loop: %d of %d)" % (run.size, G, same, run.size))
+        sys.stdout.flush()
+
+
+def vbx_probe(reps, T=4096, S=16, iters=10):
+    """One recording of T vectors and S initial speakers, ``iters`` iterations (epsilon = -inf), at d = 128 and d = 4."""
+    global DIM
+    import torch
+    from xvector_amd import backend, hiplib
+    hiplib.require_gpu()
+    print("| T | S | d | iterations | vbx_groups: device-event ms | ms / iteration |")
+    print("|---|---|---|---|---|---|")
+    for d in (128, 4):
+        DIM = d
+        x, spk, plda = planted_turns(1, T)
+        Y = torch.as_tensor(x, device="cuda:0")
+        tables = backend.GroupTables([T], Y.device)
+        init = ((np.arange(T) // 5) % S).astype(np.int32)
+        backend.vbx_groups(Y, tables, init, plda, max_iters=1)
+        _, d1, _ = best(lambda: backend.vbx_groups(Y, tables, init, plda, max_iters=1, epsilon=-np.inf), reps)
+        _, dn, res = best(lambda: backend.vbx_groups(Y, tables, init, plda, max_iters=iters + 1, epsilon=-np.inf), reps)
+        assert res["iters"][0] == iters + 1 and res["info"][0] == 0
+        print("| %d | %d | %d | %d | %.2f | %.3f |" % (T, S, d, iters + 1, dn, (dn - d1) / iters))
+        sys.stdout.flush()
+
+
 def main(shapes, loop, reps):
     import torch
     from xvector_amd import backend, hiplib
@@ -160,7 +246,11 @@ if __name__ == "__main__":
         DIM = int(args[args.index("--dim") + 1])
     target_energy = float(args[args.index("--target-energy") + 1]) if "--target-energy" in args else 1.0
     from xvector_amd import backend
-    if backend.target_energy_is_one(backend.check_target_energy(target_energy)):
+    if "--vbx-probe" in args:
+        vbx_probe(reps)
+    elif "--vbx" in args:
+        vbx_main(shapes, reps, float(args[args.index("--threshold") + 1]) if "--threshold" in args else 0.0)
+    elif backend.target_energy_is_one(backend.check_target_energy(target_energy)):
         main(shapes, loop, reps)
     else:
         pca_main(shapes, reps, target_energy)

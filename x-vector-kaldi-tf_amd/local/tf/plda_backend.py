@@ -22,6 +22,7 @@
                Turn utt2cluster into a spk2utt, fit an in-domain model with compute-plda --lda, mix it with interpolate-plda
   diarize      ivector-plda-scoring-dense | agglomerative-cluster --reco2utt [--reco2num-spk] | diarization/make_rttm.py
                (DESIGN.md §8.15): [--mean mean.vec] [--lda transform.mat] [--threshold t] [--reco2num-spk FILE] [--rttm OUT.rttm]
+               [--vbx [--vbx-fa --vbx-fb --vbx-loop-prob --vbx-max-iters --vbx-epsilon --vbx-init-smoothing]]
                [--rttm-channel c] plda <vectors> <segments> <labels-out>.  <segments> is what extract_embedding.py
                --subsegments-file writes (``key reco start end``; any Kaldi segments file).  The vectors are grouped by recording;
                every recording's PLDA score matrix comes from one launch and every recording's average-linkage clustering runs in
@@ -302,6 +303,13 @@ def cmd_diarize(args):
         backend.check_target_energy(args.target_energy)
     except ValueError:
         raise SystemExit("--target-energy must be in (0, 1], got %r" % args.target_energy)
+    try:
+        vbx = backend.check_vbx_params(args.vbx_fa, args.vbx_fb, args.vbx_loop_prob, args.vbx_init_smoothing, args.vbx_max_iters,
+                                       args.vbx_epsilon)
+    except ValueError as e:
+        raise SystemExit("the --vbx-* options: %s" % e)
+    if not args.vbx:
+        vbx = None
     segments = read_segments(args.segments)
     num_spk = {}
     if args.reco2num_spk:
@@ -344,9 +352,15 @@ def cmd_diarize(args):
         for r, n, k in zip(recos, sizes, counts):
             if k is not None and k > n:
                 logger.warning("recording %s: %d speakers asked for, %d vectors: using %d" % (r, k, n, n))
-    pca = {}
+    pca, vbx_rep = {}, {}
     try:
-        if backend.target_energy_is_one(args.target_energy):
+        if vbx is not None:
+            # VBx visits a recording's vectors in the RTTM's own order, (start, end, key); the clustering keeps the file order
+            order = [sorted(range(len(g)), key=lambda j: (segments[g[j]][2], segments[g[j]][3], segments[g[j]][0])) for g in groups]
+            vbx = dict(vbx, time_order=np.concatenate(order), keep=np.asarray([r in num_spk for r in recos]))
+            slots, _ = backend.diarize(x, sizes, plda, mean=mean, transform=t, threshold=args.threshold, num_spk=counts,
+                                       target_energy=args.target_energy, pca_report=pca, vbx=vbx, vbx_report=vbx_rep)
+        elif backend.target_energy_is_one(args.target_energy):
             slots, _ = backend.diarize(x, sizes, plda, mean=mean, transform=t, threshold=args.threshold, num_spk=counts)
         else:
             slots, _ = backend.diarize(x, sizes, plda, mean=mean, transform=t, threshold=args.threshold, num_spk=counts,
@@ -372,6 +386,14 @@ def cmd_diarize(args):
                     "global model (%d without energy, %d without convergence)" %
                     (args.target_energy, float(pca["dim"].mean()), dim, int((info != 0).sum()), int((info == 1).sum()),
                      int((info == 2).sum())))
+    if vbx_rep:
+        ran = vbx_rep["ran"]
+        many = int((vbx_rep["spk_before"] > hiplib.VBX_MAX_SPK).sum())
+        logger.info("VBx resegmentation: %d recordings, mean %.2f iterations, %d speakers before and %d after; %d fell back to the "
+                    "clustering (info 2); kept as clustered: %d named in --reco2num-spk, %d with more than %d clusters" %
+                    (int(ran.sum()), float(vbx_rep["iters"][ran].mean()) if ran.any() else 0.0, int(vbx_rep["spk_before"][ran].sum()),
+                     int(vbx_rep["spk_after"][ran].sum()), int((vbx_rep["info"] == 2).sum()),
+                     int(vbx["keep"].sum()), many, hiplib.VBX_MAX_SPK))
 
 
 def cmd_interpolate_plda(args):
@@ -520,6 +542,16 @@ def main(argv=None):
                    help="ivector-plda-scoring-dense --target-energy, in (0, 1]: score every recording in the PCA subspace of its own "
                         "vectors that holds this share of their variance, under the PLDA projected into it (the callhome recipe "
                         "passes 0.1).  The default here is 1.0 -- no PCA, the scores of earlier versions -- where Kaldi's is 0.5")
+    p.add_argument("--vbx", action="store_true",
+                   help="VBx resegmentation after the clustering (a variational-Bayes HMM over each recording's vectors in time order, "
+                        "under the global PLDA, initialised from the clustering; DESIGN.md §8.17).  Recordings named in "
+                        "--reco2num-spk and recordings with more than 64 clusters keep their clustering")
+    p.add_argument("--vbx-fa", type=float, default=0.3, help="VBx: the scale of the acoustic statistics (> 0)")
+    p.add_argument("--vbx-fb", type=float, default=17.0, help="VBx: the scale of the speaker regularisation (> 0)")
+    p.add_argument("--vbx-loop-prob", type=float, default=0.99, help="VBx: the probability of staying with the speaker, in [0, 1)")
+    p.add_argument("--vbx-max-iters", type=int, default=40, help="VBx: iterations at most, in [1, 100]")
+    p.add_argument("--vbx-epsilon", type=float, default=1e-6, help="VBx: stop when the ELBO gains less than this")
+    p.add_argument("--vbx-init-smoothing", type=float, default=5.0, help="VBx: the softmax weight of the clustering's label (>= 0)")
     p.add_argument("--rttm", help="write the speaker turns here")
     p.add_argument("--rttm-channel", type=int, default=0)
     p.add_argument("plda"); p.add_argument("vectors"); p.add_argument("segments"); p.add_argument("labels_out")

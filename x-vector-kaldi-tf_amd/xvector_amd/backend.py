@@ -789,7 +789,8 @@ def _nonfinite_upper(scores, tables):
     return bad
 
 
-def score_blocks(x, group_sizes, plda, mean=None, transform=None, device="cuda:0", target_energy=1.0, pca_max_bytes=PCA_MAX_BYTES):
+def score_blocks(x, group_sizes, plda, mean=None, transform=None, device="cuda:0", target_energy=1.0, pca_max_bytes=PCA_MAX_BYTES,
+                 keep_plain=False):
     """Every group's PLDA score matrix from one launch (xv_score_blocks_f32): x[N, D] raw vectors, group g the next
     group_sizes[g] rows.  The chain is that of ``score_matrix_self`` (two prepare calls over all rows, one-utterance enrolments),
     and a block holds the bits ``score_matrix_self`` gives that group's rows.  -> (scores, tables): the packed float32 device
@@ -798,7 +799,10 @@ def score_blocks(x, group_sizes, plda, mean=None, transform=None, device="cuda:0
     target_energy below 1 (ivector-plda-scoring-dense --target-energy): every group is scored under its own
     PCA and projected PLDA instead -- one PLAIN prepare without the PLDA, ``pca_plda_groups``, the grouped prepare for both
     sides, then the same scorer.  tables.pca is then the int32 device tensor [2 G] of the retained dimensions followed by the
-    0 / 1 / 2 fallback codes (None on the default route, which is the code above unchanged)."""
+    0 / 1 / 2 fallback codes (None on the default route, which is the code above unchanged).
+
+    keep_plain: tables.plain is then the PLAIN-prepared device rows (mean, LDA, length normalisation; no PLDA) that ``vbx_groups``
+    reads -- the PCA route's own, or one more prepare call on the default route."""
     import torch
     hiplib.require_gpu()
     target_energy = check_target_energy(target_energy)
@@ -827,9 +831,13 @@ def score_blocks(x, group_sizes, plda, mean=None, transform=None, device="cuda:0
             for side, out, rr in ((hiplib.SIDE_ENROL, E, r), (hiplib.SIDE_TEST, T, None)):
                 hiplib.backend_prepare_groups(Y, tables.row0_d[lo:hi + 1], mx, d, grp_dim[lo:hi], t["psi"], t["map"], t["off"], side, out,
                                               rr, tables.status)
+        if keep_plain:
+            tables.plain = Y
     else:
         E, r = prepare(x, hiplib.SIDE_ENROL, np.ones(n, np.int32), mean, transform, plda, ln, device)
         T, _ = prepare(x, hiplib.SIDE_TEST, None, mean, transform, plda, ln, device)
+        if keep_plain:
+            tables.plain, _ = prepare(x, hiplib.SIDE_PLAIN, None, mean, transform, None, ln, device)
     scores = torch.empty(tables.scores_elems, dtype=torch.float32, device=device)
     hiplib.score_blocks(E, T, r, tables.row0_d, tables.score0_d, tables.max_n, scores, tables.status)
     return scores, tables
@@ -900,7 +908,7 @@ def ahc_batch(scores, tables, thresholds, min_clusters, max_bytes=AHC_MAX_BYTES,
 
 
 def diarize(x, group_sizes, plda, mean=None, transform=None, threshold=0.0, num_spk=None, device="cuda:0", target_energy=1.0,
-            pca_report=None):
+            pca_report=None, vbx=None, vbx_report=None):
     """Cluster every recording's vectors on their own: x[N, D] raw vectors, recording g the next group_sizes[g] rows.  The
     recordings are sorted by size, descending, for the device, scored against themselves in one launch (``score_blocks``) and
     clustered one workgroup each (``ahc_batch``); the results come back in the caller's order.  threshold: the stop rule of every
@@ -911,11 +919,27 @@ def diarize(x, group_sizes, plda, mean=None, transform=None, threshold=0.0, num_
     target_energy below 1: every recording is scored under its own PCA and projected PLDA (``score_blocks``); the default, 1.0,
     is the route without a PCA, unchanged.  pca_report (a dict, optional) then receives 'dim' and 'info', int32 [G] in the
     caller's order: each recording's retained dimension and 0 / 1 / 2 (PCA applied / fallback for energy / for non-convergence);
-    they come down with ``ahc_batch``'s download."""
+    they come down with ``ahc_batch``'s download.
+
+    vbx (None: the route above, unchanged): a dict turns on VBx resegmentation (``vbx_groups``) after the clustering -- the scalars
+    of ``check_vbx_params`` (absent ones take VBX_DEFAULTS), and optionally 'time_order' (int [N], in the caller's row order: entry
+    row0[g] + t is the index, local to recording g, of its t-th vector in time; absent: the rows are in time order), 'keep' (bool
+    [G]: these recordings keep their clustering, e.g. those with a speaker count) and 'max_bytes'.  The PLAIN-prepared rows already
+    on the device are read again (under the GLOBAL PLDA, also when the clustering ran under a per-recording PCA), the clustering's
+    labels, renamed to 0 .. S - 1 per recording, are the initial labels, and a recording's labels become VBx's.  A recording with
+    more than hiplib.VBX_MAX_SPK clusters keeps its clustering, and so does one VBx reports info 2 for.  vbx_report (a dict,
+    optional) receives, per recording in the caller's order, 'ran' (bool), 'iters', 'info' (int32; 0 where VBx did not run),
+    'spk_before' and 'spk_after' (int32)."""
     hiplib.require_gpu()
     target_energy = check_target_energy(target_energy)
     sizes = np.asarray(group_sizes, dtype=np.int64).reshape(-1)
     thr, minc = diarize_stop_rules(sizes, threshold, num_spk)
+    if vbx is not None:
+        vbx = dict(vbx)
+        vbx_order, vbx_keep, vbx_bytes = vbx.pop("time_order", None), vbx.pop("keep", None), vbx.pop("max_bytes", VBX_MAX_BYTES)
+        vbx = check_vbx_params(**vbx)
+        if plda.dim > hiplib.PCA_MAX_DIM:
+            raise ValueError("diarize: VBx handles dimensions up to %d, the PLDA has %d" % (hiplib.PCA_MAX_DIM, plda.dim))
     x = np.asarray(x, dtype=np.float32)
     if sizes.size < 1 or int(sizes.min()) < 1 or x.ndim != 2 or int(sizes.sum()) != x.shape[0]:
         raise ValueError("diarize: x must be [N, D] and the group sizes, all at least 1, must add up to N")
@@ -923,10 +947,13 @@ def diarize(x, group_sizes, plda, mean=None, transform=None, threshold=0.0, num_
     row0 = np.concatenate([[0], np.cumsum(sizes)])
     rows = np.concatenate([np.arange(row0[g], row0[g + 1]) for g in order])
     if target_energy_is_one(target_energy):
-        scores, tables = score_blocks(x[rows], sizes[order], plda, mean, transform, device)
+        if vbx is None:
+            scores, tables = score_blocks(x[rows], sizes[order], plda, mean, transform, device)
+        else:
+            scores, tables = score_blocks(x[rows], sizes[order], plda, mean, transform, device, keep_plain=True)
         lab_sorted, merges_sorted = ahc_batch(scores, tables, thr[order], minc[order])
     else:
-        scores, tables = score_blocks(x[rows], sizes[order], plda, mean, transform, device, target_energy)
+        scores, tables = score_blocks(x[rows], sizes[order], plda, mean, transform, device, target_energy, keep_plain=vbx is not None)
         lab_sorted, merges_sorted, pca = ahc_batch(scores, tables, thr[order], minc[order], extra=tables.pca)
         if pca_report is not None:
             G = sizes.size
@@ -934,12 +961,58 @@ def diarize(x, group_sizes, plda, mean=None, transform=None, threshold=0.0, num_
             pca_report["info"] = np.empty(G, np.int32)
             pca_report["dim"][order] = pca[:G]
             pca_report["info"][order] = pca[G:]
+    if vbx is not None:
+        lab_sorted = _diarize_vbx(tables, lab_sorted, order, row0, plda, vbx, vbx_order, vbx_keep, vbx_bytes, vbx_report)
     labels = np.empty(x.shape[0], dtype=np.int32)
     labels[rows] = np.concatenate(lab_sorted)
     merges = [None] * sizes.size
     for k, g in enumerate(order.tolist()):
         merges[g] = merges_sorted[k]
     return labels, merges
+
+
+def _diarize_vbx(tables, lab_sorted, order, row0, plda, params, time_order, keep, max_bytes, report):
+    """The VBx stage of ``diarize``: lab_sorted (the clustering's labels per recording, in the device's order ``order``) with the
+    labels of every recording that VBx ran on replaced by VBx's.  row0: the caller's prefix table of the recordings."""
+    import torch
+    G = tables.sizes.size
+    keep = np.zeros(G, bool) if keep is None else np.asarray(keep, dtype=bool).reshape(-1)
+    if keep.size != G:
+        raise ValueError("diarize: %d recordings, %d entries of vbx['keep']" % (G, keep.size))
+    if time_order is not None:
+        time_order = np.asarray(time_order, dtype=np.int64).reshape(-1)
+        if time_order.size != tables.n_rows:
+            raise ValueError("diarize: %d vectors, %d entries of vbx['time_order']" % (tables.n_rows, time_order.size))
+    compact = [compact_labels(l) for l in lab_sorted]
+    before = np.asarray([c[1] for c in compact], dtype=np.int32)
+    run = np.flatnonzero(~keep[order] & (before <= hiplib.VBX_MAX_SPK))           # positions in the device's order
+    rep = dict(ran=np.zeros(G, bool), iters=np.zeros(G, np.int32), info=np.zeros(G, np.int32), spk_before=np.empty(G, np.int32),
+               spk_after=np.empty(G, np.int32))
+    rep["spk_before"][order] = before
+    rep["spk_after"][order] = before
+    out = list(lab_sorted)
+    if run.size:
+        Y = tables.plain
+        if run.size == G:
+            sub = tables
+        else:                                                    # the rows of the recordings that run, gathered on the device
+            sub = GroupTables(tables.sizes[run], Y.device)
+            idx = np.concatenate([np.arange(tables.row0[k], tables.row0[k + 1]) for k in run])
+            Y = Y.index_select(0, torch.as_tensor(idx, device=Y.device))
+        init = np.concatenate([compact[k][0] for k in run])
+        tord = None
+        if time_order is not None:
+            tord = np.concatenate([time_order[row0[order[k]]:row0[order[k] + 1]] for k in run])
+        res = vbx_groups(Y, sub, init, plda, tord, before[run], max_bytes=max_bytes, **params)
+        for j, k in enumerate(run.tolist()):
+            g = int(order[k])
+            rep["ran"][g], rep["iters"][g], rep["info"][g] = True, res["iters"][j], res["info"][j]
+            if res["info"][j] == 0:
+                out[k] = res["labels"][sub.row0[j]:sub.row0[j + 1]].copy()
+                rep["spk_after"][g] = np.unique(out[k]).size
+    if report is not None:
+        report.update(rep)
+    return out
 
 
 def diarize_stop_rules(sizes, threshold=0.0, num_spk=None):
@@ -961,6 +1034,183 @@ def diarize_stop_rules(sizes, threshold=0.0, num_spk=None):
                 thr[g] = -np.inf
                 minc[g] = min(int(k), int(sizes[g]))
     return thr, minc
+
+
+# ---- VBx resegmentation of every recording's vectors (the rule: include/xvector_hip.h) ----
+VBX_MAX_BYTES = 1 << 30            # the workspace of one xv_vbx_groups_f64 call is at most this large
+VBX_DEFAULTS = dict(fa=0.3, fb=17.0, loop_prob=0.99, init_smoothing=5.0, max_iters=40, epsilon=1e-6)
+
+
+def check_vbx_params(fa=0.3, fb=17.0, loop_prob=0.99, init_smoothing=5.0, max_iters=40, epsilon=1e-6):
+    """The VBx scalars as a dict of floats (max_iters an int); ValueError for one outside the range xv_vbx_groups_f64 takes."""
+    fa, fb, loop_prob, init_smoothing, epsilon = (float(v) for v in (fa, fb, loop_prob, init_smoothing, epsilon))
+    if not (np.isfinite(fa) and fa > 0.0):
+        raise ValueError("vbx: fa must be finite and > 0, got %r" % fa)
+    if not (np.isfinite(fb) and fb > 0.0):
+        raise ValueError("vbx: fb must be finite and > 0, got %r" % fb)
+    if not 0.0 <= loop_prob < 1.0:
+        raise ValueError("vbx: loop_prob must be in [0, 1), got %r" % loop_prob)
+    if not (np.isfinite(init_smoothing) and init_smoothing >= 0.0):
+        raise ValueError("vbx: init_smoothing must be finite and >= 0, got %r" % init_smoothing)
+    if int(max_iters) != max_iters or not 1 <= int(max_iters) <= hiplib.VBX_MAX_ITERS:
+        raise ValueError("vbx: max_iters must be an integer in [1, %d], got %r" % (hiplib.VBX_MAX_ITERS, max_iters))
+    if np.isnan(epsilon):
+        raise ValueError("vbx: epsilon is NaN")
+    return dict(fa=fa, fb=fb, loop_prob=loop_prob, init_smoothing=init_smoothing, max_iters=int(max_iters), epsilon=epsilon)
+
+
+def compact_labels(labels):
+    """(labels renamed to 0 .. S - 1 in ascending order of the old names, int32; S)."""
+    names, inv = np.unique(np.asarray(labels), return_inverse=True)
+    return inv.astype(np.int32).reshape(-1), int(names.size)
+
+
+def vbx_host(y, init_labels, plda, n_spk=None, fa=0.3, fb=17.0, loop_prob=0.99, init_smoothing=5.0, max_iters=40, epsilon=1e-6):
+    """The host float64 twin of xv_vbx_groups_f64 on ONE recording, in the kernel's linear form (the rule of
+    include/xvector_hip.h, step for step; it stands beside ``est_pca`` / ``host_pca_tables``): y[T, >= d] the recording's rows in
+    time order, after mean subtraction, LDA and length normalisation; init_labels[T] in [0, S); n_spk = S (None: the largest
+    label + 1).  The forward and backward chains pay 2 T interpreter steps an iteration.
+    -> dict(gamma [T, S], pi [S], elbo [n_iters], iters, info (0, or 2: labels are the initial ones), labels int32 [T])."""
+    p = check_vbx_params(fa, fb, loop_prob, init_smoothing, max_iters, epsilon)
+    fa, fb, lp, eps = p["fa"], p["fb"], p["loop_prob"], p["epsilon"]
+    d = plda.dim
+    y = np.asarray(y, dtype=np.float64)
+    lab = np.asarray(init_labels, dtype=np.int64).reshape(-1)
+    if y.ndim != 2 or y.shape[0] < 1 or y.shape[1] < d or lab.size != y.shape[0]:
+        raise ValueError("vbx_host: y must be [T, >= %d] with T >= 1 and one initial label per row" % d)
+    T = y.shape[0]
+    S = int(lab.max()) + 1 if n_spk is None else int(n_spk)
+    if not 1 <= S <= hiplib.VBX_MAX_SPK or int(lab.min()) < 0 or int(lab.max()) >= S:
+        raise ValueError("vbx_host: 1 <= S <= %d and every initial label in [0, S)" % hiplib.VBX_MAX_SPK)
+    phi = plda.psi
+    with np.errstate(all="ignore"):
+        z = (y[:, :d] - plda.mean) @ plda.transform.T
+        rho = z * np.sqrt(phi)
+        G = -0.5 * ((z * z).sum(axis=1) + d * np.log(2.0 * np.pi))
+        es = np.exp(p["init_smoothing"])
+        gamma = np.full((T, S), 1.0 / (es + S - 1))
+        gamma[np.arange(T), lab] = es / (es + S - 1)
+        pi = np.full(S, 1.0 / S)
+        ratio = fa / fb
+        elbo, info = [], 0
+        a, beta, c = np.empty((T, S)), np.empty((T, S)), np.empty(T)
+        for it in range(p["max_iters"]):
+            N = gamma.sum(axis=0)
+            invL = 1.0 / (1.0 + ratio * N[:, None] * phi[None, :])
+            alpha = ratio * invL * (gamma.T @ rho)
+            ll = fa * (rho @ alpha.T - 0.5 * ((invL + alpha * alpha) @ phi)[None, :] + G[:, None])
+            m = ll.max(axis=1)
+            b = np.exp(ll - m[:, None])
+            v = pi * b[0]
+            for t in range(T):
+                if t:
+                    v = (lp * a[t - 1] + (1.0 - lp) * pi) * b[t]
+                c[t] = v.sum()
+                a[t] = v / c[t]
+            beta[T - 1] = 1.0
+            for t in range(T - 2, -1, -1):
+                w = b[t + 1] * beta[t + 1]
+                beta[t] = (lp * w + (1.0 - lp) * (pi * w).sum()) / c[t + 1]
+            gamma = a * beta
+            e = (np.log(c) + m).sum() + 0.5 * fb * (np.log(invL) - invL - alpha * alpha + 1.0).sum()
+            pn = gamma[0] + (1.0 - lp) * pi * (b[1:] * beta[1:] / c[1:, None]).sum(axis=0)
+            norm = pn.sum()
+            if not (np.all(np.isfinite(c)) and np.all(c != 0.0) and np.isfinite(e) and np.isfinite(norm) and norm != 0.0):
+                info = 2
+                break
+            pi = pn / norm
+            elbo.append(e)
+            if it > 0 and elbo[-1] - elbo[-2] < eps:
+                break
+    labels = lab.astype(np.int32) if info else np.argmax(gamma, axis=1).astype(np.int32)
+    return dict(gamma=gamma, pi=pi, elbo=np.asarray(elbo), iters=len(elbo) + (1 if info else 0), info=info, labels=labels)
+
+
+def plan_vbx_groups(row0, dim, max_spk, max_bytes=VBX_MAX_BYTES):
+    """Cut the groups of the prefix table row0 [G + 1] into calls of xv_vbx_groups_f64, runs of consecutive groups whose workspace
+    fits max_bytes: -> [(g_lo, g_hi)].  One group alone above max_bytes is an error."""
+    row0 = np.asarray(row0, dtype=np.int64)
+    G = row0.size - 1
+    calls, lo = [], 0
+    for g in range(G):
+        if hiplib.vbx_groups_workspace_bytes(int(row0[g + 1] - row0[lo]), g + 1 - lo, dim, max_spk) > max_bytes:
+            if g == lo:
+                raise ValueError("vbx_groups: a group of %d rows needs a workspace of more than max_bytes = %d" %
+                                 (int(row0[g + 1] - row0[g]), max_bytes))
+            calls.append((lo, g))
+            lo = g
+            if hiplib.vbx_groups_workspace_bytes(int(row0[g + 1] - row0[g]), 1, dim, max_spk) > max_bytes:
+                raise ValueError("vbx_groups: a group of %d rows needs a workspace of more than max_bytes = %d" %
+                                 (int(row0[g + 1] - row0[g]), max_bytes))
+    calls.append((lo, G))
+    return calls
+
+
+def vbx_groups(y_rows, tables, init_labels, plda, time_order=None, n_spk=None, fa=0.3, fb=17.0, loop_prob=0.99, init_smoothing=5.0,
+               max_iters=40, epsilon=1e-6, max_bytes=VBX_MAX_BYTES, keep_gamma=False):
+    """VBx resegmentation of every group on the device (xv_vbx_groups_f64).  y_rows: float32 device rows [N, >= d], the vectors
+    after mean subtraction, LDA and length normalisation (``prepare(..., SIDE_PLAIN, plda=None)``); tables: their GroupTables;
+    init_labels: int [N], per row, in [0, S_g); n_spk: int [G] (None: every group's largest label + 1), each at most
+    hiplib.VBX_MAX_SPK; time_order: int [N] or None -- entry row0[g] + t is the index, local to group g, of its t-th vector in
+    time (None: the rows are in time order).  The fp64 model is uploaded once, the group list is cut into calls whose workspace
+    fits max_bytes (``plan_vbx_groups``), and everything comes down in one download at the end.
+    -> dict(labels int32 [N] (per row, a slot of the initial labelling), iters, info int32 [G], n_spk int32 [G],
+    pi float64 [G, max S], elbo float64 [G, max_iters] (NaN past iters), gamma float64 [N, max S] if keep_gamma)."""
+    import torch
+    hiplib.require_gpu()
+    p = check_vbx_params(fa, fb, loop_prob, init_smoothing, max_iters, epsilon)
+    d, G, N = plda.dim, tables.sizes.size, tables.n_rows
+    if d > hiplib.PCA_MAX_DIM:
+        raise ValueError("vbx_groups: dimension %d exceeds %d, the limit of xv_vbx_groups_f64" % (d, hiplib.PCA_MAX_DIM))
+    lab = np.ascontiguousarray(init_labels, dtype=np.int32).reshape(-1)
+    if lab.size != N or y_rows.shape[0] != N:
+        raise ValueError("vbx_groups: %d rows in the tables, %d on the device, %d initial labels" % (N, y_rows.shape[0], lab.size))
+    if n_spk is None:
+        n_spk = np.maximum.reduceat(lab, tables.row0[:-1].astype(np.int64)) + 1
+    spk = np.ascontiguousarray(n_spk, dtype=np.int32).reshape(-1)
+    if spk.size != G or int(spk.min()) < 1 or int(spk.max()) > hiplib.VBX_MAX_SPK:
+        raise ValueError("vbx_groups: one speaker count per group, each in [1, %d]" % hiplib.VBX_MAX_SPK)
+    order = None
+    if time_order is not None:
+        order = np.ascontiguousarray(time_order, dtype=np.int32).reshape(-1)
+        if order.size != N:
+            raise ValueError("vbx_groups: %d rows, %d entries of the time order" % (N, order.size))
+    ms, mi = int(spk.max()), p["max_iters"]
+    calls = plan_vbx_groups(tables.row0, d, ms, max_bytes)
+    dev = y_rows.device
+    with torch.cuda.device(dev):
+        model = [torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev) for a in (plda.mean, plda.transform, plda.psi)]
+        ints_in = torch.as_tensor(np.concatenate([lab, spk] + ([] if order is None else [order])), device=dev)
+        lab_d, spk_d = ints_in[:N], ints_in[N:N + G]
+        order_d = None if order is None else ints_in[N + G:]
+        # every result in one buffer, the float64 part first: one download
+        n_f64 = G * ms + G * mi + (N * ms if keep_gamma else 0)
+        out = torch.empty(8 * n_f64 + 4 * (N + 2 * G + 1), dtype=torch.uint8, device=dev)
+        f64 = out[:8 * n_f64].view(torch.float64)
+        i32 = out[8 * n_f64:].view(torch.int32)
+        pi_d, elbo_d = f64[:G * ms].view(G, ms), f64[G * ms:G * (ms + mi)].view(G, mi)
+        gamma_d = f64[G * (ms + mi):].view(N, ms) if keep_gamma else None
+        labels_d, iters_d, info_d, status_d = i32[:N], i32[N:N + G], i32[N + G:N + 2 * G], i32[N + 2 * G:]
+        f64.fill_(float("nan"))
+        i32.zero_()
+        ws = torch.empty(max(hiplib.vbx_groups_workspace_bytes(int(tables.row0[hi] - tables.row0[lo]), hi - lo, d, ms)
+                             for lo, hi in calls), dtype=torch.uint8, device=dev)
+        for lo, hi in calls:
+            r0, r1 = int(tables.row0[lo]), int(tables.row0[hi])
+            row0_d = tables.row0_d[lo:hi + 1] if r0 == 0 else tables.row0_d[lo:hi + 1] - r0
+            hiplib.vbx_groups(y_rows[r0:r1], row0_d, d, None if order_d is None else order_d[r0:r1], lab_d[r0:r1], spk_d[lo:hi], ms,
+                              *model, p["fa"], p["fb"], p["loop_prob"], p["init_smoothing"], mi, p["epsilon"], labels_d[r0:r1],
+                              None if gamma_d is None else gamma_d[r0:r1], pi_d[lo:hi], elbo_d[lo:hi], iters_d[lo:hi], info_d[lo:hi],
+                              status_d, ws)
+        out_h = out.cpu().numpy()
+    f64_h, i32_h = out_h[:8 * n_f64].view(np.float64), out_h[8 * n_f64:].view(np.int32)
+    if i32_h[N + 2 * G]:
+        raise hiplib.XvectorHipError("vbx_groups: the kernel skipped a group that broke its contract (status %d)" % i32_h[N + 2 * G])
+    res = dict(labels=i32_h[:N].copy(), iters=i32_h[N:N + G].copy(), info=i32_h[N + G:N + 2 * G].copy(), n_spk=spk.copy(),
+               pi=f64_h[:G * ms].reshape(G, ms).copy(), elbo=f64_h[G * ms:G * (ms + mi)].reshape(G, mi).copy())
+    if keep_gamma:
+        res["gamma"] = f64_h[G * (ms + mi):].reshape(N, ms).copy()
+    return res
 
 
 DENSE_MAX_BYTES = 1 << 30          # the dense score matrix of one trial list is at most this large

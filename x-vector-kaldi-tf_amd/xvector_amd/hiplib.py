@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 41
+ABI_VERSION = 42
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -144,6 +144,10 @@ _SIGNATURES = {
                                      _vp, _vp, _vp, _sz, _vp]),
     "xv_pca_plda_groups_workspace_bytes": (_sz, [_ci, _ci]),
     "xv_backend_prepare_groups_f32": (_ci, [_vp, _i64, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _i64, _vp, _vp, _vp]),
+    # diarization: VBx resegmentation of every recording's vectors
+    "xv_vbx_groups_f64": (_ci, [_vp, _i64, _ci, _vp, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double,
+                                ctypes.c_double, ctypes.c_double, _ci, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "xv_vbx_groups_workspace_bytes": (_sz, [_ci, _ci, _ci, _ci]),
     "xv_mfcc_f32": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _ci, _i64, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _ci, _vp, _ci, _ci, _ci, _ci,
                           _cf, _cf, _ci, _ci, _ci, _cf, _vp, _i64, _vp, _i64, _vp]),
     "xv_vad_energy_f32": (_ci, [_vp, _i64, _vp, _vp, _ci, _cf, _cf, _ci, _cf, _vp, _vp]),
@@ -190,6 +194,8 @@ AHC_MAX_N = 32768                  # XV_AHC_MAX_N: items of one xv_ahc_average_f
 AHC_BATCH_MAX_N = 4096             # XV_AHC_BATCH_MAX_N: items of one group of xv_ahc_average_batch_f64
 PCA_MAX_DIM = 128                  # XV_PCA_MAX_DIM: the vector dimension of xv_pca_plda_groups_f64
 PCA_MAX_SWEEPS = 30                # XV_PCA_MAX_SWEEPS: the sweep cap of its Jacobi iteration
+VBX_MAX_SPK = 64                   # XV_VBX_MAX_SPK: speakers of one group of xv_vbx_groups_f64
+VBX_MAX_ITERS = 100                # XV_VBX_MAX_ITERS: its iteration cap
 
 _lib = None
 
@@ -1558,6 +1564,41 @@ def backend_prepare_groups(y, grp_row0, max_n, dim, grp_dim, grp_psi, grp_map, g
                                              _dev(grp_map, f64, "grp_map", G * dim * dim), _dev(grp_off, f64, "grp_off", G * dim),
                                              int(side), _ptr(out), out.stride(0), _ptr(r), _dev(status, i32, "status", 1), _stream()),
            "xv_backend_prepare_groups_f32")
+
+
+def vbx_groups_workspace_bytes(n_rows, n_groups, dim, max_spk):
+    return int(load().xv_vbx_groups_workspace_bytes(int(n_rows), int(n_groups), int(dim), int(max_spk)))
+
+
+def vbx_groups(y, grp_row0, dim, row_of_t, init_label, grp_spk, max_spk, mean, transform, psi, fa, fb, loop_prob, init_smoothing,
+               max_iters, epsilon, labels, gamma, pi, elbo, grp_iters, grp_info, status, workspace=None):
+    """VBx resegmentation of every group's rows (xv_vbx_groups_f64; see include/xvector_hip.h for the rule).  y: float32 rows
+    [n_rows, >= dim] (its row stride is passed as ldy); grp_row0: int32 [G + 1]; row_of_t: int32 [n_rows] or None (the identity);
+    init_label: int32 [n_rows]; grp_spk: int32 [G]; the model mean, psi: float64 [dim], transform: float64 [dim, dim].  Outputs,
+    all on the device: labels int32 [n_rows]; gamma float64 [n_rows, max_spk] or None; pi float64 [G, max_spk]; elbo float64
+    [G, max_iters]; grp_iters, grp_info: int32 [G]; status: int32 [1], zeroed by the caller.  Nothing is read back and the stream
+    is not synchronised.  workspace: vbx_groups_workspace_bytes(n_rows, G, dim, max_spk) bytes (None: allocated here)."""
+    import torch
+    lib = require_gpu()
+    _rows2d(y, "y")
+    i32, f64 = torch.int32, torch.float64
+    G = grp_spk.numel()
+    dim, max_spk, max_iters = int(dim), int(max_spk), int(max_iters)
+    n_rows = y.shape[0]
+    assert y.shape[1] >= dim
+    if workspace is None:
+        workspace = _ws(lib.xv_vbx_groups_workspace_bytes(n_rows, G, dim, max_spk), y.device)
+    assert workspace.is_cuda and workspace.is_contiguous()
+    _check(lib.xv_vbx_groups_f64(_ptr(y), y.stride(0), n_rows, _dev(grp_row0, i32, "grp_row0", G + 1), G, dim,
+                                 None if row_of_t is None else _dev(row_of_t, i32, "row_of_t", n_rows),
+                                 _dev(init_label, i32, "init_label", n_rows), _dev(grp_spk, i32, "grp_spk"), max_spk,
+                                 _dev(mean, f64, "mean", dim), _dev(transform, f64, "transform", dim * dim), _dev(psi, f64, "psi", dim),
+                                 float(fa), float(fb), float(loop_prob), float(init_smoothing), max_iters, float(epsilon),
+                                 _dev(labels, i32, "labels", n_rows),
+                                 None if gamma is None else _dev(gamma, f64, "gamma", n_rows * max(max_spk, 0)),
+                                 _dev(pi, f64, "pi", G * max(max_spk, 0)), _dev(elbo, f64, "elbo", G * max(max_iters, 0)),
+                                 _dev(grp_iters, i32, "grp_iters", G), _dev(grp_info, i32, "grp_info", G),
+                                 _dev(status, i32, "status", 1), _ptr(workspace), _nbytes(workspace), _stream()), "xv_vbx_groups_f64")
 
 
 def mfcc(samples, utt_offset, utt_samples, utt_row0, utt_key, total_rows, tables, opts, feats, logmel=None):
