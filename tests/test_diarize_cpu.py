@@ -181,7 +181,7 @@ def test_stop_rules():
 def test_diarize_sorts_for_the_device_and_unsorts_the_results(host_only, monkeypatch):
     """backend.diarize with both device stages replaced: the device sees the recordings by size, descending, with their own stop
     rules, and every result comes back to the caller's rows and recordings."""
-    from xvector_amd import backend
+    from xvector_amd import backend, hiplib
     sizes = [3, 6, 2, 6, 1]
     n = sum(sizes)
     x = np.zeros((n, 4), np.float32)
@@ -189,12 +189,15 @@ def test_diarize_sorts_for_the_device_and_unsorts_the_results(host_only, monkeyp
     x[:, 1] = np.repeat(np.arange(len(sizes)), sizes)               # ... and its recording
     seen = {}
 
-    def fake_score_blocks(xs, group_sizes, plda, mean=None, transform=None, device=None):
+    def fake_score_blocks(xs, group_sizes, plda, mean=None, transform=None, device=None, target_energy=1.0,
+                          pca_max_bytes=backend.PCA_MAX_BYTES, keep_plain=False):
+        assert target_energy == 1.0 and pca_max_bytes == backend.PCA_MAX_BYTES and keep_plain is False
         seen["sizes"] = list(group_sizes)
         seen["x"] = np.array(xs)
         return "scores", backend.GroupTables(group_sizes)
 
-    def fake_ahc_batch(scores, tables, thresholds, min_clusters):
+    def fake_ahc_batch(scores, tables, thresholds, min_clusters, max_bytes=backend.AHC_MAX_BYTES, max_batch_n=hiplib.AHC_BATCH_MAX_N):
+        assert max_bytes == backend.AHC_MAX_BYTES and max_batch_n == hiplib.AHC_BATCH_MAX_N
         assert scores == "scores"
         seen["thr"], seen["minc"] = list(thresholds), list(min_clusters)
         labels, merges, at = [], [], 0

@@ -370,3 +370,55 @@ def test_cli_end_to_end(tmp_path, caplog):
         assert int(f[7]) >= 1
     assert "VBx resegmentation: 3 recordings" in caplog.text and "%d speakers before and %d after" % (n_before, n_after) in caplog.text
     assert not os.path.exists(p + "/vbx.labels.tmp")
+
+
+@pytest.mark.parametrize("target_energy", [1.0, 0.5])
+def test_diarize_equals_its_stages(target_energy):
+    """backend.diarize with VBx (and, at 0.5, the per-recording PCA) against its stages composed by hand, byte for byte: four
+    recordings out of size order, the third told to stop at 70 clusters (above hiplib.VBX_MAX_SPK: it keeps its clustering), the
+    second kept by the caller, every recording's rows in a shuffled time order.  Here VBx runs on one recording at a time, from the
+    caller's side of the size order; the kernel's results do not depend on the batch (test_batch_independence)."""
+    import torch
+    from xvector_amd import backend, hiplib
+    D, sizes = 16, [40, 9, 70, 25]
+    mdl = vbx_ref.model(D, 7)
+    plda = backend.Plda(*mdl)
+    x = np.concatenate([vbx_ref.turns_case(D, T, nt, nt, 20 + g, mdl=mdl, split=False, wrong=0)[0]
+                        for g, (T, nt) in enumerate(zip(sizes, (3, 2, 4, 2)))])
+    G, row0 = len(sizes), np.concatenate([[0], np.cumsum(sizes)])
+    keep = [False, True, False, False]
+    time_order = np.concatenate([np.random.default_rng(g).permutation(n) for g, n in enumerate(sizes)])
+    rep, pr = {}, {}
+    labels, merges = backend.diarize(x, sizes, plda, threshold=E2E_THRESHOLD, num_spk=[None, None, 70, None], device=DEV,
+                                     target_energy=target_energy, pca_report=pr, vbx=dict(time_order=time_order, keep=keep),
+                                     vbx_report=rep)
+    # by hand: sort by size, score, cluster ...
+    order, inverse = backend.size_order(sizes)
+    assert order.tolist() == [2, 0, 3, 1]
+    rows = np.concatenate([np.arange(row0[g], row0[g + 1]) for g in order])
+    thr, minc = np.asarray([E2E_THRESHOLD, E2E_THRESHOLD, NEG_INF, E2E_THRESHOLD]), np.asarray([1, 1, 70, 1])
+    scores, tables = backend.score_blocks(x[rows], np.asarray(sizes)[order], plda, None, None, DEV, target_energy, keep_plain=True)
+    lab_sorted, merges_sorted = backend.ahc_batch(scores, tables, thr[order], minc[order])
+    want, ran = [], []
+    for g in range(G):                                               # ... and VBx, recording by recording in the caller's order
+        k = int(inverse[g])
+        lab = lab_sorted[k]
+        init, S = backend.compact_labels(lab)
+        ran.append(not keep[g] and S <= hiplib.VBX_MAX_SPK)
+        if ran[-1]:
+            Y = tables.plain[int(tables.row0[k]):int(tables.row0[k + 1])].clone()
+            res = backend.vbx_groups(Y, backend.GroupTables([sizes[g]], DEV), init, plda, time_order[row0[g]:row0[g + 1]], [S])
+            if res["info"][0] == 0:
+                lab = res["labels"]
+        want.append(lab)
+        for a, b in zip(merges[g], merges_sorted[k]):
+            assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), g
+    want = np.concatenate(want)
+    assert labels.dtype == want.dtype == np.int32 and labels.tobytes() == want.tobytes()
+    assert ran == [True, False, False, True] and rep["ran"].tolist() == [True, False, False, True]
+    assert rep["spk_before"][2] == 70 and np.unique(labels[row0[2]:row0[3]]).size == 70
+    if target_energy == 1.0:
+        assert pr == {}
+    else:
+        assert sorted(pr) == ["dim", "info"] and pr["dim"].shape == pr["info"].shape == (G,)
+        assert np.array_equal(pr["dim"][order], tables.pca[:G].cpu().numpy()) and np.array_equal(pr["info"][order], tables.pca[G:].cpu().numpy())

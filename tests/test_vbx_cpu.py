@@ -145,19 +145,39 @@ def _rows(sizes):
 
 
 def test_diarize_without_vbx_makes_the_calls_it_made(host_only, monkeypatch):
-    """vbx=None: score_blocks and ahc_batch see exactly the arguments they saw before VBx existed -- the fakes take nothing
-    else -- and nothing of the VBx stage is touched."""
+    """vbx=None and the default target energy: the default route asks its two stages for nothing beyond their defaults -- their
+    first six (four) arguments are what they were before the PCA and VBx existed, the target energy is 1, keep_plain is False and
+    every other parameter has its declared default -- and it touches nothing of the VBx stage."""
+    import inspect
     from xvector_amd import backend
     sizes = [3, 6, 2]
+    x = _rows(sizes)
+    real = dict(score_blocks=backend.score_blocks, ahc_batch=backend.ahc_batch)
     calls = []
 
+    def bound(name, first, a, k):
+        """The call's arguments by name; asserts that all but the first ``first`` and those the caller checks hold their defaults."""
+        sig = inspect.signature(real[name])
+        b = sig.bind(*a, **k)
+        b.apply_defaults()
+        for p in list(sig.parameters.values())[first:]:
+            if p.name not in ("target_energy", "keep_plain"):
+                assert b.arguments[p.name] == p.default, (name, p.name)
+        calls.append(name)
+        return b.arguments
+
     def fake_score_blocks(*a, **k):
-        calls.append(("score_blocks", len(a), dict(k)))
-        return "scores", backend.GroupTables(a[1])
+        v = bound("score_blocks", 6, a, k)
+        assert np.array_equal(v["x"], x[[3, 4, 5, 6, 7, 8, 0, 1, 2, 9, 10]]) and list(v["group_sizes"]) == [6, 3, 2]
+        assert v["plda"] is None and v["mean"] is None and v["transform"] is None and v["device"] == "cuda:0"
+        assert backend.target_energy_is_one(v["target_energy"]) and v["keep_plain"] is False
+        return "scores", backend.GroupTables(v["group_sizes"])
 
     def fake_ahc_batch(*a, **k):
-        calls.append(("ahc_batch", len(a), dict(k)))
-        return [np.zeros(m, np.int32) for m in a[1].sizes.tolist()], ["m"] * a[1].sizes.size
+        v = bound("ahc_batch", 4, a, k)
+        assert v["scores"] == "scores" and v["tables"].sizes.tolist() == [6, 3, 2]
+        assert list(v["thresholds"]) == [0.5] * 3 and list(v["min_clusters"]) == [1] * 3
+        return [np.zeros(m, np.int32) for m in v["tables"].sizes.tolist()], ["m"] * v["tables"].sizes.size
 
     def never(*a, **k):
         raise AssertionError("the VBx stage ran")
@@ -166,8 +186,8 @@ def test_diarize_without_vbx_makes_the_calls_it_made(host_only, monkeypatch):
     monkeypatch.setattr(backend, "ahc_batch", fake_ahc_batch)
     for name in ("vbx_groups", "_diarize_vbx", "prepare", "check_vbx_params"):
         monkeypatch.setattr(backend, name, never)
-    labels, merges = backend.diarize(_rows(sizes), sizes, None, threshold=0.5)
-    assert calls == [("score_blocks", 6, {}), ("ahc_batch", 4, {})]
+    labels, merges = backend.diarize(x, sizes, None, threshold=0.5)
+    assert calls == ["score_blocks", "ahc_batch"]
     assert labels.tolist() == [0] * 11 and merges == ["m"] * 3
 
 
@@ -182,13 +202,15 @@ def test_diarize_with_vbx_hands_over_rows_labels_and_time_order(host_only, monke
     n = x.shape[0]
     seen = {}
 
-    def fake_score_blocks(xs, group_sizes, plda, mean=None, transform=None, device=None, target_energy=1.0, keep_plain=False):
-        assert keep_plain
+    def fake_score_blocks(xs, group_sizes, plda, mean=None, transform=None, device=None, target_energy=1.0,
+                          pca_max_bytes=backend.PCA_MAX_BYTES, keep_plain=False):
+        assert keep_plain and target_energy == 1.0 and pca_max_bytes == backend.PCA_MAX_BYTES
         t = backend.GroupTables(group_sizes)
         t.plain = torch.as_tensor(np.array(xs))
         return "scores", t
 
-    def fake_ahc_batch(scores, tables, thresholds, min_clusters):
+    def fake_ahc_batch(scores, tables, thresholds, min_clusters, max_bytes=backend.AHC_MAX_BYTES, max_batch_n=hiplib.AHC_BATCH_MAX_N):
+        assert max_bytes == backend.AHC_MAX_BYTES and max_batch_n == hiplib.AHC_BATCH_MAX_N
         # recording 1 (70 rows): 70 clusters, above the cap; the others: slots 0 and 5 alternating
         return [np.arange(m, dtype=np.int32) if m == 70 else (np.arange(m, dtype=np.int32) % 2) * 5 for m in tables.sizes.tolist()], \
                [None] * tables.sizes.size

@@ -87,6 +87,31 @@ def _stack(vectors, keys):
     return np.stack([vectors[k] for k in keys]).astype(np.float32)
 
 
+def _read_lda_checked(args_lda, x, plda, nothing_written):
+    """(t, dim): the LDA of --lda (None without one) and the dimension of the vectors x after it.  SystemExit when the LDA does not
+    take the vectors or the PLDA not what comes out; nothing_written ends that message ("no model written")."""
+    from xvector_amd import backend
+    t = backend.read_transform(args_lda) if args_lda else None
+    if t is not None and t.shape[1] not in (x.shape[1], x.shape[1] + 1):
+        raise SystemExit("%s has %d columns, the vectors have dimension %d" % (args_lda, t.shape[1], x.shape[1]))
+    dim = x.shape[1] if t is None else t.shape[0]
+    if dim != plda.dim:
+        raise SystemExit("the vectors have dimension %d%s, the PLDA %d: %s" %
+                         (dim, " after the LDA" if t is not None else "", plda.dim, nothing_written))
+    return t, dim
+
+
+def _stage8_chain(x, t, mean_only=False):
+    """stage 8's chain on the device: subtract the set's own mean (taken in float64, cast to float32), transform-vec with the LDA
+    t, ivector-normalize-length.  -> (mean, the PLAIN-prepared device rows; None with mean_only, for a caller that hands the mean
+    and t to a function that runs the chain itself)."""
+    from xvector_amd import backend, hiplib
+    mean = x.astype(np.float64).mean(axis=0).astype(np.float32)
+    if mean_only:
+        return mean, None
+    return mean, backend.prepare(x, hiplib.SIDE_PLAIN, mean=mean, transform=t, length_norm=True)[0]
+
+
 def cmd_mean(args):
     vectors = read_vectors(args.vectors)
     x = _stack(vectors, list(vectors)).astype(np.float64)
@@ -111,17 +136,14 @@ def cmd_compute_lda(args):
 
 
 def cmd_compute_plda(args):
-    from xvector_amd import backend, hiplib
+    from xvector_amd import backend
     vectors = read_vectors(args.vectors)
     spk2utt = read_table(args.spk2utt)
     keys = list(vectors)
     x = _stack(vectors, keys)
     if args.lda:
-        # stage 8's chain: subtract the set's own mean, transform-vec, ivector-normalize-length -- on the device
         t = backend.read_transform(args.lda)
-        mean = x.astype(np.float64).mean(axis=0).astype(np.float32)
-        rows, _ = backend.prepare(x, hiplib.SIDE_PLAIN, mean=mean, transform=t, length_norm=True)
-        x = rows[:, :t.shape[0]].cpu().numpy()
+        x = _stage8_chain(x, t)[1][:, :t.shape[0]].cpu().numpy()
     pos = {k: i for i, k in enumerate(keys)}
     groups, missing = [], 0
     for spk, utts in spk2utt.items():
@@ -149,22 +171,11 @@ def cmd_adapt_plda(args):
     if not vectors:
         raise SystemExit("no vectors in %s: nothing to adapt to, no model written" % args.vectors)
     x = _stack(vectors, list(vectors))
-    t = backend.read_transform(args.lda) if args.lda else None
-    if t is not None and t.shape[1] not in (x.shape[1], x.shape[1] + 1):
-        raise SystemExit("%s has %d columns, the vectors have dimension %d" % (args.lda, t.shape[1], x.shape[1]))
-    dim = x.shape[1] if t is None else t.shape[0]
-    if dim != plda.dim:
-        raise SystemExit("the vectors have dimension %d%s, the PLDA %d: no model written" %
-                         (dim, " after the LDA" if t is not None else "", plda.dim))
+    t, dim = _read_lda_checked(args.lda, x, plda, "no model written")
     if dim > hiplib.MOMENT_DIM_MAX:
         raise SystemExit("vectors of dimension %d: the moments kernel takes at most %d" % (dim, hiplib.MOMENT_DIM_MAX))
-    if t is not None:
-        # stage 8's chain: subtract the set's own mean, transform-vec, ivector-normalize-length -- on the device, where the rows stay
-        mean = x.astype(np.float64).mean(axis=0).astype(np.float32)
-        rows, _ = backend.prepare(x, hiplib.SIDE_PLAIN, mean=mean, transform=t, length_norm=True)
-        n, s1, s2 = backend.moment_stats(rows, dim)
-    else:
-        n, s1, s2 = backend.moment_stats(x, dim)
+    # with an LDA the rows of stage 8's chain stay on the device
+    n, s1, s2 = backend.moment_stats(x if t is None else _stage8_chain(x, t)[1], dim)
     logger.info("Read %d vectors of dimension %d" % (n, dim))
     out = backend.adapt_plda(plda, n, s1, s2, args.within_covar_scale, args.between_covar_scale, args.mean_diff_scale)
     backend.write_plda(args.plda_out, out, binary=args.binary)
@@ -184,19 +195,12 @@ def cmd_cluster(args):
     keys = list(vectors)
     x = _stack(vectors, keys)
     n = len(keys)
-    t = backend.read_transform(args.lda) if args.lda else None
-    if t is not None and t.shape[1] not in (x.shape[1], x.shape[1] + 1):
-        raise SystemExit("%s has %d columns, the vectors have dimension %d" % (args.lda, t.shape[1], x.shape[1]))
-    dim = x.shape[1] if t is None else t.shape[0]
-    if dim != plda.dim:
-        raise SystemExit("the vectors have dimension %d%s, the PLDA %d: no utt2cluster written" %
-                         (dim, " after the LDA" if t is not None else "", plda.dim))
+    t, dim = _read_lda_checked(args.lda, x, plda, "no utt2cluster written")
     if n > hiplib.AHC_MAX_N:
         raise SystemExit("%d vectors: the clustering kernel takes at most %d" % (n, hiplib.AHC_MAX_N))
     if args.num_clusters is not None and args.num_clusters > n:
         raise SystemExit("--num-clusters %d exceeds the number of vectors %d" % (args.num_clusters, n))
-    # stage 8's chain: subtract the set's own mean, transform-vec, ivector-normalize-length -- on the device
-    mean = x.astype(np.float64).mean(axis=0).astype(np.float32) if t is not None else None
+    mean = _stage8_chain(x, t, mean_only=True)[0] if t is not None else None       # cluster_vectors runs the chain
     try:
         labels, _ = backend.cluster_vectors(x, plda, mean=mean, transform=t, threshold=args.threshold, num_clusters=args.num_clusters)
     except ValueError as e:
@@ -335,13 +339,7 @@ def cmd_diarize(args):
         logger.warning("%d segments of %s have no vector: skipped" % (missing, args.segments))
     keys = [segments[i][0] for g in groups for i in g]
     x = _stack(vectors, keys)
-    t = backend.read_transform(args.lda) if args.lda else None
-    if t is not None and t.shape[1] not in (x.shape[1], x.shape[1] + 1):
-        raise SystemExit("%s has %d columns, the vectors have dimension %d" % (args.lda, t.shape[1], x.shape[1]))
-    dim = x.shape[1] if t is None else t.shape[0]
-    if dim != plda.dim:
-        raise SystemExit("the vectors have dimension %d%s, the PLDA %d: no labels written" %
-                         (dim, " after the LDA" if t is not None else "", plda.dim))
+    t, dim = _read_lda_checked(args.lda, x, plda, "no labels written")
     mean = kaldi_io.read_vec_flt(args.mean).astype(np.float32) if args.mean else None
     if mean is not None and mean.shape[0] != x.shape[1]:
         raise SystemExit("%s has dimension %d, the vectors %d: no labels written" % (args.mean, mean.shape[0], x.shape[1]))
@@ -353,18 +351,13 @@ def cmd_diarize(args):
             if k is not None and k > n:
                 logger.warning("recording %s: %d speakers asked for, %d vectors: using %d" % (r, k, n, n))
     pca, vbx_rep = {}, {}
+    if vbx is not None:
+        # VBx visits a recording's vectors in the RTTM's own order, (start, end, key); the clustering keeps the file order
+        order = [sorted(range(len(g)), key=lambda j: (segments[g[j]][2], segments[g[j]][3], segments[g[j]][0])) for g in groups]
+        vbx = dict(vbx, time_order=np.concatenate(order), keep=np.asarray([r in num_spk for r in recos]))
     try:
-        if vbx is not None:
-            # VBx visits a recording's vectors in the RTTM's own order, (start, end, key); the clustering keeps the file order
-            order = [sorted(range(len(g)), key=lambda j: (segments[g[j]][2], segments[g[j]][3], segments[g[j]][0])) for g in groups]
-            vbx = dict(vbx, time_order=np.concatenate(order), keep=np.asarray([r in num_spk for r in recos]))
-            slots, _ = backend.diarize(x, sizes, plda, mean=mean, transform=t, threshold=args.threshold, num_spk=counts,
-                                       target_energy=args.target_energy, pca_report=pca, vbx=vbx, vbx_report=vbx_rep)
-        elif backend.target_energy_is_one(args.target_energy):
-            slots, _ = backend.diarize(x, sizes, plda, mean=mean, transform=t, threshold=args.threshold, num_spk=counts)
-        else:
-            slots, _ = backend.diarize(x, sizes, plda, mean=mean, transform=t, threshold=args.threshold, num_spk=counts,
-                                       target_energy=args.target_energy, pca_report=pca)
+        slots, _ = backend.diarize(x, sizes, plda, mean=mean, transform=t, threshold=args.threshold, num_spk=counts,
+                                   target_energy=args.target_energy, pca_report=pca, vbx=vbx, vbx_report=vbx_rep)
     except ValueError as e:
         raise SystemExit("%s: no labels written" % e)
     label_of, by_reco, n_speakers, at = {}, [], 0, 0

@@ -527,14 +527,21 @@ def ahc(scores, threshold=0.0, num_clusters=None, max_bytes=AHC_MAX_BYTES):
     return lab.cpu().numpy(), (m_a[:m].cpu().numpy(), m_b[:m].cpu().numpy(), m_s[:m].cpu().numpy())
 
 
+def _self_operands(x, plda, mean, transform, device):
+    """(E, r, T): the rows of x prepared as one-utterance enrolments (with their r) and as tests, the operands that score x against
+    itself (the pair of prepare calls of the test-side AS-norm statistics)."""
+    ln = transform is not None
+    E, r = prepare(x, hiplib.SIDE_ENROL, np.ones(len(x), np.int32), mean, transform, plda, ln, device)
+    T, _ = prepare(x, hiplib.SIDE_TEST, None, mean, transform, plda, ln, device)
+    return E, r, T
+
+
 def score_matrix_self(x, plda, mean=None, transform=None, device="cuda:0"):
     """S[N, ld] on the device, ld = N rounded up to a multiple of 4: S[i, j] = the PLDA LLR of vector i as a one-utterance
-    enrolment against vector j as a test (the pair of prepare calls of the test-side AS-norm statistics)."""
+    enrolment against vector j as a test (``_self_operands``)."""
     import torch
-    ln = transform is not None
     n = len(x)
-    E, r = prepare(x, hiplib.SIDE_ENROL, np.ones(n, np.int32), mean, transform, plda, ln, device)
-    T, _ = prepare(x, hiplib.SIDE_TEST, None, mean, transform, plda, ln, device)
+    E, r, T = _self_operands(x, plda, mean, transform, device)
     s = torch.empty((n, (n + 3) // 4 * 4), dtype=torch.float32, device=device)
     hiplib.score_matrix(E, T, r, s)
     return s
@@ -560,7 +567,10 @@ class GroupTables(object):
     """The ragged-batch tables of xv_score_blocks_f32 / xv_ahc_average_batch_f64 for groups of ``sizes`` rows, in that order:
     row0 int32 [G + 1] (prefix sums), ld int64 [G] (the row stride of a group's score block, its size rounded up to a multiple of
     4), score0 int64 [G] (element offsets of the blocks, packed back to back) and scores_elems; row0_d / score0_d are their device
-    copies and status the device word both kernels report a skipped group in (zeroed here)."""
+    copies and status the device word both kernels report a skipped group in (zeroed here).  What ``score_blocks`` leaves here for
+    the later stages: pca, an int32 device tensor [2 G], every group's retained dimension followed by the 0 / 1 / 2 fallback codes
+    (None without a PCA); pca_host, its NumPy copy once ``ahc_batch`` has downloaded it; plain, the PLAIN-prepared device rows
+    (None unless asked for with keep_plain)."""
 
     def __init__(self, sizes, device=None):
         self.sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
@@ -576,6 +586,7 @@ class GroupTables(object):
         self.n_rows = int(self.row0[-1])
         self.max_n = int(self.sizes.max())
         self.row0_d = self.score0_d = self.status = None
+        self.pca = self.pca_host = self.plain = None
         if device is not None:
             import torch
             self.row0_d = torch.as_tensor(self.row0, device=device)
@@ -597,39 +608,40 @@ def size_order(sizes):
     return order, inverse
 
 
+def _cut_runs(lo, hi, fits):
+    """Cut the consecutive groups lo .. hi - 1 greedily into runs under a budget: -> [(a, b)], each run [a, b) grown while
+    fits(a, b) says that groups [a, b) fit.  ValueError(g) when group g does not fit alone; the planners say it in their words."""
+    runs, a = [], lo
+    for g in range(lo, hi):
+        if g > a and not fits(a, g + 1):
+            runs.append((a, g))
+            a = g
+        if g == a and not fits(g, g + 1):
+            raise ValueError(g)
+    return runs + [(a, hi)] if hi > lo else runs
+
+
 def plan_ahc_batch(sizes, max_bytes=AHC_MAX_BYTES, max_batch_n=hiplib.AHC_BATCH_MAX_N):
     """Cut the group list into calls of xv_ahc_average_batch_f64: -> (calls, routed).  calls: a list of (g_lo, g_hi, ws0, nbytes):
     groups [g_lo, g_hi) in one call, ws0 int64 [g_hi - g_lo] their byte offsets into a workspace of nbytes <= max_bytes.  A call
     is a run of consecutive groups, because a group's rows are found by a prefix-sum table.  routed: the groups above max_batch_n,
     which go through the single-problem ``ahc`` on their block.  A group whose own workspace exceeds max_bytes is an error."""
     max_batch_n = min(int(max_batch_n), hiplib.AHC_BATCH_MAX_N)
-    calls, routed = [], []
-    lo, offs, total = None, [], 0
-
-    def close(hi):
-        if lo is not None:
-            calls.append((lo, hi, np.asarray(offs, dtype=np.int64), total))
-
-    for g, n in enumerate(np.asarray(sizes, dtype=np.int64).tolist()):
-        if n > max_batch_n:
-            close(g)
-            lo, offs, total = None, [], 0
-            routed.append(g)
-            if hiplib.ahc_average_workspace_bytes(n) > max_bytes:
-                raise ValueError("ahc_batch: a group of %d items needs a workspace of more than max_bytes = %d" % (n, max_bytes))
-            continue
-        need = hiplib.ahc_average_batch_workspace_bytes(n)
-        if need > max_bytes:
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1).tolist()
+    routed = [g for g, n in enumerate(sizes) if n > max_batch_n]
+    need = [0 if n > max_batch_n else hiplib.ahc_average_batch_workspace_bytes(n) for n in sizes]
+    end = np.concatenate([[0], np.cumsum(need, dtype=np.int64)]).tolist()    # a call's workspace offsets: the sum of the needs before
+    calls = []
+    for lo, hi in zip([0] + [g + 1 for g in routed], routed + [len(sizes)]):       # the stretches between routed groups, in order
+        try:
+            for a, b in _cut_runs(lo, hi, lambda a, b: end[b] - end[a] <= max_bytes):
+                calls.append((a, b, np.asarray(end[a:b], dtype=np.int64) - end[a], end[b] - end[a]))
+        except ValueError as e:
+            g = e.args[0]
             raise ValueError("ahc_batch: a group of %d items needs a workspace of %d bytes, more than max_bytes = %d" %
-                             (n, need, max_bytes))
-        if lo is not None and total + need > max_bytes:
-            close(g)
-            lo, offs, total = None, [], 0
-        if lo is None:
-            lo = g
-        offs.append(total)
-        total += need
-    close(len(sizes))
+                             (sizes[g], need[g], max_bytes))
+        if hi < len(sizes) and hiplib.ahc_average_workspace_bytes(sizes[hi]) > max_bytes:
+            raise ValueError("ahc_batch: a group of %d items needs a workspace of more than max_bytes = %d" % (sizes[hi], max_bytes))
     return calls, routed
 
 
@@ -798,8 +810,7 @@ def score_blocks(x, group_sizes, plda, mean=None, transform=None, device="cuda:0
 
     target_energy below 1 (ivector-plda-scoring-dense --target-energy): every group is scored under its own
     PCA and projected PLDA instead -- one PLAIN prepare without the PLDA, ``pca_plda_groups``, the grouped prepare for both
-    sides, then the same scorer.  tables.pca is then the int32 device tensor [2 G] of the retained dimensions followed by the
-    0 / 1 / 2 fallback codes (None on the default route, which is the code above unchanged).
+    sides, then the same scorer -- and tables.pca holds the retained dimensions and fallback codes (``GroupTables``).
 
     keep_plain: tables.plain is then the PLAIN-prepared device rows (mean, LDA, length normalisation; no PLDA) that ``vbx_groups``
     reads -- the PCA route's own, or one more prepare call on the default route."""
@@ -811,7 +822,6 @@ def score_blocks(x, group_sizes, plda, mean=None, transform=None, device="cuda:0
         raise ValueError("score_blocks: the per-recording PCA handles dimensions up to %d, the PLDA has %d" %
                          (hiplib.PCA_MAX_DIM, plda.dim))
     tables = GroupTables(group_sizes, device)
-    tables.pca = None
     n = len(x)
     if n != tables.n_rows:
         raise ValueError("score_blocks: %d vectors, but the group sizes add up to %d" % (n, tables.n_rows))
@@ -834,8 +844,7 @@ def score_blocks(x, group_sizes, plda, mean=None, transform=None, device="cuda:0
         if keep_plain:
             tables.plain = Y
     else:
-        E, r = prepare(x, hiplib.SIDE_ENROL, np.ones(n, np.int32), mean, transform, plda, ln, device)
-        T, _ = prepare(x, hiplib.SIDE_TEST, None, mean, transform, plda, ln, device)
+        E, r, T = _self_operands(x, plda, mean, transform, device)
         if keep_plain:
             tables.plain, _ = prepare(x, hiplib.SIDE_PLAIN, None, mean, transform, None, ln, device)
     scores = torch.empty(tables.scores_elems, dtype=torch.float32, device=device)
@@ -843,15 +852,15 @@ def score_blocks(x, group_sizes, plda, mean=None, transform=None, device="cuda:0
     return scores, tables
 
 
-def ahc_batch(scores, tables, thresholds, min_clusters, max_bytes=AHC_MAX_BYTES, max_batch_n=hiplib.AHC_BATCH_MAX_N, extra=None):
+def ahc_batch(scores, tables, thresholds, min_clusters, max_bytes=AHC_MAX_BYTES, max_batch_n=hiplib.AHC_BATCH_MAX_N):
     """Average-linkage clustering of every group's block of the packed ``scores`` (what ``score_blocks`` returns), one workgroup
     per group (xv_ahc_average_batch_f64).  thresholds float [G] and min_clusters int [G] are each group's stop rule, as in
     ``ahc``.  The group list is cut into calls whose workspaces fit max_bytes; a group above max_batch_n goes through ``ahc`` on
     its block (identical results by the kernels' contract).  Put large groups first (``diarize`` does): workgroups start in group
-    order.  One download at the end: results, the kernels' status word and the finite check of the upper triangles.
+    order.  One download at the end: results, the kernels' status word, the finite check of the upper triangles and, when the
+    scores came from a per-group PCA, tables.pca, whose host copy lands in tables.pca_host.
     -> (labels, merges): per group, in the given order, labels int32[n_g] (the local slot of each item's cluster) and
-    (a int32[M], b int32[M], score float64[M]).  extra (an int32 device tensor, e.g. tables.pca): it rides on that download, and
-    the result is (labels, merges, extra as NumPy)."""
+    (a int32[M], b int32[M], score float64[M])."""
     import torch
     hiplib.require_gpu()
     G = tables.sizes.size
@@ -887,12 +896,14 @@ def ahc_batch(scores, tables, thresholds, min_clusters, max_bytes=AHC_MAX_BYTES,
                                          ws)
                 at += hi - lo
         flags = torch.cat([tables.status.to(torch.int32), nonfinite.to(torch.int32).reshape(1)] +
-                          ([] if extra is None else [extra.to(torch.int32).reshape(-1)]))
+                          ([] if tables.pca is None else [tables.pca.to(torch.int32).reshape(-1)]))
         ints_h, m_s_h, flags_h = ints.cpu().numpy(), m_s.cpu().numpy(), flags.cpu().numpy()
     if flags_h[1]:
         raise ValueError("ahc_batch: the upper triangle of a group's score matrix holds a value that is not finite")
     if flags_h[0]:
         raise hiplib.XvectorHipError("ahc_batch: a kernel skipped a group that broke its contract (status %d)" % flags_h[0])
+    if tables.pca is not None:
+        tables.pca_host = flags_h[2:].copy()
     labels, merges = [None] * G, [None] * G
     for g in routed:
         labels[g], merges[g] = ahc(tables.block(scores, g), float(thr[g]), int(minc[g]), max_bytes)
@@ -902,8 +913,6 @@ def ahc_batch(scores, tables, thresholds, min_clusters, max_bytes=AHC_MAX_BYTES,
             r0, r1, m = int(tables.row0[g]), int(tables.row0[g + 1]), int(cnt_h[g])
             labels[g] = lab_h[r0:r1].copy()
             merges[g] = (a_h[r0:r0 + m].copy(), b_h[r0:r0 + m].copy(), m_s_h[r0:r0 + m].copy())
-    if extra is not None:
-        return labels, merges, flags_h[2:].copy()
     return labels, merges
 
 
@@ -943,76 +952,70 @@ def diarize(x, group_sizes, plda, mean=None, transform=None, threshold=0.0, num_
     x = np.asarray(x, dtype=np.float32)
     if sizes.size < 1 or int(sizes.min()) < 1 or x.ndim != 2 or int(sizes.sum()) != x.shape[0]:
         raise ValueError("diarize: x must be [N, D] and the group sizes, all at least 1, must add up to N")
+    G, N = sizes.size, x.shape[0]
     order, _ = size_order(sizes)
     row0 = np.concatenate([[0], np.cumsum(sizes)])
     rows = np.concatenate([np.arange(row0[g], row0[g + 1]) for g in order])
-    if target_energy_is_one(target_energy):
-        if vbx is None:
-            scores, tables = score_blocks(x[rows], sizes[order], plda, mean, transform, device)
-        else:
-            scores, tables = score_blocks(x[rows], sizes[order], plda, mean, transform, device, keep_plain=True)
-        lab_sorted, merges_sorted = ahc_batch(scores, tables, thr[order], minc[order])
-    else:
-        scores, tables = score_blocks(x[rows], sizes[order], plda, mean, transform, device, target_energy, keep_plain=vbx is not None)
-        lab_sorted, merges_sorted, pca = ahc_batch(scores, tables, thr[order], minc[order], extra=tables.pca)
-        if pca_report is not None:
-            G = sizes.size
-            pca_report["dim"] = np.empty(G, np.int32)
-            pca_report["info"] = np.empty(G, np.int32)
-            pca_report["dim"][order] = pca[:G]
-            pca_report["info"][order] = pca[G:]
     if vbx is not None:
-        lab_sorted = _diarize_vbx(tables, lab_sorted, order, row0, plda, vbx, vbx_order, vbx_keep, vbx_bytes, vbx_report)
-    labels = np.empty(x.shape[0], dtype=np.int32)
+        vbx_keep = np.zeros(G, bool) if vbx_keep is None else np.asarray(vbx_keep, dtype=bool).reshape(-1)
+        if vbx_keep.size != G:
+            raise ValueError("diarize: %d recordings, %d entries of vbx['keep']" % (G, vbx_keep.size))
+        if vbx_order is not None:
+            vbx_order = np.asarray(vbx_order, dtype=np.int64).reshape(-1)
+            if vbx_order.size != N:
+                raise ValueError("diarize: %d vectors, %d entries of vbx['time_order']" % (N, vbx_order.size))
+            vbx_order = vbx_order[rows]
+    # from here to the last lines everything is in the device's order
+    scores, tables = score_blocks(x[rows], sizes[order], plda, mean, transform, device, target_energy, keep_plain=vbx is not None)
+    lab_sorted, merges_sorted = ahc_batch(scores, tables, thr[order], minc[order])
+    if pca_report is not None and tables.pca_host is not None:
+        _to_callers_order(pca_report, dict(dim=tables.pca_host[:G], info=tables.pca_host[G:]), order)
+    if vbx is not None:
+        lab_sorted, rep = _diarize_vbx(tables, lab_sorted, plda, vbx, vbx_order, vbx_keep[order], vbx_bytes)
+        if vbx_report is not None:
+            _to_callers_order(vbx_report, rep, order)
+    labels = np.empty(N, dtype=np.int32)
     labels[rows] = np.concatenate(lab_sorted)
-    merges = [None] * sizes.size
+    merges = [None] * G
     for k, g in enumerate(order.tolist()):
         merges[g] = merges_sorted[k]
     return labels, merges
 
 
-def _diarize_vbx(tables, lab_sorted, order, row0, plda, params, time_order, keep, max_bytes, report):
-    """The VBx stage of ``diarize``: lab_sorted (the clustering's labels per recording, in the device's order ``order``) with the
-    labels of every recording that VBx ran on replaced by VBx's.  row0: the caller's prefix table of the recordings."""
+def _to_callers_order(report, sorted_arrays, order):
+    """report[name] = each per-recording array of sorted_arrays (in the device's order ``order``) in the caller's order."""
+    for name, v in sorted_arrays.items():
+        report[name] = np.empty_like(v)
+        report[name][order] = v
+
+
+def _diarize_vbx(tables, lab_sorted, plda, params, time_order, keep, max_bytes):
+    """The VBx stage of ``diarize``, all of it in the device's order (that of ``tables``): lab_sorted, the clustering's labels per
+    recording; time_order int [N] or None and keep bool [G] as ``diarize`` takes them, permuted.  -> (the labels, those of every
+    recording that VBx ran on replaced by VBx's; the report arrays of ``diarize``'s vbx_report)."""
     import torch
     G = tables.sizes.size
-    keep = np.zeros(G, bool) if keep is None else np.asarray(keep, dtype=bool).reshape(-1)
-    if keep.size != G:
-        raise ValueError("diarize: %d recordings, %d entries of vbx['keep']" % (G, keep.size))
-    if time_order is not None:
-        time_order = np.asarray(time_order, dtype=np.int64).reshape(-1)
-        if time_order.size != tables.n_rows:
-            raise ValueError("diarize: %d vectors, %d entries of vbx['time_order']" % (tables.n_rows, time_order.size))
     compact = [compact_labels(l) for l in lab_sorted]
     before = np.asarray([c[1] for c in compact], dtype=np.int32)
-    run = np.flatnonzero(~keep[order] & (before <= hiplib.VBX_MAX_SPK))           # positions in the device's order
-    rep = dict(ran=np.zeros(G, bool), iters=np.zeros(G, np.int32), info=np.zeros(G, np.int32), spk_before=np.empty(G, np.int32),
-               spk_after=np.empty(G, np.int32))
-    rep["spk_before"][order] = before
-    rep["spk_after"][order] = before
+    run = np.flatnonzero(~keep & (before <= hiplib.VBX_MAX_SPK))
+    rep = dict(ran=np.zeros(G, bool), iters=np.zeros(G, np.int32), info=np.zeros(G, np.int32), spk_before=before,
+               spk_after=before.copy())
     out = list(lab_sorted)
     if run.size:
-        Y = tables.plain
-        if run.size == G:
-            sub = tables
-        else:                                                    # the rows of the recordings that run, gathered on the device
+        Y, sub = tables.plain, tables
+        if run.size < G:                                         # the rows of the recordings that run, gathered on the device
             sub = GroupTables(tables.sizes[run], Y.device)
             idx = np.concatenate([np.arange(tables.row0[k], tables.row0[k + 1]) for k in run])
             Y = Y.index_select(0, torch.as_tensor(idx, device=Y.device))
+            time_order = None if time_order is None else time_order[idx]
         init = np.concatenate([compact[k][0] for k in run])
-        tord = None
-        if time_order is not None:
-            tord = np.concatenate([time_order[row0[order[k]]:row0[order[k] + 1]] for k in run])
-        res = vbx_groups(Y, sub, init, plda, tord, before[run], max_bytes=max_bytes, **params)
+        res = vbx_groups(Y, sub, init, plda, time_order, before[run], max_bytes=max_bytes, **params)
         for j, k in enumerate(run.tolist()):
-            g = int(order[k])
-            rep["ran"][g], rep["iters"][g], rep["info"][g] = True, res["iters"][j], res["info"][j]
+            rep["ran"][k], rep["iters"][k], rep["info"][k] = True, res["iters"][j], res["info"][j]
             if res["info"][j] == 0:
                 out[k] = res["labels"][sub.row0[j]:sub.row0[j + 1]].copy()
-                rep["spk_after"][g] = np.unique(out[k]).size
-    if report is not None:
-        report.update(rep)
-    return out
+                rep["spk_after"][k] = np.unique(out[k]).size
+    return out, rep
 
 
 def diarize_stop_rules(sizes, threshold=0.0, num_spk=None):
@@ -1130,20 +1133,13 @@ def plan_vbx_groups(row0, dim, max_spk, max_bytes=VBX_MAX_BYTES):
     """Cut the groups of the prefix table row0 [G + 1] into calls of xv_vbx_groups_f64, runs of consecutive groups whose workspace
     fits max_bytes: -> [(g_lo, g_hi)].  One group alone above max_bytes is an error."""
     row0 = np.asarray(row0, dtype=np.int64)
-    G = row0.size - 1
-    calls, lo = [], 0
-    for g in range(G):
-        if hiplib.vbx_groups_workspace_bytes(int(row0[g + 1] - row0[lo]), g + 1 - lo, dim, max_spk) > max_bytes:
-            if g == lo:
-                raise ValueError("vbx_groups: a group of %d rows needs a workspace of more than max_bytes = %d" %
-                                 (int(row0[g + 1] - row0[g]), max_bytes))
-            calls.append((lo, g))
-            lo = g
-            if hiplib.vbx_groups_workspace_bytes(int(row0[g + 1] - row0[g]), 1, dim, max_spk) > max_bytes:
-                raise ValueError("vbx_groups: a group of %d rows needs a workspace of more than max_bytes = %d" %
-                                 (int(row0[g + 1] - row0[g]), max_bytes))
-    calls.append((lo, G))
-    return calls
+    try:
+        return _cut_runs(0, row0.size - 1,
+                         lambda a, b: hiplib.vbx_groups_workspace_bytes(int(row0[b] - row0[a]), b - a, dim, max_spk) <= max_bytes)
+    except ValueError as e:
+        g = e.args[0]
+        raise ValueError("vbx_groups: a group of %d rows needs a workspace of more than max_bytes = %d" %
+                         (int(row0[g + 1] - row0[g]), max_bytes))
 
 
 def vbx_groups(y_rows, tables, init_labels, plda, time_order=None, n_spk=None, fa=0.3, fb=17.0, loop_prob=0.99, init_smoothing=5.0,
