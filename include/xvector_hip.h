@@ -319,9 +319,12 @@ int xv_tdnn_pair_pool_f16mx6(const void *x, int64_t R, int cin, int cmid, int co
  *                  slot 4+c = dwords 0-3 of block c, slot 6+c = [dword 4 | dword 5 | E8M0 byte - 11, zero-extended | 0] (the 2^-11
  *                  of the cross terms rides in the byte).  All-zero bytes are a row of zeros.  Clamp and `status` as XV_FMT_SPLIT8.
  * Writers: xv_tdnn_layer_f16bf8 / xv_tdnn_layer_f16mx6 with y_format = XV_FMT_SPLIT6 where they run the 16 x 16 MFMA form of the
- *   256 x 256 tile (an even number of slabs, K in {3,5,7}, Cout % 256 == 0; else XV_ERR_UNSUPPORTED), and xv_split6_encode_f32
- *   (tooling and tests; xv_split6_decode_f32 returns hi + lo_q / 2^11 and, where cq is not NULL, the dequantised second
- *   operand c_q, both with row stride ldx).
+ *   256 x 256 tile (an even number of slabs, K in {3,5,7}, Cout % 256 == 0; else XV_ERR_UNSUPPORTED), xv_tdnn_first_f16mx6, and
+ *   xv_split6_encode_f32 (tooling and tests; xv_split6_decode_f32 returns hi + lo_q / 2^11 and, where cq is not NULL, the
+ *   dequantised second operand c_q, both with row stride ldx).  Every writer stores the rows xv_split6_encode_f32 stores for the
+ *   same fp32 values, bit for bit.
+ * xv_tdnn_first_f16mx6: xv_tdnn_first_f16bf8 (same arguments, packed weights, shapes -- else XV_ERR_UNSUPPORTED -- and `status`)
+ *   writing XV_FMT_SPLIT6 rows: the producer of a layer 1 that runs xv_tdnn_layer_f16mx6.
  * xv_tdnn_layer_f16mx6: xv_tdnn_layer_f16bf8's arguments and semantics with x in XV_FMT_SPLIT6 and wt = xv_pack_weights_f16mx6
  *   (the 16 KB tiles and fp16 planes of xv_pack_weights_f16bf8; the 8-bit plane holds the blocks [clamp(w) | 2^11 lo] of each
  *   column's channels 16c..16c+15 at the same positions, byte unshifted).  The 16 x 16 MFMA form of the 256 x 256 tile only: an
@@ -335,6 +338,9 @@ int xv_tdnn_layer_f16mx6(const void *x, int64_t R, int cin, const void *wt, cons
                          const float *bn_shift, int act_kind, const float *act_alpha, int K, int dilation, int cout,
                          const uint8_t *row_valid, const float *tap_bias, void *y, int y_format, int ldy, int32_t *status,
                          void *stream);
+int xv_tdnn_first_f16mx6(const float *x, int64_t R, int cin, int ldx, const void *wt, const float *bias, const float *bn_scale,
+                         const float *bn_shift, int act_kind, const float *act_alpha, int K, int dilation, int cout,
+                         const uint8_t *row_valid, void *y, int32_t *status, void *stream);
 
 /* xv_fc_f32 twin: fp32 rows in, fp32 rows out; wt = xv_pack_weights_bf16x3(w, 1, In, Out). */
 int xv_fc_bf16x3(const float *x, int nrows, int in_dim, const void *wt, const float *bias, const float *bn_scale,

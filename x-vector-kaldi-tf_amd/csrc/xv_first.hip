@@ -21,9 +21,11 @@
 //   * every output row is 2 KB, so workgroups that all write the same 128-byte slab of their rows at the same moment send the
 //     whole chip's stores to the same few memory channels: the workgroups start at different passes and the waves of a workgroup
 //     at different tile pairs (measured: 0.184 -> 0.156 ms).
+// The XV_FMT_SPLIT6 form of the epilogue (xv_tdnn_first_f16mx6) is the one exception to "no cross-lane exchange": an e2m3 block is
+// 16 channels, two lanes' worth, and the block maximum and one converted dword cross with v_permlane16_swap_b32 (first_block).
 // Arithmetic: bf16x3 as everywhere (hi*hi + hi*lo + lo*hi, fp32 accumulate).
 #include "xv_device.h"
-#include "xv_split8.h"
+#include "xv_split6.h"
 
 namespace {
 
@@ -54,8 +56,12 @@ struct FirstParams {
     long row_base, rows_here;  // this launch writes rows [row_base, row_base + rows_here) (a buffer descriptor addresses < 4 GB of y)
     long n_tiles;              // 16-frame tiles of this launch: ceil(rows_here / 16)
     int tpw;                   // tiles per wave: wave w of workgroup b owns tiles [(8b + w) tpw, +tpw)
-    int *status;               // Y8: bit 0 set when a value had to be clamped (may be NULL)
+    int *status;               // split8 / split6 output: bit 0 set when a value had to be clamped (may be NULL)
 };
+
+// what the epilogue writes: bf16 hi / lo planes (XV_FMT_SPLIT), fp16 hi + bf8 cross bytes (XV_FMT_SPLIT8, xv_split8.h) or fp16 hi +
+// e2m3 cross blocks (XV_FMT_SPLIT6, xv_split6.h) -- a compile-time form each
+constexpr int FR_Y3 = 0, FR_Y8 = 1, FR_Y6 = 2;
 
 // act_fn of the pair kernels (xv_device.h) but for its ReLU, which is one integer max here
 template <int MODE>
@@ -83,18 +89,29 @@ __device__ __forceinline__ float sub_f16_half(float c, int hpair)
 
 constexpr int FR_STORE_AUX = 2;                        // nt
 
+// v_permlane16_swap_b32: rows 1 and 3 (16 lanes each) of a change places with rows 0 and 2 of b.  With a = b = x on entry, a lane
+// of an even row finds its own x in a and lane ^ 16's in b, a lane of an odd row lane ^ 16's in a and its own in b.  Inline asm
+// as for v_permlane32_swap in xv_pair8.hip (the builtin hands back one result for both); the s_nop is the two wait states the
+// instruction needs behind a VALU write of its operands, which the hazard recogniser cannot see to here.
+__device__ __forceinline__ void swap_rows16(unsigned &a, unsigned &b)
+{
+    asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+}
+
 // One tile pair (32 output channels) of NT 16-frame tiles: 24 MFMAs per tile, then activation / BN / gap-row mask / split encoding
 // and two 16-byte stores per lane, without a branch (rows past the end are dropped by the buffer descriptor's range check).
 // MASK: the group has a gap row (zeroed after the arithmetic); CLAMP: clamp to the fp16 / bf8 range first -- the caller starts
 // without and repeats the pair with it once the running maximum says so.
-template <int MODE, bool Y8, int NT, bool MASK, bool CLAMP>
+template <int MODE, int YF, int NT, bool MASK, bool CLAMP>
 __device__ __forceinline__ void first_block(const bf16x8 (&xh)[FR_TILES][FR_NKS], const bf16x8 (&xl)[FR_TILES][FR_NKS],
                                             const bf16x8 (&wh0)[FR_NKS], const bf16x8 (&wl0)[FR_NKS], const bf16x8 (&wh1)[FR_NKS],
                                             const bf16x8 (&wl1)[FR_NKS], const f32x4 b0, const f32x4 b1, const f32x4 s0, const f32x4 s1,
-                                            const f32x4 o0, const f32x4 o1, const f32x4 a0, const f32x4 a1, const int (&keepm)[FR_TILES],
+                                            const f32x4 o0, const f32x4 o1, const f32x4 a0r, const f32x4 a1r, const f32x4 *Pa,
+                                            const int (&keepm)[FR_TILES],
                                             const unsigned (&hioff)[FR_TILES], const int slab_off, const __amdgpu_buffer_rsrc_t yrs,
-                                            float &amax)
+                                            const unsigned xoff6, const bool odd, float &amax)
 {
+    constexpr bool Y8 = YF == FR_Y8, Y6 = YF == FR_Y6;
     f32x4 m0[NT], m1[NT];
     auto mfma_tile = [&](int j) {
         m0[j] = b0; m1[j] = b1;                                   // the bias is where the sums start
@@ -112,6 +129,13 @@ __device__ __forceinline__ void first_block(const bf16x8 (&xh)[FR_TILES][FR_NKS]
         // lane (frame f, group G) holds rows 4G..4G+3 of both tiles; the packed weights order the rows of a tile pair so that these
         // are channels 8G..8G+3 (tile 0) and 8G+4..8G+7 (tile 1) of the pair's 32: one 16-byte slot of the output format per lane
         const f32x4 z0 = m0[j], z1 = m1[j];
+        f32x4 a0 = a0r, a1 = a1r;
+        if constexpr (Y6 && MODE != 2) {
+            // this form has no registers left to hold the activation's slopes for the pair's three tiles: every tile reads them from
+            // LDS again, under the next tile's MFMAs (the clobber: or the three reads are one)
+            asm volatile("" ::: "memory");
+            a0 = Pa[0]; a1 = Pa[1];
+        }
         float v[8];
 #pragma unroll
         for (int e = 0; e < 4; e += 2) {                          // activation, then BN as packed FMAs
@@ -159,6 +183,57 @@ __device__ __forceinline__ void first_block(const bf16x8 (&xh)[FR_TILES][FR_NKS]
             vx = (xv_i32x4){__builtin_bit_cast(int, t0), __builtin_bit_cast(int, t1), h0, h1};
             __builtin_amdgcn_raw_buffer_store_b128(vh, yrs, hioff[j], slab_off, FR_STORE_AUX);             // slot g ...
             __builtin_amdgcn_raw_buffer_store_b128(vx, yrs, hioff[j] ^ 64u, slab_off, FR_STORE_AUX);       // ... and slot 4 + g, same swizzle
+        } else if constexpr (Y6) {
+            // XV_FMT_SPLIT6: the fp16 hi slot as above; the e2m3 block of channels 16c..16c+15 belongs to the lanes (f, 2c) and
+            // (f, 2c + 1) = l and l ^ 16.  Only the block maximum and one dword cross: each lane converts ITS 8 channels under the
+            // shared scale, and its three dwords [lo'0 c0 lo'1 c1 .. lo'7 c7] are dwords 0-2 of the block in the even lane and dwords
+            // 3-5 in the odd one.  The conversion takes 2 x 16 values and there are 2 x 8: t = [lo'0..7 | c0..7] serves as BOTH
+            // sources (one 16-register operand, not two half-used ones), which gives every element twice -- dwords 0-2 =
+            // [lo'0 lo'0 lo'1 lo'1 ..], dwords 3-5 = [c0 c0 c1 c1 ..] (XV_SPLIT6_ELEM) -- and three v_bfi take the even elements of
+            // the one and the odd elements of the other.  The results are xv_split6_encode16<true>'s: same amax, clamp, scale rule
+            // and conversion.
+            typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+            xv_i32x4 vh;
+            xv_f32x16 t16;
+            float t = 0.f, ml = 0.f, mc = 0.f;
+#pragma unroll
+            for (int i = 0; i < 8; i += 2) t = fmaxf(t, fmaxf(fabsf(v[i]), fabsf(v[i + 1])));     // before the mask: canonical values, one v_max3
+            amax = fmaxf(amax, t);
+#pragma unroll
+            for (int i = 0; i < 8; i += 2) {
+                float ca = v[i], cb = v[i + 1];
+                if constexpr (CLAMP) {
+                    ca = __builtin_amdgcn_fmed3f(ca, -XV_SPLIT8_MAX, XV_SPLIT8_MAX);
+                    cb = __builtin_amdgcn_fmed3f(cb, -XV_SPLIT8_MAX, XV_SPLIT8_MAX);
+                    mc = fmaxf(mc, fmaxf(fabsf(ca), fabsf(cb)));
+                }
+                if constexpr (MASK) {
+                    ca = __builtin_bit_cast(float, __builtin_bit_cast(int, ca) & keepm[j]);
+                    cb = __builtin_bit_cast(float, __builtin_bit_cast(int, cb) & keepm[j]);
+                }
+                const f16x2 h = {(_Float16)ca, (_Float16)cb};
+                vh[i >> 1] = __builtin_bit_cast(int, h);
+                const f32x2 l2 = (f32x2){sub_f16_half<0>(ca, vh[i >> 1]), sub_f16_half<1>(cb, vh[i >> 1])} * XV_SPLIT8_LO_SCALE;   // (exact)
+                ml = fmaxf(ml, fmaxf(fabsf(l2[0]), fabsf(l2[1])));
+                t16[i] = l2[0]; t16[i + 1] = l2[1]; t16[8 + i] = ca; t16[9 + i] = cb;
+            }
+            // the largest |c| of the lane: the maximum above where nothing was clamped (the wave is in the clamping form as soon as
+            // something would be), zero in a gap row
+            if constexpr (!CLAMP) mc = t;
+            if constexpr (MASK) mc = __builtin_bit_cast(float, __builtin_bit_cast(int, mc) & keepm[j]);
+            unsigned ma = __builtin_bit_cast(unsigned, fmaxf(mc, ml)), mb = ma;
+            swap_rows16(ma, mb);
+            const int e8m0 = xv_split6_e8m0(fmaxf(__builtin_bit_cast(float, ma), __builtin_bit_cast(float, mb)));
+            const xv_u32x6 dup = xv_cvt_2xpk16_e2m3(t16, t16, __builtin_bit_cast(float, e8m0 << 23));
+            // bits of the even 6-bit elements in dwords 0 / 1 / 2 of a 96-bit string
+            constexpr unsigned EV0 = 0x3f03f03fu, EV1 = 0xf03f03f0u, EV2 = 0x03f03f03u;
+            const unsigned x6[3] = {(dup[0] & EV0) | (dup[3] & ~EV0), (dup[1] & EV1) | (dup[4] & ~EV1), (dup[2] & EV2) | (dup[5] & ~EV2)};
+            unsigned da = x6[0], db = da;
+            swap_rows16(da, db);                                  // an even row's db: dword 3 of the block, from the odd lane
+            const xv_i32x4 vx = {(int)(odd ? x6[1] : x6[0]), (int)(odd ? x6[2] : x6[1]), odd ? e8m0 - XV_SPLIT6_LO_EXP : (int)x6[2],
+                                 odd ? 0 : (int)db};
+            __builtin_amdgcn_raw_buffer_store_b128(vh, yrs, hioff[j], slab_off, FR_STORE_AUX);             // slot g ...
+            __builtin_amdgcn_raw_buffer_store_b128(vx, yrs, hioff[j] ^ xoff6, slab_off, FR_STORE_AUX);     // ... and slot 4 + c (G even) / 6 + c
         } else {
             bf16x8 vh, vl;
 #pragma unroll
@@ -184,8 +259,8 @@ __device__ __forceinline__ void first_block(const bf16x8 (&xh)[FR_TILES][FR_NKS]
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// Y8: write XV_FMT_SPLIT8 rows (fp16 hi + bf8 cross bytes, xv_split8.h) instead of the bf16 hi/lo planes
-template <int MODE, bool Y8>
+// YF: the output format (FR_Y3: the bf16 hi/lo planes; FR_Y8: XV_FMT_SPLIT8 rows; FR_Y6: XV_FMT_SPLIT6 rows)
+template <int MODE, int YF>
 __global__ __launch_bounds__(FR_WAVES * 64) void tdnn_first_kernel(const FirstParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -193,6 +268,11 @@ __global__ __launch_bounds__(FR_WAVES * 64) void tdnn_first_kernel(const FirstPa
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int G = lane >> 4, f = lane & 15;
+    // FR_Y6: lane (f, G) stores logical slot 4 + (G >> 1) (G even) or 6 + (G >> 1) (G odd) behind its hi slot G: the two differ in
+    // the same bits whatever the row swizzle
+    const unsigned xoff6 = (unsigned)((G ^ (4 + (G >> 1) + 2 * (G & 1))) << 4);
+    const bool odd = (G & 1) != 0;
+    constexpr bool RANGE = YF != FR_Y3;                          // a format with a range: running maximum, clamping form, status
     const long tile0 = ((long)blockIdx.x * FR_WAVES + wave) * p.tpw;
     const int left = ((p.K - 1) * p.dil) >> 1;
     const int n_pass = (p.cout + FR_PASS_COLS - 1) / FR_PASS_COLS;
@@ -250,13 +330,18 @@ __global__ __launch_bounds__(FR_WAVES * 64) void tdnn_first_kernel(const FirstPa
                 keepm[j] = (in && (!p.valid || p.valid[row])) ? -1 : 0;
                 hioff[j] = in ? (unsigned)lrow * yrow + (unsigned)((G ^ ((int)(row >> 1) & 7)) << 4) : 0x80000000u;
             }
+            // (FR_Y6: the tap arithmetic below depends on nothing but the lane, so the compiler does it once, in front of the step
+            // loop, and in this form -- the one with the fullest hot loop -- spills the addresses across it.  An opaque copy of kc
+            // keeps it here, once per group.)
+            int kc = p.kc;
+            if constexpr (YF == FR_Y6) asm volatile("" : "+s"(kc));
 #pragma unroll
             for (int u = 0; u < FR_NKS; ++u) {
                 const int k = 32 * u + 8 * G;
-                const int tap = k / p.kc;
+                const int tap = k / kc;
                 const bool live = tap < p.K;
                 const int tap_off = tap * p.dil - left;
-                const int c0 = k - tap * p.kc;
+                const int c0 = k - tap * kc;
 #pragma unroll
                 for (int j = 0; j < FR_TILES; ++j) {
                     const long r = p.row_base + lrow0 + 16 * j + f + tap_off;
@@ -307,25 +392,25 @@ __global__ __launch_bounds__(FR_WAVES * 64) void tdnn_first_kernel(const FirstPa
                 const f32x4 b0 = P4[c4], b1 = P4[c4 + 1], s0 = P4[FR_MAX_COUT / 4 + c4], s1 = P4[FR_MAX_COUT / 4 + c4 + 1],
                             o0 = P4[2 * FR_MAX_COUT / 4 + c4], o1 = P4[2 * FR_MAX_COUT / 4 + c4 + 1];
                 f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0;
-                if constexpr (MODE != 2) { a0 = P4[3 * FR_MAX_COUT / 4 + c4]; a1 = P4[3 * FR_MAX_COUT / 4 + c4 + 1]; }
+                if constexpr (MODE != 2 && YF != FR_Y6) { a0 = P4[3 * FR_MAX_COUT / 4 + c4]; a1 = P4[3 * FR_MAX_COUT / 4 + c4 + 1]; }
                 const int slab_off = (pass * (FR_PASS_COLS / 32) + tp) * SROW;       // (wave-uniform: the store's scalar offset)
                 // fast form first: no gap-row mask when the group has no gap row, no clamp; a value beyond the range (absurd for a
                 // BN-normalised network; the caller repeats the batch in bf16x3 anyway) sends the wave through the clamping form
                 // from then on -- the pair is done again, its stores simply land twice
-                auto run = [&](auto nt, auto mask, auto clamp) {
-                    first_block<MODE, Y8, decltype(nt)::value, decltype(mask)::value, decltype(clamp)::value>(
-                        xh, xl, wh0, wl0, wh1, wl1, b0, b1, s0, s1, o0, o1, a0, a1, keepm, hioff, slab_off, yrs, amax);
+                auto run = [&](auto nt, auto mask, auto clamp) __attribute__((always_inline)) {
+                    first_block<MODE, YF, decltype(nt)::value, decltype(mask)::value, decltype(clamp)::value>(
+                        xh, xl, wh0, wl0, wh1, wl1, b0, b1, s0, s1, o0, o1, a0, a1, P4 + 3 * FR_MAX_COUT / 4 + c4, keepm, hioff, slab_off, yrs, xoff6, odd, amax);
                 };
-                auto run_nt = [&](auto mask, auto clamp) {
+                auto run_nt = [&](auto mask, auto clamp) __attribute__((always_inline)) {
                     if (n_live == 3) run(std::integral_constant<int, 3>{}, mask, clamp);
                     else if (n_live == 2) run(std::integral_constant<int, 2>{}, mask, clamp);
                     else run(std::integral_constant<int, 1>{}, mask, clamp);
                 };
-                if (Y8 && clamping) run_nt(std::true_type{}, std::true_type{});
+                if (RANGE && clamping) run_nt(std::true_type{}, std::true_type{});
                 else {
                     if (group_masked) run_nt(std::true_type{}, std::false_type{});
                     else run_nt(std::false_type{}, std::false_type{});
-                    if (Y8 && __builtin_amdgcn_ballot_w64(!(amax <= XV_SPLIT8_MAX)) != 0) {
+                    if (RANGE && __builtin_amdgcn_ballot_w64(!(amax <= XV_SPLIT8_MAX)) != 0) {
                         clamping = true;
                         run_nt(std::true_type{}, std::true_type{});
                         stores_behind_fetch = -1000;              // (the count is off now: the next wait drains)
@@ -337,7 +422,7 @@ __global__ __launch_bounds__(FR_WAVES * 64) void tdnn_first_kernel(const FirstPa
         if (++pass == n_pass) pass = 0;
         if (++in_group == n_pass) { in_group = 0; ++group; }
     }
-    if constexpr (Y8)
+    if constexpr (RANGE)
         if (amax > XV_SPLIT8_MAX && p.status) atomicOr(p.status, 1);
 }
 
@@ -398,7 +483,7 @@ int xv_pack_first_bf16x3(const float *w, int K, int cin, int cout, void *wt, voi
 
 static int first_launch(const float *x, int64_t R, int cin, int ldx, const void *wt, const float *bias, const float *bn_scale,
                         const float *bn_shift, int act_kind, const float *act_alpha, int K, int dilation, int cout,
-                        const uint8_t *row_valid, void *y, bool y8, int32_t *status, void *stream)
+                        const uint8_t *row_valid, void *y, int yf, int32_t *status, void *stream)
 {
     if (R <= 0) return 0;
     if (!x || !wt || !y) return fail(XV_ERR_BAD_ARG, "tdnn_first: NULL pointer");
@@ -415,8 +500,9 @@ static int first_launch(const float *x, int64_t R, int cin, int ldx, const void 
     p.bias = bias; p.scale = bn_scale; p.shift = bn_shift; p.alpha = act_alpha; p.act = act_kind; p.valid = row_valid;
     p.y = (uint8_t *)y; p.ychunks = cout / 32; p.status = (int *)status;
     typedef void (*kern_t)(const FirstParams);
-    const kern_t kerns[6] = {tdnn_first_kernel<0, false>, tdnn_first_kernel<1, false>, tdnn_first_kernel<2, false>,
-                             tdnn_first_kernel<0, true>,  tdnn_first_kernel<1, true>,  tdnn_first_kernel<2, true>};
+    const kern_t kerns[9] = {tdnn_first_kernel<0, FR_Y3>, tdnn_first_kernel<1, FR_Y3>, tdnn_first_kernel<2, FR_Y3>,
+                             tdnn_first_kernel<0, FR_Y8>, tdnn_first_kernel<1, FR_Y8>, tdnn_first_kernel<2, FR_Y8>,
+                             tdnn_first_kernel<0, FR_Y6>, tdnn_first_kernel<1, FR_Y6>, tdnn_first_kernel<2, FR_Y6>};
     static std::atomic<unsigned long long> lds_done{0};
     if (const int rc = opt_in_dynamic_lds(lds_done, kerns, FR_LDS_BYTES)) return rc;
     const int mode = act_kind == XV_ACT_LRELU ? 1 : act_kind == XV_ACT_RELU ? 2 : 0;
@@ -439,7 +525,7 @@ static int first_launch(const float *x, int64_t R, int cin, int ldx, const void 
         p.n_tiles = (p.rows_here + 15) / 16;
         p.tpw = forced > 0 ? forced : (int)((p.n_tiles + waves - 1) / waves);
         const long per_wg = (long)p.tpw * FR_WAVES;
-        hipLaunchKernelGGL(kerns[mode + (y8 ? 3 : 0)], dim3((unsigned)((p.n_tiles + per_wg - 1) / per_wg)), dim3(FR_WAVES * 64), FR_LDS_BYTES,
+        hipLaunchKernelGGL(kerns[mode + 3 * yf], dim3((unsigned)((p.n_tiles + per_wg - 1) / per_wg)), dim3(FR_WAVES * 64), FR_LDS_BYTES,
                            (hipStream_t)stream, p);
     }
     return launch_status();
@@ -449,7 +535,7 @@ int xv_tdnn_first_bf16x3(const float *x, int64_t R, int cin, int ldx, const void
                          const float *bn_shift, int act_kind, const float *act_alpha, int K, int dilation, int cout,
                          const uint8_t *row_valid, void *y, void *stream)
 {
-    return first_launch(x, R, cin, ldx, wt, bias, bn_scale, bn_shift, act_kind, act_alpha, K, dilation, cout, row_valid, y, false,
+    return first_launch(x, R, cin, ldx, wt, bias, bn_scale, bn_shift, act_kind, act_alpha, K, dilation, cout, row_valid, y, FR_Y3,
                         nullptr, stream);
 }
 
@@ -457,7 +543,16 @@ int xv_tdnn_first_f16bf8(const float *x, int64_t R, int cin, int ldx, const void
                          const float *bn_shift, int act_kind, const float *act_alpha, int K, int dilation, int cout,
                          const uint8_t *row_valid, void *y, int32_t *status, void *stream)
 {
-    return first_launch(x, R, cin, ldx, wt, bias, bn_scale, bn_shift, act_kind, act_alpha, K, dilation, cout, row_valid, y, true,
+    return first_launch(x, R, cin, ldx, wt, bias, bn_scale, bn_shift, act_kind, act_alpha, K, dilation, cout, row_valid, y, FR_Y8,
+                        status, stream);
+}
+
+int xv_tdnn_first_f16mx6(const float *x, int64_t R, int cin, int ldx, const void *wt, const float *bias, const float *bn_scale,
+                         const float *bn_shift, int act_kind, const float *act_alpha, int K, int dilation, int cout,
+                         const uint8_t *row_valid, void *y, int32_t *status, void *stream)
+{
+    // (an e2m3 block needs both 8-channel halves of its 16 channels: cout % 32 == 0, which first_shape_ok asks of every form)
+    return first_launch(x, R, cin, ldx, wt, bias, bn_scale, bn_shift, act_kind, act_alpha, K, dilation, cout, row_valid, y, FR_Y6,
                         status, stream);
 }
 

@@ -245,7 +245,8 @@ class Model(object):
             # (the verdict includes the forms the probe turned off for this checkpoint)
             self.device_model = engine.DeviceModel(w, meta["topology"], _device(), self.embedding_index, known["selected"],
                                                    fold_shift=False if known.get("fold_shift") is False else None,
-                                                   layer_mx6=False if known.get("layer_mx6") is False else None)
+                                                   layer_mx6=False if known.get("layer_mx6") is False else None,
+                                                   first_mx6=False if known.get("first_mx6") is False else None)
             self.device_model.selection = dict(known, cached=True)
             self._model_key = key
         else:

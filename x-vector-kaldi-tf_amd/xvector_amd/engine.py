@@ -314,7 +314,7 @@ class DeviceModel(object):
     POOL_SPLIT_ROWS = 512
 
     def __init__(self, weights, topo, device="cuda:0", embedding_index=0, precision="bf16x3", fused_pool=None, pair_kernel=None,
-                 first_kernel=None, fold_shift=None, layer_mx6=None):
+                 first_kernel=None, fold_shift=None, layer_mx6=None, first_mx6=None):
         """precision: "fp32" = exact fp32 MFMA GEMMs; "bf16x3" = split-precision bf16 MFMA GEMMs (fp32-class
         accuracy, ~3e-6 rel-L2 on the x-vector; see include/xvector_hip.h).  fused_pool (default: on; fp32 needs a last layer whose
         width is a multiple of 4; never with attention pooling): the last frame-level layer reduces its output to 8-row block
@@ -328,7 +328,11 @@ class DeviceModel(object):
         moves into the next layer's bias (see shift_tap_table), so that the f16bf8 GEMMs read the ReLU's zeros as zeros.
         layer_mx6 (None, the default: on where supported; False: off; True: required): a hidden f16bf8 layer i >= 2 in front of the
         pair kernel whose shape xv_tdnn_layer_f16mx6 takes, fed by an f16bf8 layer that runs the same kernel form, forms its cross
-        terms on block-scaled e2m3 MFMAs at half their cycles; its producer writes FMT_SPLIT6 rows into the same buffer."""
+        terms on block-scaled e2m3 MFMAs at half their cycles; its producer writes FMT_SPLIT6 rows into the same buffer.
+        first_mx6 (None, False or True, as layer_mx6): the same form for layer 1 of an f16bf8 model, when its shape is one
+        xv_tdnn_layer_f16mx6 takes and it runs as a layer of its own (not inside the pair kernel): layer 0 then writes FMT_SPLIT6
+        rows (xv_tdnn_first_f16mx6, or the encoding pass behind the general kernel).  ``mx6_layers`` / ``layer_mx6`` keep their
+        meaning (layers >= 2); ``self.first_mx6`` records what layer 1 runs."""
         import torch
         hiplib.require_gpu()
         assert precision in ("fp32", "fp32tc", "bf16x3", "f16bf8")
@@ -457,6 +461,16 @@ class DeviceModel(object):
             self.layer_mx6 = bool(self.mx6_layers)
             assert not (layer_mx6 and not self.layer_mx6), \
                 "layer_mx6=True needs an f16bf8 model with a K in {3,5,7} layer (Cin % 64 == 0, Cout % 256 == 0) behind another one"
+            # layer 1 in the same form: its producer is layer 0, whose kernel (and whose encoding pass) writes the 6-bit rows too;
+            # layer 1 itself writes whatever its consumer reads (every output form of the e2m3 kernel exists)
+            self.first_mx6 = False
+            if self.f16bf8 and (first_mx6 is None or first_mx6) and (n - 2 if self.pair is not None else n - 1) > 1:
+                L1 = self.layers[1]
+                if hiplib.layer_mx6_supported(L1["K"], L1["dil"], L1["cin"], L1["cout"]):
+                    L1["wp6"] = hiplib.pack_weights_f16mx6(self._wdev(weights, "frame_level_info_layer-1/w:0"))
+                    self.first_mx6 = True
+            assert not (first_mx6 and not self.first_mx6), \
+                "first_mx6=True needs an f16bf8 model whose layer 1 has K in {3,5,7}, Cin % 64 == 0, Cout % 256 == 0 and is not part of the pair kernel"
             # (only ReLU leaves zeros to gain: the other activations keep today's path)
             # (and the GEMM epilogues read 8 channels of a tap's constants at a time: every K > 1 consumer's width a multiple of 8)
             can_fold = self.f16bf8 and self.act == tp.ACT_RELU and all(L["cout"] % 8 == 0 for L in self.layers[1:] if L["K"] > 1)
@@ -677,7 +691,7 @@ class DeviceModel(object):
         L = self.layers[0]
         stop = n - 2 if self.pair is not None else n - 1        # layers [1, stop) run on xv_tdnn_layer_f16bf8
         pair_fmt = S8 if self.pair8 is not None else S3         # what the pair kernel in use reads
-        h = bufs[0].view(L["cout"], pair_fmt if (self.pair is not None and stop == 1) else S8)
+        h = bufs[0].view(L["cout"], pair_fmt if (self.pair is not None and stop == 1) else S6 if self.first_mx6 else S8)
         mark("start")
         if self.first is not None:
             hiplib.tdnn_first(x, R, self.first, *ep(0), L["dil"], row_valid, h, status)
@@ -686,14 +700,15 @@ class DeviceModel(object):
             # a first layer the dedicated kernel does not take: the general bf16x3 GEMM into fp32 rows, then one encoding pass
             y32 = self._l0_rows[:R]
             hiplib.tdnn_layer(x, L["wp"], *ep(0), L["K"], L["dil"], row_valid, y32, rows=R)
-            hiplib.split_encode(y32, h, rows=R, status=status if h.fmt == S8 else None)
+            hiplib.split_encode(y32, h, rows=R, status=status if h.fmt in (S8, S6) else None)
             mark("layer 0: tdnn_gemm_bf16x3_kernel + split encode")
         for i in range(1, stop):
             L = self.layers[i]
             y = bufs[i & 1].view(L["cout"], pair_fmt if (self.pair is not None and i == stop - 1) else
                                  S6 if i + 1 in self.mx6_layers else S8)
             # (one launcher for both forms: the weight pack says which kernel reads h)
-            hiplib.tdnn_layer8(h, R, L["wp6" if i in self.mx6_layers else "wp8"], *ep(i), L["dil"], row_valid, y, status, tapbias=taps(i))
+            mx6 = i in self.mx6_layers or (i == 1 and self.first_mx6)
+            hiplib.tdnn_layer8(h, R, L["wp6" if mx6 else "wp8"], *ep(i), L["dil"], row_valid, y, status, tapbias=taps(i))
             mark("layer %d: tdnn_gemm_f16bf8 (K=%d, %d -> %d)" % (i, L["K"], L["cin"], L["cout"]))
             h = y
         if self.pair is not None:
@@ -820,7 +835,8 @@ def _max_rel_l2(a, b):
     return float(np.nan_to_num(r, nan=np.inf).max()) if len(r) else 0.0
 
 
-def select_model(weights, topo, device="cuda:0", embedding_index=0, precision="f16bf8", probe=None, fold_shift=None, layer_mx6=None):
+def select_model(weights, topo, device="cuda:0", embedding_index=0, precision="f16bf8", probe=None, fold_shift=None, layer_mx6=None,
+                 first_mx6=None):
     """``DeviceModel`` in the fastest arithmetic, not faster than ``precision``, that the accuracy probe admits for THESE weights:
     f16bf8 -> (its x-vectors of the probe batch differ from bf16x3's by more than PROBE_LIMIT_F16BF8, or are not finite, or left
     the fp16 range) -> bf16x3 -> (differs from the exact-fp32 kernels by more than PROBE_LIMIT_BF16X3) -> the exact rung.  The
@@ -834,10 +850,13 @@ def select_model(weights, topo, device="cuda:0", embedding_index=0, precision="f
     unfolded before the model is demoted (``selection["fold_shift"]`` is then False).  ``layer_mx6``: as DeviceModel's; left at
     None, a candidate with an e2m3 layer that misses the limit (unfolded too, where that applies) is tried once more without it before
     the model is demoted.  ``selection["layer_mx6"]`` (of a
-    probed model) records which form runs."""
+    probed model) records which form runs.  ``first_mx6``: as DeviceModel's; left at None, it is the FIRST of the two e2m3 forms to
+    go: a candidate that misses the limit (unfolded too) is tried with layer 1's cross terms back in bf8 -- bit for bit the
+    candidate of a build without that form -- before ``layer_mx6`` is given up, so nobody loses what they had.
+    ``selection["first_mx6"]`` records which form runs, ``selection["first_mx6_f16bf8_vs_bf16x3"]`` the value that missed."""
     if probe is None:
         probe = os.environ.get("XVECTOR_ACCURACY_PROBE", "1") != "0"
-    model = DeviceModel(weights, topo, device, embedding_index, precision, fold_shift=fold_shift, layer_mx6=layer_mx6)
+    model = DeviceModel(weights, topo, device, embedding_index, precision, fold_shift=fold_shift, layer_mx6=layer_mx6, first_mx6=first_mx6)
     sel = dict(requested=precision, selected=model.arithmetic, probed=False)
     model.selection = sel
     if not probe or not model.f16bf8:
@@ -849,7 +868,7 @@ def select_model(weights, topo, device="cuda:0", embedding_index=0, precision="f
     twin = model.fallback()
     ref = twin.probe_vectors(batch)
     err = _max_rel_l2(got, ref)
-    sel.update(probed=True, layer_mx6=model.layer_mx6, f16bf8_vs_bf16x3=err, f16bf8_limit=PROBE_LIMIT_F16BF8, probe_left_fp16_range=clamped,
+    sel.update(probed=True, layer_mx6=model.layer_mx6, first_mx6=model.first_mx6, f16bf8_vs_bf16x3=err, f16bf8_limit=PROBE_LIMIT_F16BF8, probe_left_fp16_range=clamped,
                probe_frames=int(np.sum(batch[2])))
     if err <= PROBE_LIMIT_F16BF8 and not clamped:
         return model
@@ -857,7 +876,7 @@ def select_model(weights, topo, device="cuda:0", embedding_index=0, precision="f
     if model.fold_shift and fold_shift is None:
         # The fold costs accuracy (uncentred operands: DESIGN 9.7) for a per-cent of the step; the step down to bf16x3 costs a
         # quarter of it.  A checkpoint that misses the limit folded gets the unfolded f16bf8 arithmetic before it is demoted.
-        plain = DeviceModel(weights, topo, device, embedding_index, precision, fold_shift=False, layer_mx6=layer_mx6)
+        plain = DeviceModel(weights, topo, device, embedding_index, precision, fold_shift=False, layer_mx6=layer_mx6, first_mx6=first_mx6)
         got = plain.probe_vectors(batch)
         clamped2 = int(plain.status.item()) != 0
         plain.status.zero_()
@@ -868,9 +887,23 @@ def select_model(weights, topo, device="cuda:0", embedding_index=0, precision="f
             plain.selection = sel
             return plain
         last, last_err = plain, err2
+    if last.first_mx6 and first_mx6 is None:
+        # ... then with layer 1's cross terms back in bf8: the candidate as it was before layer 1 had the e2m3 form
+        l1 = DeviceModel(weights, topo, device, embedding_index, precision, fold_shift=last.fold_shift, layer_mx6=layer_mx6, first_mx6=False)
+        got = l1.probe_vectors(batch)
+        clamped1 = int(l1.status.item()) != 0
+        l1.status.zero_()
+        err_l1 = _max_rel_l2(got, ref)
+        sel.update(first_mx6_f16bf8_vs_bf16x3=last_err, f16bf8_vs_bf16x3=err_l1, probe_left_fp16_range=clamped1, first_mx6=False)
+        if err_l1 <= PROBE_LIMIT_F16BF8 and not clamped1:
+            l1._fallback = twin
+            l1.selection = sel
+            return l1
+        last, last_err = l1, err_l1
     if last.layer_mx6 and layer_mx6 is None:
         # ... and the last candidate with that layer's cross terms back in bf8, before the arithmetic itself is given up
-        bf8 = DeviceModel(weights, topo, device, embedding_index, precision, fold_shift=last.fold_shift, layer_mx6=False)
+        bf8 = DeviceModel(weights, topo, device, embedding_index, precision, fold_shift=last.fold_shift, layer_mx6=False,
+                          first_mx6=False if first_mx6 is None else first_mx6)
         got = bf8.probe_vectors(batch)
         clamped3 = int(bf8.status.item()) != 0
         bf8.status.zero_()

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 42
+ABI_VERSION = 43
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -60,6 +60,7 @@ _SIGNATURES = {
     "xv_tdnn_layer_f16bf8": (_ci, [_vp, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _ci, _ci, _vp, _vp]),
     "xv_tdnn_layer_pool_f16bf8": (_ci, [_vp, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
     "xv_tdnn_first_f16bf8": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
+    "xv_tdnn_first_f16mx6": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
     "xv_packed_pair_f16bf8_bytes": (_sz, [_ci, _ci, _ci]),
     "xv_pack_pair_f16bf8": (_ci, [_vp, _vp, _ci, _ci, _ci, _vp, _vp]),
     "xv_tdnn_pair_pool_f16bf8": (_ci, [_vp, _i64, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp]),
@@ -690,10 +691,11 @@ def tdnn_first(x, R, w, bias, scale, shift, act, alpha, dilation, row_valid, y, 
     assert isinstance(w, PackedFirst) and isinstance(y, SplitBuf)
     _rows2d(x, "x"); assert x.shape[0] >= R and x.shape[1] >= w.cin
     assert y.channels == w.cout and y.rows >= R
-    if y.fmt == FMT_SPLIT8:
-        _check(lib.xv_tdnn_first_f16bf8(_ptr(x), int(R), w.cin, x.stride(0), _ptr(w.wt), _ptr(bias), _ptr(scale), _ptr(shift), int(act),
-                                        _ptr(alpha), w.K, int(dilation), w.cout, _valid(row_valid, R), ctypes.c_void_p(y.ptr),
-                                        _ptr(status), _stream()), "xv_tdnn_first_f16bf8")
+    if y.fmt in (FMT_SPLIT8, FMT_SPLIT6):
+        name = "xv_tdnn_first_f16bf8" if y.fmt == FMT_SPLIT8 else "xv_tdnn_first_f16mx6"
+        _check(getattr(lib, name)(_ptr(x), int(R), w.cin, x.stride(0), _ptr(w.wt), _ptr(bias), _ptr(scale), _ptr(shift), int(act),
+                                  _ptr(alpha), w.K, int(dilation), w.cout, _valid(row_valid, R), ctypes.c_void_p(y.ptr),
+                                  _ptr(status), _stream()), name)
         return
     _check(lib.xv_tdnn_first_bf16x3(_ptr(x), int(R), w.cin, x.stride(0), _ptr(w.wt), _ptr(bias), _ptr(scale), _ptr(shift), int(act),
                                     _ptr(alpha), w.K, int(dilation), w.cout, _valid(row_valid, R), ctypes.c_void_p(y.ptr), _stream()),
