@@ -274,6 +274,29 @@ def folded_row_bias(bias, taps, row_valid, dilation):
 
 
 # ------------------------------------------------------------------------------------------------
+# the f16bf8 route's formats (a constant of the model: DeviceModel asks once, _frame_level_f16bf8 walks the answer)
+# ------------------------------------------------------------------------------------------------
+def f16bf8_plan(n, pair_fmt, takes, first_mx6=None, layer_mx6=None):
+    """Which hidden layers of an ``n``-layer f16bf8 model form their cross terms on e2m3 MFMAs, and what every launch in front of
+    the last one writes and reads: ``(mx6, fmts, packs)``.  ``pair_fmt``: the format the pair kernel in use reads, None without
+    one; layers [0, stop) are launches of their own, stop = n - 2 in front of the pair kernel, else n - 1.  ``takes(i)``: layer i
+    has a shape xv_tdnn_layer_f16mx6 takes.  ``first_mx6`` / ``layer_mx6`` (None, False or True): the switches that govern layer 1
+    / the layers >= 2.  Layer i is in ``mx6`` iff 1 <= i < stop, takes(i), its producer can write the 6-bit rows (layer 0's kernel
+    and encoding pass always can; a hidden layer's epilogue does in the 16 x 16 MFMA form of the 256 x 256 tile only, the form a
+    shape with takes(i - 1) runs, whichever pack it reads) and its switch is not False.
+    ``fmts[i]``, i in [0, stop): what layer i writes -- what the pair kernel reads in front of it, else FMT_SPLIT6 for a consumer
+    in ``mx6``, else FMT_SPLIT8 (every output form exists for both packs).  ``packs[i]``, i in [1, stop): the weight pack layer i
+    runs from, "wp6" in ``mx6``, else "wp8" (packs[0] is None: layer 0 is no f16bf8 launch).  So a launch reads FMT_SPLIT6 rows
+    exactly when it runs from "wp6": the kernel behind that pack reads no other format, the one behind "wp8" not this one."""
+    stop = n - 1 if pair_fmt is None else n - 2
+    mx6 = set(i for i in range(1, stop)
+              if (first_mx6 if i == 1 else layer_mx6) is not False and takes(i) and (i == 1 or takes(i - 1)))
+    fmts = [pair_fmt if pair_fmt is not None and i == stop - 1 else hiplib.FMT_SPLIT6 if i + 1 in mx6 else hiplib.FMT_SPLIT8
+            for i in range(stop)]
+    return mx6, fmts, [None] + ["wp6" if i in mx6 else "wp8" for i in range(1, stop)]
+
+
+# ------------------------------------------------------------------------------------------------
 # device model
 # ------------------------------------------------------------------------------------------------
 class _ColumnView(object):
@@ -326,13 +349,10 @@ class DeviceModel(object):
         model on xv_tdnn_first_bf16x3 when its shape allows.  fold_shift (None, the default: on where supported -- f16bf8 models
         with ReLU whose K > 1 layers behind layer 0 are a multiple of 8 channels wide; False: off; True: required): the frame-level layers store their activations without the BN shift, which
         moves into the next layer's bias (see shift_tap_table), so that the f16bf8 GEMMs read the ReLU's zeros as zeros.
-        layer_mx6 (None, the default: on where supported; False: off; True: required): a hidden f16bf8 layer i >= 2 in front of the
-        pair kernel whose shape xv_tdnn_layer_f16mx6 takes, fed by an f16bf8 layer that runs the same kernel form, forms its cross
-        terms on block-scaled e2m3 MFMAs at half their cycles; its producer writes FMT_SPLIT6 rows into the same buffer.
-        first_mx6 (None, False or True, as layer_mx6): the same form for layer 1 of an f16bf8 model, when its shape is one
-        xv_tdnn_layer_f16mx6 takes and it runs as a layer of its own (not inside the pair kernel): layer 0 then writes FMT_SPLIT6
-        rows (xv_tdnn_first_f16mx6, or the encoding pass behind the general kernel).  ``mx6_layers`` / ``layer_mx6`` keep their
-        meaning (layers >= 2); ``self.first_mx6`` records what layer 1 runs."""
+        first_mx6 / layer_mx6 (None, the default: on where supported; False: off; True: required): layer 1 / the hidden layers
+        >= 2 of an f16bf8 model form their cross terms on block-scaled e2m3 MFMAs at half their cycles (xv_tdnn_layer_f16mx6),
+        their producers writing FMT_SPLIT6 rows into the same buffers -- wherever f16bf8_plan's one rule admits it.
+        ``self.first_mx6`` records what layer 1 runs, ``self.mx6_layers`` which layers >= 2 do, ``self.layer_mx6`` whether any."""
         import torch
         hiplib.require_gpu()
         assert precision in ("fp32", "fp32tc", "bf16x3", "f16bf8")
@@ -446,31 +466,22 @@ class DeviceModel(object):
                     sc = "frame_level_info_layer-%d" % i
                     self.layers[i]["wp8"] = hiplib.pack_weights_f16bf8(self._wdev(weights, sc + "/w:0"))
                 self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
-            # the e2m3 form of a hidden layer: both it and its producer must run the 16 x 16 MFMA form of the 256 x 256 tile (the
-            # producer's epilogue writes the 6-bit rows, layer 0's kernel does not); the layer in front of the pair kernel keeps
-            # writing what that kernel reads
-            self.mx6_layers = set()
-            if self.f16bf8 and (layer_mx6 is None or layer_mx6):
+            # the e2m3 form of the hidden layers and the format every launch writes: one rule (f16bf8_plan), asked once
+            mx6, self._fmts, self._packs = set(), (), ()
+            if self.f16bf8:
                 def takes(j):
                     Lj = self.layers[j]
                     return hiplib.layer_mx6_supported(Lj["K"], Lj["dil"], Lj["cin"], Lj["cout"])
-                for i in range(2, n - 2 if self.pair is not None else n - 1):
-                    if takes(i) and takes(i - 1):
-                        self.layers[i]["wp6"] = hiplib.pack_weights_f16mx6(self._wdev(weights, "frame_level_info_layer-%d/w:0" % i))
-                        self.mx6_layers.add(i)
+                pair_fmt = None if self.pair is None else hiplib.FMT_SPLIT8 if self.pair8 is not None else hiplib.FMT_SPLIT
+                mx6, self._fmts, self._packs = f16bf8_plan(n, pair_fmt, takes, first_mx6, layer_mx6)
+                for i in sorted(mx6):
+                    self.layers[i]["wp6"] = hiplib.pack_weights_f16mx6(self._wdev(weights, "frame_level_info_layer-%d/w:0" % i))
+            self.first_mx6, self.mx6_layers = 1 in mx6, mx6 - {1}
             self.layer_mx6 = bool(self.mx6_layers)
+            shape = "the e2m3 shape (K in {3,5,7}, Cin % 64 == 0, Cout % 256 == 0, in neither the pair kernel nor the pooling launch)"
             assert not (layer_mx6 and not self.layer_mx6), \
-                "layer_mx6=True needs an f16bf8 model with a K in {3,5,7} layer (Cin % 64 == 0, Cout % 256 == 0) behind another one"
-            # layer 1 in the same form: its producer is layer 0, whose kernel (and whose encoding pass) writes the 6-bit rows too;
-            # layer 1 itself writes whatever its consumer reads (every output form of the e2m3 kernel exists)
-            self.first_mx6 = False
-            if self.f16bf8 and (first_mx6 is None or first_mx6) and (n - 2 if self.pair is not None else n - 1) > 1:
-                L1 = self.layers[1]
-                if hiplib.layer_mx6_supported(L1["K"], L1["dil"], L1["cin"], L1["cout"]):
-                    L1["wp6"] = hiplib.pack_weights_f16mx6(self._wdev(weights, "frame_level_info_layer-1/w:0"))
-                    self.first_mx6 = True
-            assert not (first_mx6 and not self.first_mx6), \
-                "first_mx6=True needs an f16bf8 model whose layer 1 has K in {3,5,7}, Cin % 64 == 0, Cout % 256 == 0 and is not part of the pair kernel"
+                "layer_mx6=True needs an f16bf8 model with a layer i >= 2 of %s behind another such layer" % shape
+            assert not (first_mx6 and not self.first_mx6), "first_mx6=True needs an f16bf8 model whose layer 1 has %s" % shape
             # (only ReLU leaves zeros to gain: the other activations keep today's path)
             # (and the GEMM epilogues read 8 channels of a tap's constants at a time: every K > 1 consumer's width a multiple of 8)
             can_fold = self.f16bf8 and self.act == tp.ACT_RELU and all(L["cout"] % 8 == 0 for L in self.layers[1:] if L["K"] > 1)
@@ -661,8 +672,8 @@ class DeviceModel(object):
         return pooled
 
     def _frame_level_f16bf8(self, x, R, row_valid, status, marks=None):
-        """first-layer kernel -> split8; hidden layers in the f16bf8 arithmetic; the layer in front of the pair kernel writes
-        the format that kernel reads; block statistics end up in ``self._last``.  ``marks``: optional list that receives one
+        """first-layer kernel; hidden layers in the f16bf8 arithmetic, each writing the format and running from the pack that
+        f16bf8_plan gave this model; block statistics end up in ``self._last``.  ``marks``: optional list that receives one
         ``(label, event)`` per launch, the event recorded right after it (bench.py's per-kernel breakdown)."""
         def mark(label):
             if marks is not None:
@@ -671,7 +682,7 @@ class DeviceModel(object):
                 marks.append((label, ev))
         n = len(self.layers)
         bufs = (self._ping, self._pong)
-        S8, S3, S6 = hiplib.FMT_SPLIT8, hiplib.FMT_SPLIT, hiplib.FMT_SPLIT6
+        fmts, packs = self._fmts, self._packs            # layers [1, len(fmts)) run on xv_tdnn_layer_f16bf8 / _f16mx6
         fold = self.fold_shift
 
         def pp(i):
@@ -689,9 +700,7 @@ class DeviceModel(object):
         def taps(i):
             return self.layers[i].get("tapbias") if fold else None
         L = self.layers[0]
-        stop = n - 2 if self.pair is not None else n - 1        # layers [1, stop) run on xv_tdnn_layer_f16bf8
-        pair_fmt = S8 if self.pair8 is not None else S3         # what the pair kernel in use reads
-        h = bufs[0].view(L["cout"], pair_fmt if (self.pair is not None and stop == 1) else S6 if self.first_mx6 else S8)
+        h = bufs[0].view(L["cout"], fmts[0])
         mark("start")
         if self.first is not None:
             hiplib.tdnn_first(x, R, self.first, *ep(0), L["dil"], row_valid, h, status)
@@ -700,15 +709,13 @@ class DeviceModel(object):
             # a first layer the dedicated kernel does not take: the general bf16x3 GEMM into fp32 rows, then one encoding pass
             y32 = self._l0_rows[:R]
             hiplib.tdnn_layer(x, L["wp"], *ep(0), L["K"], L["dil"], row_valid, y32, rows=R)
-            hiplib.split_encode(y32, h, rows=R, status=status if h.fmt in (S8, S6) else None)
+            hiplib.split_encode(y32, h, rows=R, status=status if h.fmt != hiplib.FMT_SPLIT else None)
             mark("layer 0: tdnn_gemm_bf16x3_kernel + split encode")
-        for i in range(1, stop):
+        for i in range(1, len(fmts)):
             L = self.layers[i]
-            y = bufs[i & 1].view(L["cout"], pair_fmt if (self.pair is not None and i == stop - 1) else
-                                 S6 if i + 1 in self.mx6_layers else S8)
+            y = bufs[i & 1].view(L["cout"], fmts[i])
             # (one launcher for both forms: the weight pack says which kernel reads h)
-            mx6 = i in self.mx6_layers or (i == 1 and self.first_mx6)
-            hiplib.tdnn_layer8(h, R, L["wp6" if mx6 else "wp8"], *ep(i), L["dil"], row_valid, y, status, tapbias=taps(i))
+            hiplib.tdnn_layer8(h, R, L[packs[i]], *ep(i), L["dil"], row_valid, y, status, tapbias=taps(i))
             mark("layer %d: tdnn_gemm_f16bf8 (K=%d, %d -> %d)" % (i, L["K"], L["cin"], L["cout"]))
             h = y
         if self.pair is not None:
@@ -835,6 +842,15 @@ def _max_rel_l2(a, b):
     return float(np.nan_to_num(r, nan=np.inf).max()) if len(r) else 0.0
 
 
+# The forms an f16bf8 candidate gives up, in this order, before the arithmetic itself is given up: (DeviceModel's switch, the key of
+# ``selection`` that receives the value that missed with the form on).  The fold costs accuracy (uncentred operands: DESIGN 9.7) for
+# a per-cent of the step and each e2m3 layer a few, the step down to bf16x3 a quarter of it; first_mx6 goes before layer_mx6, so
+# that the candidate after it is bit for bit the one of a build without that form and no checkpoint loses a form it had.
+PROBE_LADDER = (("fold_shift", "folded_f16bf8_vs_bf16x3"),
+                ("first_mx6", "first_mx6_f16bf8_vs_bf16x3"),
+                ("layer_mx6", "mx6_f16bf8_vs_bf16x3"))
+
+
 def select_model(weights, topo, device="cuda:0", embedding_index=0, precision="f16bf8", probe=None, fold_shift=None, layer_mx6=None,
                  first_mx6=None):
     """``DeviceModel`` in the fastest arithmetic, not faster than ``precision``, that the accuracy probe admits for THESE weights:
@@ -846,25 +862,27 @@ def select_model(weights, topo, device="cuda:0", embedding_index=0, precision="f
     Toom-Cook kernel does not cover) -- a demoted model does not fall to the slowest form.  XVECTOR_EXACT_RUNG=fp32 (or a request
     of ``precision="fp32"``) keeps the direct contraction, the literal statement of local/tf/models.py:60.
     ``model.selection`` reports what was measured.  ``probe=False`` (or XVECTOR_ACCURACY_PROBE=0) takes ``precision`` as given.
-    ``fold_shift``: as DeviceModel's (the f16bf8 candidate only); left at None, a folded candidate that fails its probe is tried
-    unfolded before the model is demoted (``selection["fold_shift"]`` is then False).  ``layer_mx6``: as DeviceModel's; left at
-    None, a candidate with an e2m3 layer that misses the limit (unfolded too, where that applies) is tried once more without it before
-    the model is demoted.  ``selection["layer_mx6"]`` (of a
-    probed model) records which form runs.  ``first_mx6``: as DeviceModel's; left at None, it is the FIRST of the two e2m3 forms to
-    go: a candidate that misses the limit (unfolded too) is tried with layer 1's cross terms back in bf8 -- bit for bit the
-    candidate of a build without that form -- before ``layer_mx6`` is given up, so nobody loses what they had.
-    ``selection["first_mx6"]`` records which form runs, ``selection["first_mx6_f16bf8_vs_bf16x3"]`` the value that missed."""
+    ``fold_shift`` / ``first_mx6`` / ``layer_mx6``: as DeviceModel's (the f16bf8 candidates only).  An f16bf8 candidate that misses
+    the limit walks PROBE_LADDER before it is demoted: for each switch in turn that the last candidate has on and the caller left
+    at None, one more candidate with that switch False (and those given up before it), kept if it passes.  ``selection[switch]``
+    records what runs (False once given up; ``fold_shift`` only then), the ladder's key the value that missed with the form on,
+    ``f16bf8_vs_bf16x3`` / ``probe_left_fp16_range`` the candidate probed last."""
     if probe is None:
         probe = os.environ.get("XVECTOR_ACCURACY_PROBE", "1") != "0"
-    model = DeviceModel(weights, topo, device, embedding_index, precision, fold_shift=fold_shift, layer_mx6=layer_mx6, first_mx6=first_mx6)
+    asked = dict(fold_shift=fold_shift, first_mx6=first_mx6, layer_mx6=layer_mx6)
+    model = DeviceModel(weights, topo, device, embedding_index, precision, **asked)
     sel = dict(requested=precision, selected=model.arithmetic, probed=False)
     model.selection = sel
     if not probe or not model.f16bf8:
         return model
     batch = probe_batch(model.feat_dim, model.in_dim, model.gap, model.align)
-    got = model.probe_vectors(batch)
-    clamped = int(model.status.item()) != 0
-    model.status.zero_()
+
+    def probed(m):
+        got = m.probe_vectors(batch)
+        clamped = int(m.status.item()) != 0
+        m.status.zero_()
+        return got, clamped
+    got, clamped = probed(model)
     twin = model.fallback()
     ref = twin.probe_vectors(batch)
     err = _max_rel_l2(got, ref)
@@ -872,47 +890,17 @@ def select_model(weights, topo, device="cuda:0", embedding_index=0, precision="f
                probe_frames=int(np.sum(batch[2])))
     if err <= PROBE_LIMIT_F16BF8 and not clamped:
         return model
-    last, last_err = model, err                          # the f16bf8 candidate probed last
-    if model.fold_shift and fold_shift is None:
-        # The fold costs accuracy (uncentred operands: DESIGN 9.7) for a per-cent of the step; the step down to bf16x3 costs a
-        # quarter of it.  A checkpoint that misses the limit folded gets the unfolded f16bf8 arithmetic before it is demoted.
-        plain = DeviceModel(weights, topo, device, embedding_index, precision, fold_shift=False, layer_mx6=layer_mx6, first_mx6=first_mx6)
-        got = plain.probe_vectors(batch)
-        clamped2 = int(plain.status.item()) != 0
-        plain.status.zero_()
-        err2 = _max_rel_l2(got, ref)
-        sel.update(folded_f16bf8_vs_bf16x3=err, f16bf8_vs_bf16x3=err2, probe_left_fp16_range=clamped2, fold_shift=False)
-        if err2 <= PROBE_LIMIT_F16BF8 and not clamped2:
-            plain._fallback = twin
-            plain.selection = sel
-            return plain
-        last, last_err = plain, err2
-    if last.first_mx6 and first_mx6 is None:
-        # ... then with layer 1's cross terms back in bf8: the candidate as it was before layer 1 had the e2m3 form
-        l1 = DeviceModel(weights, topo, device, embedding_index, precision, fold_shift=last.fold_shift, layer_mx6=layer_mx6, first_mx6=False)
-        got = l1.probe_vectors(batch)
-        clamped1 = int(l1.status.item()) != 0
-        l1.status.zero_()
-        err_l1 = _max_rel_l2(got, ref)
-        sel.update(first_mx6_f16bf8_vs_bf16x3=last_err, f16bf8_vs_bf16x3=err_l1, probe_left_fp16_range=clamped1, first_mx6=False)
-        if err_l1 <= PROBE_LIMIT_F16BF8 and not clamped1:
-            l1._fallback = twin
-            l1.selection = sel
-            return l1
-        last, last_err = l1, err_l1
-    if last.layer_mx6 and layer_mx6 is None:
-        # ... and the last candidate with that layer's cross terms back in bf8, before the arithmetic itself is given up
-        bf8 = DeviceModel(weights, topo, device, embedding_index, precision, fold_shift=last.fold_shift, layer_mx6=False,
-                          first_mx6=False if first_mx6 is None else first_mx6)
-        got = bf8.probe_vectors(batch)
-        clamped3 = int(bf8.status.item()) != 0
-        bf8.status.zero_()
-        err_bf8 = _max_rel_l2(got, ref)
-        sel.update(mx6_f16bf8_vs_bf16x3=last_err, f16bf8_vs_bf16x3=err_bf8, probe_left_fp16_range=clamped3, layer_mx6=False)
-        if err_bf8 <= PROBE_LIMIT_F16BF8 and not clamped3:
-            bf8._fallback = twin
-            bf8.selection = sel
-            return bf8
+    for name, missed in PROBE_LADDER:
+        if getattr(model, name) and asked[name] is None:
+            asked[name] = False
+            model = DeviceModel(weights, topo, device, embedding_index, precision, **asked)
+            got, clamped = probed(model)
+            sel[missed], err = err, _max_rel_l2(got, ref)
+            sel.update({"f16bf8_vs_bf16x3": err, "probe_left_fp16_range": clamped, name: False})
+            if err <= PROBE_LIMIT_F16BF8 and not clamped:
+                model._fallback = twin
+                model.selection = sel
+                return model
     rung = "fp32" if os.environ.get("XVECTOR_EXACT_RUNG", "fp32tc") == "fp32" else "fp32tc"
     exact = DeviceModel(weights, topo, device, embedding_index, rung)
     err3 = _max_rel_l2(ref, exact.probe_vectors(batch))
