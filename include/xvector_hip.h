@@ -52,7 +52,7 @@ extern "C" {
 #define XV_ERR_BAD_ARG (-1)
 #define XV_ERR_UNSUPPORTED (-2)
 
-/* Library / ABI version (increments whenever an entry point is added or changed; currently 40). */
+/* Library / ABI version (increments whenever an entry point is added or changed; currently 44). */
 int xv_version(void);
 /* Thread-local description of the last non-zero return. */
 const char *xv_last_error(void);
@@ -1129,6 +1129,37 @@ int xv_cmn_sliding_gather_f32(const float *x, int ldx, int feat_dim, int64_t x_r
                               const int32_t *chunk_first, const int32_t *chunk_len, const int32_t *chunk_row, int n_chunks,
                               int max_chunk_len, int cmn_window, int center, int min_window, float *y, int ldy, int64_t y_rows,
                               void *stream);
+
+/* ---- speech segments from VAD decisions on the device (csrc/xv_segment.hip) ------------------------------------
+ * What Kaldi's diarization recipes do with compute_vad_decision.sh + diarization/vad_to_segments.sh, for decisions that never leave
+ * the card.  The rule is this project's own and this text is its contract.  An utterance has T frames and decisions v[t]; a frame
+ * is voiced iff v[t] != 0 (NaN counts as voiced, as in xv_vad_compact_i32).  Parameters, all in frames: max_gap G >= 0, min_len
+ * M >= 1, pad P >= 0 with 2 P <= G, max_len L = 0 (no splitting) or L >= 2 M.  Four steps, in this order:
+ *   1. close  a maximal unvoiced run [a, b) with a > 0, b < T and b - a <= G becomes voiced (leading and trailing silence is
+ *             never closed);
+ *   2. drop   of the maximal voiced runs [a, b) of the result, those with b - a >= M are kept;
+ *   3. pad    a kept run becomes [max(a - P, 0), min(b + P, T)) (2 P <= G: kept runs never touch after padding);
+ *   4. split  a run of n > L frames (L > 0) becomes k = ceil(n / L) pieces, piece i = [a + floor(i n / k), a + floor((i + 1) n / k)).
+ * The segments of the utterance are the pieces in increasing order.  Every piece has at least M and (L > 0) at most L frames, and
+ * their number is at most xv_vad_segments_capacity(T, G, M, L) = (T + G + 1) / (M + G + 1) + (L ? T / L : 0), integer division
+ * (a host function; -1 for T < 0 or parameters outside the ranges above).
+ * xv_vad_segments_i32  vad[n_frames]; utterances are addressed as in xv_vad_compact_i32 (utt_start[u], utt_len[u] in frames; any
+ *   order, gaps allowed).  seg_count[u] = the FULL number of segments of u; segment i of u goes to seg_first[seg_off[u] + i] (its
+ *   first frame, counted inside u) and seg_len[seg_off[u] + i], and an entry is written only while i < seg_cap[u] and
+ *   0 <= seg_off[u] + i < n_slots: a count above the capacity tells the caller its bound was wrong.  Nothing else is written
+ *   anywhere.  An utterance whose span leaves [0, n_frames), or with T == 0, gets count 0.  n_utts == 0 returns 0 and launches
+ *   nothing.  XV_ERR_BAD_ARG before any launch: a NULL pointer (workspace may be NULL when no bytes are needed), a negative
+ *   count, parameters outside the ranges above, workspace_bytes < xv_vad_segments_workspace_bytes(n_frames) (0 for the tiled walk
+ *   of this implementation).  One workgroup of XV_SEG_TILE threads per utterance walks it XV_SEG_TILE frames at a time and carries
+ *   the last voiced frame, the open run and the output index across tiles.  Integers only, no atomics: the same bits on every
+ *   run.  Enqueues and returns. */
+#define XV_SEG_TILE 256
+int xv_vad_segments_i32(const float *vad, const int32_t *utt_start, const int32_t *utt_len, int n_utts, int64_t n_frames,
+                        int max_gap, int min_len, int pad, int max_len, const int32_t *seg_off, const int32_t *seg_cap,
+                        int64_t n_slots, int32_t *seg_count, int32_t *seg_first, int32_t *seg_len, void *workspace,
+                        size_t workspace_bytes, void *stream);
+size_t xv_vad_segments_workspace_bytes(int64_t n_frames);
+int64_t xv_vad_segments_capacity(int64_t T, int max_gap, int min_len, int max_len);
 
 #ifdef __cplusplus
 }

@@ -877,7 +877,7 @@ void xv_internal_gemm3_tile_rows(int value);      // xv_gemm3.hip
 void xv_internal_gemm8_tile_rows(int value);      // xv_gemm8.hip
 void xv_internal_first_tiles(int tiles);          // xv_first.hip
 
-int xv_version(void) { return 43; }
+int xv_version(void) { return 44; }
 
 int xv_set_tuning(int key, int value)
 {

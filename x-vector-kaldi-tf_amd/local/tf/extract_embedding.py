@@ -88,7 +88,19 @@ _FLAGS = (
      "With --subsegments-file: milliseconds per frame (10 when not given).  Not with --wav-rspecifier: the MFCC configuration's value is used."),
     ("--subsegments-file", "subsegments_file", str, "", False, None,
      "With --window: also write '<key> <utt> <start s> <end s>' per vector to this file (a Kaldi segments file)."),
+    # build-defined extension: recordings cut into segments, windows and vectors inside them
+    ("--segment-max-gap", "segment_max_gap", int, None, False, None,
+     "With --segment-by-vad: pauses of up to this many frames are closed (30 when not given)."),
+    ("--segment-pad", "segment_pad", int, None, False, None,
+     "With --segment-by-vad: frames added on both sides of a segment, at most half of --segment-max-gap (10 when not given)."),
+    ("--segment-max-length", "segment_max_length", int, None, False, None,
+     "With --segment-by-vad: longer segments are split evenly; 0 = never, else at least twice --min-chunk-size (1000 when not given)."),
+    ("--segments", "segments", str, "", False, None,
+     "With --wav-rspecifier: a Kaldi segments file '<seg-id> <reco> <start s> <end s>' over the recordings of wav.scp (e.g. what "
+     "mfcc_vad.py vad-to-segments writes, or an external SAD's).  Each segment's feature rows are extracted as an utterance; "
+     "without --window one vector per segment is written under its seg-id.  Excludes --segment-by-vad."),
 )
+_SEGMENT_DEFAULTS = (("segment_max_gap", 30), ("segment_pad", 10), ("segment_max_length", 1000))
 
 WAV_WINDOW_SAMPLES = 1 << 26      # samples per window of the --wav-rspecifier route: the batches of mfcc_vad.py (its WINDOW_SAMPLES)
 
@@ -105,6 +117,11 @@ def get_args(argv=None):
         if choices:
             kw["choices"] = list(choices)
         parser.add_argument(flag, **kw)
+    parser.add_argument("--segment-by-vad", dest="segment_by_vad", action="store_true",
+                        help="With --wav-rspecifier: cut every recording into segments from its VAD decisions on the GPU (pauses of up "
+                             "to --segment-max-gap closed, runs shorter than --min-chunk-size dropped, --segment-pad added, runs above "
+                             "--segment-max-length split) and extract inside them: windows of --window never bridge a longer pause; "
+                             "without --window one vector per segment, under <reco>-<first>-<end>.")
     args = parser.parse_args(argv)
     # usage errors of the sliding mode leave through argparse (exit status 2), before anything is opened
     if args.window < 0 or args.period < 0:
@@ -128,6 +145,23 @@ def get_args(argv=None):
         args.frame_shift = 10.0
     if args.frame_shift <= 0:
         parser.error("--frame-shift must be positive")
+    # usage errors of the segmented route leave through argparse (exit status 2), before anything is opened
+    segment_given = [name for name, _ in _SEGMENT_DEFAULTS if getattr(args, name) is not None]
+    if (args.segment_by_vad or args.segments or segment_given) and not args.wav_rspecifier:
+        parser.error("--segment-by-vad, --segments and the --segment-* options go with --wav-rspecifier")
+    if args.segment_by_vad and args.segments:
+        parser.error("--segments and --segment-by-vad exclude each other: the segments come from the file or from the VAD")
+    if segment_given and not args.segment_by_vad:
+        parser.error("--%s goes with --segment-by-vad" % segment_given[0].replace("_", "-"))
+    for name, default in _SEGMENT_DEFAULTS:
+        if getattr(args, name) is None:
+            setattr(args, name, default)
+    if args.segment_by_vad:
+        from xvector_amd import segment
+        try:      # min_len is --min-chunk-size: a shorter segment would be rejected by the extractor anyway
+            segment.SegmentOptions(args.segment_max_gap, args.min_chunk_size, args.segment_pad, args.segment_max_length).check()
+        except ValueError as e:
+            parser.error("--segment-by-vad: %s" % e)
     # usage errors of the --wav-rspecifier route leave through argparse (exit status 2), before anything is opened
     if args.wav_rspecifier:
         if args.feature_rspecifier or args.vad_rspecifier:
@@ -266,7 +300,20 @@ def _wave_table(args):
         opts.update(mfcc.read_config(args.mfcc_config))
     if args.vad_config:
         vopts.update(mfcc.read_config(args.vad_config))
-    return extract_stream.WaveTable(args.wav_rspecifier.strip().partition(":")[2].strip(), opts, vopts, WAV_WINDOW_SAMPLES)
+    return extract_stream.WaveTable(args.wav_rspecifier.strip().partition(":")[2].strip(), opts, vopts, WAV_WINDOW_SAMPLES,
+                                    segmenter=_segmenter(args))
+
+
+def _segmenter(args):
+    """What cuts the recordings of the --wav-rspecifier route into segments: None without --segment-by-vad / --segments."""
+    from xvector_amd import segment
+    if getattr(args, "segment_by_vad", False):
+        return segment.VadSegmenter(segment.SegmentOptions(args.segment_max_gap, args.min_chunk_size, args.segment_pad,
+                                                           args.segment_max_length))
+    if getattr(args, "segments", ""):
+        import plda_backend
+        return segment.FileSegmenter(plda_backend.read_segments(args.segments))
+    return None
 
 
 def _sliding(args, subsegments_fid):

@@ -7,6 +7,9 @@
                      <vad-wspec>       (both in one pass: the VAD reads the features on the device, nothing is re-read)
   wav-to-duration    [--read-entire-file] scp:wav.scp ark,t:utt2dur
   copy-feats         [--compress[=true|false]] <feats-rspec> <wspec>     (FM, DM and CM* tables in; plain or compressed out)
+  vad-to-segments    [--max-gap 30] [--min-segment-length 50] [--pad 10] [--max-segment-length 1000] [--frame-shift 10]
+                     <vad-rspec> segments      (diarization/vad_to_segments.sh: a Kaldi segments file from VAD decisions, on the
+                     host; lengths in frames, --frame-shift in milliseconds; the rule of DESIGN.md §8.18)
 
 Options carry Kaldi's names and defaults (xvector_amd/mfcc.py); a ``--config`` file is read first, the command line
 overrides it.  ``--seed`` keys the dither noise with the utterance id.  Outputs are ``ark,scp:A,S`` or
@@ -292,6 +295,43 @@ def cmd_copy_feats(args):
     logger.info("Copied %d feature matrices.", n)
 
 
+def _read_vecs(rspec):
+    kind, _, path = rspec.partition(":")
+    kind = kind.split(",")[0]
+    if kind == "scp" and path:
+        return kaldi_io.read_vec_flt_scp(path)
+    if kind == "ark" and path:
+        return kaldi_io.read_vec_flt_ark(path)
+    raise SystemExit("unsupported rspecifier %r (scp: or ark:)" % rspec)
+
+
+def cmd_vad_to_segments(args):
+    """One ``<reco>-<first>-<end> <reco> <start s> <end s>`` line per segment of every recording of the VAD table (the key and line
+    formats of the sliding mode's subsegments file), written under ``.tmp`` and renamed: what ``extract_embedding.py --segments``
+    reads back.  Host only: the NumPy twin of the kernel the ``--segment-by-vad`` route runs."""
+    from xvector_amd import segment
+    from xvector_amd.extract_stream import subsegment_key, subsegment_line
+    opts = segment.SegmentOptions(args.max_gap, args.min_segment_length, args.pad, args.max_segment_length)
+    try:
+        opts.check()
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if args.frame_shift <= 0:
+        raise SystemExit("--frame-shift must be positive")
+    n_reco = n_seg = n_none = 0
+    with open(args.segments + ".tmp", "wt") as f:
+        for reco, v in _read_vecs(args.vad_rspecifier):
+            tab = segment.vad_segments_host(v, opts)
+            if not len(tab):
+                logger.warning("No segment for recording: '%s'", reco)
+                n_none += 1
+            f.write("".join(subsegment_line(subsegment_key(reco, a, a + n), reco, a, a + n, args.frame_shift) for a, n in tab.tolist()))
+            n_reco += 1
+            n_seg += len(tab)
+    os.rename(args.segments + ".tmp", args.segments)
+    logger.info("Wrote %d segments of %d recordings (%d without a segment)", n_seg, n_reco, n_none)
+
+
 def cmd_wav_to_duration(args):
     """key + samples / rate per entry (Kaldi's wav-to-duration); an augmented entry's length comes from its options and the
     header of its input, without evaluating it."""
@@ -341,6 +381,14 @@ def build_parser():
     _compress_flag(c)
     c.add_argument("feats_rspecifier")
     c.add_argument("feats_wspecifier")
+    g = sub.add_parser("vad-to-segments")
+    g.add_argument("--max-gap", type=int, default=30, help="pauses of up to this many frames are closed")
+    g.add_argument("--min-segment-length", type=int, default=50, help="shorter runs are dropped (frames)")
+    g.add_argument("--pad", type=int, default=10, help="frames added on both sides of a kept run (at most half of --max-gap)")
+    g.add_argument("--max-segment-length", type=int, default=1000, help="longer runs are split evenly (frames; 0: never)")
+    g.add_argument("--frame-shift", type=float, default=10.0, help="milliseconds per frame")
+    g.add_argument("vad_rspecifier")
+    g.add_argument("segments")
     d = sub.add_parser("wav-to-duration")
     d.add_argument("--read-entire-file", action="store_true", help="accepted for Kaldi compatibility: every file is read whole")
     d.add_argument("wav_rspecifier")
@@ -369,6 +417,8 @@ def main(argv=None):
             cmd_vad(args)
         elif args.cmd == "copy-feats":
             cmd_copy_feats(args)
+        elif args.cmd == "vad-to-segments":
+            cmd_vad_to_segments(args)
         elif args.cmd == "wav-to-duration":
             cmd_wav_to_duration(args)
         else:

@@ -540,7 +540,11 @@ class Model(object):
         ``period`` frames (0: = window) instead of one per utterance, ``chunk_size`` ignored; sub-segment [first, end) of ``<utt>``
         is written under ``<utt>-<first>-<end>`` (8 digits each).  ``subsegments``: a text stream that gets one line per vector,
         ``<key> <utt> <start s> <end s>`` (a Kaldi segments file), frames turned into seconds with ``frame_shift`` milliseconds (a
-        WaveTable input: its MFCC configuration's).  One process only."""
+        WaveTable input: its MFCC configuration's).  One process only.
+
+        A WaveTable with a ``segmenter`` cuts every recording into segments first and extracts each segment as an
+        utterance: sliding windows stay inside segments and are keyed ``<reco>-<first>-<end>`` in the recording's frames; without
+        ``window`` one vector is written per segment, under its id in the segments file or ``<reco>-<first>-<end>``."""
         start_time = time.time()
         from_wav = isinstance(input_stream, extract_stream.WaveTable)
         sliding = int(window or 0) > 0
@@ -649,9 +653,14 @@ class Model(object):
                 "; demoted to bf16x3 at window %d" % st["demoted_at_window"] if ex.demoted else ""))
         self.last_stats = dict(st, demoted=bool(getattr(ex, "demoted", False)),
                                selection=dict(getattr(self.device_model, "selection", None) or {}))
-        logger.info("Processed %d features of average size %d frames. Done %d and failed %d%s" %
+        segmented = from_wav and input_stream.segmenter is not None
+        logger.info("Processed %d features of average size %d frames. Done %d and failed %d%s%s" %
                     (run.total_segments, st["frames"] / max(run.total_segments, 1), run.num_success, run.num_fail,
-                     "; wrote %d sub-segment vectors" % run.num_vectors if sliding else ""))
+                     "; wrote %d sub-segment vectors" % run.num_vectors if sliding else "",
+                     "; cut %d segments" % run.num_segments if segmented else ""))
+        if segmented and (input_stream.segmenter.unknown() or input_stream.segmenter.skipped):
+            logger.info("Skipped %d line(s) of the segments file whose recording is not in the wav.scp and %d empty segment(s)" %
+                        (input_stream.segmenter.unknown(), input_stream.segmenter.skipped))
         logger.info("Total time for neural network computations is %.2f minutes." % (run.compute_time / 60.0))
         logger.info("Elapsed time for extracting whole embeddings is %.2f minutes." %
                     ((time.time() - start_time) / 60.0))

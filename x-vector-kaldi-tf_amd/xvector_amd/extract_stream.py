@@ -219,11 +219,13 @@ class WaveTable(object):
     ``window_samples`` samples, with ``mfcc_vad._planned_batches``, i.e. exactly the batches ``compute-mfcc-vad`` would launch --
     and yields ``(keys, WaveBatch, None)``; the consumer's thread runs ``compute`` (the MFCC engine's launches) and the submit.
     ``mfcc_opts`` / ``vad_opts``: ``mfcc.MfccOptions`` / ``mfcc.VadOptions``.  ``start`` starts the thread (``make_embedding``
-    calls it once it has accepted its arguments)."""
+    calls it once it has accepted its arguments).  ``segmenter`` (a ``segment.VadSegmenter`` or ``segment.FileSegmenter``; DESIGN.md
+    §8.18): every recording is cut into segments and the extractor takes each segment as an utterance of its own."""
 
-    def __init__(self, wav_scp, mfcc_opts, vad_opts, window_samples=1 << 26):
+    def __init__(self, wav_scp, mfcc_opts, vad_opts, window_samples=1 << 26, segmenter=None):
         from . import augment
         self.path, self.opts, self.vad_opts, self.window_samples = wav_scp, mfcc_opts, vad_opts, int(window_samples)
+        self.segmenter = segmenter
         self.opts.check(resample=True)                # (NotImplementedError / ValueError: before anything is read)
         self._augmenter = augment.Augmenter()
         self._engine = None
@@ -277,6 +279,20 @@ class WaveTable(object):
         if any(isinstance(w, augment.Pending) for w in batch.waves):
             return augment.mfcc_compute(self._engine, self._augmenter, batch.keys, batch.waves, device=True)
         return self._engine.compute_device(batch.keys, batch.waves)
+
+    def segments(self, batch, vad, row0, T, ready):
+        """The segment tables of a computed window, one (seg-ids or None, int32 [n, 2] of (first frame, length)) per recording:
+        the segmenter's, on the MFCC engine's stream behind ``ready``."""
+        return self.segmenter.tables(batch.keys, vad, row0, T, self.opts.frame_shift, self._engine._stream, ready)
+
+
+class SegmentKeys(list):
+    """The keys of a window whose utterances are segments of recordings: beside each key, its recording (``reco``) and its first
+    frame there (``first``, int64 array)."""
+
+    def __init__(self, keys, reco, first):
+        list.__init__(self, keys)
+        self.reco, self.first = list(reco), np.asarray(first, np.int64).reshape(-1)
 
 
 def subsegment_key(utt, first, end):
@@ -347,6 +363,7 @@ class Extraction(object):
         # sliding mode (the extractor has a ``window``): one vector per sub-segment, keys expanded by ``emit_subsegments``
         self.sliding = getattr(ex, "window", None) is not None
         self.num_vectors = 0
+        self.num_segments = 0                 # segments submitted as utterances (a WaveTable with a segmenter)
 
     def _finish_subsegments(self, handle, keep, voiced_rows):
         """Sliding mode: (vectors, spans, offsets) of the utterances ``keep`` (None: all) -- ``Extractor.finish(as_array=True)``.
@@ -385,6 +402,24 @@ class Extraction(object):
         mine = engine._Rows(mats, shards[self.rank], lens, addrs)         # (not materialised)
         return functools.partial(self._finish, self.ex.submit(mine, mine.addrs), shards=shards)
 
+    def _segment_utterances(self, recos, tables, row0):
+        """The segments of a window's recordings as utterances: (SegmentKeys, first feature row, length).  A segment's key is its id
+        in the segments file, else ``subsegment_key(reco, first, end)``; a recording without a segment is warned about and fails."""
+        keys, reco_of, first, length, start = [], [], [], [], []
+        for reco, (ids, tab), r0 in zip(recos, tables, np.asarray(row0).tolist()):
+            if not len(tab):
+                self.logger.warning("No segment for recording: '%s'" % reco)
+                self.num_fail += 1
+                continue
+            spans = tab.tolist()
+            keys.extend(ids if ids is not None else [subsegment_key(reco, f, f + n) for f, n in spans])
+            reco_of.extend([reco] * len(spans))
+            first.extend(f for f, _ in spans)
+            length.extend(n for _, n in spans)
+            start.extend(r0 + f for f, _ in spans)
+        self.num_segments += len(keys)
+        return SegmentKeys(keys, reco_of, first), np.array(start, np.int64), np.array(length, np.int64)
+
     def _warn_unvoiced(self, key):
         self.logger.warning("No voiced frames (or VAD / feature length mismatch) for utterance: '%s'" % key)
         self.num_fail += 1
@@ -398,6 +433,10 @@ class Extraction(object):
         if isinstance(mats, WaveBatch):
             # a window of a WaveTable: MFCC + VAD on the device, and the extractor reads the rows where they lie
             feats, vad, row0, T, ready = mats.table.compute(mats, self.model.device_model.device)
+            if mats.table.segmenter is not None:
+                # every segment is an utterance of its own: a row range of its recording, every frame of it counted
+                keys, row0, T = self._segment_utterances(keys, mats.table.segments(mats, vad, row0, T, ready), row0)
+                vad = None
             raw = ex.submit_device_raw(feats, row0, T, vad, front.cmn_window, front.center, front.min_window, ready)
         elif front is not None and front.cmn_window > 0 and self.world == 1 and hasattr(ex, "submit_raw") and \
                 engine._host_lib() is not None and (addrs is not None or engine.can_submit_raw(mats, self.model.device_model.feat_dim)):
@@ -410,7 +449,7 @@ class Extraction(object):
                 for i in np.flatnonzero(dropped).tolist():
                     self._warn_unvoiced(keys[i])
                 keep = np.flatnonzero(~dropped)
-                keys, lens = [keys[i] for i in keep.tolist()], lens[keep]
+                keys, lens = [keys[i] for i in keep.tolist()], lens[keep]          # (segments come without a VAD: none is dropped)
             result = functools.partial(self._finish, handle, keep)
         else:
             voiced_rows = None
@@ -480,7 +519,12 @@ class Extraction(object):
         valid = counts > 0
         if not valid.all():
             self._warn_rejected(keys, lens, valid)
-        utts = [k for k, c in zip(keys, counts.tolist()) for _ in range(c)]
+        if isinstance(keys, SegmentKeys):
+            # a window's span counts frames of its segment: recording-relative by the segment's first frame, under the recording's key
+            utts = [k for k, c in zip(keys.reco, counts.tolist()) for _ in range(c)]
+            spans = spans + np.repeat(keys.first, counts).astype(spans.dtype)[:, None]
+        else:
+            utts = [k for k, c in zip(keys, counts.tolist()) for _ in range(c)]
         out_keys = [subsegment_key(u, f, e) for u, (f, e) in zip(utts, spans.tolist())]
         self.writer.put(out_keys, vecs, (utts, spans))
         self.num_success += int(valid.sum())

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("XVECTOR_HIP_LIB") or os.path.join(_HERE, "libxvector_hip.so")     # override: kernel experiments
-ABI_VERSION = 43
+ABI_VERSION = 44
 
 # every entry point include/xvector_hip.h declares, in its order: name -> (restype, argtypes)
 _vp, _ci, _cf, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -176,6 +176,10 @@ _SIGNATURES = {
     # sliding-window extraction: the packed rows of overlapping sub-segments
     "xv_cmn_sliding_gather_f32": (_ci, [_vp, _ci, _ci, _i64, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp,
                                         _ci, _i64, _vp]),
+    # speech segments from device-resident VAD decisions
+    "xv_vad_segments_i32": (_ci, [_vp, _vp, _vp, _ci, _i64, _ci, _ci, _ci, _ci, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "xv_vad_segments_workspace_bytes": (_sz, [_i64]),
+    "xv_vad_segments_capacity": (_i64, [_i64, _ci, _ci, _ci]),
 }
 SYMBOLS = tuple(_SIGNATURES)      # tests check the header declares exactly these and the .so exports all of them
 
@@ -197,6 +201,7 @@ PCA_MAX_DIM = 128                  # XV_PCA_MAX_DIM: the vector dimension of xv_
 PCA_MAX_SWEEPS = 30                # XV_PCA_MAX_SWEEPS: the sweep cap of its Jacobi iteration
 VBX_MAX_SPK = 64                   # XV_VBX_MAX_SPK: speakers of one group of xv_vbx_groups_f64
 VBX_MAX_ITERS = 100                # XV_VBX_MAX_ITERS: its iteration cap
+SEG_TILE = 256                     # XV_SEG_TILE: frames per step of xv_vad_segments_i32
 
 _lib = None
 
@@ -1269,6 +1274,43 @@ def vad_compact(vad, utt_start, utt_len):
     rows = torch.full((max(n_frames, 1),), -1, dtype=torch.int32, device=vad.device)
     _check(lib.xv_vad_compact_i32(_ptr(vad), starts, lens, n_utts, n_frames, _ptr(count), _ptr(rows), _stream()), "xv_vad_compact_i32")
     return count, rows
+
+
+def vad_segments_workspace_bytes(n_frames):
+    """xv_vad_segments_workspace_bytes: what ``vad_segments`` needs for a buffer of ``n_frames`` decisions (host function)."""
+    return int(load().xv_vad_segments_workspace_bytes(int(n_frames)))
+
+
+def vad_segments_capacity(T, max_gap, min_len, max_len):
+    """xv_vad_segments_capacity: the most segments an utterance of ``T`` frames can have (host function); ValueError for a negative
+    ``T`` or parameters outside the rule's ranges."""
+    cap = int(load().xv_vad_segments_capacity(int(T), int(max_gap), int(min_len), int(max_len)))
+    if cap < 0:
+        raise ValueError("vad_segments_capacity: T = %d, max_gap = %d, min_len = %d, max_len = %d are outside the rule's ranges"
+                         % (T, max_gap, min_len, max_len))
+    return cap
+
+
+def vad_segments(vad, utt_start, utt_len, max_gap, min_len, pad, max_len, seg_off, seg_cap, seg_count, seg_first, seg_len,
+                 workspace=None):
+    """xv_vad_segments_i32: vad[n_frames] cuda float32 (non-zero = voiced), utt_start / utt_len / seg_off / seg_cap cuda int32, one
+    entry per utterance -> seg_count[n_utts] (the full count), and segment i of utterance u in seg_first / seg_len[seg_off[u] + i]
+    (cuda int32, equally long: the slots) while i < seg_cap[u].  The rule: include/xvector_hip.h.  Entries no segment names keep
+    their contents.  ``workspace``: a cuda uint8 tensor of at least ``vad_segments_workspace_bytes`` bytes (None: made here)."""
+    import torch
+    lib = require_gpu()
+    _f32(vad, "vad")
+    i32, n_utts, n_frames, n_slots = torch.int32, utt_start.numel(), vad.numel(), seg_first.numel()
+    assert vad.dim() == 1 and seg_len.numel() == n_slots
+    need = vad_segments_workspace_bytes(n_frames)
+    if workspace is None:
+        workspace = _ws(need, vad.device)
+    _check(lib.xv_vad_segments_i32(_ptr(vad), _dev(utt_start, i32, "utt_start"), _dev(utt_len, i32, "utt_len", n_utts), n_utts,
+                                   n_frames, int(max_gap), int(min_len), int(pad), int(max_len), _dev(seg_off, i32, "seg_off", n_utts),
+                                   _dev(seg_cap, i32, "seg_cap", n_utts), n_slots, _dev(seg_count, i32, "seg_count", n_utts),
+                                   _dev(seg_first, i32, "seg_first"), _dev(seg_len, i32, "seg_len"),
+                                   _dev(workspace, torch.uint8, "workspace", need), _nbytes(workspace), _stream()), "xv_vad_segments_i32")
+    return seg_count, seg_first, seg_len
 
 
 def voiced_rank(vad, utt_start, utt_len, n_frames, rank=None, count=None):
